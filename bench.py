@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- AV frame-pairs/s of one data-parallel training step on N MI355X of one node.
 
-  python bench.py                                   # N=1, defaults finish in ~2 minutes
+  python bench.py --gpus 1 --steps K --warmup W      # N=1: set up, warm up, time exactly K steps, print the result line
+  python bench.py --full                            # also the roofline probes, CPU-reference parity and CPU baseline
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W     # one rank per GPU over RCCL
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): the logits and, for a training
+step, the loss, a fixed, seeded sample of the updated flat parameter buffer and of Adam's two moment buffers, and the
+BatchNorm running statistics.  Inputs and initial weights are seeded, so two builds compare output for output.
 
 Default workload "c4" (BASELINE.json configs[3]/[4], SURVEY.md 8d "C4/C5"; weak scaling): per GPU 64 sequences x
 T=16 = 1024 AV frame-pairs: raw 16 kHz waveform (64,1,16*256+2047) -> WaveNet encoder "W0" (20 dilated layers,
@@ -78,6 +83,31 @@ def make_inputs(torch, n_seq, seed, device, T=T_FRAMES, L=None, kind="av"):
     target = (torch.rand(n_seq, T, 1, generator=g) > 0.5).float()
     lengths = torch.full((n_seq,), T, dtype=torch.long)
     return [t.to(device) if device else t for t in (wave, video, target, lengths)]
+
+
+DUMP_SAMPLE = 1 << 20          # entries kept of each flat optimiser buffer (the c4 model: 27 M parameters)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def sample_flat(torch, flats):
+    """The same fixed, seeded, sorted entries of each equally long flat buffer: {name: 1-D tensor}."""
+    n = next(iter(flats.values())).numel()
+    if n <= DUMP_SAMPLE:
+        return dict(flats)
+    idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(2024)).sort().values
+    return {k: v[idx.to(v.device)] for k, v in flats.items()}
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every tensor of {name: tensor} as out_dir/<name>.npy in float32."""
+    import numpy as np
+    host = {k: np.ascontiguousarray(v.detach().float().cpu().numpy(), dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def trunk_conv_shapes(n):
@@ -303,8 +333,8 @@ def bench_c1(args):
     """BASELINE configs[0]: the audio_net WaveNet-encoder forward on the CPU, one 16000-sample chunk, batch 1, through the
     evaluate_audio_net.process_utt-shaped plumbing (peak-normalise -> encoder -> (1,60,Bn) -> 2xLSTM(1024) -> FC -> sigmoid ->
     threshold).  The reference's own CPU-runnable case: timed on the oracle (a restatement of the reference's PyTorch-CPU
-    arithmetic), cores stated; where a GPU is present the same chunk also runs through the HIP path and the max |delta| of
-    the logits is reported beside it."""
+    arithmetic), cores stated; under --full, where a GPU is present, the same chunk also runs through the HIP path and the
+    max |delta| of the logits is reported beside it."""
     import torch
     from oracle import models
     from packages.models.Audio_Net import DeepVAD_audio
@@ -323,18 +353,20 @@ def bench_c1(args):
             y = models.audio_net(sd, x, [60], 2, wavenet_cfg=cfg)               # encoder -> (1,60,Bn) -> LSTM -> FC
             return y, (torch.sigmoid(y) > 0.5)                                 # :236-250 soft / hard decisions
     times = []
-    for _ in range(args.warmup + max(5, args.steps)):
+    for _ in range(args.warmup + args.steps):
         t0 = time.perf_counter()
         y_ref, _ = cpu_fwd()
         times.append(time.perf_counter() - t0)
     t = sorted(times[args.warmup:])[len(times[args.warmup:]) // 2]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": y_ref})
     out = {"metric": "audio_net WaveNet-encoder forward on CPU (frames/s)", "value": round(60 / t, 1), "unit": "frames/s", "n_gpus": 0,
            "steps": len(times) - args.warmup, "warmup": args.warmup, "ms_per_step": round(1e3 * t, 3), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": "BASELINE configs[0]: audio_net (WaveNet-W0 encoder P=60 + 2xLSTM1024 + FC) forward on one 16000-sample "
                                   "chunk, batch 1, evaluate_audio_net.process_utt plumbing, CPU oracle (kind: port)", "name": "c1",
                       "cores": cores, "samples": 16000, "frames": 60}}
-    if torch.cuda.is_available():
+    if args.full and not args.no_extras and torch.cuda.is_available():
         mg = m.to("cuda:0").eval()
         wg = wave.to("cuda:0")
         from avvad import ops
@@ -356,17 +388,22 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=sorted(CONFIGS) + ["c1"], default="c4")
-    ap.add_argument("--blocks", type=int, default=3, help="timed blocks of --steps steps each; the MEDIAN block is reported")
+    ap.add_argument("--blocks", type=int, default=1, help="timed blocks of --steps steps each; the MEDIAN block is reported")
     ap.add_argument("--global-frame-pairs", type=int, default=0, help="c4 only: fix the GLOBAL batch (BASELINE configs[3]: 1024 over 2 and 4 "
                     "GPUs) and shard it over the ranks -- strong scaling; default: 1024 frame-pairs PER GPU (weak scaling)")
     ap.add_argument("--forward-only", action="store_true", help="inference forward instead of the training step")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32", help="bf16: BASELINE configs[4] arithmetic (own line, never the headline)")
     ap.add_argument("--reserve-cus", type=int, default=-1, help="CUs left free by the persistent conv grids (room for RCCL kernels); "
                     "default: 0 on one GPU, %d at N > 1 (DESIGN.md 5)" % RESERVE_CUS_DP)
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline / parity probes")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the roofline probes, the CPU-reference "
+                    "parity probes and the CPU baseline (c1: the HIP-path comparison); a plain run times the step only")
+    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline / parity probes even under --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--ab", default="", help="tuning aid: after the timed region, time the step under library option NAME=VALUE\n"
-                    "against its current value, A/B/A/B in this process (stderr; boxes differ by several %)")
+                    "against its current value, A/B/A/B in this process (stderr; boxes differ by several %%)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config == "c1":
         return bench_c1(args)
 
@@ -410,13 +447,19 @@ def main():
     model = model.to(dev).train(not args.forward_only)
     wave, video, target, lengths = make_inputs(torch, n_seq, 1234 + rank, dev, T=T, L=cfg["L"], kind=kind)
 
+    last = {}                                  # the logits of the latest step (for --dump-outputs)
+
     def fwd():
         if kind == "av":
-            return model(wave, video, lengths)
-        if kind == "audio":
-            return model(wave, lengths)
-        return model(video, lengths)
+            y = model(wave, video, lengths)
+        elif kind == "audio":
+            y = model(wave, lengths)
+        else:
+            y = model(video, lengths)
+        last["logits"] = y.detach()
+        return y
 
+    opt = None
     if args.forward_only:
         for p_ in model.parameters():
             p_.requires_grad = False
@@ -470,6 +513,16 @@ def main():
     dt = sorted(block_dt)[len(block_dt) // 2]
     final_loss = float(loss.item())
     log("timed region (median block): %.3f s for %d steps" % (dt, args.steps))
+    if args.dump_outputs and rank == 0:        # before --ab / the probes: they run more steps or touch the model
+        outs = {"logits": last["logits"]}
+        if opt is not None:                    # a training step: its loss and the state it leaves behind
+            outs["loss"] = loss.detach()
+            outs.update(sample_flat(torch, {"params": opt.flat, "adam_exp_avg": opt.exp_avg, "adam_exp_avg_sq": opt.exp_avg_sq}))
+            bufs = [b.reshape(-1) for b in model.buffers() if b.is_floating_point()]
+            if bufs:
+                outs["bn_running_stats"] = torch.cat(bufs)
+        dump_outputs(args.dump_outputs, outs)
+        log("outputs written to %s" % args.dump_outputs)
     if args.ab and world == 1:
         from avvad import _lib as L_
         name, val = args.ab.split("=")
@@ -510,7 +563,7 @@ def main():
                           # whole-step fractions of SURVEY 8d (per GPU): algorithmic FLOPs / layer-at-a-time bytes over the step time
                           "flop_frac": round(flops / t_step / 1e12 / peak, 4), "hbm_frac": round(byts / t_step / 1e9 / PEAK_HBM_GBS, 4),
                           "algorithmic_tflop_per_step": round(flops / 1e12, 4), "layerwise_gb_per_step": round(byts / 1e9, 3)}}
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             if kind != "audio":
                 out["roofline"] = roofline_probe(torch, n_seq * T, dtype=args.dtype)
             hb = roofline_probe_hbm(torch, n_seq if kind != "video" else 64, cfg["L"] or (16 * HOP + RF - 1))

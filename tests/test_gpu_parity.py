@@ -534,13 +534,15 @@ def test_conv64_weights_stationary_kernel(N, H, W, lib_options):
         _report("conv64 %dx%dx%d %s: weights-stationary kernel vs engine" % (N, H, W, name), a, b, 1e-5 * float(b.abs().max()), 0.0)
     assert torch.equal(direct[2] - dx0, direct[2] - dx0) and float((direct[2] - (dx0 + direct[1])).abs().max()) <= 2e-6 * float(direct[2].abs().max())
     if N <= 70:
-        xr = x.permute(0, 3, 1, 2).cpu().requires_grad_(True)
-        yr = F.conv2d(xr, w.cpu(), None, 1, 1)
-        yr.backward(gy.permute(0, 3, 1, 2).cpu())
+        # the reference in float64: an fp32 CPU weight gradient sums up to 8190 products per entry in an order that depends on
+        # the host's thread count and vector width, and its own rounding error alone reaches the bound below
+        xr = x.permute(0, 3, 1, 2).cpu().double().requires_grad_(True)
+        yr = F.conv2d(xr, w.cpu().double(), None, 1, 1)
+        yr.backward(gy.permute(0, 3, 1, 2).cpu().double())
         _report("conv64 %dx%dx%d fwd vs F.conv2d" % (N, H, W), direct[0].permute(0, 3, 1, 2), yr.detach(), 2e-5, 1e-5)
         _report("conv64 %dx%dx%d dgrad vs autograd" % (N, H, W), direct[1].permute(0, 3, 1, 2), xr.grad, 2e-5, 1e-5)
-        wr = w.cpu().requires_grad_(True)
-        F.conv2d(x.permute(0, 3, 1, 2).cpu(), wr, None, 1, 1).backward(gy.permute(0, 3, 1, 2).cpu())
+        wr = w.cpu().double().requires_grad_(True)
+        F.conv2d(x.permute(0, 3, 1, 2).cpu().double(), wr, None, 1, 1).backward(gy.permute(0, 3, 1, 2).cpu().double())
         _report("conv64 %dx%dx%d wgrad vs autograd" % (N, H, W), direct[3], wr.grad.permute(2, 3, 1, 0).reshape(9 * 64, 64), 1e-4, 1e-5)
 
 
