@@ -533,7 +533,6 @@ __global__ void __launch_bounds__(256) stem_wgrad_reduce(const float* __restrict
 }
 
 // ------------------------------------------------------------------ conv launchers
-static inline bool fits_u31(long n) { return n >= 0 && n < (1L << 31); }
 // gathered operands are addressed with 32-bit BYTE offsets (Ctx.boff, fetch4): at most 2^30 floats (4 GiB).  Between the
 // buffer form's 2 GiB limit and this one the flat form serves; beyond it the launchers refuse (AVVAD_EINVAL).
 static inline bool fits_u30(long n) { return n >= 0 && n < (1L << 30); }
@@ -547,11 +546,9 @@ static inline bool stem_kernel_ok(const Geom& g) {
   return g.C == 1 && g.KS == 7 && g.stride == 2 && g.pad == 3 && g.Co == 64 && (size_t)(g.H + 6) * LDW * sizeof(float) <= 48 * 1024 &&
          !avvad_tune().no_stem_kernel;
 }
-// rows per M tile of the forward GEMM of convolution g (what the fused BatchNorm statistics are laid out by), 0: the stem
-static inline int fwd_tile_rows(const Geom& g) {
-  if (g.C == 1) return 0;
-  if (avvad_tune().bf16 == 1) return 128;                   // the bf16 engine's tiles (bgemm.h)
-  return g.Co <= 64 && !avvad_tune().no_tall ? 256 : 128;
+// (the weight-gradient kernel also wants an even output width within its register rows, and the slab for its partials)
+static inline bool stem_wgrad_ok(const Geom& g, bool slab) {
+  return stem_kernel_ok(g) && (g.Wo & 1) == 0 && g.Wo <= 2 * STEM_WH && slab && (long)g.Ho * g.Wo * 64 * 4 < (1L << 31);
 }
 // most tiles a position-class product may have (every tile is in the stream-K pool: about one split tile per worker, so the
 // fix-up's traffic grows with the tile count; option "cls_cap" overrides)
@@ -560,18 +557,18 @@ static inline long cls_tile_cap() {
   return 4L * ((avvad_tune().max_cus > 0 && avvad_tune().max_cus < 256) ? avvad_tune().max_cus : 256);     // (measured: 2/CU -> 4/CU: step -0.07 ms)
 }
 // ---- position classes (igemm.h): 3x3 / pad 1 convolutions whose tile count fits the stream-K pool skip the zero padding
-static inline bool cls_common(const Geom& g, float* slab) {
+static inline bool cls_common(const Geom& g, bool slab) {
   return avvad_tune().bf16 == 0 && !avvad_tune().no_cls && slab && g.KS == 3 && g.pad == 1 && g.N >= 128 && g.C % 32 == 0 &&
          g.Co % 32 == 0 && g.Ho >= 2 && g.Wo >= 2 && avvad_tune().igemm_variant < 0 && !avvad_tune().no_buf &&
          avvad_tune().no_streamk == 0;
 }
-static inline bool conv_fwd_cls_ok(const Geom& g, float* slab) {
+static inline bool conv_fwd_cls_ok(const Geom& g, bool slab) {
   if (!cls_common(g, slab) || g.Co % 4 || g.Co < 128) return false;
   const long tiles = (long)g.Ho * g.Wo * cdiv(g.N, 128) * cdiv(g.Co, 128);
   return tiles <= cls_tile_cap() &&
          fits_buf((long)g.N * g.H * g.W * g.C) && fits_buf(9L * g.C * g.Co);
 }
-static inline bool conv_dgrad_cls_ok(const Geom& g, float* slab) {
+static inline bool conv_dgrad_cls_ok(const Geom& g, bool slab) {
   // (stride 2: the parity classes as position classes of ONE product, igemm::ClassSched::s2, instead of four accumulating launches
   //  over a zero-filled dx; option no_s2_cls keeps the four launches)
   if (!cls_common(g, slab) || (g.stride != 1 && (g.stride != 2 || avvad_tune().no_s2_cls)) || g.C % 4 || g.C < 128) return false;
@@ -579,10 +576,153 @@ static inline bool conv_dgrad_cls_ok(const Geom& g, float* slab) {
   return tiles <= cls_tile_cap() &&
          fits_buf((long)g.N * g.Ho * g.Wo * g.Co) && fits_buf(9L * g.C * g.Co);
 }
+// weight gradient by taps (igemm.h TapSched): only the grid positions at which a tap is inside the image are contracted
+static inline bool conv_wgrad_tap_ok(const Geom& g, bool slab) {
+  if (!cls_common(g, slab) || g.C % 128 || g.Co % 4 || g.Co < 128) return false;
+  return 9L * (g.C / 128) * cdiv(g.Co, 128) <= cls_tile_cap() &&
+         fits_buf((long)g.N * g.H * g.W * g.C) && fits_buf((long)g.N * g.Ho * g.Wo * g.Co);
+}
+// ---- the 64 -> 64 channel 3x3 / 1 / 1 convolutions (ResNet layer1): weights-stationary kernel, conv64.h.  The fp32 form
+// also wants option bf16 at 0; the bf16 form (conv64::kernel16) serves the bf16 data path whatever the option
+static inline int conv64_cus() { return (avvad_tune().max_cus > 0 && avvad_tune().max_cus < 256) ? avvad_tune().max_cus : 256; }
+static inline bool conv64_ok(const Geom& g, bool b16) {
+  const long M = (long)g.N * g.H * g.W;
+  return (b16 || avvad_tune().bf16 == 0) && !avvad_tune().no_conv64 && g.C == 64 && g.Co == 64 && g.KS == 3 && g.stride == 1 &&
+         g.pad == 1 && g.Ho == g.H && g.Wo == g.W && M > 0 && fits_buf(M * 64) &&
+         (unsigned long)(M + 64) * (unsigned long)(g.H * g.W) < 0x100000000ull;
+}
+// (the weight gradient: output-stationary kernel + ordered reduction of the per-CU partials)
+static inline bool conv64_wgrad_ok(const Geom& g, bool slab) {
+  return conv64_ok(g, false) && slab && g.W <= conv64::WG_MAXW && (size_t)conv64_cus() * conv64::WG_PART <= igemm::SLAB_FLOATS &&
+         (long)g.N * g.H * g.W * 256 < (1L << 31);
+}
+
+// ---- the bf16 data path (option "bf16" = 1; bgemm.h)
+// Operands are bf16 in HBM: activations / output gradients NHWC bf16 (written by the BatchNorm elementwise kernels), weights
+// in the K-contiguous bf16 packs of pack_all.  Outputs are fp32 (raw convolution sums feed BatchNorm statistics; gradients
+// accumulate).  Channel counts must be multiples of 64 (every trunk convolution behind the stem), operands < 2 GiB.
+static inline bool native_bf16() { return avvad_tune().bf16 == 1; }
+static inline bool bf16_conv_ok(const Geom& g) {
+  return g.C % 64 == 0 && g.Co % 64 == 0 && taps_fit(g) && fits_buf((long)g.N * g.H * g.W * g.C / 2) &&
+         fits_buf((long)g.N * g.Ho * g.Wo * g.Co / 2) && fits_buf((long)g.KS * g.KS * g.C * g.Co / 2);
+}
+// position classes on the bf16 engine (the zero padding skipped: igemm.h); 64-channel chunks
+// (the bf16 kernels are bound by operand traffic, not by the matrix pipe: skipped products buy time only where they are 40 %
+//  of the tile -- the 3x3 grid -- and on larger grids the all-tiles-in-the-pool fix-up costs more than they save: measured
+//  per forward launch, 9x9 grid 55 -> 74 us, 5x5 66 -> 73 us, 3x3 78 -> 65 us)
+static inline bool cls16_common(const Geom& g, bool slab) {
+  return !avvad_tune().no_cls && slab && g.KS == 3 && g.pad == 1 && g.N >= 128 && g.Ho >= 2 && g.Wo >= 2 && g.Ho * g.Wo <= 9 &&
+         avvad_tune().no_streamk == 0;
+}
+static inline bool conv_fwd16_cls_ok(const Geom& g, bool slab) {
+  if (!cls16_common(g, slab) || g.Co < 128) return false;
+  return (long)g.Ho * g.Wo * cdiv(g.N, 128) * cdiv(g.Co, 128) <= cls_tile_cap();
+}
+// stride 2, 3x3: the four parity classes as position classes of ONE product (igemm::ClassSched::s2) -- on this engine the four
+// separate launches are ~40 us each whatever their size, so grouping pays on every grid (unlike the stride-1 classes)
+static inline bool conv_dgrad16_cls_ok(const Geom& g, bool slab) {
+  const bool form = g.stride == 1 ? cls16_common(g, slab)
+                                  : g.stride == 2 && g.KS == 3 && g.pad == 1 && !avvad_tune().no_cls && !avvad_tune().no_s2_cls &&
+                                        avvad_tune().no_streamk == 0 && slab && g.N >= 128;
+  return form && g.C >= 128 && (long)g.H * g.W * cdiv(g.N, 128) * cdiv(g.C, 128) <= cls_tile_cap();
+}
+static inline bool conv_wgrad16_tap_ok(const Geom& g, bool slab) {
+  return cls16_common(g, slab) && g.C % 128 == 0 && g.Co >= 128 && 9L * (g.C / 128) * cdiv(g.Co, 128) <= cls_tile_cap();
+}
+
+// ---- which kernel form runs a convolution: one choice per direction and data path, made at every call (the backward runs
+// under BwdCuCap, whose lower max_cus changes cls_tile_cap() and conv64_cus()).  The launchers switch on it, and the forward's
+// BatchNorm statistics read from it how many partial-sum chunks the epilogue leaves.
+// STEM: the stem's LDS-resident-frame kernels.  CONV64: conv64.h.  CLS: position classes (igemm.h; the stride-2 data gradient
+// as one product over its parity classes).  TAP: the weight gradient by taps (igemm.h TapSched).  PARITY: the stride-2 data
+// gradient as four parity-class GEMMs (conv_ops.h).  ENGINE: the im2col engine (with the stem's own gathers when C == 1).
+enum Form { STEM, CONV64, CLS, TAP, PARITY, ENGINE };
+struct ConvForm {
+  Form form;
+  int rows, cols;   // ENGINE / PARITY: the engine's tile
+  bool buf;         // ENGINE / PARITY: buffer-addressed gathers (the bf16 engine's always are)
+  int chunks;       // forward: partial-sum chunks of the column statistics its epilogue leaves in `stat` (0: none)
+};
+static ConvForm fwd_form(const Geom& g, bool b16, bool slab) {
+  const long M = (long)g.N * g.Ho * g.Wo;
+  const int cols = g.Co <= 64 ? 64 : 128;
+  if (conv64_ok(g, b16)) return {CONV64, 0, 0, false, conv64::grid_for((long)g.N * g.H * g.W, conv64_cus())};   // one per workgroup
+  if (b16 ? conv_fwd16_cls_ok(g, slab) : conv_fwd_cls_ok(g, slab)) return {CLS, 0, 0, false, g.Ho * g.Wo * cdiv(g.N, 128)};
+  if (b16) return {ENGINE, 128, cols, true, cdiv(M, 128)};
+  if (g.C == 1) return stem_kernel_ok(g) ? ConvForm{STEM, 0, 0, false, g.N} : ConvForm{ENGINE, 128, 64, false, 0};   // (per frame)
+  const int rows = g.Co <= 64 && !avvad_tune().no_tall ? 256 : 128;
+  const bool buf = fits_buf((long)g.N * g.H * g.W * g.C) && fits_buf((long)g.KS * g.KS * g.C * g.Co) && !avvad_tune().no_buf;
+  return {ENGINE, rows, cols, buf, cdiv(M, rows)};
+}
+static ConvForm dgrad_form(const Geom& g, bool b16, bool slab) {
+  if (conv64_ok(g, b16)) return {CONV64};
+  if (b16 ? conv_dgrad16_cls_ok(g, slab) : conv_dgrad_cls_ok(g, slab)) return {CLS};
+  const int cols = g.C <= 64 ? 64 : 128;
+  const bool buf = b16 || (fits_buf((long)g.N * g.Ho * g.Wo * g.Co) && fits_buf((long)g.KS * g.KS * g.C * g.Co) && !avvad_tune().no_buf);
+  if (g.stride == 2) return {PARITY, 128, cols, buf};
+  return {ENGINE, cols == 64 && !b16 && !avvad_tune().no_tall ? 256 : 128, cols, buf};
+}
+static ConvForm wgrad_form(const Geom& g, bool b16, bool slab) {
+  const int cols = g.Co <= 64 ? 64 : 128;
+  if (b16) return conv_wgrad16_tap_ok(g, slab) ? ConvForm{TAP} : ConvForm{ENGINE, 128, cols, true};
+  if (conv64_wgrad_ok(g, slab)) return {CONV64};
+  if (conv_wgrad_tap_ok(g, slab)) return {TAP};
+  if (g.C == 1) return stem_wgrad_ok(g, slab) ? ConvForm{STEM} : ConvForm{ENGINE, 64, 64, false};
+  const bool buf = fits_buf((long)g.N * g.H * g.W * g.C) && fits_buf((long)g.N * g.Ho * g.Wo * g.Co) && !avvad_tune().no_buf;
+  return {ENGINE, 128, cols, buf};
+}
+
+// ---- the schedules the launchers share between the data paths (K chunk kc: 32 channels fp32, 64 bf16)
+static igemm::ClassSched fwd_sched(const Geom& g, int kc) {
+  const int lsh = ((g.Ho - 1) * g.stride - g.pad + 2 > g.H - 1) ? 1 : 0, lsw = ((g.Wo - 1) * g.stride - g.pad + 2 > g.W - 1) ? 1 : 0;
+  return igemm::ClassSched{g.Ho, g.Wo, cdiv(g.Co, 128), g.C / kc, cdiv(g.N, 128), 3, 1, lsh, 1, lsw};
+}
+static igemm::ClassSched dgrad_sched(const Geom& g, int kc) {
+  igemm::ClassSched sc{g.H, g.W, cdiv(g.C, 128), g.Co / kc, cdiv(g.N, 128), 3, 1, 1, 1, 1};
+  if (g.stride == 2) { sc.s2 = 1; sc.Hq = g.Ho; sc.Wq = g.Wo; }
+  return sc;
+}
+// stride-2 data gradient by parity classes (conv_ops.h): per class (ph, pw) of input positions, one small GEMM over the taps
+// that reach it, accumulating into dx.  gemm(c, Mc, ntap, e) launches class c's.
+template <class Gemm>
+static int dgrad_parity(float* dx, const Geom& g, int accumulate, hipStream_t s, Gemm gemm) {
+  const long n = (long)g.N * g.H * g.W * g.C;
+  if (!accumulate) hipLaunchKernelGGL(zero_f32, dim3(ew_grid(n)), dim3(256), 0, s, dx, n);
+  for (int ph = 0; ph < 2; ++ph)
+    for (int pw = 0; pw < 2; ++pw) {
+      convop::S2Class c;
+      c.ph = ph; c.pw = pw;
+      c.Hc = (g.H - ph + 1) / 2; c.Wc = (g.W - pw + 1) / 2;
+      c.kh0 = (ph + g.pad) & 1; c.kw0 = (pw + g.pad) & 1;
+      c.nkh = c.kh0 < g.KS ? (g.KS - c.kh0 + 1) / 2 : 0;
+      c.nkw = c.kw0 < g.KS ? (g.KS - c.kw0 + 1) / 2 : 0;
+      c.oh = (ph + g.pad - c.kh0) / 2; c.ow = (pw + g.pad - c.kw0) / 2;
+      const int Mc = g.N * c.Hc * c.Wc, ntap = c.nkh * c.nkw;
+      if (Mc <= 0 || ntap <= 0) continue;
+      if (ntap > 4) return AVVAD_EINVAL;
+      c.mg_ntap = convop::div_magic(ntap); c.mg_nkw = convop::div_magic(c.nkw);
+      const convop::EpiS2 e{dx, g.C, nullptr, 1, 1, g.H, g.W, c.Hc, c.Wc, ph, pw, convop::div_magic(c.Hc * c.Wc), convop::div_magic(c.Wc)};
+      if ((unsigned long)(Mc + 128) * (unsigned long)(c.Hc * c.Wc) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
+      if (const int rc = gemm(c, Mc, ntap, e)) return rc;
+    }
+  return AVVAD_OK;
+}
+
+// y = conv(x) (flip = false, wpk = forward pack) or dx (+)= dgrad(dy) (flip = true, wpk = dgrad pack); b16: bf16 activations /
+// packs in (conv64::kernel16), fp32 out
+static int conv64_launch(bool b16, bool flip, const float* x, const float* wpk, float* y, const Geom& g, int accumulate, hipStream_t s,
+                         double* stat) {
+  const int M = g.N * g.H * g.W;
+  const int grid = conv64::grid_for(M, conv64_cus());
+  const unsigned mg_hw = convop::div_magic((unsigned)(g.H * g.W)), mg_w = convop::div_magic((unsigned)g.W);
+  auto k = b16 ? (flip ? conv64::kernel16<true> : conv64::kernel16<false>) : (flip ? conv64::kernel<true> : conv64::kernel<false>);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(conv64::NW * 64), 0, s, x, wpk, y, M, g.H, g.W, mg_hw, mg_w, accumulate, stat);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
 static int conv_fwd_cls(const float* x, const float* wf, float* y, const Geom& g, hipStream_t s, float* slab, double* stat) {
   const int MB = cdiv(g.N, 128), P = g.Ho * g.Wo;
-  const int lsh = ((g.Ho - 1) * g.stride - g.pad + 2 > g.H - 1) ? 1 : 0, lsw = ((g.Wo - 1) * g.stride - g.pad + 2 > g.W - 1) ? 1 : 0;
-  const igemm::ClassSched sc{g.Ho, g.Wo, cdiv(g.Co, 128), g.C / 32, MB, 3, 1, lsh, 1, lsw};
+  const igemm::ClassSched sc = fwd_sched(g, 32);
   const igemm::ClassRow cr{P, convop::div_magic(P)};
   convop::Im2colFwdCls a{x, g, g.N, cr, sc};
   convop::ColTapRowsCls b{wf, g.Co, g.Co, g.C, 3, 0, cr, sc};
@@ -592,8 +732,7 @@ static int conv_fwd_cls(const float* x, const float* wf, float* y, const Geom& g
 }
 static int conv_dgrad_cls(const float* dy, const float* wd, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
   const int MB = cdiv(g.N, 128), P = g.H * g.W;
-  igemm::ClassSched sc{g.H, g.W, cdiv(g.C, 128), g.Co / 32, MB, 3, 1, 1, 1, 1};
-  if (g.stride == 2) { sc.s2 = 1; sc.Hq = g.Ho; sc.Wq = g.Wo; }
+  const igemm::ClassSched sc = dgrad_sched(g, 32);
   const igemm::ClassRow cr{P, convop::div_magic(P)};
   convop::Im2colDgradCls a{dy, g, g.N, cr, sc};
   convop::ColTapRowsCls b{wd, g.C, g.C, g.Co, 3, 1, cr, sc};
@@ -601,153 +740,81 @@ static int conv_dgrad_cls(const float* dy, const float* wd, float* dx, const Geo
   e.W = g.C; e.rows = g.N; e.cr = cr; e.sched = sc;
   return igemm::launch_cls(a, b, e, MB * P * 128, g.C, s, slab);
 }
-// ---- the 64 -> 64 channel 3x3 / 1 / 1 convolutions (ResNet layer1): weights-stationary kernel, conv64.h
-static inline int conv64_cus() { return (avvad_tune().max_cus > 0 && avvad_tune().max_cus < 256) ? avvad_tune().max_cus : 256; }
-static inline bool conv64_ok(const Geom& g) {
-  const long M = (long)g.N * g.H * g.W;
-  return avvad_tune().bf16 == 0 && !avvad_tune().no_conv64 && g.C == 64 && g.Co == 64 && g.KS == 3 && g.stride == 1 && g.pad == 1 &&
-         g.Ho == g.H && g.Wo == g.W && M > 0 && fits_buf(M * 64) && (unsigned long)(M + 64) * (unsigned long)(g.H * g.W) < 0x100000000ull;
-}
-// y = conv(x) (flip = false, wpk = forward pack) or dx (+)= dgrad(dy) (flip = true, wpk = dgrad pack)
-static int conv64_launch(bool flip, const float* x, const float* wpk, float* y, const Geom& g, int accumulate, hipStream_t s, double* stat) {
-  const int M = g.N * g.H * g.W;
-  const int grid = conv64::grid_for(M, conv64_cus());
-  const unsigned mg_hw = convop::div_magic((unsigned)(g.H * g.W)), mg_w = convop::div_magic((unsigned)g.W);
-  if (flip)
-    hipLaunchKernelGGL(conv64::kernel<true>, dim3(grid), dim3(conv64::NW * 64), 0, s, x, wpk, y, M, g.H, g.W, mg_hw, mg_w, accumulate, stat);
-  else
-    hipLaunchKernelGGL(conv64::kernel<false>, dim3(grid), dim3(conv64::NW * 64), 0, s, x, wpk, y, M, g.H, g.W, mg_hw, mg_w, accumulate, stat);
-  AVVAD_LAUNCH_CHECK();
-  return AVVAD_OK;
-}
-// the same two products on the bf16 data path (bf16 activations / packs in, fp32 out): conv64::kernel16
-static inline bool conv64_16_ok(const Geom& g) {
-  const long M = (long)g.N * g.H * g.W;
-  return !avvad_tune().no_conv64 && g.C == 64 && g.Co == 64 && g.KS == 3 && g.stride == 1 && g.pad == 1 &&
-         g.Ho == g.H && g.Wo == g.W && M > 0 && fits_buf(M * 64) && (unsigned long)(M + 64) * (unsigned long)(g.H * g.W) < 0x100000000ull;
-}
-static int conv64_16_launch(bool flip, const float* x16, const float* wpk16, float* y, const Geom& g, int accumulate, hipStream_t s, double* stat) {
-  const int M = g.N * g.H * g.W;
-  const int grid = conv64::grid_for(M, conv64_cus());
-  const unsigned mg_hw = convop::div_magic((unsigned)(g.H * g.W)), mg_w = convop::div_magic((unsigned)g.W);
-  if (flip)
-    hipLaunchKernelGGL(conv64::kernel16<true>, dim3(grid), dim3(conv64::NW * 64), 0, s, x16, wpk16, y, M, g.H, g.W, mg_hw, mg_w, accumulate, stat);
-  else
-    hipLaunchKernelGGL(conv64::kernel16<false>, dim3(grid), dim3(conv64::NW * 64), 0, s, x16, wpk16, y, M, g.H, g.W, mg_hw, mg_w, accumulate, stat);
-  AVVAD_LAUNCH_CHECK();
-  return AVVAD_OK;
-}
-// number of partial-sum chunks the forward of convolution g leaves in its `stat` buffer (one per M tile of its GEMM)
-static inline int fwd_stat_chunks(const Geom& g, float* slab);
 
 // stat: per-M-tile column sums / sums of squares of y (igemm::EpiStore::stat), or null
 template <bool BUF>
-static int conv_fwd_t(const float* x, const float* wf, float* y, const Geom& g, hipStream_t s, float* slab, double* stat) {
+static int conv_fwd_t(const float* x, const float* wf, float* y, const Geom& g, const ConvForm& f, hipStream_t s, float* slab, double* stat) {
   const int M = g.N * g.Ho * g.Wo, K = g.KS * g.KS * g.C;
   igemm::EpiStore e{y, g.Co, nullptr, 0};
-  e.stat = g.C == 1 ? nullptr : stat;       // (the stem's own kernel takes `stat` directly, see below)
   if (g.C == 1) {
-    const int LDW = (g.W + 6) | 1;
-    const size_t lds = (size_t)(g.H + 6) * LDW * sizeof(float);
-    if (g.KS == 7 && g.stride == 2 && g.pad == 3 && g.Co == 64 && lds <= 48 * 1024 && !avvad_tune().no_stem_kernel) {
-      hipLaunchKernelGGL(stem_fwd_mfma, dim3(g.N), dim3(256), lds, s, x, wf, y, g.H, g.W, g.Ho, g.Wo, LDW, stat);
-      AVVAD_LAUNCH_CHECK();
-      return AVVAD_OK;
-    }
     igemm::ColPlain<4> b{wf, g.Co, g.Co, K, 0};
     convop::StemFwd a{x, g, M, K};
     return igemm::launch<128, 64>(a, b, e, M, g.Co, K, 1, s, slab);
   }
+  e.stat = stat;
   if (g.C % 32 || g.Co % 4 || !taps_fit(g)) return AVVAD_EINVAL;
   if (!fits_u30((long)g.N * g.H * g.W * g.C) || !fits_u30((long)K * g.Co)) return AVVAD_EINVAL;   // 32-bit BYTE offsets in the gathers
   const int T = g.KS * g.KS;
   convop::ColTapRows<BUF> b{wf, g.Co, g.Co, K, g.C, T, convop::div_magic(T)};
   convop::Im2colFwd<BUF> a{x, g, M, convop::tap_div(T, g.KS)};
-  if (g.Co <= 64) return avvad_tune().no_tall ? igemm::launch<128, 64>(a, b, e, M, g.Co, K, 1, s, slab) : igemm::launch<256, 64>(a, b, e, M, g.Co, K, 1, s, slab);
+  if (f.rows == 256) return igemm::launch<256, 64>(a, b, e, M, g.Co, K, 1, s, slab);
+  if (f.cols == 64) return igemm::launch<128, 64>(a, b, e, M, g.Co, K, 1, s, slab);
   return igemm::launch<128, 128>(a, b, e, M, g.Co, K, 1, s, slab);
 }
-static inline bool conv_fwd16_cls_ok(const Geom& g, float* slab);
-static inline int fwd_stat_chunks(const Geom& g, float* slab) {
-  if (avvad_tune().bf16 == 1 && conv64_16_ok(g)) return conv64::grid_for((long)g.N * g.H * g.W, conv64_cus());      // one chunk per workgroup
-  if (avvad_tune().bf16 == 1)
-    return (g.C % 64 == 0 && g.Co % 64 == 0 && conv_fwd16_cls_ok(g, slab)) ? g.Ho * g.Wo * cdiv(g.N, 128) : cdiv((long)g.N * g.Ho * g.Wo, 128);
-  if (conv64_ok(g)) return conv64::grid_for((long)g.N * g.H * g.W, conv64_cus());      // one chunk per workgroup
-  if (conv_fwd_cls_ok(g, slab)) return g.Ho * g.Wo * cdiv(g.N, 128);
-  const int rows = fwd_tile_rows(g);
-  return rows ? cdiv((long)g.N * g.Ho * g.Wo, rows) : 0;
-}
 static int conv_fwd(const float* x, const float* wf, float* y, const Geom& g, hipStream_t s, float* slab, double* stat = nullptr) {
-  if (conv64_ok(g)) return conv64_launch(false, x, wf, y, g, 0, s, stat);
-  if (conv_fwd_cls_ok(g, slab)) return conv_fwd_cls(x, wf, y, g, s, slab, stat);
-  const bool buf = fits_buf((long)g.N * g.H * g.W * g.C) && fits_buf((long)g.KS * g.KS * g.C * g.Co) && !avvad_tune().no_buf;
-  return buf ? conv_fwd_t<true>(x, wf, y, g, s, slab, stat) : conv_fwd_t<false>(x, wf, y, g, s, slab, stat);
+  const ConvForm f = fwd_form(g, false, slab);
+  switch (f.form) {
+    case STEM: {
+      const int LDW = (g.W + 6) | 1;
+      hipLaunchKernelGGL(stem_fwd_mfma, dim3(g.N), dim3(256), (size_t)(g.H + 6) * LDW * sizeof(float), s, x, wf, y, g.H, g.W, g.Ho, g.Wo,
+                         LDW, stat);
+      AVVAD_LAUNCH_CHECK();
+      return AVVAD_OK;
+    }
+    case CONV64: return conv64_launch(false, false, x, wf, y, g, 0, s, stat);
+    case CLS: return conv_fwd_cls(x, wf, y, g, s, slab, stat);
+    default: return f.buf ? conv_fwd_t<true>(x, wf, y, g, f, s, slab, stat) : conv_fwd_t<false>(x, wf, y, g, f, s, slab, stat);
+  }
 }
 // dx (+)= dgrad
 template <bool BUF>
-static int conv_dgrad_t(const float* dy, const float* wd, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
+static int conv_dgrad_t(const float* dy, const float* wd, float* dx, const Geom& g, const ConvForm& f, int accumulate, hipStream_t s,
+                        float* slab) {
   const int M = g.N * g.H * g.W, K = g.KS * g.KS * g.Co;
   if (g.Co % 32 || g.C % 4 || !taps_fit(g)) return AVVAD_EINVAL;
   if (!fits_u30((long)g.N * g.Ho * g.Wo * g.Co) || !fits_u30((long)K * g.C)) return AVVAD_EINVAL;   // 32-bit BYTE offsets in the gathers
-  if (g.stride == 2) {
-    // parity-class decomposition (conv_ops.h): 4 small GEMMs over live taps only, accumulating into dx
-    if (!accumulate) hipLaunchKernelGGL(zero_f32, dim3(ew_grid((long)M * g.C)), dim3(256), 0, s, dx, (long)M * g.C);
-    for (int ph = 0; ph < 2; ++ph)
-      for (int pw = 0; pw < 2; ++pw) {
-        convop::S2Class c;
-        c.ph = ph; c.pw = pw;
-        c.Hc = (g.H - ph + 1) / 2; c.Wc = (g.W - pw + 1) / 2;
-        c.kh0 = (ph + g.pad) & 1; c.kw0 = (pw + g.pad) & 1;
-        c.nkh = c.kh0 < g.KS ? (g.KS - c.kh0 + 1) / 2 : 0;
-        c.nkw = c.kw0 < g.KS ? (g.KS - c.kw0 + 1) / 2 : 0;
-        c.oh = (ph + g.pad - c.kh0) / 2; c.ow = (pw + g.pad - c.kw0) / 2;
-        const int Mc = g.N * c.Hc * c.Wc, ntap = c.nkh * c.nkw;
-        if (Mc <= 0 || ntap <= 0) continue;
-        if (ntap > 4) return AVVAD_EINVAL;
-        c.mg_ntap = convop::div_magic(ntap); c.mg_nkw = convop::div_magic(c.nkw);
-        convop::Im2colDgradS2<BUF> a{dy, g, c, Mc};
-        convop::ColSegRows<BUF> b{wd, g.C, g.C, ntap * g.Co, ntap, {0, 0, 0, 0}, convop::div_magic(ntap)};
-        for (int ia = 0; ia < c.nkh; ++ia)
-          for (int ib = 0; ib < c.nkw; ++ib)
-            b.rowbase[ia * c.nkw + ib] = ((c.kh0 + 2 * ia) * g.KS + (c.kw0 + 2 * ib)) * g.Co;
-        convop::EpiS2 e{dx, g.C, nullptr, 1, 1, g.H, g.W, c.Hc, c.Wc, ph, pw, convop::div_magic(c.Hc * c.Wc), convop::div_magic(c.Wc)};
-        if ((unsigned long)(Mc + 128) * (unsigned long)(c.Hc * c.Wc) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
-        int rc;
-        if (g.C <= 64) rc = igemm::launch<128, 64>(a, b, e, Mc, g.C, ntap * g.Co, 1, s, slab);
-        else rc = igemm::launch<128, 128>(a, b, e, Mc, g.C, ntap * g.Co, 1, s, slab);
-        if (rc) return rc;
-      }
-    return AVVAD_OK;
-  }
+  if (f.form == PARITY)
+    return dgrad_parity(dx, g, accumulate, s, [&](const convop::S2Class& c, int Mc, int ntap, const convop::EpiS2& e) {
+      convop::Im2colDgradS2<BUF> a{dy, g, c, Mc};
+      convop::ColSegRows<BUF> b{wd, g.C, g.C, ntap * g.Co, ntap, {0, 0, 0, 0}, convop::div_magic(ntap)};
+      for (int ia = 0; ia < c.nkh; ++ia)
+        for (int ib = 0; ib < c.nkw; ++ib) b.rowbase[ia * c.nkw + ib] = ((c.kh0 + 2 * ia) * g.KS + (c.kw0 + 2 * ib)) * g.Co;
+      return f.cols == 64 ? igemm::launch<128, 64>(a, b, e, Mc, g.C, ntap * g.Co, 1, s, slab)
+                          : igemm::launch<128, 128>(a, b, e, Mc, g.C, ntap * g.Co, 1, s, slab);
+    });
   igemm::EpiStore e{dx, g.C, nullptr, accumulate ? 1 : 0};
   const int T = g.KS * g.KS;
   convop::ColTapRows<BUF> b{wd, g.C, g.C, K, g.Co, T, convop::div_magic(T)};
   convop::Im2colDgrad<BUF> a{dy, g, M, convop::tap_div(T, g.KS)};
-  if (g.C <= 64) return avvad_tune().no_tall ? igemm::launch<128, 64>(a, b, e, M, g.C, K, 1, s, slab) : igemm::launch<256, 64>(a, b, e, M, g.C, K, 1, s, slab);
+  if (f.rows == 256) return igemm::launch<256, 64>(a, b, e, M, g.C, K, 1, s, slab);
+  if (f.cols == 64) return igemm::launch<128, 64>(a, b, e, M, g.C, K, 1, s, slab);
   return igemm::launch<128, 128>(a, b, e, M, g.C, K, 1, s, slab);
 }
 static int conv_dgrad(const float* dy, const float* wd, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
-  if (conv64_ok(g)) return conv64_launch(true, dy, wd, dx, g, accumulate, s, nullptr);
-  if (conv_dgrad_cls_ok(g, slab)) return conv_dgrad_cls(dy, wd, dx, g, accumulate, s, slab);
-  const bool buf = fits_buf((long)g.N * g.Ho * g.Wo * g.Co) && fits_buf((long)g.KS * g.KS * g.C * g.Co) && !avvad_tune().no_buf;
-  return buf ? conv_dgrad_t<true>(dy, wd, dx, g, accumulate, s, slab) : conv_dgrad_t<false>(dy, wd, dx, g, accumulate, s, slab);
+  const ConvForm f = dgrad_form(g, false, slab);
+  switch (f.form) {
+    case CONV64: return conv64_launch(false, true, dy, wd, dx, g, accumulate, s, nullptr);
+    case CLS: return conv_dgrad_cls(dy, wd, dx, g, accumulate, s, slab);
+    default: return f.buf ? conv_dgrad_t<true>(dy, wd, dx, g, f, accumulate, s, slab) : conv_dgrad_t<false>(dy, wd, dx, g, f, accumulate, s, slab);
+  }
 }
 // pk[(kh,kw,c)][co] = wgrad (overwritten; tiles split along K are combined by the engine's fix-up kernel, in a fixed order)
 template <bool BUF>
-static int conv_wgrad_t(const float* x, const float* dy, float* pk, const Geom& g, hipStream_t s, float* slab) {
+static int conv_wgrad_t(const float* x, const float* dy, float* pk, const Geom& g, const ConvForm& f, hipStream_t s, float* slab) {
   const int M = g.KS * g.KS * g.C, K = g.N * g.Ho * g.Wo;
   igemm::ColPlain<4, BUF> b{dy, g.Co, g.Co, K, 0};
   const int ktiles = cdiv(K, igemm::BK);
   if (g.C == 1) {
-    const int LDW = (g.W + 6) | 1;
-    const size_t lds = (size_t)(g.H + 6) * LDW * sizeof(float);
-    if (g.KS == 7 && g.stride == 2 && g.pad == 3 && g.Co == 64 && (g.Wo & 1) == 0 && g.Wo <= 2 * STEM_WH && lds <= 48 * 1024 &&
-        slab && !avvad_tune().no_stem_kernel && (long)g.Ho * g.Wo * 64 * 4 < (1L << 31)) {
-      const int nb = g.N < 256 ? g.N : 256;                       // one workgroup per CU, whole frames each
-      hipLaunchKernelGGL(stem_wgrad_mfma, dim3(nb), dim3(256), lds, s, x, dy, slab, g.N, g.H, g.W, g.Ho, g.Wo, LDW);
-      hipLaunchKernelGGL(stem_wgrad_reduce, dim3(49 * 64 / 32), dim3(256), 0, s, slab, nb, pk);
-      AVVAD_LAUNCH_CHECK();
-      return AVVAD_OK;
-    }
     igemm::EpiStore e{pk, g.Co, nullptr, 0};
     convop::StemWgradX a{x, g, M, K};
     int split = 1024; if (split > ktiles) split = ktiles;
@@ -758,17 +825,10 @@ static int conv_wgrad_t(const float* x, const float* dy, float* pk, const Geom& 
   if ((unsigned long)(K + igemm::BK) * (unsigned long)(g.Ho * g.Wo) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
   if (!fits_u30((long)g.N * g.H * g.W * g.C) || !fits_u30((long)K * g.Co)) return AVVAD_EINVAL;                // 32-bit BYTE offsets in the gathers
   convop::WgradX<BUF> a{x, g, M, K, convop::div_magic(g.Ho * g.Wo), convop::div_magic(g.Wo)};
-  const bool small = g.Co <= 64;
-  const int nb = cdiv(M, 128) * cdiv(g.Co, small ? 64 : 128);
+  const int nb = cdiv(M, 128) * cdiv(g.Co, f.cols);
   int split = cdiv(1024, nb); if (split > ktiles) split = ktiles;
-  if (small) return igemm::launch<128, 64>(a, b, e, M, g.Co, K, split, s, slab);
+  if (f.cols == 64) return igemm::launch<128, 64>(a, b, e, M, g.Co, K, split, s, slab);
   return igemm::launch<128, 128>(a, b, e, M, g.Co, K, split, s, slab);
-}
-// weight gradient by taps (igemm.h TapSched): only the grid positions at which a tap is inside the image are contracted
-static inline bool conv_wgrad_tap_ok(const Geom& g, float* slab) {
-  if (!cls_common(g, slab) || g.C % 128 || g.Co % 4 || g.Co < 128) return false;
-  return 9L * (g.C / 128) * cdiv(g.Co, 128) <= cls_tile_cap() &&
-         fits_buf((long)g.N * g.H * g.W * g.C) && fits_buf((long)g.N * g.Ho * g.Wo * g.Co);
 }
 static inline igemm::TapSched tap_sched(const Geom& g, int tiles_per_tap) {
   const int NP = cdiv(g.N, 128) * 128;
@@ -784,11 +844,6 @@ static int conv_wgrad_tap(const float* x, const float* dy, float* pk, const Geom
   e.Mrows = M; e.sched = sc;
   return igemm::launch_cls(a, b, e, M, g.Co, s, slab);
 }
-// the 64 -> 64 channel 3x3 convolutions: output-stationary kernel + ordered reduction of the per-CU partials (conv64.h)
-static inline bool conv64_wgrad_ok(const Geom& g, float* slab) {
-  return conv64_ok(g) && slab && g.W <= conv64::WG_MAXW && (size_t)conv64_cus() * conv64::WG_PART <= igemm::SLAB_FLOATS &&
-         (long)g.N * g.H * g.W * 256 < (1L << 31);
-}
 static int conv64_wgrad(const float* x, const float* dy, float* pk, const Geom& g, hipStream_t s, float* slab) {
   const int NR = g.N * g.H;
   const int grid = NR < conv64_cus() ? NR : conv64_cus();
@@ -799,47 +854,34 @@ static int conv64_wgrad(const float* x, const float* dy, float* pk, const Geom& 
   return AVVAD_OK;
 }
 static int conv_wgrad(const float* x, const float* dy, float* pk, const Geom& g, hipStream_t s, float* slab) {
-  if (conv64_wgrad_ok(g, slab)) return conv64_wgrad(x, dy, pk, g, s, slab);
-  if (conv_wgrad_tap_ok(g, slab)) return conv_wgrad_tap(x, dy, pk, g, s, slab);
-  const bool buf = g.C > 1 && fits_buf((long)g.N * g.H * g.W * g.C) && fits_buf((long)g.N * g.Ho * g.Wo * g.Co) && !avvad_tune().no_buf;
-  return buf ? conv_wgrad_t<true>(x, dy, pk, g, s, slab) : conv_wgrad_t<false>(x, dy, pk, g, s, slab);
+  const ConvForm f = wgrad_form(g, false, slab);
+  switch (f.form) {
+    case STEM: {
+      const int LDW = (g.W + 6) | 1;
+      const int nb = g.N < 256 ? g.N : 256;                       // one workgroup per CU, whole frames each
+      hipLaunchKernelGGL(stem_wgrad_mfma, dim3(nb), dim3(256), (size_t)(g.H + 6) * LDW * sizeof(float), s, x, dy, slab, g.N, g.H, g.W,
+                         g.Ho, g.Wo, LDW);
+      hipLaunchKernelGGL(stem_wgrad_reduce, dim3(49 * 64 / 32), dim3(256), 0, s, slab, nb, pk);
+      AVVAD_LAUNCH_CHECK();
+      return AVVAD_OK;
+    }
+    case CONV64: return conv64_wgrad(x, dy, pk, g, s, slab);
+    case TAP: return conv_wgrad_tap(x, dy, pk, g, s, slab);
+    default: return f.buf ? conv_wgrad_t<true>(x, dy, pk, g, f, s, slab) : conv_wgrad_t<false>(x, dy, pk, g, f, s, slab);
+  }
 }
 
-// ------------------------------------------------------------------ the bf16 data path (option "bf16" = 1; bgemm.h)
-// Operands are bf16 in HBM: activations / output gradients NHWC bf16 (written by the BatchNorm elementwise kernels), weights
-// in the K-contiguous bf16 packs of pack_all.  Outputs are fp32 (raw convolution sums feed BatchNorm statistics; gradients
-// accumulate).  Channel counts must be multiples of 64 (every trunk convolution behind the stem), operands < 2 GiB.
-static inline bool native_bf16() { return avvad_tune().bf16 == 1; }
-static inline bool bf16_conv_ok(const Geom& g) {
-  return g.C % 64 == 0 && g.Co % 64 == 0 && taps_fit(g) && fits_buf((long)g.N * g.H * g.W * g.C / 2) &&
-         fits_buf((long)g.N * g.Ho * g.Wo * g.Co / 2) && fits_buf((long)g.KS * g.KS * g.C * g.Co / 2);
-}
-// position classes on the bf16 engine (the zero padding skipped: igemm.h); 64-channel chunks
-// (the bf16 kernels are bound by operand traffic, not by the matrix pipe: skipped products buy time only where they are 40 %
-//  of the tile -- the 3x3 grid -- and on larger grids the all-tiles-in-the-pool fix-up costs more than they save: measured
-//  per forward launch, 9x9 grid 55 -> 74 us, 5x5 66 -> 73 us, 3x3 78 -> 65 us)
-static inline bool cls16_common(const Geom& g, float* slab) {
-  return !avvad_tune().no_cls && slab && g.KS == 3 && g.pad == 1 && g.N >= 128 && g.Ho >= 2 && g.Wo >= 2 && g.Ho * g.Wo <= 9 &&
-         avvad_tune().no_streamk == 0;
-}
-static inline bool conv_fwd16_cls_ok(const Geom& g, float* slab) {
-  if (!cls16_common(g, slab) || g.Co < 128) return false;
-  return (long)g.Ho * g.Wo * cdiv(g.N, 128) * cdiv(g.Co, 128) <= cls_tile_cap();
-}
-static inline bool conv_dgrad16_cls_ok(const Geom& g, float* slab) {
-  if (!cls16_common(g, slab) || g.stride != 1 || g.C < 128) return false;
-  return (long)g.H * g.W * cdiv(g.N, 128) * cdiv(g.C, 128) <= cls_tile_cap();
-}
+// ---- the bf16 data path's launchers
 static int conv_fwd16(const float* x16, const float* wf16, float* y, const Geom& g, hipStream_t s, float* slab, double* stat) {
   if (!bf16_conv_ok(g)) return AVVAD_EINVAL;
-  if (conv64_16_ok(g)) return conv64_16_launch(false, x16, wf16, y, g, 0, s, stat);
-  if (conv_fwd16_cls_ok(g, slab)) {
+  const ConvForm f = fwd_form(g, true, slab);
+  if (f.form == CONV64) return conv64_launch(true, false, x16, wf16, y, g, 0, s, stat);
+  Geom gp = g;
+  gp.C = g.C / 2;                                            // the gathers address bf16 PAIRS
+  if (f.form == CLS) {
     const int MB = cdiv(g.N, 128), P = g.Ho * g.Wo;
-    const int lsh = ((g.Ho - 1) * g.stride - g.pad + 2 > g.H - 1) ? 1 : 0, lsw = ((g.Wo - 1) * g.stride - g.pad + 2 > g.W - 1) ? 1 : 0;
-    const igemm::ClassSched sc{g.Ho, g.Wo, cdiv(g.Co, 128), g.C / 64, MB, 3, 1, lsh, 1, lsw};
+    const igemm::ClassSched sc = fwd_sched(g, 64);
     const igemm::ClassRow cr{P, convop::div_magic(P)};
-    Geom gp = g;
-    gp.C = g.C / 2;
     convop::Im2colFwdCls a{x16, gp, g.N, cr, sc};
     bgemm::RowPairsCls b{wf16, 9 * g.C / 2, g.Co, 9, 3, 0, cr, sc};
     igemm::EpiCls e{y, (long)P * g.Co, nullptr, 0};
@@ -847,28 +889,23 @@ static int conv_fwd16(const float* x16, const float* wf16, float* y, const Geom&
     return bgemm::launch_cls<false>(a, b, e, MB * P * 128, g.Co, s, slab);
   }
   const int M = g.N * g.Ho * g.Wo, T = g.KS * g.KS, Kp = T * g.C / 2;
-  Geom gp = g;
-  gp.C = g.C / 2;                                            // the gather addresses bf16 PAIRS
   convop::Im2colFwd<true> a{x16, gp, M, convop::tap_div(T, g.KS)};
   bgemm::RowPairs b{wf16, Kp, g.Co, Kp};
   igemm::EpiStore e{y, g.Co, nullptr, 0};
   e.stat = stat;
-  if (g.Co <= 64) return bgemm::launch<128, 64, false>(a, b, e, M, g.Co, Kp, s, slab);
+  if (f.cols == 64) return bgemm::launch<128, 64, false>(a, b, e, M, g.Co, Kp, s, slab);
   return bgemm::launch<128, 128, false>(a, b, e, M, g.Co, Kp, s, slab);
 }
 static int conv_dgrad16(const float* dy16, const float* wd16, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
   if (!bf16_conv_ok(g)) return AVVAD_EINVAL;
-  if (conv64_16_ok(g)) return conv64_16_launch(true, dy16, wd16, dx, g, accumulate, s, nullptr);
+  const ConvForm f = dgrad_form(g, true, slab);
+  if (f.form == CONV64) return conv64_launch(true, true, dy16, wd16, dx, g, accumulate, s, nullptr);
   const int M = g.N * g.H * g.W, T = g.KS * g.KS, Kp = T * g.Co / 2;
   Geom gp = g;
   gp.Co = g.Co / 2;
-  // stride 2, 3x3: the four parity classes as position classes of ONE product (igemm::ClassSched::s2) -- on this engine the four
-  // separate launches are ~40 us each whatever their size, so grouping pays on every grid (unlike the stride-1 classes)
-  if (g.stride == 2 && g.KS == 3 && g.pad == 1 && !avvad_tune().no_cls && !avvad_tune().no_s2_cls && avvad_tune().no_streamk == 0 && slab &&
-      g.N >= 128 && g.C >= 128 && (long)g.H * g.W * cdiv(g.N, 128) * cdiv(g.C, 128) <= cls_tile_cap()) {
+  if (f.form == CLS) {
     const int MB = cdiv(g.N, 128), P = g.H * g.W;
-    igemm::ClassSched sc{g.H, g.W, cdiv(g.C, 128), g.Co / 64, MB, 3, 1, 1, 1, 1};
-    sc.s2 = 1; sc.Hq = g.Ho; sc.Wq = g.Wo;
+    const igemm::ClassSched sc = dgrad_sched(g, 64);
     const igemm::ClassRow cr{P, convop::div_magic(P)};
     convop::Im2colDgradCls a{dy16, gp, g.N, cr, sc};
     bgemm::RowPairsCls b{wd16, Kp, g.C, 9, 3, 1, cr, sc};
@@ -876,56 +913,27 @@ static int conv_dgrad16(const float* dy16, const float* wd16, float* dx, const G
     e.W = g.C; e.rows = g.N; e.cr = cr; e.sched = sc;
     return bgemm::launch_cls<false>(a, b, e, MB * P * 128, g.C, s, slab);
   }
-  if (g.stride == 2) {
-    if (!accumulate) hipLaunchKernelGGL(zero_f32, dim3(ew_grid((long)M * g.C)), dim3(256), 0, s, dx, (long)M * g.C);
-    for (int ph = 0; ph < 2; ++ph)
-      for (int pw = 0; pw < 2; ++pw) {
-        convop::S2Class c;
-        c.ph = ph; c.pw = pw;
-        c.Hc = (g.H - ph + 1) / 2; c.Wc = (g.W - pw + 1) / 2;
-        c.kh0 = (ph + g.pad) & 1; c.kw0 = (pw + g.pad) & 1;
-        c.nkh = c.kh0 < g.KS ? (g.KS - c.kh0 + 1) / 2 : 0;
-        c.nkw = c.kw0 < g.KS ? (g.KS - c.kw0 + 1) / 2 : 0;
-        c.oh = (ph + g.pad - c.kh0) / 2; c.ow = (pw + g.pad - c.kw0) / 2;
-        const int Mc = g.N * c.Hc * c.Wc, ntap = c.nkh * c.nkw;
-        if (Mc <= 0 || ntap <= 0) continue;
-        if (ntap > 4) return AVVAD_EINVAL;
-        c.mg_ntap = convop::div_magic(ntap); c.mg_nkw = convop::div_magic(c.nkw);
-        convop::Im2colDgradS2<true> a{dy16, gp, c, Mc};
-        bgemm::RowPairsSeg b{wd16, Kp, g.C, ntap * g.Co / 2, T, ntap, {0, 0, 0, 0}, convop::div_magic(ntap)};
-        for (int ia = 0; ia < c.nkh; ++ia)
-          for (int ib = 0; ib < c.nkw; ++ib) b.tap[ia * c.nkw + ib] = (c.kh0 + 2 * ia) * g.KS + (c.kw0 + 2 * ib);
-        convop::EpiS2 e{dx, g.C, nullptr, 1, 1, g.H, g.W, c.Hc, c.Wc, ph, pw, convop::div_magic(c.Hc * c.Wc), convop::div_magic(c.Wc)};
-        if ((unsigned long)(Mc + 128) * (unsigned long)(c.Hc * c.Wc) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
-        int rc;
-        if (g.C <= 64) rc = bgemm::launch<128, 64, false>(a, b, e, Mc, g.C, ntap * g.Co / 2, s, slab);
-        else rc = bgemm::launch<128, 128, false>(a, b, e, Mc, g.C, ntap * g.Co / 2, s, slab);
-        if (rc) return rc;
-      }
-    return AVVAD_OK;
-  }
-  if (conv_dgrad16_cls_ok(g, slab)) {
-    const int MB = cdiv(g.N, 128), P = g.H * g.W;
-    const igemm::ClassSched sc{g.H, g.W, cdiv(g.C, 128), g.Co / 64, MB, 3, 1, 1, 1, 1};
-    const igemm::ClassRow cr{P, convop::div_magic(P)};
-    convop::Im2colDgradCls a{dy16, gp, g.N, cr, sc};
-    bgemm::RowPairsCls b{wd16, Kp, g.C, 9, 3, 1, cr, sc};
-    igemm::EpiCls e{dx, (long)P * g.C, nullptr, accumulate ? 1 : 0};
-    e.W = g.C; e.rows = g.N; e.cr = cr; e.sched = sc;
-    return bgemm::launch_cls<false>(a, b, e, MB * P * 128, g.C, s, slab);
-  }
+  if (f.form == PARITY)
+    return dgrad_parity(dx, g, accumulate, s, [&](const convop::S2Class& c, int Mc, int ntap, const convop::EpiS2& e) {
+      convop::Im2colDgradS2<true> a{dy16, gp, c, Mc};
+      bgemm::RowPairsSeg b{wd16, Kp, g.C, ntap * g.Co / 2, T, ntap, {0, 0, 0, 0}, convop::div_magic(ntap)};
+      for (int ia = 0; ia < c.nkh; ++ia)
+        for (int ib = 0; ib < c.nkw; ++ib) b.tap[ia * c.nkw + ib] = (c.kh0 + 2 * ia) * g.KS + (c.kw0 + 2 * ib);
+      return f.cols == 64 ? bgemm::launch<128, 64, false>(a, b, e, Mc, g.C, ntap * g.Co / 2, s, slab)
+                          : bgemm::launch<128, 128, false>(a, b, e, Mc, g.C, ntap * g.Co / 2, s, slab);
+    });
   convop::Im2colDgrad<true> a{dy16, gp, M, convop::tap_div(T, g.KS)};
   bgemm::RowPairs b{wd16, Kp, g.C, Kp};
   igemm::EpiStore e{dx, g.C, nullptr, accumulate ? 1 : 0};
-  if (g.C <= 64) return bgemm::launch<128, 64, false>(a, b, e, M, g.C, Kp, s, slab);
+  if (f.cols == 64) return bgemm::launch<128, 64, false>(a, b, e, M, g.C, Kp, s, slab);
   return bgemm::launch<128, 128, false>(a, b, e, M, g.C, Kp, s, slab);
 }
 static int conv_wgrad16(const float* x16, const float* dy16, float* pk, const Geom& g, hipStream_t s, float* slab) {
   if (!bf16_conv_ok(g)) return AVVAD_EINVAL;
   const int T = g.KS * g.KS, M = T * g.C, K = g.N * g.Ho * g.Wo;
   if ((unsigned long)(K + bgemm::BKU) * (unsigned long)(g.Ho * g.Wo) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
-  if (cls16_common(g, slab) && g.C % 128 == 0 && g.Co >= 128 &&
-      9L * (g.C / 128) * cdiv(g.Co, 128) <= cls_tile_cap()) {
+  const ConvForm f = wgrad_form(g, true, slab);
+  if (f.form == TAP) {
     const igemm::TapSched sc = tap_sched(g, (g.C / 128) * cdiv(g.Co, 128));
     Geom gq = g;
     gq.C = g.C / 2; gq.Co = g.Co / 2;                        // operand elements are bf16 pairs
@@ -940,7 +948,7 @@ static int conv_wgrad16(const float* x16, const float* dy16, float* pk, const Ge
   convop::WgradX<true> a{x16, gp, M / 2, K, convop::div_magic(g.Ho * g.Wo), convop::div_magic(g.Wo)};
   igemm::ColPlain<4, true> b{dy16, g.Co / 2, g.Co / 2, K, 0};
   convop::EpiWgrad e{pk, g.Co, nullptr, 0, 1, g.C, T, convop::div_magic(T), 6};
-  if (g.Co <= 64) return bgemm::launch<128, 64, true>(a, b, e, M, g.Co, K, s, slab);
+  if (f.cols == 64) return bgemm::launch<128, 64, true>(a, b, e, M, g.Co, K, s, slab);
   return bgemm::launch<128, 128, true>(a, b, e, M, g.Co, K, s, slab);
 }
 
@@ -958,23 +966,24 @@ static StatCtx stat_ctx(Plan* p, float* ws, long M, int C) {
   return c;
 }
 
-// batch statistics of conv output i -> scale/shift/mean/invstd slots i (+ running stats)
+// partial-sum chunks of conv i's batch statistics that its forward leaves in the partial-sum buffer (the form's: one per M tile of
+// its GEMM, per conv64 workgroup, per stem frame), 0: the separate column-reduction pass forms them
+static int fused_chunks(Plan* p, int i, const avvad_trunk_desc* d) {
+  if (!d->training || avvad_tune().no_fused_stats) return 0;
+  const int n = fwd_form(p->geom[i], i > 0 && native_bf16(), true).chunks;
+  return (long)n * p->conv[i].cout <= (long)STAT_CHUNKS * MAXC ? n : 0;      // the partial-sum buffer's size
+}
 // where conv i's forward can leave its fused statistics (null: take the separate column-reduction pass)
 static double* fused_stat(Plan* p, float* ws, int i, const avvad_trunk_desc* d) {
-  const int rows = fwd_tile_rows(p->geom[i]);
-  if (i == 0 && d->training && !avvad_tune().no_fused_stats && stem_kernel_ok(p->geom[0]) && (long)p->N * 64 <= (long)STAT_CHUNKS * MAXC)
-    return reinterpret_cast<double*>(ws + p->part);      // one chunk per frame, written by stem_fwd_mfma
-  if (!d->training || rows == 0 || avvad_tune().no_fused_stats) return nullptr;
-  const long chunks = fwd_stat_chunks(p->geom[i], ws + p->slab);
-  if (chunks * p->conv[i].cout > (long)STAT_CHUNKS * MAXC) return nullptr;      // the partial-sum buffer's size
-  return reinterpret_cast<double*>(ws + p->part);
+  return fused_chunks(p, i, d) ? reinterpret_cast<double*>(ws + p->part) : nullptr;
 }
+// batch statistics of conv output i -> scale/shift/mean/invstd slots i (+ running stats)
 static int bn_prepare(Plan* p, float* ws, int i, const float* craw, long M, const avvad_trunk_params* prm,
                       const avvad_trunk_desc* d, hipStream_t s) {
   const int C = p->conv[i].cout;
   StatCtx sc = stat_ctx(p, ws, M, C);
-  if (fused_stat(p, ws, i, d)) {
-    sc.nchunk = i == 0 ? p->N : fwd_stat_chunks(p->geom[i], ws + p->slab);   // one chunk per M tile of the conv's GEMM (stem: per frame)
+  if (const int n = fused_chunks(p, i, d)) {
+    sc.nchunk = n;
   } else if (d->training) {
     hipLaunchKernelGGL(col_reduce<0>, dim3(sc.nchunk), dim3(256), 0, s, craw, (const float*)nullptr, (const float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, M, C, sc.rows_per_chunk, sc.part);
@@ -1014,12 +1023,9 @@ static int bn_backward(Plan* p, float* ws, int i, const float* xraw, const float
   hipLaunchKernelGGL(bn_bwd_finalize, dim3(cdiv(C, FIN_CH)), dim3(256), 0, s, sc.part, sc.nchunk, M, C, prm->bn_w[i], invstd,
                      d->training, g->bn_w[i], g->bn_b[i], ws + p->coef);
   const long nq = M * C / 4;
-  if (out16)
-    hipLaunchKernelGGL(bn_bwd_apply<true>, dim3(ew_grid(nq)), dim3(256), 0, s, xraw, dy, qmask ? (const float*)nullptr : ymask, mean, invstd,
-                       ws + p->coef, dx, gout, nq, C, msc, msh, qmask);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply<false>, dim3(ew_grid(nq)), dim3(256), 0, s, xraw, dy, qmask ? (const float*)nullptr : ymask, mean, invstd,
-                       ws + p->coef, dx, gout, nq, C, msc, msh, qmask);
+  auto apply = out16 ? bn_bwd_apply<true> : bn_bwd_apply<false>;
+  hipLaunchKernelGGL(apply, dim3(ew_grid(nq)), dim3(256), 0, s, xraw, dy, qmask ? (const float*)nullptr : ymask, mean, invstd,
+                     ws + p->coef, dx, gout, nq, C, msc, msh, qmask);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
@@ -1194,18 +1200,17 @@ extern "C" int avvad_trunk_fwd(const float* frames, const avvad_trunk_params* pr
   if ((rc = bn_prepare(&p, ws, 0, ws + p.c0, M0, prm, d, s))) return rc;
   {
     unsigned* am = d->save_for_backward ? reinterpret_cast<unsigned*>(ws + p.am) : (unsigned*)nullptr;
-    if (b16)
-      hipLaunchKernelGGL(stem_bn_relu_pool<true>, dim3(ew_grid(N * p.h[2] * p.w[2] * 16)), dim3(256), 0, s, ws + p.c0, ws + p.bn_scale,
-                         ws + p.bn_shift, ws + p.p0, am, d->N, p.h[1], p.w[1], p.h[2], p.w[2]);
-    else
-      hipLaunchKernelGGL(stem_bn_relu_pool<false>, dim3(ew_grid(N * p.h[2] * p.w[2] * 16)), dim3(256), 0, s, ws + p.c0, ws + p.bn_scale,
-                         ws + p.bn_shift, ws + p.p0, am, d->N, p.h[1], p.w[1], p.h[2], p.w[2]);
+    auto pool = b16 ? stem_bn_relu_pool<true> : stem_bn_relu_pool<false>;
+    hipLaunchKernelGGL(pool, dim3(ew_grid(N * p.h[2] * p.w[2] * 16)), dim3(256), 0, s, ws + p.c0, ws + p.bn_scale, ws + p.bn_shift,
+                       ws + p.p0, am, d->N, p.h[1], p.w[1], p.h[2], p.w[2]);
   }
   auto cfwd = [&](const float* xin, int i, float* yout) -> int {
     if (b16) return conv_fwd16(xin, ws + p.wf16[i], yout, p.geom[i], s, ws + p.slab, fused_stat(&p, ws, i, d));
     return conv_fwd(xin, ws + p.wf[i], yout, p.geom[i], s, ws + p.slab, fused_stat(&p, ws, i, d));
   };
-  // residual stages
+  // residual stages (bn_act writes bf16 on the bf16 data path; the residual it adds is bf16 there only when it is the block's input)
+  auto act = b16 ? bn_act<true, false> : bn_act<false, false>;
+  auto act_id = b16 ? bn_act<true, true> : bn_act<false, false>;
   const float* x = ws + p.p0;
   int ci = 1;
   const int widths[4] = {64, 128, 256, 512};
@@ -1220,41 +1225,25 @@ extern "C" int avvad_trunk_fwd(const float* frames, const avvad_trunk_params* pr
       unsigned char* qmo = d->save_for_backward ? reinterpret_cast<unsigned char*>(ws + p.qm[st * 2 + b]) : (unsigned char*)nullptr;
       if ((rc = cfwd(x, i1, ws + o[0]))) return rc;
       if ((rc = bn_prepare(&p, ws, i1, ws + o[0], M, prm, d, s))) return rc;
-      if (b16)
-        hipLaunchKernelGGL((bn_act<true, false>), dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[0], ws + p.bn_scale + i1 * MAXC,
-                           ws + p.bn_shift + i1 * MAXC, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                           ws + o[1], nq, C, 1, (unsigned char*)nullptr);
-      else
-        hipLaunchKernelGGL((bn_act<false, false>), dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[0], ws + p.bn_scale + i1 * MAXC,
-                           ws + p.bn_shift + i1 * MAXC, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                           ws + o[1], nq, C, 1, (unsigned char*)nullptr);
+      hipLaunchKernelGGL(act, dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[0], ws + p.bn_scale + i1 * MAXC, ws + p.bn_shift + i1 * MAXC,
+                         (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ws + o[1], nq, C, 1, (unsigned char*)nullptr);
       if ((rc = cfwd(ws + o[1], i2, ws + o[2]))) return rc;
       if ((rc = bn_prepare(&p, ws, i2, ws + o[2], M, prm, d, s))) return rc;
       if (ds) {
         if ((rc = cfwd(x, id, ws + o[3]))) return rc;
         if ((rc = bn_prepare(&p, ws, id, ws + o[3], M, prm, d, s))) return rc;
         // (the identity input is the downsample convolution's RAW fp32 output in either data path)
-        if (b16)
-          hipLaunchKernelGGL((bn_act<true, false>), dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC,
-                             ws + p.bn_shift + i2 * MAXC, ws + o[3], ws + p.bn_scale + id * MAXC, ws + p.bn_shift + id * MAXC,
-                             ws + o[4], nq, C, 1, qmo);
-        else
-          hipLaunchKernelGGL((bn_act<false, false>), dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC,
-                             ws + p.bn_shift + i2 * MAXC, ws + o[3], ws + p.bn_scale + id * MAXC, ws + p.bn_shift + id * MAXC,
-                             ws + o[4], nq, C, 1, qmo);
+        hipLaunchKernelGGL(act, dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC, ws + p.bn_shift + i2 * MAXC,
+                           ws + o[3], ws + p.bn_scale + id * MAXC, ws + p.bn_shift + id * MAXC, ws + o[4], nq, C, 1, qmo);
       } else {
-        if (b16)     // the identity input is the block's bf16 input
-          hipLaunchKernelGGL((bn_act<true, true>), dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC,
-                             ws + p.bn_shift + i2 * MAXC, x, (const float*)nullptr, (const float*)nullptr, ws + o[4], nq, C, 1, qmo);
-        else
-          hipLaunchKernelGGL((bn_act<false, false>), dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC,
-                             ws + p.bn_shift + i2 * MAXC, x, (const float*)nullptr, (const float*)nullptr, ws + o[4], nq, C, 1, qmo);
+        hipLaunchKernelGGL(act_id, dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC, ws + p.bn_shift + i2 * MAXC,
+                           x, (const float*)nullptr, (const float*)nullptr, ws + o[4], nq, C, 1, qmo);
       }
       x = ws + o[4];
       ci += ds ? 3 : 2;
     }
-  if (b16) hipLaunchKernelGGL(avgpool_fwd<true>, dim3(ew_grid(N * 512)), dim3(256), 0, s, x, feat, d->N, p.h[5] * p.w[5], 512);
-  else hipLaunchKernelGGL(avgpool_fwd<false>, dim3(ew_grid(N * 512)), dim3(256), 0, s, x, feat, d->N, p.h[5] * p.w[5], 512);
+  auto avg = b16 ? avgpool_fwd<true> : avgpool_fwd<false>;
+  hipLaunchKernelGGL(avg, dim3(ew_grid(N * 512)), dim3(256), 0, s, x, feat, d->N, p.h[5] * p.w[5], 512);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
@@ -1272,7 +1261,6 @@ extern "C" int avvad_trunk_bwd(const float* frames, const avvad_trunk_params* pr
   float* ws = (float*)wsv;
   int rc;
   const long N = d->N;
-  const int widths[4] = {64, 128, 256, 512};
   float* G0 = ws + p.G[0];
   float* G1 = ws + p.G[1];
   float* G2 = ws + p.G[2];
@@ -1300,7 +1288,6 @@ extern "C" int avvad_trunk_bwd(const float* frames, const avvad_trunk_params* pr
       const size_t* o = p.blk[st * 2 + b];
       const float* x = (st == 0 && b == 0) ? ws + p.p0 : (b == 1 ? ws + p.blk[st * 2][4] : ws + p.blk[st * 2 - 1][4]);
       const long M = N * p.h[st + 2] * p.w[st + 2];
-      (void)widths;
       const unsigned char* qmb = reinterpret_cast<const unsigned char*>(ws + p.qm[st * 2 + b]);
       // G0 = d(block output, post-ReLU).  main branch: BN2 backward (mask out>0) -> d c2 in G1
       if (ds) {
