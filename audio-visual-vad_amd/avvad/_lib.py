@@ -70,6 +70,11 @@ class StftDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("L", C.c_long), ("n_fft", C.c_int), ("hop", C.c_int), ("T", C.c_int), ("eps", C.c_float)]
 
 
+class TargetDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("L", C.c_long), ("n_fft", C.c_int), ("hop", C.c_int), ("T", C.c_int), ("center", C.c_int),
+                ("eps", C.c_float), ("vad_coef", C.c_double), ("ibm_coef", C.c_double)]
+
+
 class LstmDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("T", C.c_int), ("In", C.c_int), ("H", C.c_int), ("lengths", FP),
                 ("save_for_backward", C.c_int)]
@@ -115,6 +120,10 @@ SIGNATURES = {
     "avvad_stft_workspace": (C.c_size_t, [C.POINTER(StftDesc)]),
     "avvad_stft": (C.c_int, [FP, FP, C.POINTER(StftDesc), C.c_int, FP, C.c_size_t, FP]),
     "avvad_stft_features": (C.c_int, [FP, FP, FP, FP, C.POINTER(StftDesc), C.c_float, FP, C.c_size_t, FP]),
+    "avvad_target_workspace": (C.c_size_t, [C.POINTER(TargetDesc)]),
+    "avvad_target_vad": (C.c_int, [FP, FP, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
+    "avvad_target_ibm": (C.c_int, [FP, FP, FP, C.c_int, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
+    "avvad_target_ibm_from_spectrum": (C.c_int, [FP, C.c_long, C.c_long, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
     "avvad_peak_normalize": (C.c_int, [FP, FP, C.c_int, C.c_long, FP]),
     "avvad_standardize": (C.c_int, [FP, FP, FP, FP, C.c_size_t, C.c_int, C.c_int, C.c_float, FP]),
     "avvad_bce_2classes": (C.c_int, [FP, FP, FP, FP, FP, FP, C.c_long, C.c_int, C.c_float, FP]),

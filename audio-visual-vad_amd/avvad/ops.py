@@ -653,3 +653,109 @@ def standardize(x, mean, std, eps=1e-8):
     L.check(L.lib().avvad_standardize(L.ptr(x), L.ptr(mean), L.ptr(std), L.ptr(out), x.numel() // F, F, nstat, float(eps),
                                       _stream()), "avvad_standardize")
     return out
+
+
+# --------------------------------------------------------------------------- training labels from clean speech (no gradient)
+_CENTER = {"reflect": 1, "constant": 2}
+
+
+def target_frames(L, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, center=False, pad_at_end=True):
+    """(samples after the end pad, frame count) of ``clean_speech_VAD`` (packages/processing/target.py:28-46): one hop of
+    zeros when ``ceil(L/fs/wlen_sec/hop_percent) != int(...)``, evaluated exactly as the reference writes it, then
+    ``n_fft//2`` per side when ``center``, then ``librosa.util.frame``'s ``1 + (len - n_fft)//hop`` frames."""
+    import math
+    nfft = int(wlen_sec * fs)
+    hop = int(hop_percent * nfft)
+    n = int(L)
+    if pad_at_end:
+        v = n / fs / wlen_sec / hop_percent
+        if math.ceil(v) != int(v):
+            n += hop
+    total = n + (2 * (nfft // 2) if center else 0)
+    if total < nfft:
+        raise L.AvvadError("utterance of %d samples is shorter than one %d-sample frame" % (L, nfft))
+    return n, 1 + (total - nfft) // hop
+
+
+def _target_call(wave, sample_lengths, fs, wlen_sec, hop_percent, center, pad_mode, pad_at_end, vad_threshold, eps, ibm_threshold):
+    w = _dev(wave, "wave")
+    w2 = w.view(1, -1) if w.dim() == 1 else w
+    B, Lp = w2.shape
+    lens = [int(v) for v in (sample_lengths.tolist() if isinstance(sample_lengths, torch.Tensor) else sample_lengths)]
+    if len(lens) != B or any(n < 0 or n > Lp for n in lens):
+        raise L.AvvadError("sample_lengths must hold %d lengths within 0..%d" % (B, Lp))
+    if center and pad_mode not in _CENTER:
+        raise L.AvvadError("pad_mode %r: the GPU labels implement 'reflect' and 'constant'" % (pad_mode,))
+    if wlen_sec * fs != int(wlen_sec * fs):
+        raise ValueError("wlen_sample of STFT is not an integer.")
+    nfft = int(wlen_sec * fs)
+    hop = int(hop_percent * nfft)
+    pads, frames = zip(*[target_frames(n, fs, wlen_sec, hop_percent, center, pad_at_end) for n in lens])
+    if center and pad_mode == "reflect" and min(pads) <= nfft // 2:
+        raise L.AvvadError("reflect padding of %d samples needs utterances longer than that" % (nfft // 2))
+    T = max(frames)
+    d = L.TargetDesc(B, Lp, nfft, hop, T, _CENTER[pad_mode] if center else 0, float(eps), float(np_power10(vad_threshold)),
+                     float(np_power10(-ibm_threshold / 20.0)))
+    ws = _ws(L.lib().avvad_target_workspace(C.byref(d)), w.device)
+    dev_counts = torch.tensor([list(pads), list(frames)], dtype=torch.int32).to(w.device)
+    return w2, d, ws, dev_counts, torch.LongTensor(frames)
+
+
+def np_power10(x):
+    """``np.power(10, x)`` of the reference as a float64 (a Python float: the same IEEE double)."""
+    import numpy as np
+    return float(np.power(10, np.float64(x)))
+
+
+def speech_targets(clean, sample_lengths, labels="vad_labels", robust=False, fs=16e3, wlen_sec=64e-3, hop_percent=0.25,
+                   center=False, pad_mode="reflect", pad_at_end=True, vad_threshold=1.70, eps=1e-8, ibm_threshold=50):
+    """Training labels of a ragged batch of clean utterances, computed on the GPU (packages/processing/target.py):
+    clean (B, L) zero-padded rows (or (L,)), ``sample_lengths`` the B real lengths.  ``labels='vad_labels'``: the
+    framed-energy VAD, target (B, T, 1); ``'ibm_labels'``: the ideal binary mask, target (B, T, n_fft/2+1) (``center``
+    False only), times the VAD when ``robust``.  Defaults are the training pipeline's (create_audio_train_files.py:44-60).
+    Returns (frame_lengths LongTensor (B,) on the host, target on the GPU); frames t >= T_b are zero -- the layout of
+    the collates, ready for ``forward_batch``.  The waveform is taken as given (callers peak-normalise, as the reference
+    does before calling target.py)."""
+    if labels not in ("vad_labels", "ibm_labels"):
+        raise L.AvvadError("labels must be 'vad_labels' or 'ibm_labels', got %r" % (labels,))
+    w2, d, ws, cnt, frames = _target_call(clean, sample_lengths, fs, wlen_sec, hop_percent, center, pad_mode, pad_at_end,
+                                          vad_threshold, eps, ibm_threshold)
+    if labels == "vad_labels":
+        out = torch.empty(d.B, d.T, 1, dtype=torch.float32, device=w2.device)
+        L.check(L.lib().avvad_target_vad(L.ptr(w2), L.ptr(cnt[0]), L.ptr(cnt[1]), L.ptr(out), C.byref(d), L.ptr(ws), ws.numel() * 4,
+                                         _stream()), "avvad_target_vad")
+        return frames, out
+    if center or d.n_fft % 32:
+        raise L.AvvadError("IBM labels from a waveform need center=False and an FFT length that is a multiple of 32")
+    out = torch.empty(d.B, d.T, d.n_fft // 2 + 1, dtype=torch.float32, device=w2.device)
+    L.check(L.lib().avvad_target_ibm(L.ptr(w2), L.ptr(cnt[0]), L.ptr(cnt[1]), int(bool(robust)), L.ptr(out), C.byref(d), L.ptr(ws),
+                                     ws.numel() * 4, _stream()), "avvad_target_ibm")
+    return frames, out
+
+
+def ibm_from_spectrum(spec, eps=1e-8, ibm_threshold=50, vad=None):
+    """``clean_speech_IBM`` of one given spectrum on the GPU: ``spec`` a complex (F, T) tensor or its real (F, T, 2) view
+    (the legacy layout ``stft_pytorch`` returns), read in place through its strides.  ``vad`` (T,) multiplies each frame
+    (``noise_robust_clean_speech_IBM``).  Returns the (F, T) mask."""
+    if isinstance(spec, torch.Tensor) and spec.is_complex():
+        if spec.dtype != torch.complex64:
+            raise L.AvvadError("spectrum must be complex64, got %s" % spec.dtype)
+        spec = torch.view_as_real(spec)
+    if not isinstance(spec, torch.Tensor) or not spec.is_cuda or spec.dtype != torch.float32:
+        raise L.AvvadError("spectrum must be a complex64 or float32 (F, T, 2) GPU tensor")
+    if spec.dim() != 3 or spec.shape[2] != 2 or spec.stride(2) != 1 or spec.shape[0] < 2 or spec.shape[1] < 1:
+        raise L.AvvadError("spectrum must be (F >= 2, T, 2) with (re, im) adjacent, got shape %s strides %s"
+                           % (tuple(spec.shape), spec.stride()))
+    if spec.stride(0) % 2 or spec.stride(1) % 2 or spec.stride(0) <= 0 or spec.stride(1) <= 0:
+        spec = spec.contiguous()
+    F, T = spec.shape[0], spec.shape[1]
+    d = L.TargetDesc(1, T, 2 * (F - 1), 1, T, 0, float(eps), 1.0, float(np_power10(-ibm_threshold / 20.0)))
+    ws = torch.empty(2, dtype=torch.float32, device=spec.device)
+    if vad is not None:
+        vad = _dev(vad, "vad").reshape(-1)
+        if vad.numel() != T:
+            raise L.AvvadError("vad holds %d frames, the spectrum %d" % (vad.numel(), T))
+    out = torch.empty(F, T, dtype=torch.float32, device=spec.device)
+    L.check(L.lib().avvad_target_ibm_from_spectrum(L.ptr(spec), spec.stride(1), spec.stride(0), L.ptr(vad), L.ptr(out), C.byref(d),
+                                                   L.ptr(ws), ws.numel() * 4, _stream()), "avvad_target_ibm_from_spectrum")
+    return out

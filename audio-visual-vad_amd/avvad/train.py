@@ -6,7 +6,8 @@ train-set statistics when given (``std_norm``: ``(x - mean.T) / (std + eps).T``,
 per-sequence masked BCE summed over the batch, backward, Adam, per-sequence accuracy/precision/recall/F1 -- with the
 reference's Python loops over the batch replaced by single fused calls, ``nn.DataParallel`` replaced by one process per
 GPU + bucketed RCCL all-reduce, and a synthetic data source for training (the reference's HDF5 readers are out of scope,
-SURVEY.md 2.1; h5py and torchaudio are not installed in this image).  The per-utterance evaluator of the audio network
+SURVEY.md 2.1; h5py and torchaudio are not installed in this image) or (noisy, clean) wav pairs whose labels are computed
+on the GPU from the clean files (``WavPairs``, ``wav_pair_step``).  The per-utterance evaluator of the audio network
 (``process_utt``, ``evaluate_audio_net.py:107-180``) runs the reference's whole chain on real waveforms: peak
 normalisation -> STFT -> power -> log -> crop to the label length -> standardise -> classifier -> sigmoid -> threshold."""
 import os
@@ -97,6 +98,84 @@ def pick_collate(kind, waveform):
     return U.collate_many2many_AV_waveform if waveform else U.collate_many2many_AV
 
 
+class WavPairs(torch.utils.data.Dataset):
+    """(noisy, clean) 16 kHz wav pairs laid out like NTCD-TIMIT -- what the reference's
+    ``NoisyWavWholeSequenceSpectrogramLabeledFrames`` reads (``data_handling.py:231-320``), with the labels computed from
+    the clean file in the training step (``wav_pair_step``) instead of read from HDF5.  ``pairs``: a list of
+    (noisy path, clean path) or a text file with one "noisy clean" pair per line.  Items: (noisy (L,), clean (L,), L),
+    both cropped to their common length."""
+
+    def __init__(self, pairs):
+        self.pairs = read_wav_pairs(pairs) if isinstance(pairs, str) else [tuple(p) for p in pairs]
+
+    def __len__(self):
+        return len(self.pairs)
+
+    def __getitem__(self, i):
+        noisy_path, clean_path = self.pairs[i]
+        noisy, fs_n = load_waveform(noisy_path)
+        clean, fs_c = load_waveform(clean_path)
+        if fs_n != 16000 or fs_c != 16000:
+            raise ValueError("%s / %s: expected 16 kHz audio, got %d / %d Hz" % (noisy_path, clean_path, fs_n, fs_c))
+        n = min(noisy.numel(), clean.numel())
+        return noisy[:n], clean[:n], n
+
+    @staticmethod
+    def collate(batch):
+        """-> (sample lengths LongTensor (B,), noisy (B, Lmax), clean (B, Lmax)), rows zero-padded."""
+        lens = [item[2] for item in batch]
+        noisy = torch.zeros(len(batch), max(lens))
+        clean = torch.zeros(len(batch), max(lens))
+        for i, (nz, cl, n) in enumerate(batch):
+            noisy[i, :n] = nz
+            clean[i, :n] = cl
+        return torch.LongTensor(lens), noisy, clean
+
+
+def read_wav_pairs(path):
+    """A text file with one "noisy clean" pair of paths per line (blank lines and # comments skipped)."""
+    pairs = []
+    with open(path) as f:
+        for line in f:
+            line = line.split("#", 1)[0].strip()
+            if line:
+                noisy, clean = line.split()
+                pairs.append((noisy, clean))
+    return pairs
+
+
+def labels_for_ydim(y_dim):
+    """The reference's scripts tie the label kind to the head's width (create_audio_train_files.py:87-90)."""
+    if y_dim == 1:
+        return "vad_labels"
+    if y_dim == 513:
+        return "ibm_labels"
+    raise ValueError("y_dim %d: wav-pair labels are VAD (y_dim 1) or IBM (y_dim 513)" % y_dim)
+
+
+def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS):
+    """A ``WavPairs.collate`` batch -> (frame lengths, features (B, T, 513), target (B, T, y_dim)) on the GPU: every file
+    peak-normalised on its own (``x / max|x|``, as the reference normalises each file it reads), log-power STFT features of
+    the noisy file (standardised when ``stats`` hold the train-set statistics), labels of the clean file with the training
+    pipeline's settings (64 ms, hop 0.25, ``center=False``, end pad; create_audio_train_files.py:44-60) and the same
+    frame counts."""
+    lens, noisy, clean = batch
+    noisy = ops.peak_normalize(noisy.to(device, non_blocking=True))
+    clean = ops.peak_normalize(clean.to(device, non_blocking=True))
+    frames, target = ops.speech_targets(clean, lens, labels, fs=fs, wlen_sec=wlen_sec, hop_percent=hop_percent, center=False,
+                                        pad_at_end=True, eps=eps)
+    nfft = int(wlen_sec * fs)
+    mean = std = None
+    if stats is not None:
+        mean, std = stats.get("audio_mean", device), stats.get("audio_std", device)
+    x = ops.stft(noisy, nfft, int(hop_percent * nfft), mode=0, eps=eps, pad_at_end=True, fs=fs, mean=mean, std=std,
+                 norm_eps=stats.eps if stats is not None else eps)
+    T = target.shape[1]
+    if x.shape[1] != T:                 # the longest row's frame count on both sides (same lengths, same rule)
+        raise RuntimeError("feature frames %d != label frames %d" % (x.shape[1], T))
+    return frames.to(device), x, target
+
+
 def forward_batch(model, kind, batch, device, waveform, stats=None):
     """H2D, ``std_norm`` standardisation (spectrogram features and video; raw waveforms are not standardised in the
     reference either), forward."""
@@ -112,13 +191,18 @@ def forward_batch(model, kind, batch, device, waveform, stats=None):
     return lengths, model(a, stats.video(data[1]) if stats else data[1], lengths), y
 
 
-def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log=None, log_interval=10, stats=None):
+def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log=None, log_interval=10, stats=None, prepare=None):
+    """``prepare`` (wav pairs): batch -> (lengths, features, target) on the GPU, the model's forward follows."""
     from packages.models.utils import batch_binary_cross_entropy, batch_f1
     train = opt is not None
     model.train(train)
     tot = dict(loss=0.0, acc=0.0, prec=0.0, rec=0.0, f1=0.0, n=0)
     for i, batch in enumerate(loader):
-        lengths, logits, y = forward_batch(model, kind, batch, device, waveform, stats)
+        if prepare is None:
+            lengths, logits, y = forward_batch(model, kind, batch, device, waveform, stats)
+        else:
+            lengths, x, y = prepare(batch)
+            logits = model(x, lengths)
         loss = batch_binary_cross_entropy(logits, y, lengths, EPS)       # sum over sequences (train_AV_net.py:298-302)
         if train:
             loss.backward()
@@ -139,9 +223,16 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
 
 
 def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_size=16, n_items=64, lr=1e-4,
-               freeze_features=False, out_dir=None, stats=None):
+               freeze_features=False, out_dir=None, stats=None, wav_pairs=None):
     """The body of ``scripts/train_{audio,video,AV}_net.py``; settings come from the caller's module-level constants
-    (the reference's "config system") and may be overridden by AVVAD_* environment variables."""
+    (the reference's "config system") and may be overridden by AVVAD_* environment variables.
+
+    ``wav_pairs`` (audio network, spectrogram input): a list of (noisy, clean) paths or a text file of them (``WavPairs``);
+    training and validation then run on real audio, the labels computed on the GPU from the clean files -- VAD for a
+    y_dim 1 head, IBM for y_dim 513 (``wav_pair_step``).  ``None`` keeps the synthetic data source."""
+    if wav_pairs is not None and (kind != "audio" or waveform):
+        raise ValueError("wav_pairs trains the audio network on spectrograms; video / AV frames and WaveNet waveform "
+                         "training on wav pairs are not supported")
     epochs = int(os.environ.get("AVVAD_EPOCHS", epochs))
     n_items = int(os.environ.get("AVVAD_ITEMS", n_items))
     batch_size = int(os.environ.get("AVVAD_BATCH", batch_size))
@@ -158,10 +249,18 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     opt = FlatAdam(model.parameters(), lr=lr, betas=(0.9, 0.999))
     reducer = avd.BucketReducer(opt.params, opt.flat_grad, opt.offsets,
                                 names=[n for n, q in model.named_parameters() if q.requires_grad]) if world > 1 else None
-    collate = pick_collate(kind, waveform)
-    per_rank = n_items // world
-    ds_train = SyntheticAV(per_rank, kind, waveform=waveform, seed=1 + rank)
-    ds_valid = SyntheticAV(max(per_rank // 4, batch_size), kind, waveform=waveform, seed=1000 + rank)
+    prepare = None
+    if wav_pairs is None:
+        collate = pick_collate(kind, waveform)
+        per_rank = n_items // world
+        ds_train = SyntheticAV(per_rank, kind, waveform=waveform, seed=1 + rank)
+        ds_valid = SyntheticAV(max(per_rank // 4, batch_size), kind, waveform=waveform, seed=1000 + rank)
+    else:
+        pairs = WavPairs(wav_pairs)
+        labels = labels_for_ydim(model.y_dim)
+        collate = WavPairs.collate
+        ds_train = ds_valid = torch.utils.data.Subset(pairs, range(rank, len(pairs), world))
+        prepare = lambda batch: wav_pair_step(batch, device, labels, stats)   # noqa: E731
     mk = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=batch_size // world or 1, shuffle=sh, collate_fn=collate)
     out_dir = out_dir or os.path.join("models", model_name)
     if rank == 0:
@@ -177,9 +276,9 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     log("- Number of learnable parameters: {}".format(count_parameters(model)))
     for epoch in range(1, epochs + 1):
         t0 = time.perf_counter()
-        tr = run_epoch(model, kind, mk(ds_train, True), device, waveform, opt, reducer, log, stats=stats)
+        tr = run_epoch(model, kind, mk(ds_train, True), device, waveform, opt, reducer, log, stats=stats, prepare=prepare)
         with torch.no_grad():
-            va = run_epoch(model, kind, mk(ds_valid, False), device, waveform, stats=stats)
+            va = run_epoch(model, kind, mk(ds_valid, False), device, waveform, stats=stats, prepare=prepare)
         log("====> Epoch: {:2d}  train loss {:.3f} f1 {:.3f} | valid loss {:.3f} f1 {:.3f} | {:.1f} s".format(
             epoch, tr["loss"], tr["f1"], va["loss"], va["f1"], time.perf_counter() - t0))
         if rank == 0:                       # same checkpoint naming as train_AV_net.py:443-448
@@ -221,6 +320,19 @@ def audio_features(x_t, stats=None, n_label_frames=None, fs=16e3, wlen_sec=64e-3
     return x
 
 
+def clean_vad_labels(clean_path, n_noisy, device, fs=16e3, wlen_sec=64e-3, hop_percent=0.25):
+    """VAD labels (1, T) of a clean file, cropped to the noisy file's length first (the evaluator's counterpart of
+    ``WavPairs``): peak normalisation, then ``clean_speech_VAD`` with the training pipeline's framing, on the GPU."""
+    c, fs_c = load_waveform(clean_path)
+    if fs_c != 16000:
+        raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (clean_path, fs_c))
+    n = min(c.numel(), int(n_noisy))
+    c = ops.peak_normalize(c[:n].to(device).view(1, -1))
+    _, vad = ops.speech_targets(c, [n], "vad_labels", fs=fs, wlen_sec=wlen_sec, hop_percent=hop_percent, center=False,
+                                pad_at_end=True)
+    return vad.view(1, -1)
+
+
 def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, eps=EPS, std_norm=True):
     """One utterance through the reference's evaluator (``evaluate_audio_net.py:107-180``; with ``video`` (T,67,67) the AV
     variant ``evaluate_AV_net.py:148-250``): returns (y_hat_soft, y_hat_hard) on the CPU, shaped (1, T) like the
@@ -237,14 +349,16 @@ def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, ep
 
 
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
-                  stats=None, labels=None):
+                  stats=None, labels=None, clean_of=None):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
 
     ``wav_list`` (audio network): paths of 16 kHz utterances (.wav / .npz) that go through ``process_utt`` -- the
     reference's plumbing on real audio; ``labels`` optionally maps a path to its label tensor (frame count crop + saved
-    next to the predictions for ``run_metrics``).  Without it a synthetic ragged data source stands in for the HDF5
+    next to the predictions for ``run_metrics``).  ``clean_of`` maps each noisy path of ``wav_list`` to its clean
+    counterpart: the labels are then the clean file's VAD (peak-normalised, the training pipeline's framing), computed on
+    the GPU, in place of ``labels``.  Without ``wav_list`` a synthetic ragged data source stands in for the HDF5
     datasets."""
     rank, world, local = avd.init_from_env("nccl")
     device = torch.device("cuda", local)
@@ -266,7 +380,10 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                 x_t, fs = load_waveform(wav_list[i])
                 if fs != 16000:
                     raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (wav_list[i], fs))
-                y = labels.get(wav_list[i]) if labels else None
+                if clean_of is not None:
+                    y = clean_vad_labels(clean_of[wav_list[i]], x_t.numel(), device)
+                else:
+                    y = labels.get(wav_list[i]) if labels else None
                 soft, hard = process_utt(model, x_t.to(device), stats, None if y is None else y.shape[-1])
                 base = os.path.join(out_dir, os.path.splitext(os.path.basename(wav_list[i]))[0])
                 torch.save(hard, base + "_y_hat_hard.pt")

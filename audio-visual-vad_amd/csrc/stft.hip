@@ -7,47 +7,9 @@
 // batched over all frames of all utterances it is a GEMM with M = B*T, K = n_fft, N = 2*(n_fft/2+1) -- MFMA work
 // (2.1 GFLOP per 1000 frames) instead of a butterfly network, and the framing gather (hop 256 -> every sample is
 // read by 4 frames) never materialises: the A functor reads wave[b][t*hop + k] directly.
-#include "igemm.h"
+#include "frames.h"
 
 namespace {
-
-// A[m = (b,t)][k] = wave[b][t*hop + k]  (zero beyond the utterance: the reference's end padding)
-struct FrameRows {
-  static constexpr bool KCONTIG = true;
-  static constexpr int VEC = 1;
-  typedef igemm::NoCtx Ctx;
-  const float* p;
-  long L;
-  int X, K, T, hop;
-  __device__ __forceinline__ Ctx prep(int) const { return Ctx(); }
-  __device__ __forceinline__ void load(const Ctx&, int x, int k0, int kin, float* v) const {
-    const int k = k0 + kin;
-    float t = 0.f;
-    if (x < X && k < K) {
-      const int b = x / T, fr = x - b * T;
-      const long idx = (long)fr * hop + k;
-      if (idx < L) t = p[(long)b * L + idx];
-    }
-    v[0] = t;
-  }
-};
-
-// basis[k][2f] = hann[k] cos(2 pi f k / N), basis[k][2f+1] = -hann[k] sin(2 pi f k / N); columns >= 2F are zero
-__global__ void dft_basis(float* __restrict__ W, int N, int F, int ld) {
-  const long n = (long)N * ld;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int k = (int)(i / ld), c = (int)(i % ld);
-    float v = 0.f;
-    if (c < 2 * F) {
-      const int f = c >> 1;
-      const double win = 0.5 - 0.5 * cospi(2.0 * (double)k / (double)N);          // periodic Hann
-      const long fk = ((long)f * k) % N;                                          // exact phase reduction
-      const double ang = 2.0 * (double)fk / (double)N;
-      v = (float)((c & 1) ? -win * sinpi(ang) : win * cospi(ang));
-    }
-    W[i] = v;
-  }
-}
 
 // out[m][f] = log(re^2 + im^2 + eps)   (or the power itself when take_log == 0)
 __global__ void power_log(const float* __restrict__ S, float* __restrict__ out, long M, int F, int ld, float eps, int take_log) {
@@ -84,8 +46,8 @@ __global__ void to_legacy_view(const float* __restrict__ S, float* __restrict__ 
   }
 }
 
-static inline int grid1(long n) { long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
-static inline int ld_of(const avvad_stft_desc* d) { return (2 * (d->n_fft / 2 + 1) + 3) / 4 * 4; }
+using frames::grid1;
+static inline int ld_of(const avvad_stft_desc* d) { return frames::spectrum_ld(d->n_fft); }
 static bool ok_desc(const avvad_stft_desc* d) {
   return d && d->B > 0 && d->L > 0 && d->n_fft >= 32 && d->n_fft % 32 == 0 && d->hop > 0 && d->T > 0 &&
          (long)(d->T - 1) * d->hop + d->n_fft <= d->L + d->hop;   // at most the reference's one-hop end pad
@@ -126,11 +88,7 @@ static int stft_impl(const float* wave, float* out, const avvad_stft_desc* d, in
   float* W = (float*)wsv;
   float* S = W + align_up((size_t)d->n_fft * ld, 64);
   const int M = d->B * d->T;
-  hipLaunchKernelGGL(dft_basis, dim3(grid1((long)d->n_fft * ld)), dim3(256), 0, s, W, d->n_fft, F, ld);
-  FrameRows a{wave, d->L, M, d->n_fft, d->T, d->hop};
-  igemm::ColPlain<4> b{W, ld, ld, d->n_fft, 0};
-  igemm::EpiStore e{S, ld, nullptr, 0};
-  int rc = igemm::launch<128, 128>(a, b, e, M, ld, d->n_fft, 1, s, S + align_up((size_t)M * ld, 64), /*allow_bf16=*/false);
+  int rc = frames::framed_dft(wave, d->L, d->B, d->T, d->n_fft, d->hop, W, S, S + align_up((size_t)M * ld, 64), s);
   if (rc) return rc;
   if (mode == 2) hipLaunchKernelGGL(to_legacy_view, dim3(grid1((long)d->T * F * 2)), dim3(256), 0, s, S, out, d->T, F, ld);
   else if (mean)

@@ -65,15 +65,16 @@ def f1_loss(y_hat_hard, y, epsilon=1e-8):
 
 def batch_f1(y_hat_hard, y, lengths, epsilon=1e-8):
     """Vectorised form of the caller loop ``scripts/train_AV_net.py:318-334``: per-sequence metrics over the
-    valid frames, averaged over the batch.  y_hat_hard / y: (B,T,1) or (B,T)."""
+    valid frames (all y_dim outputs of them, as the caller flattens ``pred[:length]``), averaged over the batch.
+    y_hat_hard / y: (B,T,Y) or (B,T)."""
     B, T = y.shape[0], y.shape[1]
-    yp = y_hat_hard.reshape(B, T).to(torch.float32)
-    yt = y.reshape(B, T).to(torch.float32)
-    m = (torch.arange(T, device=y.device)[None, :] < torch.as_tensor(lengths, device=y.device)[:, None]).float()
-    tp = (yt * yp * m).sum(1)
-    tn = ((1 - yt) * (1 - yp) * m).sum(1)
-    fp = ((1 - yt) * yp * m).sum(1)
-    fn = (yt * (1 - yp) * m).sum(1)
+    yp = y_hat_hard.reshape(B, T, -1).to(torch.float32)
+    yt = y.reshape(B, T, -1).to(torch.float32)
+    m = (torch.arange(T, device=y.device)[None, :] < torch.as_tensor(lengths, device=y.device)[:, None]).float()[..., None]
+    tp = (yt * yp * m).sum((1, 2))
+    tn = ((1 - yt) * (1 - yp) * m).sum((1, 2))
+    fp = ((1 - yt) * yp * m).sum((1, 2))
+    fn = (yt * (1 - yp) * m).sum((1, 2))
     acc = (tp + tn) / (tp + tn + fp + fn + epsilon)
     prec = tp / (tp + fp + epsilon)
     rec = tp / (tp + fn + epsilon)

@@ -8,7 +8,7 @@ Run from the package root: ``python scripts/evaluate_audio_net.py``; then ``pyth
 import sys
 sys.path.append('.')
 
-from avvad.train import Stats, evaluate_main
+from avvad.train import Stats, evaluate_main, read_wav_pairs
 from packages.models.Audio_Net import DeepVAD_audio
 
 # Settings (names as in the reference script)
@@ -26,6 +26,8 @@ classif_dir = None        # checkpoint written by scripts/train_audio_net.py or 
 classif_data_dir = 'eval_out'
 stats_dir = None          # directory holding trainset_audio_mean.npy / trainset_audio_std.npy (written by the training script)
 wav_list = None           # e.g. sorted(glob.glob('data/subset/processed/ntcd_timit/Noisy/*/*/test/*/*.wav'))
+wav_pairs = None          # text file with one "noisy.wav clean.wav" pair per line: evaluates the noisy files and scores them
+                          # against the clean files' VAD, computed on the GPU (takes the place of wav_list)
 WAVENET = False           # True: raw waveforms through the WaveNet encoder (the hook the reference left commented out)
 wavenet_params = dict(filter_width=2, quantization_channel=1, dilations=[2 ** i for i in range(10)] * 2,
                       en_residual_channel=32, en_dilation_channel=32, en_bottleneck_width=256,
@@ -38,4 +40,9 @@ def make_model():
 
 if __name__ == '__main__':
     stats = Stats.load(stats_dir, eps) if (std_norm and stats_dir) else None
-    evaluate_main('audio', make_model, checkpoint=classif_dir, waveform=WAVENET, out_dir=classif_data_dir, wav_list=wav_list, stats=stats)
+    clean_of = None
+    if wav_pairs is not None:
+        pairs = read_wav_pairs(wav_pairs)
+        wav_list, clean_of = [n for n, _ in pairs], dict(pairs)
+    evaluate_main('audio', make_model, checkpoint=classif_dir, waveform=WAVENET, out_dir=classif_data_dir, wav_list=wav_list, stats=stats,
+                  clean_of=clean_of)

@@ -4,8 +4,9 @@ process per GPU under ``python -m torch.distributed.run --nproc-per-node N scrip
 the reference's ``nn.DataParallel(model, device_ids=[0,1,2,3])`` by bucketed RCCL all-reduce.
 Inputs: 513-bin log-power spectrogram sequences (B,T,513) or, with WAVENET = True, raw waveforms through the WaveNet encoder.
 The loop body (standardise -> forward -> summed masked BCE -> backward -> Adam -> per-sequence F1 -> checkpoint
-``Video_Net_epoch_XXX_vloss_Y.pt``) is ``avvad.train.train_main``; a synthetic ragged data source stands in for the
-reference's HDF5 datasets (h5py is not installed in this image).  AVVAD_EPOCHS / AVVAD_ITEMS / AVVAD_BATCH override sizes."""
+``Video_Net_epoch_XXX_vloss_Y.pt``) is ``avvad.train.train_main``; with ``wav_pairs`` it trains on (noisy, clean) wav pairs
+and computes the labels on the GPU, otherwise a synthetic ragged data source stands in for the reference's HDF5
+datasets (h5py is not installed in this image).  AVVAD_EPOCHS / AVVAD_ITEMS / AVVAD_BATCH override sizes."""
 import sys
 sys.path.append('.')
 
@@ -23,6 +24,8 @@ eps = 1e-8
 std_norm = True           # standardise inputs with the train-set statistics when models/<model_name>/trainset_*.npy exist
 model_name = 'audio_Classif_synthetic'
 WAVENET = False           # True: raw waveforms through the WaveNet encoder (the hook the reference left commented out)
+wav_pairs = None          # text file with one "noisy.wav clean.wav" pair per line: train on real audio, labels computed on
+                          # the GPU from the clean files (VAD for y_dim 1, IBM for y_dim 513); None: synthetic data
 wavenet_params = dict(filter_width=2, quantization_channel=1, dilations=[2 ** i for i in range(10)] * 2,
                       en_residual_channel=32, en_dilation_channel=32, en_bottleneck_width=256,
                       en_pool_kernel_size=16, use_bias=True)
@@ -35,4 +38,4 @@ def make_model():
 if __name__ == '__main__':
     stats = Stats.load('models/' + model_name, eps) if std_norm else None
     train_main('audio', make_model, model_name, waveform=WAVENET, epochs=end_epoch, batch_size=batch_size,
-               lr=learning_rate, stats=stats)
+               lr=learning_rate, stats=stats, wav_pairs=wav_pairs)

@@ -40,7 +40,9 @@ typedef void* avvad_stream_t; /* hipStream_t */
 /* library / build identification ("gfx950", ABI version).  AVVAD_ABI_VERSION is what THIS header describes; a binding
  * must refuse a library whose avvad_abi_version() differs (signatures changed incompatibly between versions:
  * 2 = (ws, ws_bytes) in front of the stream of avvad_gemm_f32 / avvad_conv2d_*, avvad_wavenet_desc.shared_device). */
-#define AVVAD_ABI_VERSION 3   /* 3 = + avvad_conv2d_*_bf16 */
+#define AVVAD_ABI_VERSION 3   /* 3 = + avvad_conv2d_*_bf16.  Added entry points alone (the avvad_target_* labels) change no
+                                 existing signature, so they keep the version: a version-3 binding still describes the
+                                 library exactly for every symbol it binds. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -335,6 +337,46 @@ int avvad_peak_normalize(const float* x, float* out, int B, long L, avvad_stream
  * 513 x 1 in the reference); nstat == 1: one scalar pair (video, 1 x 1).  out may alias x. */
 int avvad_standardize(const float* x, const float* mean, const float* std_, float* out, size_t rows, int F,
                       int nstat, float eps, avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Training labels from clean speech: framed-energy VAD and ideal binary mask (IBM)
+ * Replaces: packages/processing/target.py clean_speech_VAD (:5-56), clean_speech_IBM (:58-70) and
+ *   noise_robust_clean_speech_IBM (:72-107), which the reference runs offline into HDF5 label files
+ *   (scripts/create_audio_train_files.py:96-160); here they run in the training step next to the features.
+ * A ragged batch: wave [B][L] (rows zero-padded past each utterance), n_samples / n_frames device int32 [B] computed
+ * on the host with the reference's rules:
+ *   n_samples[b] = L_b, plus one hop of zeros when ceil(L_b/fs/wlen_sec/hop_percent) != int(...) (the end pad);
+ *   n_frames[b]  = 1 + (n_samples[b] + 2 * (center ? n_fft/2 : 0) - n_fft) / hop  (librosa.util.frame).
+ * Outputs are batch-first with frame pitch d->T; frames t >= n_frames[b] are written as 0.  No reduction crosses an
+ * utterance.  Results are bit-identical run to run (fp64 energies in a fixed order; maxima by integer atomics).
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int B;           /* utterances                                                          */
+  long L;          /* sample pitch of wave [B][L]                                         */
+  int n_fft, hop;  /* frame length and hop, samples                                      */
+  int T;           /* frame pitch of the outputs (the largest n_frames[b])                */
+  int center;      /* 0: no centring; n_fft/2 samples per side of 1: reflect, 2: zero padding (VAD only) */
+  float eps;       /* IBM: 20 log10(|S| + eps)                                            */
+  double vad_coef; /* 10**vad_threshold: vad = E_t > vad_coef * min_t E_t (compared in double)          */
+  double ibm_coef; /* 10**(-ibm_threshold/20): ibm = |S| > (max|S| + eps) * ibm_coef - eps            */
+} avvad_target_desc;
+/* Bytes of workspace for the descriptor (the largest need of the entry points below); 0 on a bad descriptor
+ * (B <= 0, hop <= 0, T beyond the frames that L, one hop of end pad and the centring allow, ...). */
+size_t avvad_target_workspace(const avvad_target_desc* d);
+/* vad [B][T] = framed-energy VAD: energies accumulated in fp64 from the wave itself (no padded copy). */
+int avvad_target_vad(const float* wave, const int* n_samples, const int* n_frames, float* vad, const avvad_target_desc* d,
+                     void* ws, size_t ws_bytes, avvad_stream_t s);
+/* ibm [B][T][F] (F = n_fft/2 + 1, batch-first like the collates' targets) from the waveform: the STFT front-end's DFT
+ * (periodic Hann, center = 0 only, n_fft % 32 == 0), the per-utterance maximum of |S|, one threshold pass; robust != 0
+ * multiplies each frame by the utterance's VAD (noise_robust_clean_speech_IBM with the same framing). */
+int avvad_target_ibm(const float* wave, const int* n_samples, const int* n_frames, int robust, float* ibm,
+                     const avvad_target_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
+/* IBM of ONE given spectrum (d->B == 1; only n_fft, T, eps, ibm_coef are read): spec holds interleaved (re, im) float
+ * pairs, bin (t, f) at spec[t * stride_t + f * stride_f] (float strides, even) -- the legacy (F, T, 2) view of
+ * stft_pytorch and torch.view_as_real of a complex (F, T) tensor go in as they are.  out [F][T]; vad [T] (may be
+ * NULL) multiplies each frame.  ws: at least 8 bytes (the workspace query of a descriptor always covers it). */
+int avvad_target_ibm_from_spectrum(const float* spec, long stride_t, long stride_f, const float* vad, float* out,
+                                   const avvad_target_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Masked BCE-with-eps loss, summed over sequences

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz by RUNNING THE REFERENCE in the build container.
 
-    python tools/gen_golden.py            # needs /root/reference (absent on the GPU box)
+    python tools/gen_golden.py [group ...]   # needs /root/reference (absent on the GPU box); groups: wavenet audio
+                                             # video av misc metrics eval targets (default: all)
 
 The reference's own classes/functions are imported from /root/reference and run
 on seeded inputs; only inputs, (small) weights and outputs are written -- data,
@@ -302,7 +303,67 @@ def gen_metrics():
     save("metrics", per_utt=per_utt, snr=snr, noise=noise, ci=ci, table=np.frombuffer(text.encode(), dtype=np.uint8))
 
 
+# ------------------------------------------------------------------ training labels (packages/processing/target.py): the
+# reference's own functions on the clean and noisy sa1 and on seeded edge cases.  librosa is not installed here: its
+# util.frame is stubbed by a numpy frame with librosa's documented semantics (1-D y -> (frame_length, n_frames) view).
+TARGET_CFGS = {"c64f": dict(wlen_sec=64e-3, center=False), "c64t": dict(wlen_sec=64e-3, center=True),
+               "d50": dict()}                                 # d50: the function's defaults (50 ms, centred, reflect)
+
+
+def _librosa_stub():
+    def frame(y, frame_length, hop_length):
+        y = np.ascontiguousarray(y)
+        n = 1 + (len(y) - frame_length) // hop_length
+        if n < 1:
+            raise ValueError("Input is too short (n=%d) for frame_length=%d" % (len(y), frame_length))
+        return np.lib.stride_tricks.as_strided(y, shape=(frame_length, n), strides=(y.itemsize, hop_length * y.itemsize),
+                                               writeable=False)
+    lib = types.ModuleType("librosa")
+    lib.util = types.ModuleType("librosa.util")
+    lib.util.frame = frame
+    sys.modules.update({"librosa": lib, "librosa.util": lib.util})
+
+
+def gen_targets():
+    from scipy.io import wavfile
+    from oracle import frontend
+    _librosa_stub()
+    from packages.processing import target as ref_target
+    fs, wav = wavfile.read(os.path.join(REF, "data/subset/processed/ntcd_timit/Clean/test/34M/sa1.wav"))
+    assert fs == 16000 and wav.dtype == np.int16 and wav.ndim == 1
+    wav = wav[:3 * 16000 + 100]                               # the crop of utt_sa1.npz
+    np.savez_compressed(os.path.join(OUT, "utt_sa1_clean.npz"), samples=wav, fs=np.array(fs))
+    noisy = np.load(os.path.join(OUT, "utt_sa1.npz"))["samples"]
+    arrs = {}
+    sig = {}
+    for tag, x in (("clean", wav), ("noisy", noisy)):
+        x = x.astype(np.float32) / 32768.0
+        sig[tag] = x / np.max(np.abs(x))                      # peak-normalised, as create_audio_train_files.py:107-108
+        for cfg, kw in TARGET_CFGS.items():
+            arrs["vad_%s_%s" % (tag, cfg)] = ref_target.clean_speech_VAD(sig[tag], **kw).astype(np.uint8)
+
+    def spectrum(x):                                           # stft_pytorch(center=False, 64 ms) with return_complex
+        return torch.view_as_complex(frontend.stft(torch.from_numpy(x), wlen_sec=64e-3, center=False)).numpy()
+    S = spectrum(sig["clean"])
+    for thr in (50, 65):
+        arrs["ibm%d_clean" % thr] = ref_target.clean_speech_IBM(S, eps=1e-8, ibm_threshold=thr).astype(np.uint8)
+    arrs["robust_clean"] = ref_target.noise_robust_clean_speech_IBM(sig["clean"], S, wlen_sec=64e-3, center=False,
+                                                                    ibm_threshold=50).astype(np.uint8)
+    # seeded edge cases (64 ms, center=False): leading digital silence (min E = 0), all zeros, a whole number of hops
+    # (no end pad), one frame
+    rng = np.random.RandomState(2024)
+    edges = {"silence": np.concatenate([np.zeros(2000, np.float32), (rng.randn(6000) * 0.1).astype(np.float32)]),
+             "zeros": np.zeros(3000, np.float32),
+             "whole": (rng.randn(7680) * 0.05).astype(np.float32),
+             "one": (rng.randn(1024) * 0.2).astype(np.float32)}
+    for name, x in edges.items():
+        arrs["edge_%s" % name] = x
+        arrs["edge_vad_%s" % name] = ref_target.clean_speech_VAD(x, wlen_sec=64e-3, center=False).astype(np.uint8)
+    arrs["edge_ibm_zeros"] = ref_target.clean_speech_IBM(spectrum(edges["zeros"])).astype(np.uint8)
+    save("targets", **arrs)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["wavenet", "audio", "video", "av", "misc", "metrics", "eval"]
+    which = sys.argv[1:] or ["wavenet", "audio", "video", "av", "misc", "metrics", "eval", "targets"]
     for w in which:
         globals()["gen_" + w]()
