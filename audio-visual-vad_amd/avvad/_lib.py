@@ -120,6 +120,11 @@ SIGNATURES = {
     "avvad_stft_workspace": (C.c_size_t, [C.POINTER(StftDesc)]),
     "avvad_stft": (C.c_int, [FP, FP, C.POINTER(StftDesc), C.c_int, FP, C.c_size_t, FP]),
     "avvad_stft_features": (C.c_int, [FP, FP, FP, FP, C.POINTER(StftDesc), C.c_float, FP, C.c_size_t, FP]),
+    "avvad_stats_workspace": (C.c_size_t, [C.c_size_t, C.c_int]),
+    "avvad_stats_accumulate": (C.c_int, [FP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_int, FP, C.c_size_t, FP]),
+    "avvad_stft_stats_workspace": (C.c_size_t, [C.POINTER(StftDesc)]),
+    "avvad_stft_stats": (C.c_int, [FP, FP, FP, C.POINTER(StftDesc), FP, C.c_size_t, FP]),
+    "avvad_stats_finalize": (C.c_int, [FP, C.c_int, FP, FP, FP]),
     "avvad_target_workspace": (C.c_size_t, [C.POINTER(TargetDesc)]),
     "avvad_target_vad": (C.c_int, [FP, FP, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
     "avvad_target_ibm": (C.c_int, [FP, FP, FP, C.c_int, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),

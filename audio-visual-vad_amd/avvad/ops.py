@@ -655,6 +655,84 @@ def standardize(x, mean, std, eps=1e-8):
     return out
 
 
+# --------------------------------------------------------------------------- train-set statistics (no gradient)
+def stats_new(nstat, device):
+    """A zeroed statistics accumulator: float64 ``[sum (nstat), sumsq (nstat), count]`` on the GPU (include/avvad.h,
+    avvad_stats_*).  ``nstat`` is the feature width (per-bin statistics: audio, 513) or 1 (one scalar pair: video)."""
+    if int(nstat) < 1:
+        raise L.AvvadError("nstat must be positive, got %r" % (nstat,))
+    if torch.device(device).type != "cuda":
+        raise L.AvvadError("the statistics accumulate on the GPU: the AV-VAD hot path has no CPU fallback")
+    return torch.zeros(2 * int(nstat) + 1, dtype=torch.float64, device=device)
+
+
+def _acc_nstat(acc):
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.dtype != torch.float64 or acc.dim() != 1 \
+            or not acc.is_contiguous() or acc.numel() < 3 or acc.numel() % 2 == 0:
+        raise L.AvvadError("acc must be a contiguous float64 GPU vector of 2 * nstat + 1 values (ops.stats_new)")
+    return (acc.numel() - 1) // 2
+
+
+def stft_stats(acc, wave, sample_lengths, n_fft=1024, hop=256, eps=1e-8, pad_at_end=True, fs=16e3):
+    """Adds the log-power STFT features of a ragged batch to ``acc`` without writing them (avvad_stft_stats): wave (B, L)
+    zero-padded rows (or (L,)), ``sample_lengths`` the B real lengths; row b counts its first ``n_frames(L_b)`` frames,
+    the rule ``ops.stft`` uses for the frame count.  Returns ``acc``."""
+    w = _dev(wave, "wave")
+    w2 = w.view(1, -1) if w.dim() == 1 else w
+    B, Ls = w2.shape
+    lens = [int(v) for v in (sample_lengths.tolist() if isinstance(sample_lengths, torch.Tensor) else sample_lengths)]
+    if len(lens) != B or any(n < 0 or n > Ls for n in lens):
+        raise L.AvvadError("sample_lengths must hold %d lengths within 0..%d" % (B, Ls))
+    F = n_fft // 2 + 1
+    if _acc_nstat(acc) != F:
+        raise L.AvvadError("acc holds %d statistics, the STFT has %d bins" % (_acc_nstat(acc), F))
+    T = n_frames(Ls, n_fft, hop, pad_at_end, fs)
+    counts = torch.tensor([max(0, n_frames(n, n_fft, hop, pad_at_end, fs)) for n in lens], dtype=torch.int32).to(w.device)
+    d = L.StftDesc(B, Ls, n_fft, hop, T, float(eps))
+    ws = _ws(L.lib().avvad_stft_stats_workspace(C.byref(d)), w.device)
+    L.check(L.lib().avvad_stft_stats(L.ptr(w2), L.ptr(counts), L.ptr(acc), C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()),
+            "avvad_stft_stats")
+    return acc
+
+
+def accumulate_stats(acc, x, lengths=None, nstat=None):
+    """Adds materialised features x (B, T, F) (or (T, F)) to ``acc`` (avvad_stats_accumulate); rows t >= lengths[b] are
+    not counted.  ``nstat`` (default: what ``acc`` holds) is F or 1 -- spectrogram batches of a loader, or video frames
+    flattened to (B, T, H*W) with one scalar pair.  Returns ``acc``."""
+    x = _dev(x, "x")
+    if x.dim() == 2:
+        x = x.view(1, *x.shape)
+    if x.dim() != 3:
+        raise L.AvvadError("x must be (B, T, F), got shape %s" % (tuple(x.shape),))
+    B, T, F = x.shape
+    have = _acc_nstat(acc)
+    nstat = have if nstat is None else int(nstat)
+    if nstat != have or nstat not in (1, F):
+        raise L.AvvadError("accumulate_stats: statistics must hold 1 or %d values, acc holds %d, nstat %d" % (F, have, nstat))
+    lens32 = None
+    if lengths is not None:
+        lens32 = lengths_i32(lengths, x.device)
+        if lens32.numel() != B:
+            raise L.AvvadError("lengths must hold %d values" % B)
+    ws = _ws(L.lib().avvad_stats_workspace(B * T, nstat), x.device)
+    L.check(L.lib().avvad_stats_accumulate(L.ptr(x), L.ptr(lens32), L.ptr(acc), B, T, F, nstat, L.ptr(ws), ws.numel() * 4,
+                                           _stream()), "avvad_stats_accumulate")
+    return acc
+
+
+def finalize_stats(acc):
+    """(mean, std) float32 (nstat,) on the GPU: ``mean = sum / n``, ``std = sqrt((sumsq - n mean^2) / (n - 1))`` in
+    double (avvad_stats_finalize).  Fewer than two counted values raise."""
+    nstat = _acc_nstat(acc)
+    n = float(acc[-1])
+    if not n >= 2:
+        raise L.AvvadError("statistics of %g values: mean / empirical std need at least two" % n)
+    mean = torch.empty(nstat, dtype=torch.float32, device=acc.device)
+    std = torch.empty_like(mean)
+    L.check(L.lib().avvad_stats_finalize(L.ptr(acc), nstat, L.ptr(mean), L.ptr(std), _stream()), "avvad_stats_finalize")
+    return mean, std
+
+
 # --------------------------------------------------------------------------- training labels from clean speech (no gradient)
 _CENTER = {"reflect": 1, "constant": 2}
 

@@ -42,6 +42,18 @@ class Stats:
                 kw[k] = np.load(path, allow_pickle=False)
         return cls(eps=eps, **kw)
 
+    def save(self, model_dir):
+        """Writes the statistics this object holds as ``trainset_{audio,video}_{mean,std}.npy`` in the shapes the
+        reference writes and ``load`` reads -- (513, 1) per-bin columns, (1, 1) scalars, float32 -- and returns
+        ``model_dir``: ``Stats.load(stats.save(d))`` holds the same values bit for bit."""
+        import numpy as np
+        os.makedirs(model_dir, exist_ok=True)
+        for k, v in self._raw.items():
+            if v is not None:
+                v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+                np.save(os.path.join(model_dir, "trainset_%s.npy" % k), np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 1))
+        return model_dir
+
     def get(self, key, device):
         if self._raw.get(key) is None:
             return None
@@ -176,6 +188,46 @@ def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, ho
     return frames.to(device), x, target
 
 
+def rank_shard(n, rank, world):
+    """The items rank ``rank`` of ``world`` takes out of ``n``: every item belongs to exactly one rank."""
+    return range(rank, n, world)
+
+
+def merge_stats(accs):
+    """Sum of statistics accumulators (``ops.stats_new`` layout: sums, sums of squares, count), added in the given order:
+    accumulating a set in parts and merging equals accumulating it in one up to double rounding of the additions."""
+    accs = list(accs)
+    out = accs[0].clone()
+    for a in accs[1:]:
+        out += a
+    return out
+
+
+def wav_pair_stats(pairs, device, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS):
+    """Train-set statistics of the audio features over (noisy, clean) wav pairs -> ``Stats`` (audio (513, 1) mean / std):
+    what ``create_audio_train_files.py:196-214, 340-392`` computes offline.  ``pairs``: a ``WavPairs``, a list of pairs or
+    a text file of them.  Every noisy file is peak-normalised as ``wav_pair_step`` does and its log-power STFT frames --
+    the frame counts ``wav_pair_step`` uses -- are accumulated on the GPU without materialising the features
+    (``ops.stft_stats``).  With ``torch.distributed`` initialised every rank takes ``rank_shard`` of the pairs and the
+    float64 accumulators are summed by one all-reduce."""
+    import torch.distributed as dist
+    if not isinstance(pairs, WavPairs):
+        pairs = WavPairs(pairs)
+    multi = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
+    nfft = int(wlen_sec * fs)
+    acc = ops.stats_new(nfft // 2 + 1, device)
+    loader = torch.utils.data.DataLoader(torch.utils.data.Subset(pairs, rank_shard(len(pairs), rank, world)),
+                                         batch_size=batch_size, shuffle=False, collate_fn=WavPairs.collate)
+    for lens, noisy, _ in loader:
+        noisy = ops.peak_normalize(noisy.to(device, non_blocking=True))
+        ops.stft_stats(acc, noisy, lens, nfft, int(hop_percent * nfft), eps=eps, pad_at_end=True, fs=fs)
+    if multi:
+        dist.all_reduce(acc)                 # the merge across ranks: merge_stats of the ranks' accumulators
+    mean, std = ops.finalize_stats(acc)
+    return Stats(audio_mean=mean.cpu().numpy().reshape(-1, 1), audio_std=std.cpu().numpy().reshape(-1, 1), eps=eps)
+
+
 def forward_batch(model, kind, batch, device, waveform, stats=None):
     """H2D, ``std_norm`` standardisation (spectrogram features and video; raw waveforms are not standardised in the
     reference either), forward."""
@@ -223,13 +275,17 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
 
 
 def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_size=16, n_items=64, lr=1e-4,
-               freeze_features=False, out_dir=None, stats=None, wav_pairs=None):
+               freeze_features=False, out_dir=None, stats=None, wav_pairs=None, compute_stats=False):
     """The body of ``scripts/train_{audio,video,AV}_net.py``; settings come from the caller's module-level constants
     (the reference's "config system") and may be overridden by AVVAD_* environment variables.
 
     ``wav_pairs`` (audio network, spectrogram input): a list of (noisy, clean) paths or a text file of them (``WavPairs``);
     training and validation then run on real audio, the labels computed on the GPU from the clean files -- VAD for a
-    y_dim 1 head, IBM for y_dim 513 (``wav_pair_step``).  ``None`` keeps the synthetic data source."""
+    y_dim 1 head, IBM for y_dim 513 (``wav_pair_step``).  ``None`` keeps the synthetic data source.
+
+    ``compute_stats``: with ``wav_pairs`` and no audio statistics in ``stats``, the train-set mean / std of the features
+    are computed over the training pairs on the GPU before the first epoch (``wav_pair_stats``), saved under ``out_dir``
+    (``Stats.save``: the directory the evaluate scripts' ``stats_dir`` takes) and used for training."""
     if wav_pairs is not None and (kind != "audio" or waveform):
         raise ValueError("wav_pairs trains the audio network on spectrograms; video / AV frames and WaveNet waveform "
                          "training on wav pairs are not supported")
@@ -274,6 +330,16 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
 
     from packages.utils import count_parameters
     log("- Number of learnable parameters: {}".format(count_parameters(model)))
+    if compute_stats and wav_pairs is not None and (stats is None or stats.get("audio_mean", device) is None):
+        t0 = time.perf_counter()
+        made = wav_pair_stats(pairs, device, batch_size=batch_size)          # wav_pair_step's framing and log eps
+        if stats is None:
+            stats = made                    # `prepare` reads this variable when it is called
+        else:
+            stats._raw.update(audio_mean=made._raw["audio_mean"], audio_std=made._raw["audio_std"])
+        if rank == 0:
+            stats.save(out_dir)
+        log("- Train-set statistics over {} pairs in {:.1f} s, saved in {}".format(len(pairs), time.perf_counter() - t0, out_dir))
     for epoch in range(1, epochs + 1):
         t0 = time.perf_counter()
         tr = run_epoch(model, kind, mk(ds_train, True), device, waveform, opt, reducer, log, stats=stats, prepare=prepare)

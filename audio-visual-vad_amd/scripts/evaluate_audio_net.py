@@ -24,7 +24,8 @@ center = False
 pad_at_end = True
 classif_dir = None        # checkpoint written by scripts/train_audio_net.py or by the reference (same state_dict keys)
 classif_data_dir = 'eval_out'
-stats_dir = None          # directory holding trainset_audio_mean.npy / trainset_audio_std.npy (written by the training script)
+stats_dir = None          # directory holding trainset_audio_mean.npy / trainset_audio_std.npy (models/<model_name> of the training
+                          # script with compute_stats = True, or the output_dir of scripts/create_audio_train_files.py)
 wav_list = None           # e.g. sorted(glob.glob('data/subset/processed/ntcd_timit/Noisy/*/*/test/*/*.wav'))
 wav_pairs = None          # text file with one "noisy.wav clean.wav" pair per line: evaluates the noisy files and scores them
                           # against the clean files' VAD, computed on the GPU (takes the place of wav_list)

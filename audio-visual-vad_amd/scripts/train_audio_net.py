@@ -26,6 +26,8 @@ model_name = 'audio_Classif_synthetic'
 WAVENET = False           # True: raw waveforms through the WaveNet encoder (the hook the reference left commented out)
 wav_pairs = None          # text file with one "noisy.wav clean.wav" pair per line: train on real audio, labels computed on
                           # the GPU from the clean files (VAD for y_dim 1, IBM for y_dim 513); None: synthetic data
+compute_stats = False     # with wav_pairs and no trainset_audio_*.npy yet: compute the train-set mean / std over the pairs on
+                          # the GPU before the first epoch and save them in models/<model_name> (the evaluate scripts' stats_dir)
 wavenet_params = dict(filter_width=2, quantization_channel=1, dilations=[2 ** i for i in range(10)] * 2,
                       en_residual_channel=32, en_dilation_channel=32, en_bottleneck_width=256,
                       en_pool_kernel_size=16, use_bias=True)
@@ -38,4 +40,4 @@ def make_model():
 if __name__ == '__main__':
     stats = Stats.load('models/' + model_name, eps) if std_norm else None
     train_main('audio', make_model, model_name, waveform=WAVENET, epochs=end_epoch, batch_size=batch_size,
-               lr=learning_rate, stats=stats, wav_pairs=wav_pairs)
+               lr=learning_rate, stats=stats, wav_pairs=wav_pairs, compute_stats=compute_stats and std_norm)

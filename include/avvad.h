@@ -42,7 +42,7 @@ typedef void* avvad_stream_t; /* hipStream_t */
  * 2 = (ws, ws_bytes) in front of the stream of avvad_gemm_f32 / avvad_conv2d_*, avvad_wavenet_desc.shared_device). */
 #define AVVAD_ABI_VERSION 3   /* 3 = + avvad_conv2d_*_bf16.  Added entry points alone (the avvad_target_* labels) change no
                                  existing signature, so they keep the version: a version-3 binding still describes the
-                                 library exactly for every symbol it binds. */
+                                 library exactly for every symbol it binds.  The avvad_stats_* section is such an addition. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -337,6 +337,45 @@ int avvad_peak_normalize(const float* x, float* out, int B, long L, avvad_stream
  * 513 x 1 in the reference); nstat == 1: one scalar pair (video, 1 x 1).  out may alias x. */
 int avvad_standardize(const float* x, const float* mean, const float* std_, float* out, size_t rows, int F,
                       int nstat, float eps, avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Train-set standardisation statistics: the producers of the mean / std that avvad_standardize and
+ * avvad_stft_features apply
+ * Replaces: scripts/create_audio_train_files.py:196-214, 273-280, 340-392 (per file n_samples, channels_sum,
+ *   channels_squared_sum of the log-power spectrogram, then mean = sum / n, std = sqrt((sumsq - n mean^2) / (n - 1)),
+ *   513 x 1 each) and the same triples over all pixels in scripts/create_video_train_files_upsampled.py (1 x 1), which
+ *   the reference computes offline and stores in HDF5.
+ * An accumulator is caller-owned device memory of 2 * nstat + 1 doubles: sum[nstat], sumsq[nstat], count.  nstat is the
+ * feature width F (per-column statistics: audio) or 1 (one scalar pair over all values: video), as for
+ * avvad_standardize.  The caller zeroes it; every call ADDS to it, so a training set is a sequence of batches into one
+ * accumulator, and accumulators of several ranks add element-wise.
+ * Deliberate difference from the reference: it keeps sum and sumsq in float32 (`0. + float32 array` stays float32; numpy's
+ * pairwise sum per file, left to right across files), which degrades with the size of the set.  Here every step behind
+ * the float32 feature value is double.
+ * Reductions use no floating-point atomics: rows are cut into chunks whose size depends on the shape only, per-chunk
+ * double partials go to the workspace and are added in a fixed order that depends on the chunk count only (sixteen
+ * contiguous segments of chunks, ascending inside, then the segments ascending), so results are bit-identical run to
+ * run and independent of the "max_cus" option.
+ * ---------------------------------------------------------------------- */
+/* Bytes of workspace of avvad_stats_accumulate for rows = B * T rows; 0 on rows == 0, rows >= 2^31 or nstat <= 0. */
+size_t avvad_stats_workspace(size_t rows, int nstat);
+/* x [B][T][F] materialised features (spectrogram batches of a loader; video frames with F = H*W, nstat = 1);
+ * lengths: device int32 [B], rows t >= lengths[b] are not counted (NULL: every row counts).  nstat must be F or 1. */
+int avvad_stats_accumulate(const float* x, const int* lengths, double* acc, int B, int T, int F, int nstat, void* ws,
+                           size_t ws_bytes, avvad_stream_t s);
+/* Fused from the waveform: wave [B][L] ragged (rows zero-padded), n_frames device int32 [B] valid frames per row, d as
+ * for avvad_stft.  Runs the STFT's DFT GEMM, then ONE pass over the spectrum that forms log(re^2 + im^2 + d->eps) (the
+ * expression of avvad_stft mode 0, bit for bit), widens to double and accumulates x and x^2 per bin over the frames
+ * t < n_frames[b]; the [B][T][F] feature tensor is never written.  nstat = F = n_fft/2 + 1.  The workspace holds the
+ * STFT's (the spectrum is live while the partials are written) followed by the partials: avvad_stft_stats_workspace,
+ * 0 on a bad descriptor.  avvad_stft_workspace is unchanged. */
+size_t avvad_stft_stats_workspace(const avvad_stft_desc* d);
+int avvad_stft_stats(const float* wave, const int* n_frames, double* acc, const avvad_stft_desc* d, void* ws,
+                     size_t ws_bytes, avvad_stream_t s);
+/* mean[i] = sum[i] / n, std[i] = sqrt(max((sumsq[i] - n mean[i]^2) / (n - 1), 0)) (the reference's "empirical std"),
+ * computed in double and written as float [nstat].  The clamp keeps constant data (where the difference can round to a
+ * tiny negative number) from producing a NaN; n < 2 gives NaN as numpy would. */
+int avvad_stats_finalize(const double* acc, int nstat, float* mean, float* std_, avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Training labels from clean speech: framed-energy VAD and ideal binary mask (IBM)
