@@ -75,6 +75,11 @@ class TargetDesc(C.Structure):
                 ("eps", C.c_float), ("vad_coef", C.c_double), ("ibm_coef", C.c_double)]
 
 
+class LipDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("n_max", C.c_int), ("rows", C.c_long), ("T", C.c_int), ("W", C.c_int), ("H", C.c_int),
+                ("p", C.c_int), ("q", C.c_int), ("quantize", C.c_int), ("norm_eps", C.c_float)]
+
+
 class LstmDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("T", C.c_int), ("In", C.c_int), ("H", C.c_int), ("lengths", FP),
                 ("save_for_backward", C.c_int)]
@@ -129,6 +134,8 @@ SIGNATURES = {
     "avvad_target_vad": (C.c_int, [FP, FP, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
     "avvad_target_ibm": (C.c_int, [FP, FP, FP, C.c_int, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
     "avvad_target_ibm_from_spectrum": (C.c_int, [FP, C.c_long, C.c_long, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
+    "avvad_lip_decode_workspace": (C.c_size_t, [C.POINTER(LipDesc)]),
+    "avvad_lip_decode": (C.c_int, [FP] * 9 + [C.POINTER(LipDesc), FP, C.c_size_t, FP]),
     "avvad_peak_normalize": (C.c_int, [FP, FP, C.c_int, C.c_long, FP]),
     "avvad_standardize": (C.c_int, [FP, FP, FP, FP, C.c_size_t, C.c_int, C.c_int, C.c_float, FP]),
     "avvad_bce_2classes": (C.c_int, [FP, FP, FP, FP, FP, FP, C.c_long, C.c_int, C.c_float, FP]),

@@ -837,3 +837,96 @@ def ibm_from_spectrum(spec, eps=1e-8, ibm_threshold=50, vad=None):
     L.check(L.lib().avvad_target_ibm_from_spectrum(L.ptr(spec), spec.stride(1), spec.stride(0), L.ptr(vad), L.ptr(out), C.byref(d),
                                                    L.ptr(ws), ws.numel() * 4, _stream()), "avvad_target_ibm_from_spectrum")
     return out
+
+
+# --------------------------------------------------------------------------- video front-end: lip DCT frames (no gradient)
+LIP_W = LIP_H = 67
+
+
+def lip_rate(fs=16000, hop=256, fps_in=30):
+    """(p, q): output frames per input frame ``fs / (hop * fps_in)`` in lowest terms -- 25 / 12 for the defaults."""
+    from fractions import Fraction
+    r = Fraction(fs).limit_denominator(10 ** 6) / (Fraction(hop).limit_denominator(10 ** 6) * Fraction(fps_in).limit_denominator(10 ** 6))
+    if r <= 0:
+        raise L.AvvadError("fs, hop and fps_in must be positive")
+    return r.numerator, r.denominator
+
+
+def lip_frame_starts(N, fs=16000, hop=256, fps_in=30):
+    """``[s(0), ..., s(N)]``: output frame ``k`` shows input frame ``i`` for ``s(i) <= k < s(i+1)``, with
+    ``s(i) = round_half_away(i p / q) = (2 i p + q) // (2 q)`` -- our reading of the nearest-timestamp rule of ffmpeg's
+    ``fps`` filter (create_video_train_files_upsampled.py:122).  Integer arithmetic only."""
+    p, q = lip_rate(fs, hop, fps_in)
+    return [(2 * i * p + q) // (2 * q) for i in range(int(N) + 1)]
+
+
+def lip_out_frames(N, fs=16000, hop=256, fps_in=30):
+    """``T_video = s(N)``: frames of an utterance of ``N`` coefficient frames after the rate conversion."""
+    p, q = lip_rate(fs, hop, fps_in)
+    return (2 * int(N) * p + q) // (2 * q)
+
+
+def _int_list(v, name, B=None):
+    out = [int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+    if B is not None and len(out) != B:
+        raise L.AvvadError("%s must hold %d values, got %d" % (name, B, len(out)))
+    return out
+
+
+def lip_decode(coef, n_in, n_out=None, quantize=True, acc=None, mean=None, std=None, eps=1e-8, fs=16000, hop=256, fps_in=30):
+    """Lip-region DCT coefficients -> video crops at the STFT's frame rate (avvad_lip_decode; what the reference's
+    ``process_write_video`` computes offline, create_video_train_files_upsampled.py:105-173): 2-D inverse DCT of every
+    frame, ``(A - min over the utterance) / (largest per-frame range) * 255``, ``rot90(., 3)``, clip to [0, 255] and round
+    towards zero (``quantize``; the codec round trip of the reference is not modelled), each input frame repeated over the
+    output frames ``lip_frame_starts`` assigns to it.
+
+    ``coef``: float32 on the GPU, a padded batch (B, Nmax, 4489) or the utterances' rows packed one after the other
+    (sum N_b, 4489); ``n_in`` the B frame counts.  ``n_out`` (optional, B values: the label frame counts) caps the output
+    lengths.  ``acc`` (``ops.stats_new(1, device)``) receives the written frames' sum / sum of squares / pixel count --
+    what ``accumulate_stats(acc, video.view(B, T, 4489), lengths, nstat=1)`` would add, before any standardisation;
+    ``mean`` / ``std`` (one value each) store ``(x - mean) / (std + eps)``, the standardisation of ``Stats.video``.
+    An utterance of constant frames (range 0) is written as 0.  Returns (video (B, Tmax, 67, 67) on the GPU with frames
+    ``k >= lengths[b]`` zero, lengths LongTensor (B,) on the host)."""
+    c = _dev(coef, "coef")
+    npix = LIP_W * LIP_H
+    if c.dim() not in (2, 3) or c.shape[-1] != npix:
+        raise L.AvvadError("coef must be (B, Nmax, %d) or (sum N, %d), got shape %s" % (npix, npix, tuple(c.shape)))
+    n_in = _int_list(n_in, "n_in")
+    B = len(n_in)
+    if B == 0 or min(n_in) < 0:
+        raise L.AvvadError("n_in must hold at least one non-negative frame count")
+    if c.dim() == 3:
+        if c.shape[0] != B or max(n_in) > c.shape[1]:
+            raise L.AvvadError("n_in must hold %d counts within 0..%d" % (c.shape[0], c.shape[1]))
+        starts = [b * c.shape[1] for b in range(B)]
+    else:
+        starts = [sum(n_in[:b]) for b in range(B)]
+        if sum(n_in) > c.shape[0]:
+            raise L.AvvadError("n_in counts %d frames, coef holds %d" % (sum(n_in), c.shape[0]))
+    rows = c.numel() // npix
+    p, q = lip_rate(fs, hop, fps_in)
+    lens = [(2 * n * p + q) // (2 * q) for n in n_in]
+    if n_out is not None:
+        n_out = _int_list(n_out, "n_out", B)
+        lens = [min(t, max(m, 0)) for t, m in zip(lens, n_out)]
+    if acc is not None and _acc_nstat(acc) != 1:
+        raise L.AvvadError("the video statistics are one scalar pair: acc must come from stats_new(1, device)")
+    if (mean is None) != (std is None):
+        raise L.AvvadError("the fused standardisation needs both mean and std")
+    if mean is not None:
+        mean, std = _dev(mean, "mean").reshape(-1), _dev(std, "std").reshape(-1)
+        if mean.numel() != 1 or std.numel() != 1:
+            raise L.AvvadError("the video statistics are scalars, got %d / %d values" % (mean.numel(), std.numel()))
+    T = max(lens)
+    video = torch.empty(B, T, LIP_H, LIP_W, dtype=torch.float32, device=c.device)
+    if T == 0 or rows == 0:                     # nothing to decode, nothing to count
+        return video.zero_(), torch.LongTensor(lens)
+    if c.data_ptr() % 16:
+        c = c.clone()
+    d = L.LipDesc(B, max(n_in), rows, T, LIP_W, LIP_H, p, q, int(bool(quantize)), float(eps))
+    ws = _ws(L.lib().avvad_lip_decode_workspace(C.byref(d)), c.device)
+    idx = torch.tensor([starts, n_in, n_out if n_out is not None else lens, [0] * B], dtype=torch.int32).to(c.device)
+    L.check(L.lib().avvad_lip_decode(L.ptr(c), L.ptr(idx[0]), L.ptr(idx[1]), L.ptr(idx[2]) if n_out is not None else None, L.ptr(video),
+                                     L.ptr(idx[3]), L.ptr(acc), L.ptr(mean), L.ptr(std), C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()),
+            "avvad_lip_decode")
+    return video, torch.LongTensor(lens)

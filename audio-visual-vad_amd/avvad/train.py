@@ -6,8 +6,9 @@ train-set statistics when given (``std_norm``: ``(x - mean.T) / (std + eps).T``,
 per-sequence masked BCE summed over the batch, backward, Adam, per-sequence accuracy/precision/recall/F1 -- with the
 reference's Python loops over the batch replaced by single fused calls, ``nn.DataParallel`` replaced by one process per
 GPU + bucketed RCCL all-reduce, and a synthetic data source for training (the reference's HDF5 readers are out of scope,
-SURVEY.md 2.1; h5py and torchaudio are not installed in this image) or (noisy, clean) wav pairs whose labels are computed
-on the GPU from the clean files (``WavPairs``, ``wav_pair_step``).  The per-utterance evaluator of the audio network
+SURVEY.md 2.1; h5py and torchaudio are not installed in this image), (noisy, clean) wav pairs whose labels are computed
+on the GPU from the clean files (``WavPairs``, ``wav_pair_step``), or such pairs with the utterance's lip-region DCT
+coefficients, decoded to video frames on the GPU (``AVFiles``, ``av_file_step``).  The per-utterance evaluator of the audio network
 (``process_utt``, ``evaluate_audio_net.py:107-180``) runs the reference's whole chain on real waveforms: peak
 normalisation -> STFT -> power -> log -> crop to the label length -> standardise -> classifier -> sigmoid -> threshold."""
 import os
@@ -228,6 +229,100 @@ def wav_pair_stats(pairs, device, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_pe
     return Stats(audio_mean=mean.cpu().numpy().reshape(-1, 1), audio_std=std.cpu().numpy().reshape(-1, 1), eps=eps)
 
 
+def read_av_files(path):
+    """A text file with one "noisy clean coefficients.npy" triple of paths per line (blank lines and # comments skipped)."""
+    triples = []
+    with open(path) as f:
+        for line in f:
+            line = line.split("#", 1)[0].strip()
+            if line:
+                noisy, clean, coef = line.split()
+                triples.append((noisy, clean, coef))
+    return triples
+
+
+class AVFiles(torch.utils.data.Dataset):
+    """(noisy wav, clean wav, lip coefficients) triples: ``WavPairs`` plus the utterance's lip-region DCT coefficients, an
+    ``.npy`` of shape (N, 4489) at 30 frames/s -- the matrix of NTCD-TIMIT's ``matlab_raw`` files, written with one
+    ``numpy.save`` (the reference reads it from the .mat file, create_video_train_files_upsampled.py:110-112).
+    ``files``: a list of triples or a text file of them.  Items: (noisy (L,), clean (L,), L, coef (N, 4489) float32)."""
+
+    def __init__(self, files):
+        self.files = read_av_files(files) if isinstance(files, str) else [tuple(p) for p in files]
+        self.pairs = WavPairs([(n, c) for n, c, _ in self.files])
+
+    def __len__(self):
+        return len(self.files)
+
+    def __getitem__(self, i):
+        noisy, clean, n = self.pairs[i]
+        coef = load_coefficients(self.files[i][2])
+        return noisy, clean, n, coef
+
+    @staticmethod
+    def collate(batch):
+        """-> (sample lengths (B,), noisy (B, Lmax), clean (B, Lmax), coefficient frame counts (B,), coef (sum N, 4489)):
+        the waveforms zero-padded, the coefficient rows packed one utterance after the other."""
+        lens, noisy, clean = WavPairs.collate([item[:3] for item in batch])
+        return lens, noisy, clean, torch.LongTensor([item[3].shape[0] for item in batch]), torch.cat([item[3] for item in batch], 0)
+
+
+def load_coefficients(path):
+    """(N, 4489) float32 lip coefficients of one utterance from an ``.npy`` (doubles are cast, as the caller of the
+    decoder must)."""
+    import numpy as np
+    x = np.load(path, allow_pickle=False)
+    if x.ndim != 2 or x.shape[1] != ops.LIP_W * ops.LIP_H:
+        raise ValueError("%s: expected (N, %d) coefficients, got shape %s" % (path, ops.LIP_W * ops.LIP_H, x.shape))
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+
+
+def av_file_step(batch, device, labels, stats=None, acc=None, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS, fps_in=30):
+    """An ``AVFiles.collate`` batch -> (frame lengths, features (B, T, 513), video (B, T, 67, 67), target (B, T, y_dim)) on
+    the GPU: ``wav_pair_step`` for the audio side and the labels, and the lip coefficients decoded and resampled to the
+    STFT's frame rate (``ops.lip_decode``), capped to each utterance's label frame count and standardised with the video
+    scalars of ``stats`` in the same pass.  ``acc`` (``ops.stats_new(1, device)``) collects the unstandardised frames'
+    statistics.  Where the video is shorter than the labels the sequence ends with the video, as in the reference
+    (create_video_train_files_upsampled.py:237-241)."""
+    lens, noisy, clean, n_coef, coef = batch
+    frames, x, target = wav_pair_step((lens, noisy, clean), device, labels, stats, fs, wlen_sec, hop_percent, eps)
+    mean = std = None
+    if stats is not None:
+        mean, std = stats.get("video_mean", device), stats.get("video_std", device)
+    nfft = int(wlen_sec * fs)
+    video, vlen = ops.lip_decode(coef.to(device, non_blocking=True), n_coef, frames.tolist(), acc=acc, mean=mean, std=std,
+                                 eps=stats.eps if stats is not None else eps, fs=int(fs), hop=int(hop_percent * nfft), fps_in=fps_in)
+    T = video.shape[1]
+    if T < x.shape[1]:
+        x, target = x[:, :T].contiguous(), target[:, :T].contiguous()
+    return vlen.to(device), x, video, target
+
+
+def av_file_stats(files, device, batch_size=16, eps=EPS):
+    """Train-set statistics over (noisy, clean, coefficients) triples -> ``Stats`` with the audio per-bin vectors
+    (``wav_pair_stats``) and the video scalars: the decoded frames' sum / sum of squares / pixel count, accumulated in the
+    pass that writes them (``ops.lip_decode(acc=...)``), each utterance capped to its label frame count -- what
+    create_video_train_files_upsampled.py:294-310, 350-361 computes offline.  Ranks share the files as ``wav_pair_stats``
+    does."""
+    import torch.distributed as dist
+    if not isinstance(files, AVFiles):
+        files = AVFiles(files)
+    multi = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
+    made = wav_pair_stats(files.pairs, device, batch_size=batch_size, eps=eps)
+    acc = ops.stats_new(1, device)
+    loader = torch.utils.data.DataLoader(torch.utils.data.Subset(files, rank_shard(len(files), rank, world)),
+                                         batch_size=batch_size, shuffle=False, collate_fn=AVFiles.collate)
+    for lens, _, _, n_coef, coef in loader:
+        n_label = [ops.target_frames(int(n))[1] for n in lens]
+        ops.lip_decode(coef.to(device, non_blocking=True), n_coef, n_label, acc=acc)
+    if multi:
+        dist.all_reduce(acc)
+    mean, std = ops.finalize_stats(acc)
+    made._raw.update(video_mean=mean.cpu().numpy().reshape(1, 1), video_std=std.cpu().numpy().reshape(1, 1))
+    return made
+
+
 def forward_batch(model, kind, batch, device, waveform, stats=None):
     """H2D, ``std_norm`` standardisation (spectrogram features and video; raw waveforms are not standardised in the
     reference either), forward."""
@@ -244,7 +339,8 @@ def forward_batch(model, kind, batch, device, waveform, stats=None):
 
 
 def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log=None, log_interval=10, stats=None, prepare=None):
-    """``prepare`` (wav pairs): batch -> (lengths, features, target) on the GPU, the model's forward follows."""
+    """``prepare`` (wav pairs, av files): batch -> (lengths, the model's inputs ..., target) on the GPU, the model's forward
+    follows."""
     from packages.models.utils import batch_binary_cross_entropy, batch_f1
     train = opt is not None
     model.train(train)
@@ -253,8 +349,8 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
         if prepare is None:
             lengths, logits, y = forward_batch(model, kind, batch, device, waveform, stats)
         else:
-            lengths, x, y = prepare(batch)
-            logits = model(x, lengths)
+            lengths, *x, y = prepare(batch)
+            logits = model(*x, lengths)
         loss = batch_binary_cross_entropy(logits, y, lengths, EPS)       # sum over sequences (train_AV_net.py:298-302)
         if train:
             loss.backward()
@@ -275,7 +371,7 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
 
 
 def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_size=16, n_items=64, lr=1e-4,
-               freeze_features=False, out_dir=None, stats=None, wav_pairs=None, compute_stats=False):
+               freeze_features=False, out_dir=None, stats=None, wav_pairs=None, compute_stats=False, av_files=None):
     """The body of ``scripts/train_{audio,video,AV}_net.py``; settings come from the caller's module-level constants
     (the reference's "config system") and may be overridden by AVVAD_* environment variables.
 
@@ -285,7 +381,14 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
 
     ``compute_stats``: with ``wav_pairs`` and no audio statistics in ``stats``, the train-set mean / std of the features
     are computed over the training pairs on the GPU before the first epoch (``wav_pair_stats``), saved under ``out_dir``
-    (``Stats.save``: the directory the evaluate scripts' ``stats_dir`` takes) and used for training."""
+    (``Stats.save``: the directory the evaluate scripts' ``stats_dir`` takes) and used for training.
+
+    ``av_files`` (video and AV networks, ``kind`` "video" / "AV", spectrogram input): a list of (noisy wav, clean wav,
+    coefficient .npy) triples or a text file of them (``AVFiles``); the lip frames are decoded on the GPU in the step
+    (``av_file_step``).  ``compute_stats`` then also fills the video scalars (``av_file_stats``)."""
+    if av_files is not None and (kind.lower() not in ("video", "av") or waveform or wav_pairs is not None):
+        raise ValueError("av_files trains the video or the AV network on spectrograms and lip coefficients; give either "
+                         "wav_pairs (audio) or av_files, and no WaveNet waveform input")
     if wav_pairs is not None and (kind != "audio" or waveform):
         raise ValueError("wav_pairs trains the audio network on spectrograms; video / AV frames and WaveNet waveform "
                          "training on wav pairs are not supported")
@@ -306,7 +409,16 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     reducer = avd.BucketReducer(opt.params, opt.flat_grad, opt.offsets,
                                 names=[n for n, q in model.named_parameters() if q.requires_grad]) if world > 1 else None
     prepare = None
-    if wav_pairs is None:
+    if av_files is not None:
+        pairs = AVFiles(av_files)
+        labels = labels_for_ydim(model.y_dim)
+        collate = AVFiles.collate
+        ds_train = ds_valid = torch.utils.data.Subset(pairs, range(rank, len(pairs), world))
+        if kind.lower() == "video":
+            prepare = lambda batch: (lambda r: (r[0], r[2], r[3]))(av_file_step(batch, device, labels, stats))   # noqa: E731
+        else:
+            prepare = lambda batch: av_file_step(batch, device, labels, stats)   # noqa: E731
+    elif wav_pairs is None:
         collate = pick_collate(kind, waveform)
         per_rank = n_items // world
         ds_train = SyntheticAV(per_rank, kind, waveform=waveform, seed=1 + rank)
@@ -340,6 +452,16 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         if rank == 0:
             stats.save(out_dir)
         log("- Train-set statistics over {} pairs in {:.1f} s, saved in {}".format(len(pairs), time.perf_counter() - t0, out_dir))
+    if compute_stats and av_files is not None and (stats is None or stats.get("video_mean", device) is None):
+        t0 = time.perf_counter()
+        made = av_file_stats(pairs, device, batch_size=batch_size)
+        if stats is None:
+            stats = made
+        else:
+            stats._raw.update({k: v for k, v in made._raw.items() if stats._raw.get(k) is None})
+        if rank == 0:
+            stats.save(out_dir)
+        log("- Train-set statistics over {} utterances in {:.1f} s, saved in {}".format(len(pairs), time.perf_counter() - t0, out_dir))
     for epoch in range(1, epochs + 1):
         t0 = time.perf_counter()
         tr = run_epoch(model, kind, mk(ds_train, True), device, waveform, opt, reducer, log, stats=stats, prepare=prepare)
@@ -415,7 +537,7 @@ def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, ep
 
 
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
-                  stats=None, labels=None, clean_of=None):
+                  stats=None, labels=None, clean_of=None, av_files=None):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
@@ -424,8 +546,10 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
     reference's plumbing on real audio; ``labels`` optionally maps a path to its label tensor (frame count crop + saved
     next to the predictions for ``run_metrics``).  ``clean_of`` maps each noisy path of ``wav_list`` to its clean
     counterpart: the labels are then the clean file's VAD (peak-normalised, the training pipeline's framing), computed on
-    the GPU, in place of ``labels``.  Without ``wav_list`` a synthetic ragged data source stands in for the HDF5
-    datasets."""
+    the GPU, in place of ``labels``.  ``av_files`` (video and AV networks): (noisy wav, clean wav, coefficient .npy)
+    triples or a text file of them; every utterance goes through ``av_file_step`` on its own -- features and decoded lip
+    frames standardised with ``stats``, the clean file's VAD as the label.  Without either a synthetic ragged data
+    source stands in for the HDF5 datasets."""
     rank, world, local = avd.init_from_env("nccl")
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
@@ -438,7 +562,20 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
         p.requires_grad = False
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.perf_counter()
-    if wav_list is not None:
+    if av_files is not None:
+        if kind.lower() not in ("video", "av") or waveform or wav_list is not None:
+            raise ValueError("av_files drives the video and AV evaluators on spectrograms; wav_list is the audio evaluator's")
+        files = AVFiles(av_files)
+        with torch.no_grad():
+            for i in range(rank, len(files), world):
+                lengths, x, video, y = av_file_step(AVFiles.collate([files[i]]), device, "vad_labels", stats)
+                logits = model(video, lengths) if kind.lower() == "video" else model(x, video, lengths)
+                soft = torch.sigmoid(logits[..., 0].detach().cpu())
+                base = os.path.join(out_dir, os.path.splitext(os.path.basename(files.files[i][0]))[0])
+                torch.save((soft > 0.5).int(), base + "_y_hat_hard.pt")
+                torch.save(soft, base + "_y_hat_soft.pt")
+                torch.save(y[:, :int(lengths[0]), 0].int().cpu(), base + "_label.pt")
+    elif wav_list is not None:
         if kind != "audio":
             raise ValueError("wav_list drives the audio evaluator (evaluate_audio_net.py); video needs the HDF5 readers")
         with torch.no_grad():

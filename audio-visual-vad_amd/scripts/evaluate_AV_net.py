@@ -23,6 +23,8 @@ center = False
 pad_at_end = True
 classif_dir = None        # checkpoint written by scripts/train_AV_net.py or by the reference (same state_dict keys)
 classif_data_dir = 'eval_out'
+av_files = None           # text file with one "noisy.wav clean.wav lips.npy" triple per line (avvad.train.AVFiles): score real
+                          # utterances, the lip coefficients decoded on the GPU; None: synthetic data
 use_mcb = True
 stats_dir = None          # directory holding trainset_{audio,video}_{mean,std}.npy
 WAVENET = False           # True: raw waveforms through the WaveNet encoder (the hook the reference left commented out)
@@ -37,4 +39,4 @@ def make_model():
 
 if __name__ == '__main__':
     stats = Stats.load(stats_dir, eps) if (std_norm and stats_dir) else None
-    evaluate_main('av', make_model, checkpoint=classif_dir, waveform=WAVENET, out_dir=classif_data_dir, stats=stats)
+    evaluate_main('av', make_model, checkpoint=classif_dir, waveform=WAVENET, out_dir=classif_data_dir, stats=stats, av_files=av_files)

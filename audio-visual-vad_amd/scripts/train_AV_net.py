@@ -23,6 +23,10 @@ end_epoch = 1
 eps = 1e-8
 std_norm = True           # standardise inputs with the train-set statistics when models/<model_name>/trainset_*.npy exist
 model_name = 'AV_Classif_synthetic'
+av_files = None           # text file with one "noisy.wav clean.wav lips.npy" triple per line: train on real data, the lip
+                          # coefficients ((N, 4489) at 30 frames/s) decoded on the GPU, labels from the clean files; None: synthetic
+compute_stats = False     # with av_files and no trainset_*.npy yet: compute the train-set statistics (audio per bin, video
+                          # scalars) on the GPU before the first epoch and save them in models/<model_name>
 use_mcb = True
 freeze_resnet = False
 WAVENET = False           # True: raw waveforms through the WaveNet encoder (the hook the reference left commented out)
@@ -38,4 +42,5 @@ def make_model():
 if __name__ == '__main__':
     stats = Stats.load('models/' + model_name, eps) if std_norm else None
     train_main('av', make_model, model_name, waveform=WAVENET, epochs=end_epoch, batch_size=batch_size,
-               lr=learning_rate, stats=stats, freeze_features=freeze_resnet)
+               lr=learning_rate, stats=stats, freeze_features=freeze_resnet, av_files=av_files,
+               compute_stats=compute_stats and std_norm)

@@ -22,6 +22,10 @@ end_epoch = 1
 eps = 1e-8
 std_norm = True           # standardise inputs with the train-set statistics when models/<model_name>/trainset_*.npy exist
 model_name = 'video_Classif_synthetic'
+av_files = None           # text file with one "noisy.wav clean.wav lips.npy" triple per line: train on real data, the lip
+                          # coefficients ((N, 4489) at 30 frames/s) decoded on the GPU, labels from the clean files; None: synthetic
+compute_stats = False     # with av_files and no trainset_*.npy yet: compute the train-set statistics (audio per bin, video
+                          # scalars) on the GPU before the first epoch and save them in models/<model_name>
 
 
 def make_model():
@@ -31,4 +35,4 @@ def make_model():
 if __name__ == '__main__':
     stats = Stats.load('models/' + model_name, eps) if std_norm else None
     train_main('video', make_model, model_name, waveform=False, epochs=end_epoch, batch_size=batch_size,
-               lr=learning_rate, stats=stats)
+               lr=learning_rate, stats=stats, av_files=av_files, compute_stats=compute_stats and std_norm)

@@ -418,6 +418,45 @@ int avvad_target_ibm_from_spectrum(const float* spec, long stride_t, long stride
                                    const avvad_target_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
+ * Video front-end: lip-region DCT coefficients -> the 67 x 67 crops of the trunk, at the STFT's frame rate
+ * Replaces: scripts/create_video_train_files_upsampled.py:105-173 (process_write_video: scipy's unnormalised type-2 idct
+ *   along both axes of every frame, (A - min over the utterance) / (largest per-frame max - min) * 255, np.rot90(., 3),
+ *   ffmpeg's `fps` filter through a temporary mp4) and the pixel statistics of :294-310, :350-361.
+ * coef [rows][W*H] holds the utterances' coefficient frames; utterance b owns the n_in[b] rows from starts[b] on (a
+ * packed or a padded batch alike).  video [B][T][H][W]; output frame k of utterance b shows input frame i for
+ *   s(i) <= k < s(i+1),  s(i) = (2 i p + q) / (2 q)   (i p / q rounded half away from zero),
+ * p / q = fs / (hop * fps_in) in lowest terms (25 / 12 for 16 kHz, hop 256, 30 frames/s), up to
+ * out_len[b] = min(s(n_in[b]), n_out[b], T); frames k >= out_len[b] are written as 0.  n_out may be NULL (no cap).
+ * quantize != 0: clip to [0, 255] and round towards zero (the uint8 conversion of the reference's frame writer); the
+ * codec round trip that follows there is not modelled.  An utterance whose frames are all constant (range 0, a division
+ * by zero in the reference) is written as 0.  No reduction crosses an utterance.
+ * Fused extras: acc (may be NULL) is a statistics accumulator with nstat == 1 (avvad_stats_*): the written frames'
+ * sum, sum of squares and pixel count are ADDED to it, exactly what avvad_stats_accumulate(video, out_len, nstat = 1)
+ * adds, taken before the standardisation; mean / std_ (one float each on the device, both or neither) store
+ * (x - mean) / (std + norm_eps) instead of x.  Double accumulation in a fixed order, no floating-point atomics:
+ * bit-identical run to run and independent of "max_cus".
+ * starts / n_in / n_out / out_len are device int32 [B]; coef and ws are 16-byte aligned.  The workspace holds the
+ * un-normalised frames between the two passes (rows * W * H floats) besides per-frame minima, maxima and partial sums:
+ * the utterance's minimum and range are needed before a frame can be written, and re-reading the frames measured faster
+ * than forming them twice.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int B;           /* utterances                                                          */
+  int n_max;       /* the largest n_in[b] (sizes the grid only)                           */
+  long rows;       /* rows of coef                                                        */
+  int T;           /* frame pitch of video (at least the largest out_len[b])              */
+  int W, H;        /* 67, 67                                                              */
+  int p, q;        /* output frames per input frame, in lowest terms                      */
+  int quantize;    /* clip and truncate to 8-bit levels                                   */
+  float norm_eps;  /* eps of the fused standardisation                                    */
+} avvad_lip_desc;
+/* Bytes of workspace; 0 on a bad descriptor (B, rows, n_max, T, p, q <= 0, W or H != 67, B or T > 65535, ...). */
+size_t avvad_lip_decode_workspace(const avvad_lip_desc* d);
+int avvad_lip_decode(const float* coef, const int* starts, const int* n_in, const int* n_out, float* video, int* out_len,
+                     double* acc, const float* mean, const float* std_, const avvad_lip_desc* d, void* ws, size_t ws_bytes,
+                     avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
  * Masked BCE-with-eps loss, summed over sequences
  * Replaces: binary_cross_entropy packages/models/utils.py:108-113 and its caller
  *   loop scripts/train_AV_net.py:298-301  (per-sequence mean over valid frames
