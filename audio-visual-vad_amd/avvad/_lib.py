@@ -115,6 +115,12 @@ SIGNATURES = {
     "avvad_lstm_workspace": (C.c_size_t, [C.POINTER(LstmDesc)]),
     "avvad_lstm_layer_fwd": (C.c_int, [FP, FP, FP, FP, FP, FP, C.POINTER(LstmDesc), FP, C.c_size_t, FP]),
     "avvad_lstm_layer_bwd": (C.c_int, [FP, FP, FP, FP, FP, FP, FP, FP, FP, FP, C.POINTER(LstmDesc), FP, C.c_size_t, FP]),
+    "avvad_lstm_state_workspace": (C.c_size_t, [C.POINTER(LstmDesc)]),
+    "avvad_lstm_layer_fwd_state": (C.c_int, [FP] * 10 + [C.POINTER(LstmDesc), FP, C.c_size_t, FP]),
+    "avvad_wavenet_stream_state_bytes": (C.c_size_t, [C.POINTER(WavenetDesc)]),
+    "avvad_wavenet_stream_workspace": (C.c_size_t, [C.POINTER(WavenetDesc)]),
+    "avvad_wavenet_stream_fwd": (C.c_int, [FP, C.POINTER(WavenetPtrs), FP, FP, FP, C.c_int, FP, C.c_int,
+                                           C.POINTER(WavenetDesc), FP, C.c_size_t, FP]),
     "avvad_mcb_workspace": (C.c_size_t, [C.POINTER(McbDesc)]),
     "avvad_mcb_fusion_fwd": (C.c_int, [FP] * 11 + [C.POINTER(McbDesc), FP, C.c_size_t, FP]),
     "avvad_mcb_fusion_bwd": (C.c_int, [FP] * 12 + [C.POINTER(McbDesc), FP, C.c_size_t, FP]),

@@ -293,6 +293,108 @@ class WavenetFn(torch.autograd.Function):
         return (dwave, None) + grads
 
 
+# --------------------------------------------------------------------------- streaming inference (csrc/stream.hip)
+def _lstm_check(lstm_module):
+    if lstm_module.bidirectional or not lstm_module.bias or lstm_module.proj_size:
+        raise L.AvvadError("only the unidirectional, biased LSTM of the reference is supported")
+
+
+def lstm_stack_state(x, lengths, lstm_module, state=None, out=None):
+    """The parameters of an ``nn.LSTM`` container over the next ``T`` steps of ``B`` independent rows, state in and out
+    (inference only).  x (B,T,In); ``lengths`` per-row step counts in [0, T]: padded output steps are zero, a row's state
+    stops at its length, length 0 passes it through bit for bit.  ``state`` = (h, c), each (num_layers, B, H) like
+    torch's, or None for zeros; ``out`` = (h, c) tensors to receive the new state (may be ``state`` itself: in place),
+    or None for fresh ones.  -> (y (B,T,H), (h_n, c_n))."""
+    _lstm_check(lstm_module)
+    x = _dev(x, "x")
+    if x.dim() != 3:
+        raise L.AvvadError("x must be (B, T, In), got %s" % (tuple(x.shape),))
+    B, T, In = x.shape
+    nl, H = lstm_module.num_layers, lstm_module.hidden_size
+    if In != lstm_module.input_size or B < 1 or T < 1:
+        raise L.AvvadError("x %s does not fit an LSTM with input size %d" % (tuple(x.shape), lstm_module.input_size))
+
+    def pair(p, what):
+        h, c = p
+        for t in (h, c):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
+                    tuple(t.shape) != (nl, B, H):
+                raise L.AvvadError("%s must be two contiguous float32 GPU tensors of shape %s" % (what, (nl, B, H)))
+        return h, c
+    h0, c0 = pair(state, "state") if state is not None else (None, None)
+    if out is not None:
+        hn, cn = pair(out, "out")
+    else:
+        hn = torch.empty(nl, B, H, dtype=torch.float32, device=x.device)
+        cn = torch.empty_like(hn)
+    lens32 = lengths_i32(lengths, x.device)
+    if lens32.numel() != B:
+        raise L.AvvadError("lengths must have one entry per row")
+    y = x
+    with torch.no_grad():
+        for l in range(nl):
+            w_ih, w_hh, b_ih, b_hh = (_dev(getattr(lstm_module, "%s_l%d" % (n, l)), n)
+                                      for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+            d = L.LstmDesc(B, T, y.shape[2], H, lens32.data_ptr(), 0)
+            ws = _ws(L.lib().avvad_lstm_state_workspace(C.byref(d)), x.device)
+            y_l = torch.empty(B, T, H, dtype=torch.float32, device=x.device)
+            L.check(L.lib().avvad_lstm_layer_fwd_state(
+                L.ptr(y), L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_ih), L.ptr(b_hh), L.ptr(h0[l]) if h0 is not None else None,
+                L.ptr(c0[l]) if c0 is not None else None, L.ptr(y_l), L.ptr(hn[l]), L.ptr(cn[l]), C.byref(d), L.ptr(ws),
+                ws.numel() * 4, _stream()), "avvad_lstm_layer_fwd_state")
+            y = y_l
+    return y, (hn, cn)
+
+
+def _stream_desc(enc, B, Lc):
+    n = len(enc.dilations)
+    dil_arr = (C.c_int * max(1, n))(*enc.dilations)
+    d = L.WavenetDesc(B, Lc, enc.quantization_channel, enc.en_residual_channel, enc.en_dilation_channel,
+                      enc.en_bottleneck_width, enc.filter_width, 1, n, dil_arr, int(enc.use_bias), 0, 0)
+    return d, dil_arr
+
+
+def wavenet_stream_state(enc, B, device):
+    """Zeroed state blocks (B, floats) of the streaming encoder for ``B`` rows of the ``wavenet_autoencoder`` ``enc``:
+    all zeros is "start of utterance"."""
+    d, _keep = _stream_desc(enc, B, 1)
+    nbytes = L.lib().avvad_wavenet_stream_state_bytes(C.byref(d))
+    if nbytes == 0:
+        raise L.AvvadError("streaming encoder: bad configuration")
+    return torch.zeros(B, nbytes // 4, dtype=torch.float32, device=device)
+
+
+def wavenet_stream(chunk, n_valid, skip, enc, state, k, out_frames):
+    """The next samples of ``B`` rows through the encoder (inference only).  chunk (B,qc,n); ``n_valid`` / ``skip``
+    per-row counts (lists or int32 GPU tensors): row b consumes n_valid[b] columns, drops its first skip[b] output
+    columns (remaining warm-up) and averages the rest in frames of ``k`` columns.  ``state`` (from
+    ``wavenet_stream_state``) is updated in place.  -> (B, out_frames, Bn), frame-major; frames a row does not fill are
+    zero.  The caller keeps (n_valid - skip) % k == 0 wherever n_valid > skip (``avvad.stream`` does)."""
+    chunk = _dev(chunk, "chunk")
+    if chunk.dim() != 3 or chunk.shape[1] != enc.quantization_channel or chunk.shape[2] < 1:
+        raise L.AvvadError("chunk must be (B, %d, n >= 1), got %s" % (enc.quantization_channel, tuple(chunk.shape)))
+    B, _, Lc = chunk.shape
+    d, _keep = _stream_desc(enc, B, Lc)
+    nbytes = L.lib().avvad_wavenet_stream_state_bytes(C.byref(d))
+    if not isinstance(state, torch.Tensor) or not state.is_cuda or state.dtype != torch.float32 or \
+            not state.is_contiguous() or tuple(state.shape) != (B, nbytes // 4):
+        raise L.AvvadError("state must be the contiguous float32 GPU tensor of wavenet_stream_state(enc, %d, device)" % B)
+    nv, sk = lengths_i32(n_valid, chunk.device), lengths_i32(skip, chunk.device)
+    if nv.numel() != B or sk.numel() != B:
+        raise L.AvvadError("n_valid and skip must have one entry per row")
+    params = [enc.en_causal_layer.weight, enc.en_causal_layer.bias, enc.bottleneck_layer.weight, enc.bottleneck_layer.bias]
+    for dil, dense in zip(enc.en_dilation_layer_stack, enc.en_dense_layer_stack):
+        params += [dil.weight, dil.bias, dense.weight, dense.bias]
+    params = tuple(None if t is None else _dev(t.detach(), "param") for t in params)
+    p, _keep2 = WavenetFn._ptrs(params, len(enc.dilations))
+    ws = _ws(L.lib().avvad_wavenet_stream_workspace(C.byref(d)), chunk.device)
+    out = torch.empty(B, int(out_frames), enc.en_bottleneck_width, dtype=torch.float32, device=chunk.device)
+    L.check(L.lib().avvad_wavenet_stream_fwd(L.ptr(chunk), C.byref(p), L.ptr(state), L.ptr(nv), L.ptr(sk), int(k),
+                                             L.ptr(out) if out.numel() else None, int(out_frames), C.byref(d), L.ptr(ws),
+                                             ws.numel() * 4, _stream()), "avvad_wavenet_stream_fwd")
+    return out
+
+
 # --------------------------------------------------------------------------- ResNet-18 trunk
 class TrunkFn(torch.autograd.Function):
     """frames (N,H,W) -> (N,512).  tensors: 20 conv_w, 20 bn_w, 20 bn_b, 20 running_mean, 20 running_var

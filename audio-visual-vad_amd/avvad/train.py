@@ -18,6 +18,7 @@ import torch
 
 from . import dist as avd
 from . import ops
+from . import stream
 from .optim import FlatAdam
 
 EPS = 1e-8
@@ -323,19 +324,28 @@ def av_file_stats(files, device, batch_size=16, eps=EPS):
     return made
 
 
-def forward_batch(model, kind, batch, device, waveform, stats=None):
+def forward_batch(model, kind, batch, device, waveform, stats=None, chunk_frames=None):
     """H2D, ``std_norm`` standardisation (spectrogram features and video; raw waveforms are not standardised in the
-    reference either), forward."""
+    reference either), forward.  ``chunk_frames``: evaluate through a streaming session in chunks of that many frames
+    (``avvad.stream``; eval-mode models only) instead of one whole-length forward."""
     lengths = batch[0].to(device)
     data = [t.to(device, non_blocking=True) for t in batch[1:]]
     y = data[-1]
     if kind == "audio":
         x = data[0].unsqueeze(1) if waveform else (stats.audio(data[0]) if stats else data[0])
+        if chunk_frames is not None:
+            return lengths, stream.forward_chunked(model, x, None, lengths, chunk_frames), y
         return lengths, model(x, lengths), y
     if kind == "video":
-        return lengths, model(stats.video(data[0]) if stats else data[0], lengths), y
+        v = stats.video(data[0]) if stats else data[0]
+        if chunk_frames is not None:
+            return lengths, stream.forward_chunked(model, None, v, lengths, chunk_frames), y
+        return lengths, model(v, lengths), y
     a = data[0].unsqueeze(1) if waveform else (stats.audio(data[0]) if stats else data[0])
-    return lengths, model(a, stats.video(data[1]) if stats else data[1], lengths), y
+    v = stats.video(data[1]) if stats else data[1]
+    if chunk_frames is not None:
+        return lengths, stream.forward_chunked(model, a, v, lengths, chunk_frames), y
+    return lengths, model(a, v, lengths), y
 
 
 def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log=None, log_interval=10, stats=None, prepare=None):
@@ -521,23 +531,30 @@ def clean_vad_labels(clean_path, n_noisy, device, fs=16e3, wlen_sec=64e-3, hop_p
     return vad.view(1, -1)
 
 
-def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, eps=EPS, std_norm=True):
+def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, eps=EPS, std_norm=True, chunk_frames=None):
     """One utterance through the reference's evaluator (``evaluate_audio_net.py:107-180``; with ``video`` (T,67,67) the AV
     variant ``evaluate_AV_net.py:148-250``): returns (y_hat_soft, y_hat_hard) on the CPU, shaped (1, T) like the
-    reference's ``y_hat_soft[..., 0]``."""
+    reference's ``y_hat_soft[..., 0]``.  ``chunk_frames``: score through a streaming session (``avvad.stream``), that
+    many frames per step; the features are still formed from the whole utterance, because its peak normalisation is a
+    statistic of all of it."""
     x = audio_features(x_t, stats, n_label_frames, eps=eps, std_norm=std_norm)
     lengths = [x.shape[1]]
-    if video is None:
+    v = None
+    if video is not None:
+        v = video[None, :x.shape[1]].contiguous()
+        v = stats.video(v) if (stats is not None and std_norm) else v
+    if chunk_frames is not None:
+        y = stream.forward_chunked(classifier, x, v, lengths, chunk_frames)
+    elif video is None:
         y = classifier(x, lengths)
     else:
-        v = video[None, :x.shape[1]].contiguous()
-        y = classifier(x, stats.video(v) if (stats is not None and std_norm) else v, lengths)
+        y = classifier(x, v, lengths)
     soft = torch.sigmoid(y[..., 0].detach().cpu())
     return soft, (soft > 0.5).int()
 
 
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
-                  stats=None, labels=None, clean_of=None, av_files=None):
+                  stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
@@ -549,7 +566,9 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
     the GPU, in place of ``labels``.  ``av_files`` (video and AV networks): (noisy wav, clean wav, coefficient .npy)
     triples or a text file of them; every utterance goes through ``av_file_step`` on its own -- features and decoded lip
     frames standardised with ``stats``, the clean file's VAD as the label.  Without either a synthetic ragged data
-    source stands in for the HDF5 datasets."""
+    source stands in for the HDF5 datasets.  ``chunk_frames``: every utterance is scored through a streaming session
+    (``avvad.stream``) in chunks of that many frames -- same files, same values up to summation order; ``None`` is the
+    whole-length forward."""
     rank, world, local = avd.init_from_env("nccl")
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
@@ -569,7 +588,10 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
         with torch.no_grad():
             for i in range(rank, len(files), world):
                 lengths, x, video, y = av_file_step(AVFiles.collate([files[i]]), device, "vad_labels", stats)
-                logits = model(video, lengths) if kind.lower() == "video" else model(x, video, lengths)
+                if chunk_frames is not None:
+                    logits = stream.forward_chunked(model, None if kind.lower() == "video" else x, video, lengths, chunk_frames)
+                else:
+                    logits = model(video, lengths) if kind.lower() == "video" else model(x, video, lengths)
                 soft = torch.sigmoid(logits[..., 0].detach().cpu())
                 base = os.path.join(out_dir, os.path.splitext(os.path.basename(files.files[i][0]))[0])
                 torch.save((soft > 0.5).int(), base + "_y_hat_hard.pt")
@@ -587,7 +609,8 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                     y = clean_vad_labels(clean_of[wav_list[i]], x_t.numel(), device)
                 else:
                     y = labels.get(wav_list[i]) if labels else None
-                soft, hard = process_utt(model, x_t.to(device), stats, None if y is None else y.shape[-1])
+                soft, hard = process_utt(model, x_t.to(device), stats, None if y is None else y.shape[-1],
+                                         chunk_frames=chunk_frames)
                 base = os.path.join(out_dir, os.path.splitext(os.path.basename(wav_list[i]))[0])
                 torch.save(hard, base + "_y_hat_hard.pt")
                 torch.save(soft, base + "_y_hat_soft.pt")
@@ -599,7 +622,7 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
         with torch.no_grad():
             for i in range(rank, n_items, world):
                 batch = collate([ds[i]])
-                lengths, logits, y = forward_batch(model, kind, batch, device, waveform, stats)
+                lengths, logits, y = forward_batch(model, kind, batch, device, waveform, stats, chunk_frames)
                 soft = torch.sigmoid(logits[..., 0].detach().cpu())                      # (1,T), evaluate_AV_net.py:236-240
                 torch.save(soft, os.path.join(out_dir, "utt%04d_y_hat_soft.pt" % i))
                 torch.save((soft > 0.5).int(), os.path.join(out_dir, "utt%04d_y_hat_hard.pt" % i))

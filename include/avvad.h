@@ -264,6 +264,47 @@ int avvad_lstm_layer_bwd(const float* x, const float* w_ih, const float* w_hh, c
                          avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
+ * Streaming (stateful, chunked) inference.  Inference only: nothing is kept for a backward pass, and a descriptor with
+ * save_for_backward set is refused (AVVAD_EINVAL).  Deterministic: no float atomics, fixed summation orders.  No kernel
+ * of this section waits on another workgroup; a time step is a launch.
+ * Replaces: nothing the reference has -- it scores whole utterances (scripts/evaluate_*_net.py).  Fed an utterance in
+ * chunks, these entry points compute what the whole-utterance forward computes (same call sites as the sections above),
+ * because the encoder is left-context-only, the LSTMs are unidirectional and everything else is per frame.
+ * ---------------------------------------------------------------------- */
+/* One LSTM layer over the next T steps of B independent rows, with the state in and out.  x [B][T][In], y [B][T][H],
+ * h0 / c0 / hT / cT [B][H].  h0 / c0 may be NULL (zeros); hT / cT may be the same buffers as h0 / c0.  Row b advances
+ * lengths[b] steps (0 <= lengths[b] <= T): later output steps are zero, its state stops there, and length 0 passes the
+ * state through bit for bit.  Any B, T, In, H >= 1; ws must be 16-byte aligned.  A row's results do not depend on the
+ * other rows' values.
+ * Form: the input projection of all steps is one product on the GEMM engine; then one launch per step in which
+ * workgroups own four hidden units each, stream their 16 rows of W_hh once and contract them against up to 64 rows per
+ * workgroup in MFMA column blocks of 16 (few rows: a weight-streaming product, not a tile GEMM). */
+size_t avvad_lstm_state_workspace(const avvad_lstm_desc* d);
+int avvad_lstm_layer_fwd_state(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                               const float* b_hh, const float* h0, const float* c0, float* y, float* hT, float* cT,
+                               const avvad_lstm_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
+
+/* The encoder on a stream of samples.  d describes the network as for avvad_wavenet_fwd (every configuration that accepts
+ * is accepted here; R = D = 32 with filter_width 2 runs on MFMA, the others in a plain direct form); d->L is the column
+ * pitch of the chunk, d->P is ignored (a whole-utterance output count has no meaning here), save_for_backward must be 0.
+ * state: B opaque blocks of avvad_wavenet_stream_state_bytes(d) each -- per row the number of columns consumed, the
+ * causal layer's last (fw-1) input columns and each residual layer's last (fw-1) d_i input columns.  ALL ZEROS means
+ * "start of utterance"; there is no other special case: the first RF-1 output columns are computed from the zero
+ * history and dropped by the caller's skip count.
+ * chunk [B][qc][L]; n_valid / skip: device int32 [B].  Row b consumes its first n_valid[b] columns (0 leaves its state
+ * untouched).  Its output columns c < skip[b] are dropped (remaining warm-up); the others are averaged in runs of k:
+ *   out[b][f][:] = mean over the k columns of frame f of relu(bottleneck(s_N)),  f < (n_valid[b] - skip[b]) / k,
+ * frame-major [B][out_frames][Bn] -- the layout the fusion and the LSTM read; frames a row does not fill are written
+ * as 0.  The caller keeps n_valid[b] <= skip[b] or (n_valid[b] - skip[b]) % k == 0, so no frame straddles two calls.
+ * One workgroup per row walks the whole stack in one launch, up to 256 columns per pass held in LDS (more than 64 KB of
+ * it: the entry point clears the kernel for that once per device). */
+size_t avvad_wavenet_stream_state_bytes(const avvad_wavenet_desc* d);
+size_t avvad_wavenet_stream_workspace(const avvad_wavenet_desc* d);
+int avvad_wavenet_stream_fwd(const float* chunk, const avvad_wavenet_params* p, float* state, const int* n_valid,
+                             const int* skip, int k, float* out, int out_frames, const avvad_wavenet_desc* d, void* ws,
+                             size_t ws_bytes, avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
  * Multimodal compact bilinear fusion + signed sqrt + whole-tensor L2 normalisation + BatchNorm1d
  * Replaces: the use_mcb branch of DeepVAD_AV.forward, packages/models/AV_Net.py:109-121, i.e.
  *   CompactBilinearPooling (packages/models/compact_bilinear_pooling.py:7-27,140-220: count sketches
