@@ -70,6 +70,11 @@ class StftDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("L", C.c_long), ("n_fft", C.c_int), ("hop", C.c_int), ("T", C.c_int), ("eps", C.c_float)]
 
 
+class StftStreamDesc(C.Structure):
+    _fields_ = [("B", C.c_int), ("L", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("T", C.c_int), ("M", C.c_int),
+                ("eps", C.c_float), ("norm_eps", C.c_float)]
+
+
 class TargetDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("L", C.c_long), ("n_fft", C.c_int), ("hop", C.c_int), ("T", C.c_int), ("center", C.c_int),
                 ("eps", C.c_float), ("vad_coef", C.c_double), ("ibm_coef", C.c_double)]
@@ -131,6 +136,10 @@ SIGNATURES = {
     "avvad_stft_workspace": (C.c_size_t, [C.POINTER(StftDesc)]),
     "avvad_stft": (C.c_int, [FP, FP, C.POINTER(StftDesc), C.c_int, FP, C.c_size_t, FP]),
     "avvad_stft_features": (C.c_int, [FP, FP, FP, FP, C.POINTER(StftDesc), C.c_float, FP, C.c_size_t, FP]),
+    "avvad_abs_max": (C.c_int, [FP, FP, C.c_int, C.c_long, FP]),
+    "avvad_stft_stream_basis_bytes": (C.c_size_t, [C.c_int]),
+    "avvad_stft_stream_basis": (C.c_int, [C.c_int, FP, FP]),
+    "avvad_stft_stream_fwd": (C.c_int, [FP] * 12 + [C.POINTER(StftStreamDesc), FP]),
     "avvad_stats_workspace": (C.c_size_t, [C.c_size_t, C.c_int]),
     "avvad_stats_accumulate": (C.c_int, [FP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_int, FP, C.c_size_t, FP]),
     "avvad_stft_stats_workspace": (C.c_size_t, [C.POINTER(StftDesc)]),

@@ -757,6 +757,108 @@ def standardize(x, mean, std, eps=1e-8):
     return out
 
 
+# --------------------------------------------------------------------------- streaming STFT front-end (csrc/stft_stream.hip)
+def _n_fft_check(n_fft):
+    n_fft = int(n_fft)
+    if n_fft < 32 or n_fft % 32 or n_fft > 2048:
+        raise L.AvvadError("the streaming front-end needs 32 <= n_fft <= 2048 and n_fft %% 32 == 0, got %d" % n_fft)
+    return n_fft
+
+
+def peak(wave):
+    """max|x| per utterance, (B,): the constant ``peak_normalize`` divides by; wave (B,L) or (L,)."""
+    w = _dev(wave, "wave")
+    w2 = w.view(1, -1) if w.dim() == 1 else w
+    out = torch.empty(w2.shape[0], dtype=torch.float32, device=w.device)
+    L.check(L.lib().avvad_abs_max(L.ptr(w2), L.ptr(out), w2.shape[0], w2.shape[1], _stream()), "avvad_abs_max")
+    return out
+
+
+def stft_stream_basis(n_fft, device):
+    """The windowed DFT basis of ``stft`` in the streaming kernel's packed layout (an opaque float tensor): built once,
+    reused by every ``stft_stream`` call with that ``n_fft``."""
+    n_fft = _n_fft_check(n_fft)
+    out = torch.empty(L.lib().avvad_stft_stream_basis_bytes(n_fft) // 4, dtype=torch.float32, device=device)
+    if not out.is_cuda:
+        raise L.AvvadError("the basis lives on the GPU: no CPU fallback")
+    with torch.cuda.device(out.device):
+        L.check(L.lib().avvad_stft_stream_basis(n_fft, L.ptr(out), _stream()), "avvad_stft_stream_basis")
+    return out
+
+
+def stft_stream_state(B, n_fft, device):
+    """Zeroed front-end state (B, n_fft) -- each row's pending samples; all zeros with a count of 0 (a fresh
+    ``SampleClock``) is "start of utterance"."""
+    if int(B) < 1:
+        raise L.AvvadError("B must be >= 1")
+    return torch.zeros(int(B), _n_fft_check(n_fft), dtype=torch.float32, device=device)
+
+
+def _row_vector(v, B, name):
+    v = _dev(v, name).reshape(-1)
+    if v.numel() != B:
+        raise L.AvvadError("%s must hold one value per row (%d), got %d" % (name, B, v.numel()))
+    return v
+
+
+def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=None, final=None, out_state=None, eps=1e-8,
+                norm_eps=1e-8):
+    """The next samples of ``B`` rows through the STFT front-end (inference only): one kernel launch.
+
+    chunk (B, n) float32 on the GPU, of which row b's first ``n_valid[b]`` samples are real (None: all n).  ``clock``
+    is the rows' :class:`avvad.stream.SampleClock` (n_fft, hop and the per-row counts); it is advanced by this call.
+    ``state`` (B, n_fft) from ``stft_stream_state`` holds the pending samples; the new tails go to ``out_state`` -- a spare
+    tensor the caller swaps with ``state`` -- or, with ``out_state`` None or ``state`` itself, back into ``state``.
+    ``peak`` (B,): every sample is divided by its row's value (None: 1, which changes no bit).  ``mean`` / ``std`` (F each):
+    the standardisation of ``stft(mean=, std=)``.  ``final``: rows that end with this call; they also yield the
+    reference's zero-padded last frame where it has one and must be reset on the clock before they take samples again.
+    -> (features (B, tmax, F) with tmax = max(frames) and zeros behind a row's frames, frames per row (list)).
+    Every argument is checked before the clock or a state changes.  Any split of a stream into calls gives the same bits."""
+    chunk = _dev(chunk, "chunk")
+    if chunk.dim() != 2 or chunk.shape[0] < 1:
+        raise L.AvvadError("chunk must be (B, n) samples, got %s" % (tuple(chunk.shape),))
+    B, n = chunk.shape
+    n_fft, hop = _n_fft_check(clock.n_fft), int(clock.hop)
+    F = n_fft // 2 + 1
+    nv = [n] * B if n_valid is None else [int(x) for x in (n_valid.tolist() if isinstance(n_valid, torch.Tensor) else n_valid)]
+    if len(nv) != B or any(x < 0 or x > n for x in nv):
+        raise L.AvvadError("n_valid must hold one count in [0, %d] per row (%d rows), got %s" % (n, B, nv))
+
+    def st(t, what):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
+                tuple(t.shape) != (B, n_fft) or t.device != chunk.device:
+            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of stft_stream_state(%d, %d, device)" % (what, B, n_fft))
+        return t
+    state = st(state, "state")
+    if out_state is not None and out_state is not state:
+        st(out_state, "out_state")
+    in_place = out_state is None or out_state.data_ptr() == state.data_ptr()
+    if not isinstance(basis, torch.Tensor) or not basis.is_cuda or basis.dtype != torch.float32 or \
+            basis.numel() * 4 != L.lib().avvad_stft_stream_basis_bytes(n_fft) or basis.device != chunk.device:
+        raise L.AvvadError("basis must be stft_stream_basis(%d, device)" % n_fft)
+    pk = None if peak is None else _row_vector(peak, B, "peak")
+    if (mean is None) != (std is None):
+        raise L.AvvadError("standardisation needs both mean and std")
+    if mean is not None:
+        mean, std = _dev(mean, "mean").reshape(-1), _dev(std, "std").reshape(-1)
+        if mean.numel() != F or std.numel() != F:
+            raise L.AvvadError("mean / std must hold %d values" % F)
+    frames, pending, pad = clock.advance(nv, final=() if final is None else final)      # raises before it changes anything
+    tmax = max(frames)
+    counts = torch.tensor([nv, pending, frames, pad], dtype=torch.int32).to(chunk.device, non_blocking=False)
+    out = torch.empty(B, tmax, F, dtype=torch.float32, device=chunk.device)
+    new = torch.empty_like(state) if in_place else out_state
+    src = chunk if n > 0 else chunk.new_zeros(B, 1)
+    d = L.StftStreamDesc(B, max(n, 1), n_fft, hop, tmax, sum(frames), float(eps), float(norm_eps))
+    with torch.cuda.device(chunk.device):
+        L.check(L.lib().avvad_stft_stream_fwd(L.ptr(src), L.ptr(counts[0]), L.ptr(counts[1]), L.ptr(counts[2]), L.ptr(counts[3]),
+                                              L.ptr(pk), L.ptr(state), L.ptr(new), L.ptr(basis), L.ptr(mean), L.ptr(std),
+                                              L.ptr(out) if tmax else None, C.byref(d), _stream()), "avvad_stft_stream_fwd")
+    if in_place:
+        state.copy_(new)
+    return out, frames
+
+
 # --------------------------------------------------------------------------- train-set statistics (no gradient)
 def stats_new(nstat, device):
     """A zeroed statistics accumulator: float64 ``[sum (nstat), sumsq (nstat), count]`` on the GPU (include/avvad.h,

@@ -65,6 +65,76 @@ class FrameClock:
         return frames, used
 
 
+class SampleClock:
+    """Host-side bookkeeping of the streaming STFT front-end, per row, beside :class:`FrameClock`: ``total`` samples
+    taken since the reset, ``emitted`` frames, and ``pending`` = total - emitted * hop < n_fft samples held in the
+    front-end state (they completed no frame yet, or later frames still overlap them).  After N samples a row has
+    emitted max(0, (N - n_fft) // hop + 1) frames, so a frame may straddle any number of calls.  A row named in ``final``
+    ends with that call and also yields what ``ops.n_frames(N)`` -- the reference's count, one-hop end pad and its float
+    test included -- has beyond that (0 or 1 frame, read with zeros behind the last sample); it must be ``reset`` before
+    it takes samples again."""
+
+    def __init__(self, batch, n_fft=1024, hop=256):
+        if int(batch) < 1 or int(n_fft) < 1 or int(hop) < 1 or int(hop) > int(n_fft):
+            raise L.AvvadError("SampleClock needs batch >= 1 and 1 <= hop <= n_fft")
+        self.n_fft, self.hop = int(n_fft), int(hop)
+        self.total = [0] * int(batch)
+        self.emitted = [0] * int(batch)
+        self.pending = [0] * int(batch)
+        self.ended = [False] * int(batch)
+
+    def reset(self, rows=None):
+        for b in (range(len(self.total)) if rows is None else rows):
+            self.total[b] = self.emitted[b] = self.pending[b] = 0
+            self.ended[b] = False
+
+    def _plan(self, n, final):
+        B = len(self.total)
+        n = [int(x) for x in (n.tolist() if isinstance(n, torch.Tensor) else n)]
+        if len(n) != B:
+            raise L.AvvadError("one sample count per row expected (%d), got %d" % (B, len(n)))
+        final = set(int(b) for b in (final.tolist() if isinstance(final, torch.Tensor) else final))
+        if any(b < 0 or b >= B for b in final):
+            raise L.AvvadError("final rows must be in [0, %d)" % B)
+        frames, pad, state = [], [], []
+        for b, nb in enumerate(n):
+            if nb < 0:
+                raise L.AvvadError("row %d: negative sample count" % b)
+            if self.ended[b] and (nb > 0 or b in final):
+                raise L.AvvadError("row %d ended with a final call: reset it before it takes samples again" % b)
+            if self.ended[b]:                       # idles until its reset
+                frames.append(0)
+                pad.append(0)
+                state.append((self.total[b], self.emitted[b], self.pending[b], True))
+                continue
+            N = self.total[b] + nb
+            e = max(0, (N - self.n_fft) // self.hop + 1)
+            extra = 0
+            if b in final:
+                extra = max(ops.n_frames(N, self.n_fft, self.hop), 0) - e
+                if extra < 0 or extra > 1:          # cannot happen for the reference's framing; never emit a wrong count
+                    raise L.AvvadError("row %d: %d samples end %d frames away from the reference's count" % (b, N, extra))
+            frames.append(e - self.emitted[b] + extra)
+            pad.append(extra)
+            state.append((N, e + extra, max(N - (e + extra) * self.hop, 0), b in final))
+        return n, frames, pad, state
+
+    def plan(self, n, final=()):
+        """Frames each row yields from ``n[b]`` more samples (rows in ``final`` end with them); raises
+        :class:`AvvadError` when a count is negative or a row that ended is fed again.  Changes nothing."""
+        return self._plan(n, final)[1]
+
+    def advance(self, n, final=()):
+        """``plan`` and then consume: -> (frames per row, the pending counts that applied to THIS call, per row 1 where
+        the last frame is the zero-padded one)."""
+        _, frames, pad, state = self._plan(n, final)
+        used = list(self.pending)
+        for b, (N, e, p, end) in enumerate(state):
+            self.total[b], self.emitted[b], self.pending[b] = N, e, p
+            self.ended[b] = self.ended[b] or end
+        return frames, used, pad
+
+
 def _int_list(v, B, what, hi):
     if v is None:
         return [hi] * B
@@ -112,6 +182,13 @@ class Session:
         self.c = torch.zeros_like(self.h)
         self._spare = (torch.zeros_like(self.h), torch.zeros_like(self.h))   # a step writes here, then the pairs swap
         self.enc_state = self.clock = None
+        # the waveform front-end of the spectrogram models (step_wave), built on first use
+        # (sample_clock is host bookkeeping and exists from the start; the GPU side is built by prepare_frontend)
+        self.sample_clock = self.stft_state = self._stft_spare = self._basis = None
+        self._frontend = dict(stats=None, eps=1e-8, n_fft=1024, hop=256)
+        if self.kind != "video" and self.enc is None:
+            self.sample_clock = SampleClock(self.batch, 1024, 256)
+        self.peak = torch.ones(self.batch, dtype=torch.float32, device=dev)
         if self.enc is not None:
             self.clock = FrameClock(self.batch, self.enc.receptive_field, samples_per_frame)
             self.enc_state = ops.wavenet_stream_state(self.enc, self.batch, dev)
@@ -127,6 +204,85 @@ class Session:
         if self.enc is not None:
             self.enc_state.index_fill_(0, idx, 0.0)
             self.clock.reset(rows)
+        self.peak.index_fill_(0, idx, 1.0)
+        if self.sample_clock is not None:
+            self.sample_clock.reset(rows)
+        if self.stft_state is not None:
+            self.stft_state.index_fill_(0, idx, 0.0)
+
+    # ------------------------------------------------------------------ waveform front-end (csrc/stft_stream.hip)
+    def _wave_check(self):
+        if self.kind == "video" or self.enc is not None:
+            raise L.AvvadError("step_wave feeds the STFT front-end of DeepVAD_audio / DeepVAD_AV without the encoder; "
+                               "a model with the encoder takes samples through step(), the video model takes none")
+
+    def set_frontend(self, stats=None, eps=1e-8, n_fft=1024, hop=256):
+        """Configuration of ``step_wave``'s front-end: ``stats`` (``train.Stats``-like: ``get("audio_mean" /
+        "audio_std", device)`` and ``.eps``) standardises the log-power features, ``eps`` is the log's.  Changing
+        ``n_fft`` / ``hop`` starts every row's front-end over."""
+        self._wave_check()
+        n_fft, hop = ops._n_fft_check(n_fft), int(hop)
+        if hop < 1 or hop > n_fft:
+            raise L.AvvadError("hop must be in [1, n_fft]")
+        if (n_fft, hop) != (self.sample_clock.n_fft, self.sample_clock.hop):
+            self.stft_state = self._stft_spare = self._basis = None
+            self.sample_clock = SampleClock(self.batch, n_fft, hop)
+        self._frontend = dict(stats=stats, eps=float(eps), n_fft=n_fft, hop=hop)
+
+    def prepare_frontend(self):
+        """Builds what ``step_wave`` needs on the GPU -- the windowed basis, ``stft_state`` and its spare -- if it is not
+        there yet (``step_wave`` does it on first use; a caller that restores a saved ``stft_state`` does it first)."""
+        self._wave_check()
+        if self.stft_state is None:
+            f = self._frontend
+            self._basis = ops.stft_stream_basis(f["n_fft"], self.device)
+            self.stft_state = ops.stft_stream_state(self.batch, f["n_fft"], self.device)
+            self._stft_spare = torch.zeros_like(self.stft_state)
+
+    def step_wave(self, wave, samples=None, video=None, final=None):
+        """The next SAMPLES of every row of a spectrogram model: wave (B, n) float32 on the GPU, of which row b's first
+        ``samples[b]`` are real (default: all n; any count >= 0 -- a frame may straddle calls).  Each sample is divided by
+        ``self.peak[b]``; the frames the samples complete go through the STFT front-end (``set_frontend``) and the model.
+        ``final``: rows whose utterance ends with this call (they also yield the reference's zero-padded last frame;
+        ``reset`` them before they take samples again).  For the AV model ``video`` must hold exactly
+        ``max(self.sample_clock.plan(samples, final))`` lip frames (None when that is 0).
+        -> (logits (B, tmax, y_dim), frames per row); (B, 0, y_dim) when no row completes a frame."""
+        self._wave_check()
+        B = self.batch
+        if not isinstance(wave, torch.Tensor) or not wave.is_cuda:
+            raise L.AvvadError("wave must be a GPU tensor: no CPU fallback")
+        if wave.dtype != torch.float32 or wave.dim() != 2 or wave.shape[0] != B:
+            raise L.AvvadError("wave must be (%d, n) float32 samples, got %s %s" % (B, wave.dtype, tuple(wave.shape)))
+        n = _int_list(samples, B, "samples", wave.shape[1])
+        self.prepare_frontend()
+        final = () if final is None else final
+        frames = self.sample_clock.plan(n, final)
+        tmax = max(frames)
+        with torch.no_grad():
+            vfeats = None
+            if self.kind == "av":
+                vt = self._check_video(video, True)
+                if vt != tmax:
+                    raise L.AvvadError("the samples yield %d frames but the video holds %d" % (tmax, vt))
+                vfeats = self._video_feats(video) if tmax > 0 else None
+            elif video is not None:
+                raise L.AvvadError("the audio model takes no video")
+            f = self._frontend
+            mean = std = None
+            if f["stats"] is not None:
+                mean, std = f["stats"].get("audio_mean", self.device), f["stats"].get("audio_std", self.device)
+            x, frames = ops.stft_stream(wave, n, self.sample_clock, self.stft_state, self._basis, self.peak, mean, std, final,
+                                        self._stft_spare, eps=f["eps"],
+                                        norm_eps=f["stats"].eps if f["stats"] is not None else f["eps"])
+            self.stft_state, self._stft_spare = self._stft_spare, self.stft_state
+            if tmax == 0:
+                return torch.zeros(B, 0, self.linear.out_features, dtype=torch.float32, device=self.device), frames
+            if vfeats is not None:
+                x = ops.ConcatColsFn.apply(x, vfeats)
+            old = (self.h, self.c)
+            y, (self.h, self.c) = ops.lstm_stack_state(x, frames, self.lstm, state=old, out=self._spare)
+            self._spare = old
+            return ops.LinearFn.apply(y, self.linear.weight, self.linear.bias), frames
 
     def _audio_frames(self, audio, lengths, samples, video=None, with_video=False):
         """-> (audio features (B, T, F), frames per row, video features (B, T, 512) or None).  Every argument is checked
@@ -257,3 +413,59 @@ def forward_chunked(model, audio=None, video=None, lengths=None, chunk_frames=1,
             y = torch.cat([y, bias.expand(B, t1 - t0 - y.shape[1], bias.numel())], dim=1)
         outs.append(y)
     return torch.cat(outs, dim=1)
+
+
+def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=256, stats=None, peak=None, eps=1e-8,
+                         n_fft=1024, hop=256, max_frames=None):
+    """A spectrogram model (``DeepVAD_audio`` / concat ``DeepVAD_AV`` without the encoder, in ``eval()`` mode) scored
+    from RAW SAMPLES through a session: wave (B, Lmax) on the GPU, row b's first ``lengths[b]`` samples real, fed in
+    packets of ``chunk_samples`` with each row's last packet ``final``.  ``peak`` (B,) is what every sample is divided by
+    (``ops.peak(wave)`` reproduces the evaluators' x / max|x|; None: 1), ``stats`` standardises the features, ``video``
+    (B, T, 67, 67) holds the lip frames already decoded and standardised.  ``max_frames[b]`` ends row b after that many
+    frames (the evaluators' crop to the label length).  -> logits (B, T, y_dim), T = the longest row's frame count
+    (``ops.n_frames``, capped by ``max_frames``); positions behind a row's frames hold the Linear layer's bias."""
+    c = int(chunk_samples)
+    if c < 1:
+        raise L.AvvadError("chunk_samples must be >= 1")
+    w = ops._dev(wave, "wave")
+    w = w.view(1, -1) if w.dim() == 1 else w
+    if w.dim() != 2:
+        raise L.AvvadError("wave must be (B, L) samples, got %s" % (tuple(w.shape),))
+    B, Lmax = w.shape
+    lens = _int_list(lengths, B, "lengths", Lmax)
+    sess = open(model, B)
+    sess.set_frontend(stats, eps, n_fft, hop)
+    sess.prepare_frontend()
+    if peak is not None:
+        sess.peak.copy_(ops._row_vector(peak, B, "peak"))
+    total = [max(ops.n_frames(l, n_fft, hop), 0) for l in lens]
+    ends = [True] * B                                   # the row ends with its last sample (and may owe the padded frame)
+    if max_frames is not None:
+        for b, mf in enumerate(_int_list(max_frames, B, "max_frames", 1 << 30)):
+            if mf < total[b]:                           # exactly mf frames: the samples they need and no end
+                total[b], ends[b] = mf, False
+                lens[b] = (mf - 1) * hop + n_fft if mf > 0 else 0
+    T = max(total)
+    if sess.kind == "av" and (video is None or video.dim() != 4 or video.shape[0] != B or video.shape[1] < T):
+        raise L.AvvadError("the AV model needs video (B, >= %d, H, W)" % T)
+    bias = sess.linear.bias.detach()
+    out = bias.expand(B, T, bias.numel()).clone()
+    done, ended = [0] * B, set()
+    for s0 in range(0, max(max(lens), 1), c):
+        n = [min(max(l - s0, 0), c) for l in lens]
+        fin = [b for b in range(B) if ends[b] and b not in ended and s0 + c >= lens[b]]
+        ended.update(fin)
+        frames = sess.sample_clock.plan(n, fin)
+        tl = max(frames)
+        v = None
+        if sess.kind == "av" and tl > 0:                # every row's next lip frames start where its own frames stand
+            v = video.new_zeros((B, tl) + tuple(video.shape[2:]))
+            for b, f in enumerate(frames):
+                if f:
+                    v[b, :f] = video[b, done[b]:done[b] + f]
+        y, frames = sess.step_wave(w[:, s0:s0 + c].contiguous(), n, v, fin)
+        for b, f in enumerate(frames):
+            if f:
+                out[b, done[b]:done[b] + f] = y[b, :f]
+                done[b] += f
+    return out

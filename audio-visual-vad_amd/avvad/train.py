@@ -531,12 +531,32 @@ def clean_vad_labels(clean_path, n_noisy, device, fs=16e3, wlen_sec=64e-3, hop_p
     return vad.view(1, -1)
 
 
-def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, eps=EPS, std_norm=True, chunk_frames=None):
+def _one_chunking(chunk_frames, chunk_samples):
+    if chunk_frames is not None and chunk_samples is not None:
+        raise ValueError("chunk_frames (features in, frames per step) and chunk_samples (samples in) exclude each other")
+
+
+def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, eps=EPS, std_norm=True, chunk_frames=None,
+                chunk_samples=None):
     """One utterance through the reference's evaluator (``evaluate_audio_net.py:107-180``; with ``video`` (T,67,67) the AV
     variant ``evaluate_AV_net.py:148-250``): returns (y_hat_soft, y_hat_hard) on the CPU, shaped (1, T) like the
     reference's ``y_hat_soft[..., 0]``.  ``chunk_frames``: score through a streaming session (``avvad.stream``), that
-    many frames per step; the features are still formed from the whole utterance, because its peak normalisation is a
-    statistic of all of it."""
+    many frames per step; the features are still formed from the whole utterance.  ``chunk_samples``: the RAW samples go
+    through the session in packets of that many (``stream.forward_wave_chunked``): the peak -- the one statistic of the
+    whole utterance -- is one reduction up front, everything behind it is streamed."""
+    _one_chunking(chunk_frames, chunk_samples)
+    if chunk_samples is not None:
+        w = x_t.reshape(1, -1)
+        T = ops.n_frames(w.shape[1], 1024, 256)
+        T = T if n_label_frames is None else min(T, int(n_label_frames))
+        v = None
+        if video is not None:
+            v = video[None, :T].contiguous()
+            v = stats.video(v) if (stats is not None and std_norm) else v
+        y = stream.forward_wave_chunked(classifier, w, None, v, chunk_samples, stats if std_norm else None, ops.peak(w),
+                                        eps=eps, max_frames=[T])
+        soft = torch.sigmoid(y[..., 0].detach().cpu())
+        return soft, (soft > 0.5).int()
     x = audio_features(x_t, stats, n_label_frames, eps=eps, std_norm=std_norm)
     lengths = [x.shape[1]]
     v = None
@@ -554,7 +574,7 @@ def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, ep
 
 
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
-                  stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None):
+                  stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None, chunk_samples=None):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
@@ -568,7 +588,13 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
     frames standardised with ``stats``, the clean file's VAD as the label.  Without either a synthetic ragged data
     source stands in for the HDF5 datasets.  ``chunk_frames``: every utterance is scored through a streaming session
     (``avvad.stream``) in chunks of that many frames -- same files, same values up to summation order; ``None`` is the
-    whole-length forward."""
+    whole-length forward.  ``chunk_samples`` (``wav_list``, and ``av_files`` with the AV network): every utterance's raw
+    samples are streamed in packets of that many, the STFT front-end included (``process_utt``); for ``av_files`` the
+    whole-utterance step still runs first, for the labels, the decoded lip frames and the frame count, and its audio
+    features are not used."""
+    _one_chunking(chunk_frames, chunk_samples)
+    if chunk_samples is not None and (wav_list is None and av_files is None or kind.lower() == "video"):
+        raise ValueError("chunk_samples streams the waveform of wav_list / av_files utterances into an audio or AV network")
     rank, world, local = avd.init_from_env("nccl")
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
@@ -587,8 +613,13 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
         files = AVFiles(av_files)
         with torch.no_grad():
             for i in range(rank, len(files), world):
-                lengths, x, video, y = av_file_step(AVFiles.collate([files[i]]), device, "vad_labels", stats)
-                if chunk_frames is not None:
+                batch = AVFiles.collate([files[i]])
+                lengths, x, video, y = av_file_step(batch, device, "vad_labels", stats)
+                if chunk_samples is not None:
+                    w = batch[1].to(device)
+                    logits = stream.forward_wave_chunked(model, w, None, video, chunk_samples, stats, ops.peak(w),
+                                                         max_frames=lengths.tolist())
+                elif chunk_frames is not None:
                     logits = stream.forward_chunked(model, None if kind.lower() == "video" else x, video, lengths, chunk_frames)
                 else:
                     logits = model(video, lengths) if kind.lower() == "video" else model(x, video, lengths)
@@ -610,7 +641,7 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                 else:
                     y = labels.get(wav_list[i]) if labels else None
                 soft, hard = process_utt(model, x_t.to(device), stats, None if y is None else y.shape[-1],
-                                         chunk_frames=chunk_frames)
+                                         chunk_frames=chunk_frames, chunk_samples=chunk_samples)
                 base = os.path.join(out_dir, os.path.splitext(os.path.basename(wav_list[i]))[0])
                 torch.save(hard, base + "_y_hat_hard.pt")
                 torch.save(soft, base + "_y_hat_soft.pt")

@@ -371,6 +371,46 @@ int avvad_stft(const float* wave, float* out, const avvad_stft_desc* d, int mode
  * mean / std: [F] train-set statistics.  out [B][T][F]. */
 int avvad_stft_features(const float* wave, const float* mean, const float* std_, float* out,
                         const avvad_stft_desc* d, float norm_eps, void* ws, size_t ws_bytes, avvad_stream_t s);
+/* The same front-end on a STREAM of samples (inference; nothing the reference has: it transforms whole utterances).
+ * Row b's logical stream is its pending tail -- the n_pending[b] < n_fft samples that earlier calls left without a
+ * complete frame, or that later frames still overlap -- followed by chunk[b][0 .. n_valid[b]).  The call emits the row's
+ * next n_frames[b] frames, frame t from samples [t hop, t hop + n_fft) of that stream, each sample divided by peak[b]
+ * (a division: a peak of 1 changes no bit; peak == NULL is 1 everywhere):
+ *   out[b][t][f] = log(re^2 + im^2 + eps),  then with mean / std (both or neither)  (v - mean[f]) / (std[f] + norm_eps),
+ * and the rest of out [B][T][F] is zero.  Samples past the end of a stream read as zero -- the reference's one-hop end
+ * padding -- and only a row with pad_frames[b] != 0 (it ends here) may emit the one frame that does so.  The stream from
+ * sample n_frames[b] hop on is the new tail: state_out[b] (raw samples, zero behind them).  A row with no new sample and
+ * no frame keeps its state bit for bit.
+ * state_in / state_out: plain float [B][n_fft], different buffers (every workgroup reads tails while others are written:
+ * the caller swaps, as for h / c); all zeros with n_pending 0 is "start of utterance".  chunk [B][L] is never written.
+ * n_valid / n_pending / n_frames / pad_frames: device int32 [B]; the counts are the caller's bookkeeping (frames after N
+ * samples: max(0, (N - n_fft) / hop + 1)); the kernel clamps them so that wrong ones cannot leave a buffer.  d->M is the
+ * HOST's sum of n_frames (0: unknown, B T is assumed); it sizes the grid and selects nothing that changes a value.
+ * basis: avvad_stft_stream_basis_bytes(n_fft) bytes filled ONCE by avvad_stft_stream_basis (16-byte aligned) -- the
+ * windowed basis of avvad_stft (periodic Hann, exact phase reduction, evaluated in double) packed per block of 16 bins,
+ * real and imaginary columns apart.  n_fft % 32 == 0, 1 <= hop <= n_fft, n_fft <= 2048 (a pass of frames sits in LDS).
+ * No workspace.
+ * DETERMINISM: the order in which one output value is summed depends on (n_fft, bin) alone -- not on the number of
+ * frames, the row, the frame's place in the call or n_pending.  One kernel serves every size: workgroups own 16 bins,
+ * 8 waves split K round-robin in groups of 16 samples on v_mfma_f32_16x16x4_f32 and their partial sums are added in wave
+ * order.  Any split of a stream into calls therefore gives the same bits. */
+typedef struct {
+  int B;         /* rows */
+  int L;         /* pitch of chunk (floats), >= 1 */
+  int n_fft, hop;
+  int T;         /* frame pitch of out (>= every n_frames[b]); 0: no row emits a frame, out may be NULL */
+  int M;         /* host's sum of n_frames, or 0 */
+  float eps, norm_eps;
+} avvad_stft_stream_desc;
+/* out[b] = max|x[b][:]|, x [B][L]: the peak avvad_peak_normalize divides by, as a value -- what a caller hands to
+ * avvad_stft_stream_fwd when it knows the whole utterance (the evaluators) */
+int avvad_abs_max(const float* x, float* out, int B, long L, avvad_stream_t s);
+size_t avvad_stft_stream_basis_bytes(int n_fft);
+int avvad_stft_stream_basis(int n_fft, float* out, avvad_stream_t s);
+int avvad_stft_stream_fwd(const float* chunk, const int* n_valid, const int* n_pending, const int* n_frames,
+                          const int* pad_frames, const float* peak, const float* state_in, float* state_out,
+                          const float* basis, const float* mean, const float* std_, float* out,
+                          const avvad_stft_stream_desc* d, avvad_stream_t s);
 /* out[b][:] = x[b][:] / max|x[b][:]|   (peak normalisation, scripts/evaluate_audio_net.py:125-127); out may alias x */
 int avvad_peak_normalize(const float* x, float* out, int B, long L, avvad_stream_t s);
 /* out[r][f] = (x[r][f] - mean[f]) / (std[f] + eps)  -- input standardisation of the train / evaluate loops
