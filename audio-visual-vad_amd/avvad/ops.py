@@ -757,6 +757,142 @@ def standardize(x, mean, std, eps=1e-8):
     return out
 
 
+# --------------------------------------------------------------------------- masked inverse STFT (csrc/istft.hip, no gradient)
+def istft_length(T, n_fft, hop, center=False):
+    """Samples librosa's ``istft`` returns for T frames when no ``length`` is given: ``n_fft + hop (T - 1)``, less
+    ``n_fft/2`` at either end when ``center``."""
+    T, n_fft, hop = int(T), int(n_fft), int(hop)
+    if T < 1:
+        return 0
+    return n_fft + hop * (T - 1) - (2 * (n_fft // 2) if center else 0)
+
+
+def stft_complex(wave, n_fft=1024, hop=256, pad_at_end=True, fs=16e3):
+    """wave (B,L) or (L,) on the GPU -> the complex spectrum of ``stft``'s DFT as a real (B,T,F,2) tensor (re, im)."""
+    w = _dev(wave, "wave")
+    w2 = w.view(1, -1) if w.dim() == 1 else w
+    B, Ls = w2.shape
+    T = n_frames(Ls, n_fft, hop, pad_at_end, fs)
+    d = L.StftDesc(B, Ls, n_fft, hop, T, 0.0)
+    ws = _ws(L.lib().avvad_stft_workspace(C.byref(d)), w.device)
+    out = torch.empty((B, T, n_fft // 2 + 1, 2), dtype=torch.float32, device=w.device)
+    L.check(L.lib().avvad_stft_complex(L.ptr(w2), L.ptr(out), C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()), "avvad_stft_complex")
+    return out
+
+
+def _mask_args(mask, mask_mode, B, T, F):
+    if mask_mode is None:
+        mask_mode = 0 if mask is None else 1
+    mask_mode = int(mask_mode)
+    if mask_mode not in (0, 1, 2, 3):
+        raise L.AvvadError("mask_mode must be 0 (none), 1 (mask), 2 (sigmoid of logits) or 3 (logits > 0), got %r" % (mask_mode,))
+    if mask_mode == 0:
+        if mask is not None:
+            raise L.AvvadError("mask_mode 0 takes no mask")
+        return None, 0
+    m = _dev(mask, "mask")
+    if m.numel() != B * T * F or m.shape[-1] != F:
+        raise L.AvvadError("mask must be (%d, %d, %d), got shape %s" % (B, T, F, tuple(m.shape)))
+    return m, mask_mode
+
+
+def _row_counts(v, B, hi, name, device):
+    """per-row int32 counts on the device (None stays None) and the host list"""
+    if v is None:
+        return None, None
+    vals = [int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+    if len(vals) != B or any(n < 0 or n > hi for n in vals):
+        raise L.AvvadError("%s must hold %d values within 0..%d" % (name, B, hi))
+    return torch.tensor(vals, dtype=torch.int32).to(device), vals
+
+
+def istft(spec, n_fft=1024, hop=256, mask=None, mask_mode=None, n_frames=None, length=None, center=False, scale=None):
+    """Masked inverse STFT on the GPU (librosa's ``istft``: Hann synthesis window, overlap-add, window sum-of-squares
+    normalisation).  ``spec``: (B,T,F,2) (re, im), or ONE utterance in the legacy (F,T,2) layout ``stft_pytorch`` returns,
+    or a complex64 (F,T) tensor; read in place through its strides.  ``mask`` (B,T,F) with ``mask_mode`` 1 (multiply;
+    the default when a mask is given), 2 (``sigmoid(mask)``) or 3 (``mask > 0``); the product is formed while the spectrum
+    is loaded.  ``n_frames``: frames per row (default T); ``length``: output samples, one value or one per row (default
+    ``istft_length`` of the row's frames); ``center`` trims ``n_fft/2`` at the start; ``scale`` (B,) multiplies each row.
+    Returns (B, Lout); samples past a row's length are zero."""
+    legacy = False
+    if isinstance(spec, torch.Tensor) and spec.is_complex():
+        if spec.dtype != torch.complex64 or spec.dim() != 2:
+            raise L.AvvadError("a complex spectrum must be a complex64 (F, T) tensor, got %s %s" % (spec.dtype, tuple(spec.shape)))
+        spec = torch.view_as_real(spec)
+    if not isinstance(spec, torch.Tensor) or not spec.is_cuda:
+        raise L.AvvadError("spec must be a GPU tensor: the inverse STFT has no CPU fallback")
+    if spec.dtype != torch.float32 or spec.dim() not in (3, 4) or spec.shape[-1] != 2:
+        raise L.AvvadError("spec must be float32 (B,T,F,2) or (F,T,2), or complex64 (F,T); got %s %s" % (spec.dtype, tuple(spec.shape)))
+    n_fft, hop = int(n_fft), int(hop)
+    F = n_fft // 2 + 1
+    if spec.dim() == 3:
+        legacy = True
+        if spec.stride(2) != 1 or spec.stride(0) <= 0 or spec.stride(1) <= 0:
+            spec = spec.contiguous()
+        B, T = 1, spec.shape[1]
+        strides = (0, spec.stride(1), spec.stride(0))
+    else:
+        spec = spec.contiguous()
+        B, T = spec.shape[0], spec.shape[1]
+        strides = (T * F * 2, F * 2, 2)
+    if spec.shape[0 if legacy else 2] != F:
+        raise L.AvvadError("spec holds %d bins, n_fft = %d has %d" % (spec.shape[0 if legacy else 2], n_fft, F))
+    if T < 1:
+        raise L.AvvadError("spec holds no frame")
+    m, mode = _mask_args(mask, mask_mode, B, T, F)
+    nf_dev, nf = _row_counts(n_frames, B, T, "n_frames", spec.device)
+    if length is None:
+        lens = [istft_length(n, n_fft, hop, center) for n in (nf if nf is not None else [T] * B)]
+    elif isinstance(length, (list, tuple, torch.Tensor)):
+        lens = [int(v) for v in (length.tolist() if isinstance(length, torch.Tensor) else length)]
+        if len(lens) != B or min(lens) < 0:
+            raise L.AvvadError("length must hold %d non-negative values" % B)
+    else:
+        lens = [int(length)] * B
+    Lout = max(lens)
+    if Lout < 1:
+        raise L.AvvadError("the output would be empty (length %r, %d frames)" % (length, T))
+    len_dev = None if min(lens) == Lout else torch.tensor(lens, dtype=torch.int32).to(spec.device)
+    sc = None if scale is None else _row_vector(scale, B, "scale")
+    d = L.IstftDesc(B, T, n_fft, hop, n_fft // 2 if center else 0, Lout, mode)
+    out = torch.empty(B, Lout, dtype=torch.float32, device=spec.device)
+    with torch.cuda.device(spec.device):
+        ws = _ws(L.lib().avvad_istft_workspace(C.byref(d)), spec.device)
+        L.check(L.lib().avvad_istft(L.ptr(spec), strides[0], strides[1], strides[2], L.ptr(m), L.ptr(nf_dev), L.ptr(len_dev),
+                                    L.ptr(sc), L.ptr(out), C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()), "avvad_istft")
+    return out
+
+
+def resynth(wave, mask, mask_mode=1, n_fft=1024, hop=256, sample_lengths=None, pad_at_end=True, fs=16e3, scale=None):
+    """mask x STFT(wave) -> waveform in one call (avvad_resynth): the forward DFT of ``stft``, the masked inverse and the
+    overlap-add, the spectrum never leaving the workspace.  wave (B,L) zero-padded rows (or (L,)), ``sample_lengths`` the
+    B real lengths (default L); ``mask`` (B,T,F) with T = ``n_frames(L)``, read by ``mask_mode`` as in ``istft`` (``None``
+    with mode 0).  Row b uses its own ``n_frames(L_b)`` frames and comes back with exactly L_b samples, zero behind them
+    (cropped where the frames run past the utterance -- the end pad -- and zero-filled where they stop short of it).
+    Returns (B, L)."""
+    w = _dev(wave, "wave")
+    w2 = w.view(1, -1) if w.dim() == 1 else w
+    B, Ls = w2.shape
+    n_fft, hop = int(n_fft), int(hop)
+    T = n_frames(Ls, n_fft, hop, pad_at_end, fs)
+    if T < 1:
+        raise L.AvvadError("a wave of %d samples holds no %d-sample frame" % (Ls, n_fft))
+    F = n_fft // 2 + 1
+    m, mode = _mask_args(mask, mask_mode, B, T, F)
+    len_dev, lens = _row_counts(sample_lengths, B, Ls, "sample_lengths", w.device)
+    nf_dev = None
+    if lens is not None:
+        nf_dev = torch.tensor([min(T, max(0, n_frames(n, n_fft, hop, pad_at_end, fs))) for n in lens], dtype=torch.int32).to(w.device)
+    sc = None if scale is None else _row_vector(scale, B, "scale")
+    sd = L.StftDesc(B, Ls, n_fft, hop, T, 0.0)
+    d = L.IstftDesc(B, T, n_fft, hop, 0, Ls, mode)
+    ws = _ws(L.lib().avvad_resynth_workspace(C.byref(sd), C.byref(d)), w.device)
+    out = torch.empty(B, Ls, dtype=torch.float32, device=w.device)
+    L.check(L.lib().avvad_resynth(L.ptr(w2), L.ptr(m), L.ptr(nf_dev), L.ptr(len_dev), L.ptr(sc), L.ptr(out), C.byref(sd), C.byref(d),
+                                  L.ptr(ws), ws.numel() * 4, _stream()), "avvad_resynth")
+    return out
+
+
 # --------------------------------------------------------------------------- streaming STFT front-end (csrc/stft_stream.hip)
 def _n_fft_check(n_fft):
     n_fft = int(n_fft)

@@ -573,8 +573,26 @@ def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, ep
     return soft, (soft > 0.5).int()
 
 
+def resynth_utt(classifier, x_t, stats=None, hard=True, eps=EPS, std_norm=True):
+    """Enhanced waveform of one utterance from a mask-predicting audio model (``y_dim = n_fft/2 + 1 = 513``): peak
+    normalisation -> features -> model as in ``process_utt``, then the logits go straight in as the mask of
+    ``ops.resynth`` on the peak-normalised wave -- ``hard``: ``logit > 0`` (the evaluator's ``sigmoid > 0.5``), else
+    ``sigmoid(logit)`` -- with the peak as the output scale, so the result is in the input's scale.  x_t (L,) on the GPU
+    -> (L,) on the GPU."""
+    n_fft = 1024
+    if getattr(classifier, "y_dim", None) != n_fft // 2 + 1:
+        raise ValueError("resynthesis needs a model that predicts a %d-bin mask (y_dim = %d), got y_dim = %r"
+                         % (n_fft // 2 + 1, n_fft // 2 + 1, getattr(classifier, "y_dim", None)))
+    w = x_t.reshape(1, -1)
+    x = audio_features(x_t, stats, None, eps=eps, std_norm=std_norm)
+    logits = classifier(x, [x.shape[1]]).detach().contiguous()
+    out = ops.resynth(ops.peak_normalize(w), logits, mask_mode=3 if hard else 2, n_fft=n_fft, hop=256, scale=ops.peak(w))
+    return out.view(-1)
+
+
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
-                  stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None, chunk_samples=None):
+                  stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None, chunk_samples=None,
+                  resynth_dir=None, resynth_hard=True):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
@@ -591,21 +609,37 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
     whole-length forward.  ``chunk_samples`` (``wav_list``, and ``av_files`` with the AV network): every utterance's raw
     samples are streamed in packets of that many, the STFT front-end included (``process_utt``); for ``av_files`` the
     whole-utterance step still runs first, for the labels, the decoded lip frames and the frame count, and its audio
-    features are not used."""
+    features are not used.
+
+    ``resynth_dir`` (``wav_list`` with a 513-output audio model): every utterance is also resynthesised from the model's
+    mask (``resynth_utt``; ``resynth_hard``: binary mask, else the soft one) and written there as ``<base>_enhanced.wav``
+    -- float32, 16 kHz, as many samples as the input.  ``None`` writes nothing."""
     _one_chunking(chunk_frames, chunk_samples)
+    model = None
+    if resynth_dir is not None:
+        if wav_list is None or kind != "audio":
+            raise ValueError("resynth_dir writes the enhanced utterances of wav_list for the audio network")
+        torch.manual_seed(0)
+        model = make_model()
+        if getattr(model, "y_dim", None) != 513:
+            raise ValueError("resynth_dir needs a model that predicts a 513-bin mask (y_dim = 513), got y_dim = %r"
+                             % (getattr(model, "y_dim", None),))
     if chunk_samples is not None and (wav_list is None and av_files is None or kind.lower() == "video"):
         raise ValueError("chunk_samples streams the waveform of wav_list / av_files utterances into an audio or AV network")
     rank, world, local = avd.init_from_env("nccl")
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
     torch.manual_seed(0)
-    model = make_model()
+    if model is None:
+        model = make_model()
     if checkpoint:
         model.load_state_dict(torch.load(checkpoint, map_location="cpu", weights_only=True))
     model = model.to(device).eval()
     for p in model.parameters():
         p.requires_grad = False
     os.makedirs(out_dir, exist_ok=True)
+    if resynth_dir is not None:
+        os.makedirs(resynth_dir, exist_ok=True)
     t0 = time.perf_counter()
     if av_files is not None:
         if kind.lower() not in ("video", "av") or waveform or wav_list is not None:
@@ -647,6 +681,11 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                 torch.save(soft, base + "_y_hat_soft.pt")
                 if y is not None:
                     torch.save(y.int().cpu(), base + "_label.pt")
+                if resynth_dir is not None:
+                    from scipy.io import wavfile
+                    enhanced = resynth_utt(model, x_t.to(device), stats, hard=resynth_hard)
+                    wavfile.write(os.path.join(resynth_dir, os.path.basename(base) + "_enhanced.wav"), 16000,
+                                  enhanced.cpu().numpy())
     else:
         ds = SyntheticAV(n_items, kind, waveform=waveform, seed=7)
         collate = pick_collate(kind, waveform)

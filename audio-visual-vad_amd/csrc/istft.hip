@@ -1,0 +1,236 @@
+// istft.hip -- masked inverse STFT on the GPU: mask x spectrum -> per-frame inverse real DFT + synthesis window as ONE
+// fp32-MFMA GEMM against a windowed cos/sin basis, then a fixed-order overlap-add gather with librosa's window
+// sum-of-squares normalisation.
+//
+// Replaces istft of packages/processing/stft.py:63-99 (librosa.core.istft: irfft of every frame, periodic Hann, overlap-add,
+// division by the window sum of squares where it exceeds float32 tiny, centre trim / length fix).  The mirror of
+// frames::framed_dft: Y[(b,t)][n] = sum_c A[(b,t)][c] Winv[c][n] with M = B*T, N = n_fft, K = spectrum_ld -- the same flop
+// count as the forward transform.  The mask (given, sigmoid of a logit, or logit > 0) is applied while the A operand is
+// loaded, so the masked spectrum never exists in memory; the spectrum is read through element strides, so the STFT's own
+// workspace rows, a batched (B,T,F,2) tensor and the legacy (F,T,2) view all go in as they are.
+#include "frames.h"
+
+namespace {
+
+// Winv[c][n]: row 2f = hann[n] w_f/N cos(2 pi f n / N), row 2f+1 = -hann[n] w_f/N sin(2 pi f n / N), w_f = 1 for DC and
+// Nyquist, else 2 (irfft of a half spectrum, then the synthesis window); rows >= 2F are zero.  Evaluated like
+// frames::dft_basis: periodic Hann, exact phase reduction, double, rounded once.  win2[n] = hann[n]^2 as doubles.
+__global__ void idft_basis(float* __restrict__ W, double* __restrict__ win2, int N, int F, int rows) {
+  const long n_el = (long)rows * N;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i / N), n = (int)(i % N);
+    const double win = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)N);           // periodic Hann
+    float v = 0.f;
+    if (c < 2 * F) {
+      const int f = c >> 1;
+      const double wf = (f == 0 || 2 * f == N) ? 1.0 : 2.0;
+      const long fn = ((long)f * n) % N;                                          // exact phase reduction
+      const double ang = 2.0 * (double)fn / (double)N;
+      v = (float)((c & 1) ? -win * (wf / (double)N) * sinpi(ang) : win * (wf / (double)N) * cospi(ang));
+    }
+    W[i] = v;
+    if (c == 0) win2[n] = win * win;
+  }
+}
+
+// A[m = (b,t)][c] = S[b,t,c] * m(b,t,c>>1)  (zero for c >= 2F); S through element strides, (re, im) adjacent.  Offsets are
+// 32-bit (the entry points check that the last element of spec and mask lies below 2^31).  SIG: the mask is sigmoid(logit)
+// (mode 2; its own instantiation, so that the exponential's registers do not weigh on the other modes).
+template <bool SIG>
+struct MaskedSpec {
+  static constexpr bool KCONTIG = true;
+  static constexpr int VEC = 1;
+  typedef igemm::NoCtx Ctx;
+  const float* S;
+  const float* mask;     // [B][T][F]: the mask (mode 1) or its logit (modes 2, 3)
+  unsigned sb, st, sf;
+  int X, T, F, mode;
+  // (the row's offsets are recomputed per K tile: kept in a per-vector context they cost 16 registers of the 8-wave
+  //  kernel's 128 and spilled 84 bytes per lane against 24 in this form)
+  __device__ __forceinline__ Ctx prep(int) const { return Ctx(); }
+  __device__ __forceinline__ void load(const Ctx&, int x, int k0, int kin, float* v) const {
+    const int c = k0 + kin;
+    float r = 0.f;
+    if (x < X && c < 2 * F) {
+      const unsigned b = (unsigned)x / (unsigned)T, t = (unsigned)x - b * (unsigned)T, f = (unsigned)c >> 1;
+      r = S[b * sb + t * st + f * sf + (c & 1)];
+      if (mode) {
+        const float g = mask[(unsigned)x * (unsigned)F + f];
+        if constexpr (SIG) r *= 1.f / (1.f + expf(-g));
+        else r *= mode == 1 ? g : (g > 0.f ? 1.f : 0.f);
+      }
+    }
+    v[0] = r;
+  }
+};
+
+constexpr float F32_TINY = 1.17549435e-38f;
+
+// out[b][s] = scale[b] * (sum_t Y[b,t][s' - t hop]) / wss(s'),  s' = s + start, t ascending over the frames that cover s';
+// no atomics: one thread gathers one sample.  Exact zeros at and beyond out_len[b] and the row's natural length.
+__global__ void overlap_add(const float* __restrict__ Y, const double* __restrict__ win2, const int* __restrict__ n_frames,
+                            const int* __restrict__ out_len, const float* __restrict__ scale, float* __restrict__ out, int B,
+                            int T, int N, int hop, int start, int pitch) {
+  const long n_el = (long)B * pitch;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / pitch), s = (int)(i % pitch);
+    int nf = n_frames ? n_frames[b] : T;
+    nf = nf < 0 ? 0 : (nf > T ? T : nf);
+    int len = out_len ? out_len[b] : pitch;
+    len = len > pitch ? pitch : len;
+    const long natural = nf > 0 ? (long)N + (long)hop * (nf - 1) - start : 0;
+    float y = 0.f;
+    if (s < len && s < natural) {
+      const long sp = (long)s + start;
+      const long lo = sp - N + 1;
+      int t0 = lo > 0 ? (int)((lo + hop - 1) / hop) : 0;
+      long t1 = sp / hop;
+      if (t1 > nf - 1) t1 = nf - 1;
+      float acc = 0.f;
+      double wss = 0.0;
+      for (int t = t0; t <= (int)t1; ++t) {
+        const int n = (int)(sp - (long)t * hop);
+        acc += Y[((long)b * T + t) * N + n];
+        wss += win2[n];
+      }
+      const float w = (float)wss;
+      y = w > F32_TINY ? acc / w : acc;
+      if (scale) y *= scale[b];
+    }
+    out[i] = y;
+  }
+}
+
+// out[m][f][{re,im}] = S[m][2f + {re,im}]: the workspace spectrum without its row padding
+__global__ void to_complex(const float* __restrict__ S, float* __restrict__ out, long M, int F, int ld) {
+  const long n = M * F * 2;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long m = i / (2 * F);
+    out[i] = S[m * ld + (i - m * 2 * F)];
+  }
+}
+
+using frames::grid1;
+
+static bool ok_desc(const avvad_istft_desc* d) {
+  return d && d->B > 0 && d->T > 0 && d->n_fft >= 32 && d->n_fft % 32 == 0 && d->hop > 0 && d->hop <= d->n_fft &&
+         d->start >= 0 && d->start < d->n_fft && d->out_pitch > 0 && d->mask_mode >= 0 && d->mask_mode <= 3 &&
+         (long)d->B * d->T * (d->n_fft / 2 + 1) < (1L << 31);       // 32-bit offsets into the mask; B T fits an int
+}
+// the last element the A functor reads lies below 2^31 (32-bit offsets)
+static bool ok_strides(const avvad_istft_desc* d, long sb, long st, long sf) {
+  if (sb < 0 || st <= 0 || sf <= 0 || sb >= (1L << 31) || st >= (1L << 31) || sf >= (1L << 31)) return false;
+  const double last = (double)(d->B - 1) * sb + (double)(d->T - 1) * st + (double)(d->n_fft / 2) * sf + 1;
+  return last < 2147483648.0;
+}
+
+// workspace of the inverse: [Winv ld x n_fft][Y B*T x n_fft][win2 n_fft doubles][slab]
+struct Carve {
+  size_t winv, y, win2, slab, total;   // float offsets; total in floats
+};
+static Carve carve(const avvad_istft_desc* d, size_t base) {
+  const size_t ld = frames::spectrum_ld(d->n_fft);
+  Carve c;
+  c.winv = base;
+  c.y = c.winv + align_up(ld * d->n_fft, 64);
+  c.win2 = c.y + align_up((size_t)d->B * d->T * d->n_fft, 64);
+  c.slab = c.win2 + align_up((size_t)2 * d->n_fft, 64);
+  c.total = c.slab + igemm::SLAB_FLOATS;
+  return c;
+}
+// floats of the forward transform's part of the fused workspace: [W n_fft x ld][S B*T x ld]
+static size_t stft_floats(const avvad_stft_desc* d) {
+  const size_t ld = frames::spectrum_ld(d->n_fft);
+  return align_up((size_t)d->n_fft * ld, 64) + align_up((size_t)d->B * d->T * ld, 64);
+}
+
+static int inverse(const float* spec, long sb, long st, long sf, const float* mask, const int* n_frames, const int* out_len,
+                   const float* scale, float* out, const avvad_istft_desc* d, float* ws, const Carve& c, hipStream_t s) {
+  const int N = d->n_fft, F = N / 2 + 1, ld = frames::spectrum_ld(N), M = d->B * d->T;
+  float* Winv = ws + c.winv;
+  float* Y = ws + c.y;
+  double* win2 = reinterpret_cast<double*>(ws + c.win2);
+  hipLaunchKernelGGL(idft_basis, dim3(grid1((long)ld * N)), dim3(256), 0, s, Winv, win2, N, F, ld);
+  igemm::ColPlain<4> b{Winv, N, N, ld, 0};
+  igemm::EpiStore e{Y, N, nullptr, 0};
+  int rc;
+  if (d->mask_mode == 2) {
+    MaskedSpec<true> a{spec, mask, (unsigned)sb, (unsigned)st, (unsigned)sf, M, d->T, F, d->mask_mode};
+    rc = igemm::launch<128, 128>(a, b, e, M, N, ld, 1, s, ws + c.slab, /*allow_bf16=*/false);
+  } else {
+    MaskedSpec<false> a{spec, mask, (unsigned)sb, (unsigned)st, (unsigned)sf, M, d->T, F, d->mask_mode};
+    rc = igemm::launch<128, 128>(a, b, e, M, N, ld, 1, s, ws + c.slab, /*allow_bf16=*/false);
+  }
+  if (rc) return rc;
+  hipLaunchKernelGGL(overlap_add, dim3(grid1((long)d->B * d->out_pitch)), dim3(256), 0, s, Y, win2, n_frames, out_len, scale, out,
+                     d->B, d->T, N, d->hop, d->start, d->out_pitch);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+}  // namespace
+
+extern "C" size_t avvad_istft_workspace(const avvad_istft_desc* d) {
+  if (!ok_desc(d)) return 0;
+  return carve(d, 0).total * sizeof(float);
+}
+
+extern "C" int avvad_istft(const float* spec, long stride_b, long stride_t, long stride_f, const float* mask, const int* n_frames,
+                           const int* out_len, const float* scale, float* out, const avvad_istft_desc* d, void* wsv,
+                           size_t ws_bytes, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!spec || !out || !wsv || !ok_desc(d) || !ok_strides(d, stride_b, stride_t, stride_f) || (d->mask_mode != 0 && !mask) ||
+      ((uintptr_t)wsv & 15))
+    return AVVAD_EINVAL;
+  if (ws_bytes < avvad_istft_workspace(d)) return AVVAD_EWORKSPACE;
+  return inverse(spec, stride_b, stride_t, stride_f, mask, n_frames, out_len, scale, out, d, (float*)wsv, carve(d, 0),
+                 (hipStream_t)sv);
+}
+
+static bool ok_pair(const avvad_stft_desc* sd, const avvad_istft_desc* d) {
+  return sd && ok_desc(d) && avvad_stft_workspace(sd) != 0 && sd->B == d->B && sd->T == d->T && sd->n_fft == d->n_fft &&
+         sd->hop == d->hop && ok_strides(d, (long)d->T * frames::spectrum_ld(d->n_fft), frames::spectrum_ld(d->n_fft), 2);
+}
+
+extern "C" size_t avvad_resynth_workspace(const avvad_stft_desc* sd, const avvad_istft_desc* d) {
+  if (!ok_pair(sd, d)) return 0;
+  return carve(d, stft_floats(sd)).total * sizeof(float);
+}
+
+// framed_dft -> masked inverse -> overlap-add; the spectrum stays in the workspace
+extern "C" int avvad_resynth(const float* wave, const float* mask, const int* n_frames, const int* out_len, const float* scale,
+                             float* out, const avvad_stft_desc* sd, const avvad_istft_desc* d, void* wsv, size_t ws_bytes,
+                             avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!wave || !out || !wsv || !ok_pair(sd, d) || (d->mask_mode != 0 && !mask) || ((uintptr_t)wsv & 15)) return AVVAD_EINVAL;
+  if (ws_bytes < avvad_resynth_workspace(sd, d)) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  const int ld = frames::spectrum_ld(sd->n_fft);
+  float* ws = (float*)wsv;
+  float* W = ws;
+  float* S = W + align_up((size_t)sd->n_fft * ld, 64);
+  const Carve c = carve(d, stft_floats(sd));
+  const int rc = frames::framed_dft(wave, sd->L, sd->B, sd->T, sd->n_fft, sd->hop, W, S, ws + c.slab, s);
+  if (rc) return rc;
+  return inverse(S, (long)sd->T * ld, ld, 2, mask, n_frames, out_len, scale, out, d, ws, c, s);
+}
+
+// out [B][T][F][2] = the complex spectrum of avvad_stft's DFT (workspace: avvad_stft_workspace)
+extern "C" int avvad_stft_complex(const float* wave, float* out, const avvad_stft_desc* sd, void* wsv, size_t ws_bytes,
+                                  avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!wave || !out || !wsv || !sd) return AVVAD_EINVAL;
+  const size_t need = avvad_stft_workspace(sd);
+  if (need == 0) return AVVAD_EINVAL;
+  if (ws_bytes < need) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  const int F = sd->n_fft / 2 + 1, ld = frames::spectrum_ld(sd->n_fft);
+  const long M = (long)sd->B * sd->T;
+  float* W = (float*)wsv;
+  float* S = W + align_up((size_t)sd->n_fft * ld, 64);
+  const int rc = frames::framed_dft(wave, sd->L, sd->B, sd->T, sd->n_fft, sd->hop, W, S, S + align_up((size_t)M * ld, 64), s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(to_complex, dim3(grid1(M * F * 2)), dim3(256), 0, s, S, out, M, F, ld);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}

@@ -40,6 +40,34 @@ def stft_pytorch(x, fs=16e3, wlen_sec=50e-3, win='hann', hop_percent=0.25, cente
     raise AvvadError("stft_pytorch: x must be a GPU tensor -- the AV-VAD front-end has no CPU fallback")
 
 
+def istft(Sxx, fs=16000, wlen_sec=50e-3, win='hann', hop_percent=0.25, center=True, dtype='float32', max_len=None):
+    """Drop-in for ``istft`` of ``packages/processing/stft.py:63-99`` (``librosa.core.istft``) on the GPU: ``Sxx`` a
+    complex64 (bins, frames) tensor or its real (bins, frames, 2) view, as ``stft_pytorch`` returns it; returns the
+    (samples,) float32 waveform.  ``max_len`` is handed on as librosa's ``length`` -- a count of SAMPLES -- and the
+    reference's following ``x[:int(max_len*fs)]`` then cuts nothing; both are kept as they are."""
+    from avvad import ops
+    from avvad._lib import AvvadError
+    if wlen_sec * fs != int(wlen_sec * fs):
+        raise ValueError("wlen_sample of iSTFT is not an integer.")
+    nfft = int(wlen_sec * fs)
+    hopsamp = int(hop_percent * nfft)
+    if not (isinstance(Sxx, torch.Tensor) and Sxx.is_cuda):
+        raise AvvadError("istft: Sxx must be a GPU tensor -- the inverse STFT has no CPU fallback")
+    if not (isinstance(win, str) and win == 'hann'):
+        raise AvvadError("GPU istft implements the reference's periodic Hann window only")
+    import numpy as np
+    if dtype is not torch.float32 and np.dtype(dtype) != np.float32:
+        raise AvvadError("GPU istft returns float32, got dtype %r" % (dtype,))
+    if nfft % 32:
+        raise AvvadError("GPU istft needs an FFT length that is a multiple of 32 (got %d)" % nfft)
+    if Sxx.dim() == 4:
+        raise AvvadError("istft takes ONE utterance, (bins, frames) complex or (bins, frames, 2); use avvad.ops.istft for batches")
+    x = ops.istft(Sxx, nfft, hopsamp, center=center, length=max_len).view(-1)
+    if max_len:
+        x = x[:int(max_len * fs)]
+    return x
+
+
 def log_power_spectrogram(x, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=1e-8, pad_at_end=True):
     """Fused form of the callers' stft_pytorch -> re^2+im^2 -> log(.+eps) -> transpose chain
     (scripts/evaluate_audio_net.py:131-163): x (B,L) or (L,) on the GPU -> (B,T,513) log-power features."""

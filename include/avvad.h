@@ -411,6 +411,49 @@ int avvad_stft_stream_fwd(const float* chunk, const int* n_valid, const int* n_p
                           const int* pad_frames, const float* peak, const float* state_in, float* state_out,
                           const float* basis, const float* mean, const float* std_, float* out,
                           const avvad_stft_stream_desc* d, avvad_stream_t s);
+/* ------------------------------------------------------------------------
+ * Masked inverse STFT: mask x spectrum -> waveform
+ * Replaces: istft packages/processing/stft.py:63-99 (librosa.core.istft: per-frame irfft, periodic Hann, overlap-add,
+ *   division by the window sum of squares where it exceeds float32 tiny, centre trim, length fix), and the
+ *   "mask x noisy spectrum" product in front of it, which is never written to memory.
+ * The inverse DFT and the synthesis window are ONE fp32-MFMA GEMM, Y[(b,t)][n] = sum_c A[(b,t)][c] Winv[c][n]
+ * (c = 2f + {re,im}; the forward transform's flop count), then a gather per output sample in ascending frame order:
+ *   out[b][s] = scale[b] * (sum_t Y[b,t][s + start - t hop]) / wss(s + start),   wss(s') = sum_t hann^2[s' - t hop]
+ * over the frames t < n_frames[b] that cover s' (the division only where wss > 1.17549435e-38).  No float atomics:
+ * results are bit-identical run to run.  Samples at or beyond out_len[b], beyond the row's natural length
+ * n_fft + hop (n_frames[b] - 1) - start, and rows without frames are written as exact zeros.
+ * spec: interleaved (re, im) pairs, bin (b, t, f) at spec[b * stride_b + t * stride_t + f * stride_f] (float strides): a
+ * batched [B][T][F][2] tensor (T F 2, F 2, 2), the legacy [F][T][2] view of ONE utterance (0, 2, 2 T) and the forward
+ * transform's workspace rows go in as they are.  F = n_fft/2 + 1, n_fft % 32 == 0, n_fft >= 32, 1 <= hop <= n_fft (hop
+ * need not divide n_fft).  The last element of spec and of mask lies below 2^31 floats (32-bit offsets in the operand
+ * load; AVVAD_EINVAL otherwise).
+ * mask_mode 0: none (mask may be NULL); 1: multiply by mask [B][T][F]; 2: by sigmoid(mask) (a soft mask from logits);
+ * 3: by (mask > 0 ? 1 : 0) (the evaluators' sigmoid > 0.5).
+ * n_frames / out_len: device int32 [B], NULL = T frames / out_pitch samples for every row (values are clamped to those).
+ * scale: device float [B] or NULL (undoes the evaluators' peak normalisation).  out [B][out_pitch].  start = n_fft/2
+ * for librosa's center=True, else 0.  ws: 16-byte aligned.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int B, T;        /* rows, frame pitch of spec / mask                       */
+  int n_fft, hop;
+  int start;       /* samples trimmed at the front (0 <= start < n_fft)      */
+  int out_pitch;   /* floats per row of out                                  */
+  int mask_mode;   /* 0 .. 3                                                 */
+} avvad_istft_desc;
+size_t avvad_istft_workspace(const avvad_istft_desc* d);   /* 0 on a bad descriptor */
+int avvad_istft(const float* spec, long stride_b, long stride_t, long stride_f, const float* mask, const int* n_frames,
+                const int* out_len, const float* scale, float* out, const avvad_istft_desc* d, void* ws, size_t ws_bytes,
+                avvad_stream_t s);
+/* wave [B][L] -> out [B][out_pitch] in one call: the forward DFT of avvad_stft (sd), the masked inverse and the
+ * overlap-add; the spectrum stays in the workspace.  sd and d must agree in B, T, n_fft and hop. */
+size_t avvad_resynth_workspace(const avvad_stft_desc* sd, const avvad_istft_desc* d);
+int avvad_resynth(const float* wave, const float* mask, const int* n_frames, const int* out_len, const float* scale,
+                  float* out, const avvad_stft_desc* sd, const avvad_istft_desc* d, void* ws, size_t ws_bytes,
+                  avvad_stream_t s);
+/* The batched complex spectrum of avvad_stft's DFT: out [B][T][F][2] = (re, im).  ws: avvad_stft_workspace(d). */
+int avvad_stft_complex(const float* wave, float* out, const avvad_stft_desc* d, void* ws, size_t ws_bytes,
+                       avvad_stream_t s);
+
 /* out[b][:] = x[b][:] / max|x[b][:]|   (peak normalisation, scripts/evaluate_audio_net.py:125-127); out may alias x */
 int avvad_peak_normalize(const float* x, float* out, int B, long L, avvad_stream_t s);
 /* out[r][f] = (x[r][f] - mean[f]) / (std[f] + eps)  -- input standardisation of the train / evaluate loops
