@@ -1168,7 +1168,7 @@ def ibm_from_spectrum(spec, eps=1e-8, ibm_threshold=50, vad=None):
         spec = spec.contiguous()
     F, T = spec.shape[0], spec.shape[1]
     d = L.TargetDesc(1, T, 2 * (F - 1), 1, T, 0, float(eps), 1.0, float(np_power10(-ibm_threshold / 20.0)))
-    ws = torch.empty(2, dtype=torch.float32, device=spec.device)
+    ws = _ws(8, spec.device)
     if vad is not None:
         vad = _dev(vad, "vad").reshape(-1)
         if vad.numel() != T:

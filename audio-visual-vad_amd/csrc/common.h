@@ -67,6 +67,10 @@ struct BwdCuCap {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Pointer class "workspace" of the C ABI (include/avvad.h, caller-owned buffers): 16-byte aligned.  The carve-ups keep
+// every sub-buffer on a 256-byte multiple of the base and the kernels read them 16 bytes at a time, so an entry point
+// refuses (AVVAD_EINVAL) a workspace that is not, before anything is launched.  A null pointer is not misaligned.
+static inline bool ws_misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 
 // fp32-input MFMA 32x32x2: D(32x32) += A(32x2) . B(2x32).
 //   lane l supplies A[i = l&31][k = l>>5] and B[k = l>>5][j = l&31];

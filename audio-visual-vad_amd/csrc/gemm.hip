@@ -59,6 +59,7 @@ int avvad_gemm_impl(const float* A, const float* B, const float* bias, float* C,
 extern "C" int avvad_gemm_f32(const float* A, const float* B, const float* bias, float* C, const avvad_gemm_desc* d, void* ws,
                               size_t ws_bytes, avvad_stream_t s) {
   AVVAD_ENTER();
+  if (ws_misaligned(ws)) return AVVAD_EINVAL;
   float* slab = (ws && ws_bytes >= igemm::SLAB_FLOATS * sizeof(float)) ? (float*)ws : nullptr;
   return avvad_gemm_impl(A, B, bias, C, d, (hipStream_t)s, slab);
 }

@@ -219,7 +219,7 @@ extern "C" int avvad_resynth(const float* wave, const float* mask, const int* n_
 extern "C" int avvad_stft_complex(const float* wave, float* out, const avvad_stft_desc* sd, void* wsv, size_t ws_bytes,
                                   avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!wave || !out || !wsv || !sd) return AVVAD_EINVAL;
+  if (!wave || !out || !wsv || ws_misaligned(wsv) || !sd) return AVVAD_EINVAL;
   const size_t need = avvad_stft_workspace(sd);
   if (need == 0) return AVVAD_EINVAL;
   if (ws_bytes < need) return AVVAD_EWORKSPACE;

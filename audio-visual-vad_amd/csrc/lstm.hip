@@ -513,7 +513,7 @@ extern "C" int avvad_lstm_layer_fwd(const float* x, const float* w_ih, const flo
                                     avvad_stream_t sv) {
   AVVAD_ENTER();
   if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !y || !d || !wsv || !d->lengths || d->B <= 0 || d->T <= 0 || d->In <= 0 ||
-      d->H <= 0)
+      d->H <= 0 || ws_misaligned(wsv))
     return AVVAD_EINVAL;
   hipStream_t s = (hipStream_t)sv;
   Ws w = carve(d, (float*)wsv);
@@ -526,8 +526,10 @@ extern "C" int avvad_lstm_layer_fwd(const float* x, const float* w_ih, const flo
   const int split = pick_split(B, 4 * H, H);
   // sequences are handled in groups of BG = min(B, 64) (blockIdx.y); a group's 16 waves are BG/16 sequence blocks x KS K-slices
   const int BG = B < 64 ? B : 64;
+  // (the fused step and the persistent kernel read rows of W_hh and of y 16 bytes at a time: a base pointer off that
+  //  boundary -- a contiguous slice of a larger buffer -- takes the GEMM + gate kernels, whose loads adapt)
   const bool fused_step = (B == 16 || B == 32 || (B % 64 == 0 && B <= 65535 * 64)) && (H % (16 * (256 / BG)) == 0) &&
-                          !avvad_tune().lstm_no_fused_step;
+                          !avvad_tune().lstm_no_fused_step && (((uintptr_t)w_hh | (uintptr_t)y) & 15) == 0;
   // ONE persistent launch for steps 1 .. T-1 (option lstm_no_persistent: the per-step kernels)
   const int NKp = H / 64;
   const bool persistent = fused_step && !avvad_tune().lstm_no_persistent && B <= 64 && B % 16 == 0 && T > 1 &&
@@ -568,7 +570,7 @@ extern "C" int avvad_lstm_layer_bwd(const float* x, const float* w_ih, const flo
                                     const avvad_lstm_desc* d, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
   BwdCuCap cu_cap;
-  if (!x || !w_ih || !w_hh || !y || !dy || !d || !wsv || !d->lengths) return AVVAD_EINVAL;
+  if (!x || !w_ih || !w_hh || !y || !dy || !d || !wsv || !d->lengths || ws_misaligned(wsv)) return AVVAD_EINVAL;
   hipStream_t s = (hipStream_t)sv;
   Ws w = carve(d, (float*)wsv);
   if (ws_bytes < w.total * sizeof(float)) return AVVAD_EWORKSPACE;

@@ -23,10 +23,26 @@ constexpr int MAXD = 2048;
 
 static inline int ew_grid(long n) { long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
-// count sketch of one row into LDS: p[h[i]] += s[i] * x[i]
+// count sketch of one row into LDS: p[h[i]] += s[i] * x[i].  Thread t owns the buckets t, t + 256, ... and adds the values
+// that fall into them in ascending i: a FIXED order, no float atomics (LDS atomics met in whatever order the waves
+// arrived, and the signed square root's derivative 0.5 / sqrt(|y|) turns a last-bit difference of a small y into 1e-5 of a
+// gradient).  i is uniform over the workgroup, so h / s / x are broadcast loads; four buckets share one pass over them.
+// Writes every p[j], j < D (blockDim.x == 256): the callers do not zero p, and synchronise before they read it.
 __device__ __forceinline__ void sketch_row(const float* __restrict__ x, const int64_t* __restrict__ h,
-                                           const float* __restrict__ s, int n, float* p) {
-  for (int i = threadIdx.x; i < n; i += blockDim.x) atomicAdd(&p[(int)h[i]], s[i] * x[i]);
+                                           const float* __restrict__ s, int n, float* p, int D) {
+  for (int j0 = threadIdx.x; j0 < D; j0 += 1024) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < n; ++i) {
+      const int hb = (int)h[i];
+      const float t = s[i] * x[i];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (hb == j0 + u * 256) acc[u] += t;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (j0 + u * 256 < D) p[j0 + u * 256] = acc[u];
+  }
 }
 
 __global__ void __launch_bounds__(256)
@@ -35,10 +51,8 @@ __global__ void __launch_bounds__(256)
                    float* __restrict__ y, int A, int V, int D) {
   __shared__ float px[MAXD], py[MAXD];
   const int row = blockIdx.x;
-  for (int j = threadIdx.x; j < D; j += 256) { px[j] = 0.f; py[j] = 0.f; }
-  __syncthreads();
-  sketch_row(a + (long)row * A, h1, s1, A, px);
-  sketch_row(v + (long)row * V, h2, s2, V, py);
+  sketch_row(a + (long)row * A, h1, s1, A, px, D);
+  sketch_row(v + (long)row * V, h2, s2, V, py, D);
   __syncthreads();
   for (int j0 = threadIdx.x; j0 < D; j0 += 1024) {   // 4 outputs per thread per pass
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -64,10 +78,9 @@ __global__ void __launch_bounds__(256)
                    const float* __restrict__ dy, float* __restrict__ da, float* __restrict__ dv, int A, int V, int D) {
   __shared__ float px[MAXD], py[MAXD], g[MAXD];
   const int row = blockIdx.x;
-  for (int j = threadIdx.x; j < D; j += 256) { px[j] = 0.f; py[j] = 0.f; g[j] = dy[(long)row * D + j]; }
-  __syncthreads();
-  sketch_row(a + (long)row * A, h1, s1, A, px);
-  sketch_row(v + (long)row * V, h2, s2, V, py);
+  for (int j = threadIdx.x; j < D; j += 256) g[j] = dy[(long)row * D + j];
+  sketch_row(a + (long)row * A, h1, s1, A, px, D);
+  sketch_row(v + (long)row * V, h2, s2, V, py, D);
   __syncthreads();
   // only the A (resp. V) sketch buckets that are actually hit need a gradient: one output per input channel
   for (int i = threadIdx.x; i < A + V; i += 256) {
@@ -87,9 +100,10 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// z = sign(y) sqrt(|y| + eps); sumsq += sum z^2 (fp64)
+// z = sign(y) sqrt(|y| + eps); part[blockIdx.x] = this workgroup's sum z^2 (fp64), added up by sum_partials in a fixed
+// order (no atomics: the norm, and with it every output, is the same bits run to run)
 __global__ void __launch_bounds__(256)
-    ssqrt_kernel(const float* __restrict__ y, float* __restrict__ z, double* __restrict__ sumsq, long n, float eps) {
+    ssqrt_kernel(const float* __restrict__ y, float* __restrict__ z, double* __restrict__ part, long n, float eps) {
   __shared__ double sm[256];
   double acc = 0.0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
@@ -105,9 +119,20 @@ __global__ void __launch_bounds__(256)
     if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) atomicAdd(sumsq, sm[0]);
+  if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
 }
-__global__ void zero_d(double* p) { *p = 0.0; }
+__global__ void __launch_bounds__(256) sum_partials(const double* __restrict__ part, int nb, double* __restrict__ sumsq) {
+  __shared__ double sm[256];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 256) acc += part[i];
+  sm[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *sumsq = sm[0];
+}
 __global__ void scale_by_norm(const float* __restrict__ z, const double* __restrict__ sumsq, float* __restrict__ y2, long n) {
   const float inv = (float)(1.0 / sqrt(*sumsq));
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y2[i] = z[i] * inv;
@@ -128,9 +153,7 @@ __global__ void __launch_bounds__(256)
                             float* __restrict__ out, int In, int D) {
   __shared__ float p[MAXD];
   const int row = blockIdx.x;
-  for (int j = threadIdx.x; j < D; j += 256) p[j] = 0.f;
-  __syncthreads();
-  sketch_row(x + (long)row * In, h, s, In, p);
+  sketch_row(x + (long)row * In, h, s, In, p, D);
   __syncthreads();
   for (int j = threadIdx.x; j < D; j += 256) out[(long)row * D + j] = p[j];
 }
@@ -191,15 +214,16 @@ extern "C" int avvad_mcb_fusion_fwd(const float* audio, const float* video, cons
                                     float* bn_rv, float* out, const avvad_mcb_desc* d, void* wsv, size_t ws_bytes,
                                     avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!audio || !video || !h1 || !s1 || !h2 || !s2 || !bn_w || !bn_b || !bn_rm || !bn_rv || !out || !wsv || !ok_desc(d))
+  if (!audio || !video || !h1 || !s1 || !h2 || !s2 || !bn_w || !bn_b || !bn_rm || !bn_rv || !out || !wsv || ws_misaligned(wsv) || !ok_desc(d))
     return AVVAD_EINVAL;
   hipStream_t s = (hipStream_t)sv;
   Ws w = carve(d, (float*)wsv);
   if (ws_bytes < w.total * sizeof(float)) return AVVAD_EWORKSPACE;
   const long n = (long)d->rows * d->D;
   hipLaunchKernelGGL(mcb_fwd_kernel, dim3(d->rows), dim3(256), 0, s, audio, video, h1, s1, h2, s2, w.Y, d->A, d->V, d->D);
-  hipLaunchKernelGGL(zero_d, dim3(1), dim3(1), 0, s, w.sumsq);
-  hipLaunchKernelGGL(ssqrt_kernel, dim3(ew_grid(n) > 1024 ? 1024 : ew_grid(n)), dim3(256), 0, s, w.Y, w.Z, w.sumsq, n, d->eps);
+  const int nb = ew_grid(n) > 1024 ? 1024 : ew_grid(n);      // (w.part is free until the column reduction below: >= 1024 doubles)
+  hipLaunchKernelGGL(ssqrt_kernel, dim3(nb), dim3(256), 0, s, w.Y, w.Z, w.part, n, d->eps);
+  hipLaunchKernelGGL(sum_partials, dim3(1), dim3(256), 0, s, w.part, nb, w.sumsq);
   hipLaunchKernelGGL(scale_by_norm, dim3(ew_grid(n)), dim3(256), 0, s, w.Z, w.sumsq, w.Y2, n);
   const Chunks c = chunks(d->rows, d->D);
   if (d->training)
@@ -218,7 +242,7 @@ extern "C" int avvad_mcb_fusion_bwd(const float* audio, const float* video, cons
                                     float* dvideo, float* dbn_w, float* dbn_b, const avvad_mcb_desc* d, void* wsv,
                                     size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!audio || !video || !h1 || !s1 || !h2 || !s2 || !bn_w || !dout || !wsv || !ok_desc(d)) return AVVAD_EINVAL;
+  if (!audio || !video || !h1 || !s1 || !h2 || !s2 || !bn_w || !dout || !wsv || ws_misaligned(wsv) || !ok_desc(d)) return AVVAD_EINVAL;
   hipStream_t s = (hipStream_t)sv;
   Ws w = carve(d, (float*)wsv);
   if (ws_bytes < w.total * sizeof(float)) return AVVAD_EWORKSPACE;

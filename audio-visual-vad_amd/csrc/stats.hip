@@ -253,7 +253,7 @@ extern "C" size_t avvad_stats_workspace(size_t rows, int nstat) {
 extern "C" int avvad_stats_accumulate(const float* x, const int* lengths, double* acc, int B, int T, int F, int nstat, void* ws,
                                       size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!x || !acc || !ws || B <= 0 || T <= 0 || ((uintptr_t)ws & 7) || ((uintptr_t)acc & 7)) return AVVAD_EINVAL;
+  if (!x || !acc || !ws || B <= 0 || T <= 0 || ws_misaligned(ws) || ((uintptr_t)acc & 7)) return AVVAD_EINVAL;
   const long rows = (long)B * T;
   if (!ok_shape(rows, F, nstat)) return AVVAD_EINVAL;
   if (ws_bytes < partial_bytes(rows, F, nstat)) return AVVAD_EWORKSPACE;

@@ -81,7 +81,7 @@ extern "C" int avvad_stft_features(const float* wave, const float* mean, const f
 static int stft_impl(const float* wave, float* out, const avvad_stft_desc* d, int mode, const float* mean, const float* stdv,
                      float norm_eps, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!wave || !out || !wsv || !ok_desc(d) || mode < 0 || mode > 2 || (mode == 2 && d->B != 1)) return AVVAD_EINVAL;
+  if (!wave || !out || !wsv || ws_misaligned(wsv) || !ok_desc(d) || mode < 0 || mode > 2 || (mode == 2 && d->B != 1)) return AVVAD_EINVAL;
   if (ws_bytes < avvad_stft_workspace(d)) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
   const int F = d->n_fft / 2 + 1, ld = ld_of(d);

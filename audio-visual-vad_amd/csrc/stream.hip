@@ -441,6 +441,7 @@ extern "C" int avvad_wavenet_stream_fwd(const float* chunk, const avvad_wavenet_
   if (!chunk || !prm || !state || !n_valid || !skip || !stream_desc_ok(d) || k < 1 || out_frames < 0 ||
       (out_frames > 0 && !out) || (long)d->qc * d->L >= (1L << 31) / d->B)
     return AVVAD_EINVAL;
+  if (ws_misaligned(wsv)) return AVVAD_EINVAL;
   if (!wsv || ws_bytes < 256) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
   WsTab tab;

@@ -278,7 +278,7 @@ extern "C" size_t avvad_target_workspace(const avvad_target_desc* d) {
 extern "C" int avvad_target_vad(const float* wave, const int* n_samples, const int* n_frames, float* vad, const avvad_target_desc* d,
                                 void* ws, size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!wave || !n_samples || !n_frames || !vad || !ws || !ok_desc(d)) return AVVAD_EINVAL;
+  if (!wave || !n_samples || !n_frames || !vad || !ws || ws_misaligned(ws) || !ok_desc(d)) return AVVAD_EINVAL;
   const Layout l = layout(d);
   if (ws_bytes < l.total) return AVVAD_EWORKSPACE;
   return vad_impl(wave, n_samples, n_frames, vad, d, (char*)ws, l, (hipStream_t)sv);
@@ -287,7 +287,8 @@ extern "C" int avvad_target_vad(const float* wave, const int* n_samples, const i
 extern "C" int avvad_target_ibm(const float* wave, const int* n_samples, const int* n_frames, int robust, float* ibm,
                                 const avvad_target_desc* d, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!wave || !n_samples || !n_frames || !ibm || !wsv || !ok_desc(d) || d->center != 0 || d->n_fft % 32 != 0) return AVVAD_EINVAL;
+  if (!wave || !n_samples || !n_frames || !ibm || !wsv || ws_misaligned(wsv) || !ok_desc(d) || d->center != 0 || d->n_fft % 32 != 0)
+    return AVVAD_EINVAL;
   const int ld = frames::spectrum_ld(d->n_fft), F = d->n_fft / 2 + 1;
   if ((long)d->B * d->T * ld >= (1L << 31)) return AVVAD_EINVAL;
   const Layout l = layout(d);
@@ -319,9 +320,9 @@ extern "C" int avvad_target_ibm_from_spectrum(const float* spec, long stride_t, 
   // only B, n_fft (F = n_fft/2 + 1), T, eps and ibm_coef are read: the spectrum is given, there is no framing
   if (!spec || !out || !wsv || !d || d->B != 1 || d->n_fft < 2 || d->T <= 0 || (long)d->T * (d->n_fft / 2 + 1) >= (1L << 31) ||
       !(d->eps >= 0.f) || !isfinite(d->ibm_coef) || !(d->ibm_coef > 0.0) || stride_t <= 0 || stride_f <= 0 || (stride_t | stride_f) & 1 ||
-      ((uintptr_t)spec & 7))
+      ((uintptr_t)spec & 7) || ws_misaligned(wsv))
     return AVVAD_EINVAL;
-  if (ws_bytes < sizeof(unsigned long long) || ((uintptr_t)wsv & 7)) return AVVAD_EWORKSPACE;
+  if (ws_bytes < sizeof(unsigned long long)) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
   const int F = d->n_fft / 2 + 1, T = d->T;
   unsigned long long* maxbits = (unsigned long long*)wsv;

@@ -1059,7 +1059,7 @@ extern "C" int avvad_conv2d_fwd(const float* x, const float* wf, float* y, const
                                 avvad_stream_t s) {
   AVVAD_ENTER();
   Geom g;
-  if (!x || !wf || !y || !conv_geom(d, &g)) return AVVAD_EINVAL;
+  if (!x || !wf || !y || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
   return conv_fwd(x, wf, y, g, (hipStream_t)s, slab_of(ws, ws_bytes));
 }
 #ifdef AVVAD_PROF
@@ -1085,14 +1085,14 @@ extern "C" int avvad_conv2d_dgrad(const float* dy, const float* wd, float* dx, c
                                   void* ws, size_t ws_bytes, avvad_stream_t s) {
   AVVAD_ENTER();
   Geom g;
-  if (!dy || !wd || !dx || !conv_geom(d, &g)) return AVVAD_EINVAL;
+  if (!dy || !wd || !dx || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
   return conv_dgrad(dy, wd, dx, g, accumulate, (hipStream_t)s, slab_of(ws, ws_bytes));
 }
 extern "C" int avvad_conv2d_wgrad(const float* x, const float* dy, float* dw_packed, const avvad_conv_desc* d, void* ws,
                                   size_t ws_bytes, avvad_stream_t s) {
   AVVAD_ENTER();
   Geom g;
-  if (!x || !dy || !dw_packed || !conv_geom(d, &g)) return AVVAD_EINVAL;
+  if (!x || !dy || !dw_packed || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
   return conv_wgrad(x, dy, dw_packed, g, (hipStream_t)s, slab_of(ws, ws_bytes));
 }
 
@@ -1124,21 +1124,21 @@ extern "C" int avvad_conv2d_fwd_bf16(const void* x16, const void* wf16, float* y
                                      avvad_stream_t s) {
   AVVAD_ENTER();
   Geom g;
-  if (!x16 || !wf16 || !y || !conv_geom(d, &g)) return AVVAD_EINVAL;
+  if (!x16 || !wf16 || !y || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
   return conv_fwd16((const float*)x16, (const float*)wf16, y, g, (hipStream_t)s, slab_of(ws, ws_bytes), nullptr);
 }
 extern "C" int avvad_conv2d_dgrad_bf16(const void* dy16, const void* wd16, float* dx, const avvad_conv_desc* d, int accumulate,
                                        void* ws, size_t ws_bytes, avvad_stream_t s) {
   AVVAD_ENTER();
   Geom g;
-  if (!dy16 || !wd16 || !dx || !conv_geom(d, &g)) return AVVAD_EINVAL;
+  if (!dy16 || !wd16 || !dx || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
   return conv_dgrad16((const float*)dy16, (const float*)wd16, dx, g, accumulate, (hipStream_t)s, slab_of(ws, ws_bytes));
 }
 extern "C" int avvad_conv2d_wgrad_bf16(const void* x16, const void* dy16, float* dw_packed, const avvad_conv_desc* d, void* ws,
                                        size_t ws_bytes, avvad_stream_t s) {
   AVVAD_ENTER();
   Geom g;
-  if (!x16 || !dy16 || !dw_packed || !conv_geom(d, &g)) return AVVAD_EINVAL;
+  if (!x16 || !dy16 || !dw_packed || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
   return conv_wgrad16((const float*)x16, (const float*)dy16, dw_packed, g, (hipStream_t)s, slab_of(ws, ws_bytes));
 }
 
@@ -1167,7 +1167,7 @@ extern "C" int avvad_trunk_activation(const avvad_trunk_desc* d, int index, size
 extern "C" int avvad_trunk_fwd(const float* frames, const avvad_trunk_params* prm, float* feat, const avvad_trunk_desc* d,
                                void* wsv, size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!frames || !prm || !feat || !d || !wsv || d->N <= 0 || d->H < 32 || d->W < 32) return AVVAD_EINVAL;
+  if (!frames || !prm || !feat || !d || !wsv || ws_misaligned(wsv) || d->N <= 0 || d->H < 32 || d->W < 32) return AVVAD_EINVAL;
   hipStream_t s = (hipStream_t)sv;
   Plan p;
   make_plan(d, &p);
@@ -1253,7 +1253,7 @@ extern "C" int avvad_trunk_bwd(const float* frames, const avvad_trunk_params* pr
                                avvad_stream_t sv) {
   AVVAD_ENTER();
   BwdCuCap cu_cap;
-  if (!frames || !prm || !dfeat || !g || !d || !wsv || !d->save_for_backward) return AVVAD_EINVAL;
+  if (!frames || !prm || !dfeat || !g || !d || !wsv || ws_misaligned(wsv) || !d->save_for_backward) return AVVAD_EINVAL;
   hipStream_t s = (hipStream_t)sv;
   Plan p;
   make_plan(d, &p);

@@ -2104,7 +2104,7 @@ extern "C" int avvad_wavenet_fwd(const float* wave, const avvad_wavenet_params* 
                                  void* wsv, size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
   Plan p;
-  if (!wave || !prm || !out || !wsv || make_plan(d, &p)) return AVVAD_EINVAL;
+  if (!wave || !prm || !out || !wsv || ws_misaligned(wsv) || make_plan(d, &p)) return AVVAD_EINVAL;
   if (ws_bytes < p.total * sizeof(float)) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
   float* ws = (float*)wsv;
@@ -2163,7 +2163,7 @@ extern "C" int avvad_wavenet_bwd(const float* wave, const avvad_wavenet_params* 
                                  size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
   Plan p;
-  if (!wave || !prm || !dout || !g || !wsv || make_plan(d, &p) || !d->save_for_backward) return AVVAD_EINVAL;
+  if (!wave || !prm || !dout || !g || !wsv || ws_misaligned(wsv) || make_plan(d, &p) || !d->save_for_backward) return AVVAD_EINVAL;
   if (ws_bytes < p.total * sizeof(float)) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
   float* ws = (float*)wsv;

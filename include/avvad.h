@@ -11,7 +11,43 @@
  *   - plain C types only; every pointer is a DEVICE pointer unless the
  *     parameter name ends in _h (host);
  *   - the caller allocates every buffer, including the workspace
- *     (size from the matching *_workspace() query, bytes);
+ *     (size from the matching *_workspace() query, bytes).  The contract
+ *     (tests/test_abi_contract_gpu.py runs every entry-point family under it):
+ *       * contents on entry are unspecified: what a workspace or an output
+ *         buffer holds when the call starts never reaches a result.  Outputs
+ *         are written in full -- padded steps, frames behind a row's length and
+ *         gradients of masked rows are stored as zeros, not left alone.
+ *         (In/out arguments are what their entry point says: C with
+ *         accumulate, gradient pointers that are accumulated into (+=),
+ *         running statistics, float64 statistics accumulators, stream state.)
+ *       * nothing outside [ws, ws + ws_bytes) and outside the stated extent of
+ *         an output is written;
+ *       * a workspace below the queried size is refused (AVVAD_EWORKSPACE)
+ *         before anything is launched: no buffer has changed (tested per
+ *         entry point, forward and backward).  The one
+ *         exception is the optional engine scratch of avvad_gemm_f32 /
+ *         avvad_conv2d_*: ws == NULL or fewer than avvad_engine_workspace()
+ *         bytes select the whole-tile schedule and the scratch is not touched;
+ *       * a backward entry point takes the workspace its forward filled
+ *         (save_for_backward), unmodified in between, at the same address or
+ *         copied as a whole; it may overwrite it (one backward per forward);
+ *       * alignment is per pointer class, checked before anything is launched
+ *         where a wrong one would be an error (AVVAD_EINVAL):
+ *           workspace                      16 bytes, every entry point
+ *           float64 statistics accumulator  8 bytes
+ *           int64 / int32 index arrays      their natural alignment
+ *           bf16 operands, avvad_lip_decode's coef, the avvad_stft_stream basis,
+ *           activations, weights, outputs and gradients of the encoder, the
+ *           trunk, the convolutions and the fusion: 16 bytes (the base address
+ *           of any allocation; not checked unless the entry point says so)
+ *           any 4-byte aligned float pointer (a contiguous slice such as
+ *           wave + 3): A / B of avvad_gemm_f32, the four vectors of
+ *           avvad_adam_step, wave / vad / ibm / out of avvad_target_*, wave of
+ *           avvad_stft*, w_hh / h0 / hT of the LSTM entry points, and every
+ *           argument of the element-wise helpers (loss, copy, transpose,
+ *           standardise, peak).  These pick a vector form when the pointer
+ *           (and the shape) allows it and a scalar form otherwise: same
+ *           values up to the fp32 summation order;
  *   - asynchronous on the given hipStream_t, never synchronises, never
  *     allocates, keeps no per-call state -> re-entrant across streams and
  *     devices, capturable into a hipGraph.  The only process-wide state is the
@@ -537,7 +573,8 @@ int avvad_target_ibm(const float* wave, const int* n_samples, const int* n_frame
 /* IBM of ONE given spectrum (d->B == 1; only n_fft, T, eps, ibm_coef are read): spec holds interleaved (re, im) float
  * pairs, bin (t, f) at spec[t * stride_t + f * stride_f] (float strides, even) -- the legacy (F, T, 2) view of
  * stft_pytorch and torch.view_as_real of a complex (F, T) tensor go in as they are.  out [F][T]; vad [T] (may be
- * NULL) multiplies each frame.  ws: at least 8 bytes (the workspace query of a descriptor always covers it). */
+ * NULL) multiplies each frame.  ws: at least 8 bytes (the workspace query of a descriptor always covers it), 16-byte
+ * aligned like every workspace. */
 int avvad_target_ibm_from_spectrum(const float* spec, long stride_t, long stride_f, const float* vad, float* out,
                                    const avvad_target_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
 

@@ -1100,7 +1100,7 @@ def test_count_sketch_and_compact_bilinear_pooling_modules():
     _report_grad("CompactBilinearPooling d/dx", ag.grad, ar.grad)
     _report_grad("CompactBilinearPooling d/dy", vg.grad, vr.grad)
     sq = CompactBilinearPooling(513, 513, 1024, h1, s1, T(rng.randint(0, 1024, 513)), s1.clone()).to(DEV)
-    _report("CompactBilinearPooling(x) == (x, x)", sq(ag.detach()), sq(ag.detach(), ag.detach()), 1e-5, 1e-6)   # LDS-atomic bucket order
+    _report("CompactBilinearPooling(x) == (x, x)", sq(ag.detach()), sq(ag.detach(), ag.detach()), 1e-5, 1e-6)
 
 
 def test_bce_2classes_vs_reference():
