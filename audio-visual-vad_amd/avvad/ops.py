@@ -5,6 +5,7 @@ every arithmetic step of the hot path runs in the HIP kernels.  All tensors
 must be fp32, contiguous and live on the GPU -- anything else raises.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -77,6 +78,29 @@ def _dev(t, name):
     if t.dtype != torch.float32:
         raise L.AvvadError("%s must be float32, got %s" % (name, t.dtype))
     return t.contiguous()
+
+
+def _wave2d(wave):
+    """wave (B, L) or (L,) on the GPU -> (the tensor as given, its (B, L) view)"""
+    w = _dev(wave, "wave")
+    return w, (w.view(1, -1) if w.dim() == 1 else w)
+
+
+def _ints(v, B=None, hi=None, msg=None):
+    """Host list of ints from a tensor or a sequence.  With ``msg``: B values within 0..hi (``hi`` None: no upper bound),
+    or AvvadError(msg)."""
+    vals = [int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+    if msg is not None and (len(vals) != B or any(n < 0 or (hi is not None and n > hi) for n in vals)):
+        raise L.AvvadError(msg)
+    return vals
+
+
+def _mean_std(mean, std, F, msg=None):
+    """the statistics as flat GPU vectors of F values each"""
+    mean, std = _dev(mean, "mean").reshape(-1), _dev(std, "std").reshape(-1)
+    if mean.numel() != F or std.numel() != F:
+        raise L.AvvadError(msg or "mean / std must hold %d values" % F)
+    return mean, std
 
 
 def _ws(nbytes, device):
@@ -696,15 +720,18 @@ class TransposeLast2Fn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- STFT front-end (no gradient)
+def _end_pad(L, fs, wlen_sec, hop_percent):
+    """The reference appends one hop of zeros when the utterance is not a whole number of hops -- by this test, in its
+    floats and its order of divisions (packages/processing/stft.py:134-139, target.py:28-46)."""
+    v = L / fs / wlen_sec / hop_percent
+    return math.ceil(v) != int(v)
+
+
 def n_frames(L, n_fft, hop, pad_at_end=True, fs=16e3):
     """frame count of stft_pytorch(center=False): one hop of zeros is appended when the utterance is not a whole
     number of hops (packages/processing/stft.py:134-139)."""
-    import math
-    wlen_sec, hop_percent = n_fft / fs, hop / n_fft
-    if pad_at_end:
-        v = L / fs / wlen_sec / hop_percent
-        if math.ceil(v) != int(v):
-            L = L + hop
+    if pad_at_end and _end_pad(L, fs, n_fft / fs, hop / n_fft):
+        L = L + hop
     return (L - n_fft) // hop + 1
 
 
@@ -712,8 +739,7 @@ def stft(wave, n_fft=1024, hop=256, mode=0, eps=1e-8, pad_at_end=True, fs=16e3, 
     """wave (B,L) or (L,) on the GPU.  mode 0: log-power (B,T,F); 1: power (B,T,F); 2: legacy real view (F,T,2).
     With ``mean`` / ``std`` (F values each, mode 0) the train-set standardisation (x - mean) / (std + norm_eps) of the
     evaluate scripts is applied in the same pass (avvad_stft_features)."""
-    w = _dev(wave, "wave")
-    w2 = w.view(1, -1) if w.dim() == 1 else w
+    w, w2 = _wave2d(wave)
     B, Ls = w2.shape
     T = n_frames(Ls, n_fft, hop, pad_at_end, fs)
     F = n_fft // 2 + 1
@@ -723,9 +749,7 @@ def stft(wave, n_fft=1024, hop=256, mode=0, eps=1e-8, pad_at_end=True, fs=16e3, 
     if mean is not None:
         if mode != 0 or std is None:
             raise L.AvvadError("standardisation is fused into the log-power mode only and needs both mean and std")
-        mean, std = _dev(mean, "mean").reshape(-1), _dev(std, "std").reshape(-1)
-        if mean.numel() != F or std.numel() != F:
-            raise L.AvvadError("mean / std must hold %d values" % F)
+        mean, std = _mean_std(mean, std, F)
         L.check(L.lib().avvad_stft_features(L.ptr(w2), L.ptr(mean), L.ptr(std), L.ptr(out), C.byref(d), float(norm_eps), L.ptr(ws),
                                             ws.numel() * 4, _stream()), "avvad_stft_features")
         return out
@@ -735,8 +759,7 @@ def stft(wave, n_fft=1024, hop=256, mode=0, eps=1e-8, pad_at_end=True, fs=16e3, 
 
 def peak_normalize(wave):
     """x / max|x| per utterance (evaluate_audio_net.py:125-127); wave (B,L) or (L,)."""
-    w = _dev(wave, "wave")
-    w2 = w.view(1, -1) if w.dim() == 1 else w
+    w, w2 = _wave2d(wave)
     out = torch.empty_like(w2)
     L.check(L.lib().avvad_peak_normalize(L.ptr(w2), L.ptr(out), w2.shape[0], w2.shape[1], _stream()), "avvad_peak_normalize")
     return out.view(w.shape)
@@ -769,8 +792,7 @@ def istft_length(T, n_fft, hop, center=False):
 
 def stft_complex(wave, n_fft=1024, hop=256, pad_at_end=True, fs=16e3):
     """wave (B,L) or (L,) on the GPU -> the complex spectrum of ``stft``'s DFT as a real (B,T,F,2) tensor (re, im)."""
-    w = _dev(wave, "wave")
-    w2 = w.view(1, -1) if w.dim() == 1 else w
+    w, w2 = _wave2d(wave)
     B, Ls = w2.shape
     T = n_frames(Ls, n_fft, hop, pad_at_end, fs)
     d = L.StftDesc(B, Ls, n_fft, hop, T, 0.0)
@@ -800,9 +822,7 @@ def _row_counts(v, B, hi, name, device):
     """per-row int32 counts on the device (None stays None) and the host list"""
     if v is None:
         return None, None
-    vals = [int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
-    if len(vals) != B or any(n < 0 or n > hi for n in vals):
-        raise L.AvvadError("%s must hold %d values within 0..%d" % (name, B, hi))
+    vals = _ints(v, B, hi, "%s must hold %d values within 0..%d" % (name, B, hi))
     return torch.tensor(vals, dtype=torch.int32).to(device), vals
 
 
@@ -844,9 +864,7 @@ def istft(spec, n_fft=1024, hop=256, mask=None, mask_mode=None, n_frames=None, l
     if length is None:
         lens = [istft_length(n, n_fft, hop, center) for n in (nf if nf is not None else [T] * B)]
     elif isinstance(length, (list, tuple, torch.Tensor)):
-        lens = [int(v) for v in (length.tolist() if isinstance(length, torch.Tensor) else length)]
-        if len(lens) != B or min(lens) < 0:
-            raise L.AvvadError("length must hold %d non-negative values" % B)
+        lens = _ints(length, B, None, "length must hold %d non-negative values" % B)
     else:
         lens = [int(length)] * B
     Lout = max(lens)
@@ -870,8 +888,7 @@ def resynth(wave, mask, mask_mode=1, n_fft=1024, hop=256, sample_lengths=None, p
     with mode 0).  Row b uses its own ``n_frames(L_b)`` frames and comes back with exactly L_b samples, zero behind them
     (cropped where the frames run past the utterance -- the end pad -- and zero-filled where they stop short of it).
     Returns (B, L)."""
-    w = _dev(wave, "wave")
-    w2 = w.view(1, -1) if w.dim() == 1 else w
+    w, w2 = _wave2d(wave)
     B, Ls = w2.shape
     n_fft, hop = int(n_fft), int(hop)
     T = n_frames(Ls, n_fft, hop, pad_at_end, fs)
@@ -903,8 +920,7 @@ def _n_fft_check(n_fft):
 
 def peak(wave):
     """max|x| per utterance, (B,): the constant ``peak_normalize`` divides by; wave (B,L) or (L,)."""
-    w = _dev(wave, "wave")
-    w2 = w.view(1, -1) if w.dim() == 1 else w
+    w, w2 = _wave2d(wave)
     out = torch.empty(w2.shape[0], dtype=torch.float32, device=w.device)
     L.check(L.lib().avvad_abs_max(L.ptr(w2), L.ptr(out), w2.shape[0], w2.shape[1], _stream()), "avvad_abs_max")
     return out
@@ -956,7 +972,7 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
     B, n = chunk.shape
     n_fft, hop = _n_fft_check(clock.n_fft), int(clock.hop)
     F = n_fft // 2 + 1
-    nv = [n] * B if n_valid is None else [int(x) for x in (n_valid.tolist() if isinstance(n_valid, torch.Tensor) else n_valid)]
+    nv = [n] * B if n_valid is None else _ints(n_valid)
     if len(nv) != B or any(x < 0 or x > n for x in nv):
         raise L.AvvadError("n_valid must hold one count in [0, %d] per row (%d rows), got %s" % (n, B, nv))
 
@@ -976,9 +992,7 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
     if (mean is None) != (std is None):
         raise L.AvvadError("standardisation needs both mean and std")
     if mean is not None:
-        mean, std = _dev(mean, "mean").reshape(-1), _dev(std, "std").reshape(-1)
-        if mean.numel() != F or std.numel() != F:
-            raise L.AvvadError("mean / std must hold %d values" % F)
+        mean, std = _mean_std(mean, std, F)
     frames, pending, pad = clock.advance(nv, final=() if final is None else final)      # raises before it changes anything
     tmax = max(frames)
     counts = torch.tensor([nv, pending, frames, pad], dtype=torch.int32).to(chunk.device, non_blocking=False)
@@ -1017,12 +1031,9 @@ def stft_stats(acc, wave, sample_lengths, n_fft=1024, hop=256, eps=1e-8, pad_at_
     """Adds the log-power STFT features of a ragged batch to ``acc`` without writing them (avvad_stft_stats): wave (B, L)
     zero-padded rows (or (L,)), ``sample_lengths`` the B real lengths; row b counts its first ``n_frames(L_b)`` frames,
     the rule ``ops.stft`` uses for the frame count.  Returns ``acc``."""
-    w = _dev(wave, "wave")
-    w2 = w.view(1, -1) if w.dim() == 1 else w
+    w, w2 = _wave2d(wave)
     B, Ls = w2.shape
-    lens = [int(v) for v in (sample_lengths.tolist() if isinstance(sample_lengths, torch.Tensor) else sample_lengths)]
-    if len(lens) != B or any(n < 0 or n > Ls for n in lens):
-        raise L.AvvadError("sample_lengths must hold %d lengths within 0..%d" % (B, Ls))
+    lens = _ints(sample_lengths, B, Ls, "sample_lengths must hold %d lengths within 0..%d" % (B, Ls))
     F = n_fft // 2 + 1
     if _acc_nstat(acc) != F:
         raise L.AvvadError("acc holds %d statistics, the STFT has %d bins" % (_acc_nstat(acc), F))
@@ -1081,14 +1092,11 @@ def target_frames(L, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, center=False, pa
     """(samples after the end pad, frame count) of ``clean_speech_VAD`` (packages/processing/target.py:28-46): one hop of
     zeros when ``ceil(L/fs/wlen_sec/hop_percent) != int(...)``, evaluated exactly as the reference writes it, then
     ``n_fft//2`` per side when ``center``, then ``librosa.util.frame``'s ``1 + (len - n_fft)//hop`` frames."""
-    import math
     nfft = int(wlen_sec * fs)
     hop = int(hop_percent * nfft)
     n = int(L)
-    if pad_at_end:
-        v = n / fs / wlen_sec / hop_percent
-        if math.ceil(v) != int(v):
-            n += hop
+    if pad_at_end and _end_pad(n, fs, wlen_sec, hop_percent):
+        n += hop
     total = n + (2 * (nfft // 2) if center else 0)
     if total < nfft:
         raise L.AvvadError("utterance of %d samples is shorter than one %d-sample frame" % (L, nfft))
@@ -1096,12 +1104,9 @@ def target_frames(L, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, center=False, pa
 
 
 def _target_call(wave, sample_lengths, fs, wlen_sec, hop_percent, center, pad_mode, pad_at_end, vad_threshold, eps, ibm_threshold):
-    w = _dev(wave, "wave")
-    w2 = w.view(1, -1) if w.dim() == 1 else w
+    w, w2 = _wave2d(wave)
     B, Lp = w2.shape
-    lens = [int(v) for v in (sample_lengths.tolist() if isinstance(sample_lengths, torch.Tensor) else sample_lengths)]
-    if len(lens) != B or any(n < 0 or n > Lp for n in lens):
-        raise L.AvvadError("sample_lengths must hold %d lengths within 0..%d" % (B, Lp))
+    lens = _ints(sample_lengths, B, Lp, "sample_lengths must hold %d lengths within 0..%d" % (B, Lp))
     if center and pad_mode not in _CENTER:
         raise L.AvvadError("pad_mode %r: the GPU labels implement 'reflect' and 'constant'" % (pad_mode,))
     if wlen_sec * fs != int(wlen_sec * fs):
@@ -1206,13 +1211,6 @@ def lip_out_frames(N, fs=16000, hop=256, fps_in=30):
     return (2 * int(N) * p + q) // (2 * q)
 
 
-def _int_list(v, name, B=None):
-    out = [int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
-    if B is not None and len(out) != B:
-        raise L.AvvadError("%s must hold %d values, got %d" % (name, B, len(out)))
-    return out
-
-
 def lip_decode(coef, n_in, n_out=None, quantize=True, acc=None, mean=None, std=None, eps=1e-8, fs=16000, hop=256, fps_in=30):
     """Lip-region DCT coefficients -> video crops at the STFT's frame rate (avvad_lip_decode; what the reference's
     ``process_write_video`` computes offline, create_video_train_files_upsampled.py:105-173): 2-D inverse DCT of every
@@ -1231,7 +1229,7 @@ def lip_decode(coef, n_in, n_out=None, quantize=True, acc=None, mean=None, std=N
     npix = LIP_W * LIP_H
     if c.dim() not in (2, 3) or c.shape[-1] != npix:
         raise L.AvvadError("coef must be (B, Nmax, %d) or (sum N, %d), got shape %s" % (npix, npix, tuple(c.shape)))
-    n_in = _int_list(n_in, "n_in")
+    n_in = _ints(n_in)
     B = len(n_in)
     if B == 0 or min(n_in) < 0:
         raise L.AvvadError("n_in must hold at least one non-negative frame count")
@@ -1247,16 +1245,16 @@ def lip_decode(coef, n_in, n_out=None, quantize=True, acc=None, mean=None, std=N
     p, q = lip_rate(fs, hop, fps_in)
     lens = [(2 * n * p + q) // (2 * q) for n in n_in]
     if n_out is not None:
-        n_out = _int_list(n_out, "n_out", B)
+        n_out = _ints(n_out)
+        if len(n_out) != B:
+            raise L.AvvadError("n_out must hold %d values, got %d" % (B, len(n_out)))
         lens = [min(t, max(m, 0)) for t, m in zip(lens, n_out)]
     if acc is not None and _acc_nstat(acc) != 1:
         raise L.AvvadError("the video statistics are one scalar pair: acc must come from stats_new(1, device)")
     if (mean is None) != (std is None):
         raise L.AvvadError("the fused standardisation needs both mean and std")
     if mean is not None:
-        mean, std = _dev(mean, "mean").reshape(-1), _dev(std, "std").reshape(-1)
-        if mean.numel() != 1 or std.numel() != 1:
-            raise L.AvvadError("the video statistics are scalars, got %d / %d values" % (mean.numel(), std.numel()))
+        mean, std = _mean_std(mean, std, 1, "the video statistics are scalars: mean / std must hold one value each")
     T = max(lens)
     video = torch.empty(B, T, LIP_H, LIP_W, dtype=torch.float32, device=c.device)
     if T == 0 or rows == 0:                     # nothing to decode, nothing to count

@@ -90,10 +90,10 @@ class SampleClock:
 
     def _plan(self, n, final):
         B = len(self.total)
-        n = [int(x) for x in (n.tolist() if isinstance(n, torch.Tensor) else n)]
+        n = ops._ints(n)
         if len(n) != B:
             raise L.AvvadError("one sample count per row expected (%d), got %d" % (B, len(n)))
-        final = set(int(b) for b in (final.tolist() if isinstance(final, torch.Tensor) else final))
+        final = set(ops._ints(final))
         if any(b < 0 or b >= B for b in final):
             raise L.AvvadError("final rows must be in [0, %d)" % B)
         frames, pad, state = [], [], []
@@ -138,7 +138,7 @@ class SampleClock:
 def _int_list(v, B, what, hi):
     if v is None:
         return [hi] * B
-    v = [int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+    v = ops._ints(v)
     if len(v) != B or any(x < 0 or x > hi for x in v):
         raise L.AvvadError("%s must hold one value in [0, %d] per row (%d rows), got %s" % (what, hi, B, v))
     return v
@@ -427,8 +427,7 @@ def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=25
     c = int(chunk_samples)
     if c < 1:
         raise L.AvvadError("chunk_samples must be >= 1")
-    w = ops._dev(wave, "wave")
-    w = w.view(1, -1) if w.dim() == 1 else w
+    w = ops._wave2d(wave)[1]
     if w.dim() != 2:
         raise L.AvvadError("wave must be (B, L) samples, got %s" % (tuple(w.shape),))
     B, Lmax = w.shape

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 #include "avvad.h"
 
@@ -64,6 +65,23 @@ struct BwdCuCap {
   }
   ~BwdCuCap() { avvad_tune().max_cus = saved; }
 };
+
+// A launch with more than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize raised first, per kernel
+// AND per device.  Every kernel (the template argument) has its own flags, one per device, atomic: a second thread at
+// worst repeats the call; an unknown device pays the call every time.  `limit`: the most the kernel is ever launched with.
+template <auto Kernel>
+int allow_large_lds(size_t bytes, size_t limit) {
+  if (bytes <= 64 * 1024) return AVVAD_OK;
+  static std::atomic<unsigned char> allowed[64];
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return AVVAD_ELAUNCH;
+  const bool known = dev >= 0 && dev < 64;
+  if (known && allowed[dev].load(std::memory_order_acquire)) return AVVAD_OK;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit) != hipSuccess)
+    return AVVAD_ELAUNCH;
+  if (known) allowed[dev].store(1, std::memory_order_release);
+  return AVVAD_OK;
+}
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -147,6 +165,8 @@ __device__ __forceinline__ TileWalk xcd_walk(long ntiles) {
   }
   return w;
 }
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -1,65 +1,55 @@
-// frames.h -- the framing + windowed-DFT operands shared by the STFT front-end (stft.hip) and the training labels
-// (target.hip): a real DFT of every frame of a [B][L] batch is ONE fp32-MFMA GEMM, S[(b,t)][2f + {re,im}] =
-// sum_k wave[b][t*hop + k] basis[k][2f + {re,im}], run through igemm::launch.
+// frames.h -- what the STFT family (stft.hip, stft_stream.hip, target.hip, stats.hip, istft.hip) shares about the framed,
+// windowed DFT: the descriptor rule, the basis formula, the spectrum workspace and the transform itself.  A real DFT of
+// every frame of a [B][L] batch is ONE fp32-MFMA GEMM, S[(b,t)][2f + {re,im}] = sum_k wave[b][t*hop + k] basis[k][2f + {re,im}],
+// run through igemm::launch; it is compiled once, in stft.hip.
 #pragma once
 #include "igemm.h"
 
 namespace frames {
-namespace {     // internal linkage: every translation unit that includes this gets its own copy of the kernel
 
-// A[m = (b,t)][k] = wave[b][t*hop + k]  (zero beyond the utterance: the reference's end padding)
-struct FrameRows {
-  static constexpr bool KCONTIG = true;
-  static constexpr int VEC = 1;
-  typedef igemm::NoCtx Ctx;
-  const float* p;
-  long L;
-  int X, K, T, hop;
-  __device__ __forceinline__ Ctx prep(int) const { return Ctx(); }
-  __device__ __forceinline__ void load(const Ctx&, int x, int k0, int kin, float* v) const {
-    const int k = k0 + kin;
-    float t = 0.f;
-    if (x < X && k < K) {
-      const int b = x / T, fr = x - b * T;
-      const long idx = (long)fr * hop + k;
-      if (idx < L) t = p[(long)b * L + idx];
-    }
-    v[0] = t;
-  }
+// transform lengths the engine's K steps and the streaming kernel's 16-sample groups take
+static inline bool ok_n_fft(int n_fft) { return n_fft >= 32 && n_fft % 32 == 0; }
+static inline bool ok_desc(const avvad_stft_desc* d) {
+  return d && d->B > 0 && d->L > 0 && ok_n_fft(d->n_fft) && d->hop > 0 && d->T > 0 &&
+         (long)(d->T - 1) * d->hop + d->n_fft <= d->L + d->hop;   // at most the reference's one-hop end pad
+}
+
+// ---- the basis formula: periodic Hann and the exactly reduced phase, in double; a caller rounds its product once
+__device__ __forceinline__ double hann(int k, int N) { return 0.5 - 0.5 * cospi(2.0 * (double)k / (double)N); }
+// cos and sin of 2 pi f k / N.  An element of a basis needs one of the two, so each is evaluated where it is asked for.
+struct Phase {
+  double ang;   // in units of pi
+  __device__ __forceinline__ double cos() const { return cospi(ang); }
+  __device__ __forceinline__ double sin() const { return sinpi(ang); }
 };
-
-// basis[k][2f] = hann[k] cos(2 pi f k / N), basis[k][2f+1] = -hann[k] sin(2 pi f k / N); columns >= 2F are zero
-__global__ void dft_basis(float* __restrict__ W, int N, int F, int ld) {
-  const long n = (long)N * ld;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int k = (int)(i / ld), c = (int)(i % ld);
-    float v = 0.f;
-    if (c < 2 * F) {
-      const int f = c >> 1;
-      const double win = 0.5 - 0.5 * cospi(2.0 * (double)k / (double)N);          // periodic Hann
-      const long fk = ((long)f * k) % N;                                          // exact phase reduction
-      const double ang = 2.0 * (double)fk / (double)N;
-      v = (float)((c & 1) ? -win * sinpi(ang) : win * cospi(ang));
-    }
-    W[i] = v;
-  }
+__device__ __forceinline__ Phase phase(int f, int k, int N) {
+  const long fk = ((long)f * k) % N;                                              // exact phase reduction
+  return Phase{2.0 * (double)fk / (double)N};
 }
 
 static inline int grid1(long n) { long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 // row pitch (floats) of S: the 2F interleaved (re, im) columns rounded up to a float4
 static inline int spectrum_ld(int n_fft) { return (2 * (n_fft / 2 + 1) + 3) / 4 * 4; }
 
-// S [B*T][ld] = framed, windowed DFT of wave [B][L] (W: n_fft x ld basis scratch; slab: igemm::SLAB_FLOATS floats)
-static inline int framed_dft(const float* wave, long L, int B, int T, int n_fft, int hop, float* W, float* S, float* slab,
-                             hipStream_t s) {
-  const int F = n_fft / 2 + 1, ld = spectrum_ld(n_fft);
-  const int M = B * T;
-  hipLaunchKernelGGL(dft_basis, dim3(grid1((long)n_fft * ld)), dim3(256), 0, s, W, n_fft, F, ld);
-  FrameRows a{wave, L, M, n_fft, T, hop};
-  igemm::ColPlain<4> b{W, ld, ld, n_fft, 0};
-  igemm::EpiStore e{S, ld, nullptr, 0};
-  return igemm::launch<128, 128>(a, b, e, M, ld, n_fft, 1, s, slab, /*allow_bf16=*/false);
+// The spectrum workspace [W n_fft x ld][S M x ld][engine slab], M = B*T: float offsets from the workspace's start, every
+// part a multiple of 64 floats behind `base`.  A module that puts buffers of its own between S and the slab (istft.hip)
+// starts them at S_end and sets `slab` to where its own carve-up has it.
+struct SpecWs {
+  int ld;
+  size_t W, S, S_end, slab, total;
+};
+static inline SpecWs spec_ws(int n_fft, size_t M, size_t base = 0) {
+  SpecWs w;
+  w.ld = spectrum_ld(n_fft);
+  w.W = base;
+  w.S = w.W + align_up((size_t)n_fft * w.ld, 64);
+  w.S_end = w.S + align_up(M * w.ld, 64);
+  w.slab = w.S_end;
+  w.total = w.slab + igemm::SLAB_FLOATS;
+  return w;
 }
 
-}  // namespace
+// ws + w.S [B*T][ld] = framed, windowed DFT of wave [B][L]; w = spec_ws(n_fft, B*T, ...) within the workspace ws
+int framed_dft(const float* wave, long L, int B, int T, int n_fft, int hop, float* ws, const SpecWs& w, hipStream_t s);
+
 }  // namespace frames

@@ -13,20 +13,18 @@
 namespace {
 
 // Winv[c][n]: row 2f = hann[n] w_f/N cos(2 pi f n / N), row 2f+1 = -hann[n] w_f/N sin(2 pi f n / N), w_f = 1 for DC and
-// Nyquist, else 2 (irfft of a half spectrum, then the synthesis window); rows >= 2F are zero.  Evaluated like
-// frames::dft_basis: periodic Hann, exact phase reduction, double, rounded once.  win2[n] = hann[n]^2 as doubles.
+// Nyquist, else 2 (irfft of a half spectrum, then the synthesis window); rows >= 2F are zero.  win2[n] = hann[n]^2 as doubles.
 __global__ void idft_basis(float* __restrict__ W, double* __restrict__ win2, int N, int F, int rows) {
   const long n_el = (long)rows * N;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i / N), n = (int)(i % N);
-    const double win = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)N);           // periodic Hann
+    const double win = frames::hann(n, N);
     float v = 0.f;
     if (c < 2 * F) {
       const int f = c >> 1;
       const double wf = (f == 0 || 2 * f == N) ? 1.0 : 2.0;
-      const long fn = ((long)f * n) % N;                                          // exact phase reduction
-      const double ang = 2.0 * (double)fn / (double)N;
-      v = (float)((c & 1) ? -win * (wf / (double)N) * sinpi(ang) : win * (wf / (double)N) * cospi(ang));
+      const frames::Phase ph = frames::phase(f, n, N);
+      v = (float)((c & 1) ? -win * (wf / (double)N) * ph.sin() : win * (wf / (double)N) * ph.cos());
     }
     W[i] = v;
     if (c == 0) win2[n] = win * win;
@@ -101,19 +99,10 @@ __global__ void overlap_add(const float* __restrict__ Y, const double* __restric
   }
 }
 
-// out[m][f][{re,im}] = S[m][2f + {re,im}]: the workspace spectrum without its row padding
-__global__ void to_complex(const float* __restrict__ S, float* __restrict__ out, long M, int F, int ld) {
-  const long n = M * F * 2;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const long m = i / (2 * F);
-    out[i] = S[m * ld + (i - m * 2 * F)];
-  }
-}
-
 using frames::grid1;
 
 static bool ok_desc(const avvad_istft_desc* d) {
-  return d && d->B > 0 && d->T > 0 && d->n_fft >= 32 && d->n_fft % 32 == 0 && d->hop > 0 && d->hop <= d->n_fft &&
+  return d && d->B > 0 && d->T > 0 && frames::ok_n_fft(d->n_fft) && d->hop > 0 && d->hop <= d->n_fft &&
          d->start >= 0 && d->start < d->n_fft && d->out_pitch > 0 && d->mask_mode >= 0 && d->mask_mode <= 3 &&
          (long)d->B * d->T * (d->n_fft / 2 + 1) < (1L << 31);       // 32-bit offsets into the mask; B T fits an int
 }
@@ -138,12 +127,6 @@ static Carve carve(const avvad_istft_desc* d, size_t base) {
   c.total = c.slab + igemm::SLAB_FLOATS;
   return c;
 }
-// floats of the forward transform's part of the fused workspace: [W n_fft x ld][S B*T x ld]
-static size_t stft_floats(const avvad_stft_desc* d) {
-  const size_t ld = frames::spectrum_ld(d->n_fft);
-  return align_up((size_t)d->n_fft * ld, 64) + align_up((size_t)d->B * d->T * ld, 64);
-}
-
 static int inverse(const float* spec, long sb, long st, long sf, const float* mask, const int* n_frames, const int* out_len,
                    const float* scale, float* out, const avvad_istft_desc* d, float* ws, const Carve& c, hipStream_t s) {
   const int N = d->n_fft, F = N / 2 + 1, ld = frames::spectrum_ld(N), M = d->B * d->T;
@@ -188,13 +171,21 @@ extern "C" int avvad_istft(const float* spec, long stride_b, long stride_t, long
 }
 
 static bool ok_pair(const avvad_stft_desc* sd, const avvad_istft_desc* d) {
-  return sd && ok_desc(d) && avvad_stft_workspace(sd) != 0 && sd->B == d->B && sd->T == d->T && sd->n_fft == d->n_fft &&
-         sd->hop == d->hop && ok_strides(d, (long)d->T * frames::spectrum_ld(d->n_fft), frames::spectrum_ld(d->n_fft), 2);
+  return frames::ok_desc(sd) && ok_desc(d) && sd->B == d->B && sd->T == d->T && sd->n_fft == d->n_fft && sd->hop == d->hop &&
+         ok_strides(d, (long)d->T * frames::spectrum_ld(d->n_fft), frames::spectrum_ld(d->n_fft), 2);
+}
+// the fused workspace: the forward transform's [W][S], then the inverse's carve-up, whose slab both transforms use
+static Carve fused(const avvad_istft_desc* d, frames::SpecWs* f) {
+  *f = frames::spec_ws(d->n_fft, (size_t)d->B * d->T);
+  const Carve c = carve(d, f->S_end);
+  f->slab = c.slab;
+  return c;
 }
 
 extern "C" size_t avvad_resynth_workspace(const avvad_stft_desc* sd, const avvad_istft_desc* d) {
   if (!ok_pair(sd, d)) return 0;
-  return carve(d, stft_floats(sd)).total * sizeof(float);
+  frames::SpecWs f;
+  return fused(d, &f).total * sizeof(float);
 }
 
 // framed_dft -> masked inverse -> overlap-add; the spectrum stays in the workspace
@@ -205,32 +196,10 @@ extern "C" int avvad_resynth(const float* wave, const float* mask, const int* n_
   if (!wave || !out || !wsv || !ok_pair(sd, d) || (d->mask_mode != 0 && !mask) || ((uintptr_t)wsv & 15)) return AVVAD_EINVAL;
   if (ws_bytes < avvad_resynth_workspace(sd, d)) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
-  const int ld = frames::spectrum_ld(sd->n_fft);
   float* ws = (float*)wsv;
-  float* W = ws;
-  float* S = W + align_up((size_t)sd->n_fft * ld, 64);
-  const Carve c = carve(d, stft_floats(sd));
-  const int rc = frames::framed_dft(wave, sd->L, sd->B, sd->T, sd->n_fft, sd->hop, W, S, ws + c.slab, s);
+  frames::SpecWs f;
+  const Carve c = fused(d, &f);
+  const int rc = frames::framed_dft(wave, sd->L, sd->B, sd->T, sd->n_fft, sd->hop, ws, f, s);
   if (rc) return rc;
-  return inverse(S, (long)sd->T * ld, ld, 2, mask, n_frames, out_len, scale, out, d, ws, c, s);
-}
-
-// out [B][T][F][2] = the complex spectrum of avvad_stft's DFT (workspace: avvad_stft_workspace)
-extern "C" int avvad_stft_complex(const float* wave, float* out, const avvad_stft_desc* sd, void* wsv, size_t ws_bytes,
-                                  avvad_stream_t sv) {
-  AVVAD_ENTER();
-  if (!wave || !out || !wsv || ws_misaligned(wsv) || !sd) return AVVAD_EINVAL;
-  const size_t need = avvad_stft_workspace(sd);
-  if (need == 0) return AVVAD_EINVAL;
-  if (ws_bytes < need) return AVVAD_EWORKSPACE;
-  hipStream_t s = (hipStream_t)sv;
-  const int F = sd->n_fft / 2 + 1, ld = frames::spectrum_ld(sd->n_fft);
-  const long M = (long)sd->B * sd->T;
-  float* W = (float*)wsv;
-  float* S = W + align_up((size_t)sd->n_fft * ld, 64);
-  const int rc = frames::framed_dft(wave, sd->L, sd->B, sd->T, sd->n_fft, sd->hop, W, S, S + align_up((size_t)M * ld, 64), s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(to_complex, dim3(grid1(M * F * 2)), dim3(256), 0, s, S, out, M, F, ld);
-  AVVAD_LAUNCH_CHECK();
-  return AVVAD_OK;
+  return inverse(ws + f.S, (long)sd->T * f.ld, f.ld, 2, mask, n_frames, out_len, scale, out, d, ws, c, s);
 }

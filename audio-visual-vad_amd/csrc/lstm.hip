@@ -14,7 +14,6 @@
 
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 __global__ void add_bias2(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ o, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

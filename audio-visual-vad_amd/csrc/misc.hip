@@ -145,11 +145,9 @@ __global__ void standardize_kernel(const float* __restrict__ x, const float* __r
   }
 }
 
-// x / max|x| per utterance (scripts/evaluate_audio_net.py:125-127): one workgroup per row
-__global__ void __launch_bounds__(1024) peak_normalize_kernel(const float* __restrict__ x, float* __restrict__ out, long L) {
+// max|x[:L]| of one row, in every thread of its 1024-thread workgroup
+__device__ __forceinline__ float row_abs_max(const float* __restrict__ xr, long L) {
   __shared__ float sm[1024];
-  const float* xr = x + (long)blockIdx.x * L;
-  float* orow = out + (long)blockIdx.x * L;
   float m = 0.f;
   for (long i = threadIdx.x; i < L; i += 1024) m = fmaxf(m, fabsf(xr[i]));
   sm[threadIdx.x] = m;
@@ -158,8 +156,19 @@ __global__ void __launch_bounds__(1024) peak_normalize_kernel(const float* __res
     if (threadIdx.x < o) sm[threadIdx.x] = fmaxf(sm[threadIdx.x], sm[threadIdx.x + o]);
     __syncthreads();
   }
-  const float peak = sm[0];
+  return sm[0];
+}
+// x / max|x| per utterance (scripts/evaluate_audio_net.py:125-127): one workgroup per row
+__global__ void __launch_bounds__(1024) peak_normalize_kernel(const float* __restrict__ x, float* __restrict__ out, long L) {
+  const float* xr = x + (long)blockIdx.x * L;
+  float* orow = out + (long)blockIdx.x * L;
+  const float peak = row_abs_max(xr, L);
   for (long i = threadIdx.x; i < L; i += 1024) orow[i] = xr[i] / peak;
+}
+// out[b] = max|x[b][:]|: the constant peak_normalize_kernel divides by, for a caller that streams the samples afterwards
+__global__ void __launch_bounds__(1024) abs_max_kernel(const float* __restrict__ x, float* __restrict__ out, long L) {
+  const float peak = row_abs_max(x + (long)blockIdx.x * L, L);
+  if (threadIdx.x == 0) out[blockIdx.x] = peak;
 }
 
 // torch.optim.Adam semantics (no weight decay, no amsgrad): scripts/train_AV_net.py:238,306
@@ -273,6 +282,14 @@ extern "C" int avvad_peak_normalize(const float* x, float* out, int B, long L, a
   AVVAD_ENTER();
   if (!x || !out || B <= 0 || L <= 0) return AVVAD_EINVAL;
   hipLaunchKernelGGL(peak_normalize_kernel, dim3(B), dim3(1024), 0, (hipStream_t)s, x, out, L);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+extern "C" int avvad_abs_max(const float* x, float* out, int B, long L, avvad_stream_t s) {
+  AVVAD_ENTER();
+  if (!x || !out || B <= 0 || L <= 0) return AVVAD_EINVAL;
+  hipLaunchKernelGGL(abs_max_kernel, dim3(B), dim3(1024), 0, (hipStream_t)s, x, out, L);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }

@@ -270,13 +270,15 @@ extern "C" int avvad_stats_accumulate(const float* x, const int* lengths, double
 
 // workspace of the fused call: the STFT's (basis, spectrum, GEMM slab: the spectrum is live while the partials are
 // written) followed by the partials
+static size_t partials_offset(const frames::SpecWs& w) { return align_up(w.total * sizeof(float), 256); }
+
 extern "C" size_t avvad_stft_stats_workspace(const avvad_stft_desc* d) {
-  const size_t stft = avvad_stft_workspace(d);                       // 0 on a bad descriptor
-  if (!stft) return 0;
+  if (!frames::ok_desc(d)) return 0;
   const long rows = (long)d->B * d->T;
   const int F = d->n_fft / 2 + 1;
-  if (!ok_shape(rows, F, F) || rows * frames::spectrum_ld(d->n_fft) >= (1L << 31)) return 0;
-  return align_up(stft, 256) + partial_bytes(rows, F, F);
+  const frames::SpecWs w = frames::spec_ws(d->n_fft, rows);
+  if (!ok_shape(rows, F, F) || rows * w.ld >= (1L << 31)) return 0;
+  return partials_offset(w) + partial_bytes(rows, F, F);
 }
 
 extern "C" int avvad_stft_stats(const float* wave, const int* n_frames, double* acc, const avvad_stft_desc* d, void* wsv,
@@ -287,15 +289,14 @@ extern "C" int avvad_stft_stats(const float* wave, const int* n_frames, double* 
   if (!need) return AVVAD_EINVAL;
   if (ws_bytes < need) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
-  const int F = d->n_fft / 2 + 1, ld = frames::spectrum_ld(d->n_fft);
+  const int F = d->n_fft / 2 + 1;
   const long rows = (long)d->B * d->T;
-  float* W = (float*)wsv;                                            // the carve-up of avvad_stft
-  float* S = W + align_up((size_t)d->n_fft * ld, 64);
-  float* slab = S + align_up((size_t)rows * ld, 64);
-  double* part = (double*)((char*)wsv + align_up(avvad_stft_workspace(d), 256));
-  int rc = frames::framed_dft(wave, d->L, d->B, d->T, d->n_fft, d->hop, W, S, slab, s);
+  const frames::SpecWs w = frames::spec_ws(d->n_fft, rows);
+  float* ws = (float*)wsv;
+  double* part = (double*)((char*)wsv + partials_offset(w));
+  int rc = frames::framed_dft(wave, d->L, d->B, d->T, d->n_fft, d->hop, ws, w, s);
   if (rc) return rc;
-  launch_columns(SpectrumLogPower{S, ld, d->eps}, rows, d->T, F, n_frames, part, s);
+  launch_columns(SpectrumLogPower{ws + w.S, w.ld, d->eps}, rows, d->T, F, n_frames, part, s);
   launch_add(part, rows, F, F, n_frames, d->B, d->T, acc, s);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;

@@ -11,6 +11,42 @@
 
 namespace {
 
+// A[m = (b,t)][k] = wave[b][t*hop + k]  (zero beyond the utterance: the reference's end padding)
+struct FrameRows {
+  static constexpr bool KCONTIG = true;
+  static constexpr int VEC = 1;
+  typedef igemm::NoCtx Ctx;
+  const float* p;
+  long L;
+  int X, K, T, hop;
+  __device__ __forceinline__ Ctx prep(int) const { return Ctx(); }
+  __device__ __forceinline__ void load(const Ctx&, int x, int k0, int kin, float* v) const {
+    const int k = k0 + kin;
+    float t = 0.f;
+    if (x < X && k < K) {
+      const int b = x / T, fr = x - b * T;
+      const long idx = (long)fr * hop + k;
+      if (idx < L) t = p[(long)b * L + idx];
+    }
+    v[0] = t;
+  }
+};
+
+// basis[k][2f] = hann[k] cos(2 pi f k / N), basis[k][2f+1] = -hann[k] sin(2 pi f k / N); columns >= 2F are zero
+__global__ void dft_basis(float* __restrict__ W, int N, int F, int ld) {
+  const long n = (long)N * ld;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int k = (int)(i / ld), c = (int)(i % ld);
+    float v = 0.f;
+    if (c < 2 * F) {
+      const double win = frames::hann(k, N);
+      const frames::Phase ph = frames::phase(c >> 1, k, N);
+      v = (float)((c & 1) ? -win * ph.sin() : win * ph.cos());
+    }
+    W[i] = v;
+  }
+}
+
 // out[m][f] = log(re^2 + im^2 + eps)   (or the power itself when take_log == 0)
 __global__ void power_log(const float* __restrict__ S, float* __restrict__ out, long M, int F, int ld, float eps, int take_log) {
   const long n = M * F;
@@ -45,21 +81,33 @@ __global__ void to_legacy_view(const float* __restrict__ S, float* __restrict__ 
     out[i] = S[(long)t * ld + 2 * f + ri];
   }
 }
+// out[m][f][{re,im}] = S[m][2f + {re,im}]: the workspace spectrum without its row padding
+__global__ void to_complex(const float* __restrict__ S, float* __restrict__ out, long M, int F, int ld) {
+  const long n = M * F * 2;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long m = i / (2 * F);
+    out[i] = S[m * ld + (i - m * 2 * F)];
+  }
+}
 
 using frames::grid1;
-static inline int ld_of(const avvad_stft_desc* d) { return frames::spectrum_ld(d->n_fft); }
-static bool ok_desc(const avvad_stft_desc* d) {
-  return d && d->B > 0 && d->L > 0 && d->n_fft >= 32 && d->n_fft % 32 == 0 && d->hop > 0 && d->T > 0 &&
-         (long)(d->T - 1) * d->hop + d->n_fft <= d->L + d->hop;   // at most the reference's one-hop end pad
-}
+using frames::ok_desc;
+static inline frames::SpecWs ws_of(const avvad_stft_desc* d) { return frames::spec_ws(d->n_fft, (size_t)d->B * d->T); }
 
 }  // namespace
 
-extern "C" size_t avvad_stft_workspace(const avvad_stft_desc* d) {
-  if (!ok_desc(d)) return 0;
-  const size_t ld = ld_of(d);
-  return (align_up((size_t)d->n_fft * ld, 64) + align_up((size_t)d->B * d->T * ld, 64) + igemm::SLAB_FLOATS) * sizeof(float);
+int frames::framed_dft(const float* wave, long L, int B, int T, int n_fft, int hop, float* ws, const SpecWs& w, hipStream_t s) {
+  const int F = n_fft / 2 + 1, ld = w.ld;
+  const int M = B * T;
+  float* W = ws + w.W;
+  hipLaunchKernelGGL(dft_basis, dim3(grid1((long)n_fft * ld)), dim3(256), 0, s, W, n_fft, F, ld);
+  FrameRows a{wave, L, M, n_fft, T, hop};
+  igemm::ColPlain<4> b{W, ld, ld, n_fft, 0};
+  igemm::EpiStore e{ws + w.S, ld, nullptr, 0};
+  return igemm::launch<128, 128>(a, b, e, M, ld, n_fft, 1, s, ws + w.slab, /*allow_bf16=*/false);
 }
+
+extern "C" size_t avvad_stft_workspace(const avvad_stft_desc* d) { return ok_desc(d) ? ws_of(d).total * sizeof(float) : 0; }
 
 static int stft_impl(const float* wave, float* out, const avvad_stft_desc* d, int mode, const float* mean, const float* stdv,
                      float norm_eps, void* wsv, size_t ws_bytes, avvad_stream_t sv);
@@ -84,17 +132,34 @@ static int stft_impl(const float* wave, float* out, const avvad_stft_desc* d, in
   if (!wave || !out || !wsv || ws_misaligned(wsv) || !ok_desc(d) || mode < 0 || mode > 2 || (mode == 2 && d->B != 1)) return AVVAD_EINVAL;
   if (ws_bytes < avvad_stft_workspace(d)) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
-  const int F = d->n_fft / 2 + 1, ld = ld_of(d);
-  float* W = (float*)wsv;
-  float* S = W + align_up((size_t)d->n_fft * ld, 64);
-  const int M = d->B * d->T;
-  int rc = frames::framed_dft(wave, d->L, d->B, d->T, d->n_fft, d->hop, W, S, S + align_up((size_t)M * ld, 64), s);
+  const frames::SpecWs w = ws_of(d);
+  const int F = d->n_fft / 2 + 1, ld = w.ld, M = d->B * d->T;
+  float *ws = (float*)wsv, *S = ws + w.S;
+  int rc = frames::framed_dft(wave, d->L, d->B, d->T, d->n_fft, d->hop, ws, w, s);
   if (rc) return rc;
   if (mode == 2) hipLaunchKernelGGL(to_legacy_view, dim3(grid1((long)d->T * F * 2)), dim3(256), 0, s, S, out, d->T, F, ld);
   else if (mean)
     hipLaunchKernelGGL(power_log_standardize, dim3(grid1((long)M * F)), dim3(256), 0, s, S, mean, stdv, out, (long)M, F, ld, d->eps,
                        norm_eps);
   else hipLaunchKernelGGL(power_log, dim3(grid1((long)M * F)), dim3(256), 0, s, S, out, (long)M, F, ld, d->eps, mode == 0);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+// out [B][T][F][2] = the complex spectrum of avvad_stft's DFT (workspace: avvad_stft_workspace)
+extern "C" int avvad_stft_complex(const float* wave, float* out, const avvad_stft_desc* d, void* wsv, size_t ws_bytes,
+                                  avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!wave || !out || !wsv || ws_misaligned(wsv) || !ok_desc(d)) return AVVAD_EINVAL;
+  if (ws_bytes < avvad_stft_workspace(d)) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  const frames::SpecWs w = ws_of(d);
+  const int F = d->n_fft / 2 + 1;
+  const long M = (long)d->B * d->T;
+  float *ws = (float*)wsv, *S = ws + w.S;
+  const int rc = frames::framed_dft(wave, d->L, d->B, d->T, d->n_fft, d->hop, ws, w, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(to_complex, dim3(grid1(M * F * 2)), dim3(256), 0, s, S, out, M, F, w.ld);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }

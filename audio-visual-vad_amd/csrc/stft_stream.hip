@@ -12,8 +12,7 @@
 // the number of pending samples: wave w of 8 accumulates the 16-sample groups kk = w, w + 8, ... of its K-slice in that
 // order (an MFMA column does not see the other columns), and the 8 partial sums are added in wave order.  Nothing else
 // enters: no atomics, no second kernel form above a size.
-#include "common.h"
-#include <atomic>
+#include "frames.h"
 
 namespace {
 
@@ -37,8 +36,8 @@ struct SsArgs {
 // k index that lane-quarter q reads in MFMA j of sample group kk: both operands use it, so the product is a plain sum over k
 __device__ __forceinline__ int ss_k(int K, int kk, int q, int j) { return (K >> 2) * q + 4 * kk + j; }
 
-// packed basis: [bin block][re, im][kk][lane][4]; value = hann[k] cos(2 pi f k / N) / -hann[k] sin(2 pi f k / N), the formula
-// of frames::dft_basis (periodic Hann, exact phase reduction, double evaluation); bins >= F are zero
+// packed basis: [bin block][re, im][kk][lane][4]; value = hann[k] cos(2 pi f k / N) / -hann[k] sin(2 pi f k / N); bins >= F
+// are zero
 __global__ void ss_basis_kernel(float* __restrict__ W, int N, int F, long n) {
   const int KQ = N >> 4;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
@@ -49,28 +48,12 @@ __global__ void ss_basis_kernel(float* __restrict__ W, int N, int F, long n) {
     const int k = ss_k(N, kk, lane >> 4, j), f = 16 * nb + (lane & 15);
     float v = 0.f;
     if (f < F) {
-      const double win = 0.5 - 0.5 * cospi(2.0 * (double)k / (double)N);
-      const long fk = ((long)f * k) % N;
-      const double ang = 2.0 * (double)fk / (double)N;
-      v = (float)(c ? -win * sinpi(ang) : win * cospi(ang));
+      const double win = frames::hann(k, N);
+      const frames::Phase ph = frames::phase(f, k, N);
+      v = (float)(c ? -win * ph.sin() : win * ph.cos());
     }
     W[idx] = v;
   }
-}
-
-// out[b] = max|x[b][:]|: the constant avvad_peak_normalize divides by, for a caller that streams the samples afterwards
-__global__ void __launch_bounds__(1024) ss_abs_max_kernel(const float* __restrict__ x, float* __restrict__ out, long L) {
-  __shared__ float sm[1024];
-  const float* xr = x + (long)blockIdx.x * L;
-  float m = 0.f;
-  for (long i = threadIdx.x; i < L; i += 1024) m = fmaxf(m, fabsf(xr[i]));
-  sm[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (threadIdx.x < o) sm[threadIdx.x] = fmaxf(sm[threadIdx.x], sm[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = sm[0];
 }
 
 struct SsRow { int nv, np, nf; };
@@ -228,7 +211,7 @@ __global__ void __launch_bounds__(SS_NT) ss_fwd_kernel(const SsArgs a) {
 }
 
 bool ss_desc_ok(const avvad_stft_stream_desc* d) {
-  return d && d->B > 0 && d->L >= 1 && d->n_fft >= 32 && d->n_fft % 32 == 0 && d->hop >= 1 && d->hop <= d->n_fft && d->T >= 0 &&
+  return d && d->B > 0 && d->L >= 1 && frames::ok_n_fft(d->n_fft) && d->hop >= 1 && d->hop <= d->n_fft && d->T >= 0 &&
          d->M >= 0 && (long)d->T * d->hop < (1L << 30) && (long)d->B * d->L < (1L << 40) &&
          (long)d->B * d->T < (1L << 31) - 64;
 }
@@ -241,44 +224,23 @@ inline int ss_bin_blocks(int n_fft) { return (n_fft / 2 + 1 + 15) / 16; }
 
 template <int NG>
 int ss_launch(const SsArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (lds > 64 * 1024) {       // more than 64 KB of dynamic LDS is cleared per kernel and per device, once
-    static std::atomic<unsigned char> cleared[64];
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return AVVAD_ELAUNCH;
-    const bool known = dev >= 0 && dev < 64;
-    if (!known || !cleared[dev].load(std::memory_order_acquire)) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(ss_fwd_kernel<NG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)SS_LDS_MAX) != hipSuccess)
-        return AVVAD_ELAUNCH;
-      if (known) cleared[dev].store(1, std::memory_order_release);
-    }
-  }
+  if (int rc = allow_large_lds<ss_fwd_kernel<NG>>(lds, SS_LDS_MAX)) return rc;
   hipLaunchKernelGGL(ss_fwd_kernel<NG>, grid, dim3(SS_NT), lds, s, a);
   return AVVAD_OK;
 }
 
 }  // namespace
 
-extern "C" int avvad_abs_max(const float* x, float* out, int B, long L, avvad_stream_t s) {
-  AVVAD_ENTER();
-  if (!x || !out || B <= 0 || L <= 0) return AVVAD_EINVAL;
-  hipLaunchKernelGGL(ss_abs_max_kernel, dim3(B), dim3(1024), 0, (hipStream_t)s, x, out, L);
-  AVVAD_LAUNCH_CHECK();
-  return AVVAD_OK;
-}
-
 extern "C" size_t avvad_stft_stream_basis_bytes(int n_fft) {
-  if (n_fft < 32 || n_fft % 32) return 0;
+  if (!frames::ok_n_fft(n_fft)) return 0;
   return (size_t)ss_bin_blocks(n_fft) * 2 * 16 * n_fft * sizeof(float);
 }
 
 extern "C" int avvad_stft_stream_basis(int n_fft, float* out, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!out || n_fft < 32 || n_fft % 32 || ((uintptr_t)out & 15)) return AVVAD_EINVAL;
+  if (!out || !frames::ok_n_fft(n_fft) || ((uintptr_t)out & 15)) return AVVAD_EINVAL;
   const long n = (long)(avvad_stft_stream_basis_bytes(n_fft) / sizeof(float));
-  long blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(ss_basis_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)sv, out, n_fft, n_fft / 2 + 1, n);
+  hipLaunchKernelGGL(ss_basis_kernel, dim3(frames::grid1(n)), dim3(256), 0, (hipStream_t)sv, out, n_fft, n_fft / 2 + 1, n);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }

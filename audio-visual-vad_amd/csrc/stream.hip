@@ -8,12 +8,8 @@
 // Video_Net.py:102-116, AV_Net.py:124-140, wavenet_autoencoder.py:74-93).
 #include "gemm_api.h"
 #include <stdlib.h>
-#include <atomic>
 
 namespace {
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // ==================================================================== LSTM layer with state
 __global__ void st_copy(const float* __restrict__ src, float* __restrict__ dst, long n) {
@@ -48,7 +44,7 @@ __global__ void __launch_bounds__(256)
     lstm_state_step(const float* __restrict__ G, const float* __restrict__ w_hh, const float* __restrict__ b_hh,
                     const float* __restrict__ hprev, float* __restrict__ hnext, const float* cin, float* cout,
                     float* __restrict__ y, const int* __restrict__ lengths, int B, int T, int H, int t) {
-  __shared__ f32x4v part[NG][4][64];
+  __shared__ f32x4 part[NG][4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, q = lane >> 4;
   const int cb = blockIdx.y * (16 * NG);
@@ -56,13 +52,13 @@ __global__ void __launch_bounds__(256)
   if (unit > H - 1) unit = H - 1;                            // H % 4 != 0: the surplus rows repeat the last unit, never stored
   const float* wrow = w_hh + ((long)(i & 3) * H + unit) * H;
   const float* hrow[NG];
-  f32x4v acc[NG];
+  f32x4 acc[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     int b = cb + 16 * g + i;
     if (b > B - 1) b = B - 1;
     hrow[g] = hprev ? hprev + (long)b * H : nullptr;
-    acc[g] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const int nkc = (H + 15) >> 4;
   for (int kk = wave; hprev && kk < nkc; kk += 4) {
@@ -81,9 +77,9 @@ __global__ void __launch_bounds__(256)
   for (int g = 0; g < NG; ++g) part[g][wave][lane] = acc[g];
   __syncthreads();
   if (wave >= NG) return;
-  f32x4v r = part[wave][0][lane];
+  f32x4 r = part[wave][0][lane];
   for (int s2 = 1; s2 < 4; ++s2) {
-    const f32x4v p = part[wave][s2][lane];
+    const f32x4 p = part[wave][s2][lane];
     r[0] += p[0]; r[1] += p[1]; r[2] += p[2]; r[3] += p[3];
   }
   // r[gate] = recurrent part of the gate of unit j for batch row b
@@ -467,19 +463,8 @@ extern "C" int avvad_wavenet_stream_fwd(const float* chunk, const avvad_wavenet_
   }
   const size_t lds = stream_lds_bytes(d, mf, NC);
   if (lds > WS_LDS_MAX) return AVVAD_EINVAL;
-  if (lds > 64 * 1024) {
-    // more than 64 KB of dynamic LDS must be cleared per kernel AND per device: remembered per device, atomically (a
-    // second thread at worst repeats the call); an unknown device pays the call every time
-    static std::atomic<unsigned char> cleared[2][64];
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return AVVAD_ELAUNCH;
-    const bool known = dev >= 0 && dev < 64;
-    if (!known || !cleared[mf][dev].load(std::memory_order_acquire)) {
-      const void* fn = mf ? reinterpret_cast<const void*>(wn_stream_kernel<true>) : reinterpret_cast<const void*>(wn_stream_kernel<false>);
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WS_LDS_MAX) != hipSuccess) return AVVAD_ELAUNCH;
-      if (known) cleared[mf][dev].store(1, std::memory_order_release);
-    }
-  }
+  if (int rc = mf ? allow_large_lds<wn_stream_kernel<true>>(lds, WS_LDS_MAX) : allow_large_lds<wn_stream_kernel<false>>(lds, WS_LDS_MAX))
+    return rc;
   const long sf = (long)stream_state_floats(d);
   if (mf)
     hipLaunchKernelGGL(wn_stream_kernel<true>, dim3(d->B), dim3(WS_NT), lds, s, chunk, state, n_valid, skip, out, tab, d->L,

@@ -232,24 +232,22 @@ bool ok_desc(const avvad_target_desc* d) {
          (long)(d->T - 1) * d->hop + d->n_fft <= d->L + d->hop + 2L * pad_off(d);
 }
 
-struct Layout {                     // workspace carve-up, byte offsets
-  size_t E, vad, maxbits, W, S, slab, total;
+struct Layout {                     // workspace carve-up: byte offsets, then the spectrum workspace (float offsets)
+  size_t E, vad, maxbits, total;
+  frames::SpecWs f;
 };
 Layout layout(const avvad_target_desc* d) {
-  Layout l;
+  Layout l = {};
   const size_t nseg = (size_t)d->T + seg_R(d) - 1;
   size_t o = 0;
   l.E = o, o += align_up((size_t)d->B * nseg * sizeof(double), 256);
   l.vad = o, o += align_up((size_t)d->B * d->T * sizeof(float), 256);
   l.maxbits = o, o += align_up((size_t)d->B * sizeof(unsigned long long), 256);
-  l.W = l.S = l.slab = o;
-  if (d->n_fft % 32 == 0) {         // the DFT GEMM of the waveform IBM
-    const size_t ld = frames::spectrum_ld(d->n_fft);
-    l.W = o, o += align_up((size_t)d->n_fft * ld * sizeof(float), 256);
-    l.S = o, o += align_up((size_t)d->B * d->T * ld * sizeof(float), 256);
-    l.slab = o, o += igemm::SLAB_FLOATS * sizeof(float);
-  }
   l.total = o;
+  if (frames::ok_n_fft(d->n_fft)) { // the DFT GEMM of the waveform IBM
+    l.f = frames::spec_ws(d->n_fft, (size_t)d->B * d->T, o / sizeof(float));
+    l.total = l.f.total * sizeof(float);
+  }
   return l;
 }
 
@@ -287,11 +285,11 @@ extern "C" int avvad_target_vad(const float* wave, const int* n_samples, const i
 extern "C" int avvad_target_ibm(const float* wave, const int* n_samples, const int* n_frames, int robust, float* ibm,
                                 const avvad_target_desc* d, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!wave || !n_samples || !n_frames || !ibm || !wsv || ws_misaligned(wsv) || !ok_desc(d) || d->center != 0 || d->n_fft % 32 != 0)
+  if (!wave || !n_samples || !n_frames || !ibm || !wsv || ws_misaligned(wsv) || !ok_desc(d) || d->center != 0 || !frames::ok_n_fft(d->n_fft))
     return AVVAD_EINVAL;
-  const int ld = frames::spectrum_ld(d->n_fft), F = d->n_fft / 2 + 1;
-  if ((long)d->B * d->T * ld >= (1L << 31)) return AVVAD_EINVAL;
   const Layout l = layout(d);
+  const int ld = l.f.ld, F = d->n_fft / 2 + 1;
+  if ((long)d->B * d->T * ld >= (1L << 31)) return AVVAD_EINVAL;
   if (ws_bytes < l.total) return AVVAD_EWORKSPACE;
   hipStream_t s = (hipStream_t)sv;
   char* ws = (char*)wsv;
@@ -301,8 +299,8 @@ extern "C" int avvad_target_ibm(const float* wave, const int* n_samples, const i
     int rc = vad_impl(wave, n_samples, n_frames, vad, d, ws, l, s);
     if (rc) return rc;
   }
-  float* S = (float*)(ws + l.S);
-  int rc = frames::framed_dft(wave, d->L, d->B, d->T, d->n_fft, d->hop, (float*)(ws + l.W), S, (float*)(ws + l.slab), s);
+  float* S = (float*)ws + l.f.S;
+  int rc = frames::framed_dft(wave, d->L, d->B, d->T, d->n_fft, d->hop, (float*)ws, l.f, s);
   if (rc) return rc;
   unsigned long long* maxbits = (unsigned long long*)(ws + l.maxbits);
   if (hipMemsetAsync(maxbits, 0, (size_t)d->B * sizeof(unsigned long long), s) != hipSuccess) return AVVAD_ELAUNCH;

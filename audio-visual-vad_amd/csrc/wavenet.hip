@@ -2185,22 +2185,12 @@ extern "C" int avvad_wavenet_bwd(const float* wave, const avvad_wavenet_params* 
     if (!avvad_tune().wn_no_tail_pair) {
       // two waves per time tile, 8 waves per workgroup (tail_bwd_wgrad_pair)
       const size_t lds = ((size_t)Bn * 33 + (size_t)Bn * 33 + 16 * 1056 + 4 * 1056) * sizeof(float);
-      static bool attr_set2 = false;
-      if (!attr_set2) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(tail_bwd_wgrad_pair<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess) return AVVAD_ELAUNCH;
-        attr_set2 = true;
-      }
+      if ((rc = allow_large_lds<tail_bwd_wgrad_pair<8>>(lds, lds))) return rc;
       hipLaunchKernelGGL(tail_bwd_wgrad_pair<8>, dim3((int)blocks), dim3(512), lds, s, ws + p.s[p.n], prm->bott_w,
                          d->use_bias ? prm->bott_b : (const float*)nullptr, dout, GA, ws + p.slab, B, Lv, d->P);
     } else {
     const size_t lds = ((size_t)Bn * 33 + (size_t)Bn * 33 + 8 * 1056) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(tail_bwd_wgrad_mfma<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds) != hipSuccess) return AVVAD_ELAUNCH;
-      attr_set = true;
-    }
+    if ((rc = allow_large_lds<tail_bwd_wgrad_mfma<8>>(lds, lds))) return rc;
     hipLaunchKernelGGL(tail_bwd_wgrad_mfma<8>, dim3((int)blocks), dim3(256), lds, s, ws + p.s[p.n], prm->bott_w,
                        d->use_bias ? prm->bott_b : (const float*)nullptr, dout, GA, ws + p.slab, B, Lv, d->P);
     }

@@ -47,6 +47,59 @@ def test_workspace_queries_and_descriptor_validation():
     assert h.avvad_adam_step(None, None, None, None, 10, 1e-3, 0.9, 0.999, 1e-8, 1, None) == -1
 
 
+# (B, L, n_fft, hop, T) -> bytes of the stft, istft, resynth and stft_stats workspaces, as recorded values: callers size
+# their buffers by these queries, so a change of the layout behind them (csrc/frames.h) must not pass unseen
+SPECTRUM_WS = {
+    (1, 64, 32, 8, 5): (37754112, 37754368, 37759744, 37754624),
+    (2, 200, 64, 16, 9): (37771264, 37771264, 37793792, 37772032),
+    (3, 16000, 1024, 256, 59): (42687488, 42692608, 47631360, 42704128),
+    (1, 70000, 512, 128, 544): (39928320, 39923712, 42103296, 39949056),
+    (5, 1000, 96, 32, 30): (37847296, 37845504, 37944064, 37849088),
+    (7, 3000, 160, 40, 72): (38184448, 38177536, 38613248, 38189824),
+}
+
+
+def _spectrum_queries(h, B, Ls, n_fft, hop, T):
+    """-> (stft, istft, resynth, stft_stats, target) workspace bytes; center = 0, the inverse writes rows of L samples"""
+    import ctypes as C
+    from avvad import _lib as L
+    sd = L.StftDesc(B, Ls, n_fft, hop, T, 1e-8)
+    d = L.IstftDesc(B, T, n_fft, hop, 0, Ls, 0)
+    td = L.TargetDesc(B, Ls, n_fft, hop, T, 0, 1e-8, 50.0, 0.003)
+    return (h.avvad_stft_workspace(C.byref(sd)), h.avvad_istft_workspace(C.byref(d)),
+            h.avvad_resynth_workspace(C.byref(sd), C.byref(d)), h.avvad_stft_stats_workspace(C.byref(sd)),
+            h.avvad_target_workspace(C.byref(td)))
+
+
+@pytest.mark.parametrize("desc", sorted(SPECTRUM_WS))
+def test_spectrum_workspace_queries_agree(desc):
+    """The STFT family's size queries are one layout seen from five entry points: [W n_fft x ld][S B*T x ld][engine
+    slab], each part rounded up to 64 floats, with each module's own buffers before or behind it."""
+    from avvad import _lib as L
+    h = L.lib()
+    B, Ls, n_fft, hop, T = desc
+    a64 = lambda v: (v + 63) // 64 * 64
+    a256 = lambda v: (v + 255) // 256 * 256
+    F = n_fft // 2 + 1
+    ld = (2 * F + 3) // 4 * 4
+    engine = h.avvad_engine_workspace()
+    stft, istft, resynth, stft_stats, target = _spectrum_queries(h, *desc)
+    assert (stft, istft, resynth, stft_stats) == SPECTRUM_WS[desc]
+    assert stft == (a64(n_fft * ld) + a64(B * T * ld)) * 4 + engine
+    assert resynth == stft + istft - engine                              # the two transforms share the slab
+    assert stft_stats == stft + h.avvad_stats_workspace(B * T, F)
+    R = n_fft // hop if n_fft % hop == 0 else 1
+    assert target == a256(B * (T + R - 1) * 8) + a256(B * T * 4) + a256(B * 8) + stft
+    # descriptors no DFT takes: a transform length that is no multiple of 32 or below it, no frame, a frame beyond the
+    # one-hop end pad (the inverse has no wave to run past; the VAD labels alone take any n_fft, without a spectrum part)
+    t_past = (Ls + hop - n_fft) // hop + 2
+    for bad in ((B, Ls, 48, hop, T), (B, Ls, 16, hop, T), (B, Ls, n_fft, hop, 0), (B, Ls, n_fft, hop, t_past)):
+        q = _spectrum_queries(h, *bad)
+        assert q[0] == q[2] == q[3] == 0, bad
+        assert q[1] == 0 or bad[4] == t_past, bad
+        assert q[4] == 0 if bad[4] in (0, t_past) else q[4] < engine, bad
+
+
 def test_dropin_state_dict_keys_and_sizes():
     from packages.models.AV_Net import DeepVAD_AV
     from packages.models.Audio_Net import DeepVAD_audio

@@ -344,3 +344,29 @@ def test_av_evaluator_from_samples_writes_what_the_whole_utterance_route_writes(
             soft = torch.load(os.path.join(outs["whole"], f.replace("_hard", "_soft")), weights_only=True)
             differ = a != b
             assert int(differ.sum()) == 0 or float((soft - 0.5).abs()[differ].max()) < 1e-4, f
+
+
+@pytest.mark.parametrize("n_fft", [32, 64])
+def test_streaming_basis_is_the_whole_utterance_basis(n_fft):
+    """Frame t of the wave is a unit impulse at sample t, so the whole-utterance DFT returns its basis exactly (one
+    non-zero product per sum); the streaming kernel's packed basis must hold the same floats, and zeros for the bins of
+    its last 16-bin block that lie at or beyond F."""
+    from avvad import ops
+    N, F = n_fft, n_fft // 2 + 1
+    wave = torch.zeros(1, N * N, device=DEV)
+    wave[0, torch.arange(N, device=DEV) * (N + 1)] = 1.0
+    whole = ops.stft_complex(wave, N, N, pad_at_end=False)[0].cpu()                  # [k][f][re, im]
+    assert whole.shape == (N, F, 2)
+    blocks = (F + 15) // 16
+    packed = ops.stft_stream_basis(N, DEV).cpu().view(blocks, 2, N // 16, 64, 4)     # [bin block][re, im][kk][lane][j]
+    lane = torch.arange(64).view(1, 64, 1)
+    k = (N // 4) * (lane >> 4) + 4 * torch.arange(N // 16).view(-1, 1, 1) + torch.arange(4).view(1, 1, 4)
+    for b in range(blocks):
+        f = (16 * b + (lane & 15)).expand_as(k)
+        inside = f < F
+        for c in range(2):
+            want = torch.zeros(N // 16, 64, 4)
+            want[inside] = whole[k[inside], f[inside], c]
+            assert bool((packed[b, c] == want).all()), (b, c)
+            assert not packed[b, c][~inside].any()
+    assert blocks * 16 > F                                                           # the last block is partly beyond F
