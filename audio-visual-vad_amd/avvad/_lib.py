@@ -79,6 +79,10 @@ class IstftDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "T", "n_fft", "hop", "start", "out_pitch", "mask_mode")]
 
 
+class IstftStreamDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "T", "n_fft", "hop", "L", "M", "mask_mode")]
+
+
 class TargetDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("L", C.c_long), ("n_fft", C.c_int), ("hop", C.c_int), ("T", C.c_int), ("center", C.c_int),
                 ("eps", C.c_float), ("vad_coef", C.c_double), ("ibm_coef", C.c_double)]
@@ -144,6 +148,11 @@ SIGNATURES = {
     "avvad_stft_stream_basis_bytes": (C.c_size_t, [C.c_int]),
     "avvad_stft_stream_basis": (C.c_int, [C.c_int, FP, FP]),
     "avvad_stft_stream_fwd": (C.c_int, [FP] * 12 + [C.POINTER(StftStreamDesc), FP]),
+    "avvad_stft_stream_fwd_spec": (C.c_int, [FP] * 13 + [C.POINTER(StftStreamDesc), FP]),
+    "avvad_istft_stream_basis_bytes": (C.c_size_t, [C.c_int]),
+    "avvad_istft_stream_basis": (C.c_int, [C.c_int, FP, FP]),
+    "avvad_istft_stream_workspace": (C.c_size_t, [C.POINTER(IstftStreamDesc)]),
+    "avvad_istft_stream": (C.c_int, [FP] * 10 + [C.POINTER(IstftStreamDesc), FP, C.c_size_t, FP]),
     "avvad_istft_workspace": (C.c_size_t, [C.POINTER(IstftDesc)]),
     "avvad_istft": (C.c_int, [FP, C.c_long, C.c_long, C.c_long, FP, FP, FP, FP, FP, C.POINTER(IstftDesc), FP, C.c_size_t, FP]),
     "avvad_resynth_workspace": (C.c_size_t, [C.POINTER(StftDesc), C.POINTER(IstftDesc)]),

@@ -954,7 +954,7 @@ def _row_vector(v, B, name):
 
 
 def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=None, final=None, out_state=None, eps=1e-8,
-                norm_eps=1e-8):
+                norm_eps=1e-8, return_spec=False):
     """The next samples of ``B`` rows through the STFT front-end (inference only): one kernel launch.
 
     chunk (B, n) float32 on the GPU, of which row b's first ``n_valid[b]`` samples are real (None: all n).  ``clock``
@@ -965,6 +965,8 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
     the standardisation of ``stft(mean=, std=)``.  ``final``: rows that end with this call; they also yield the
     reference's zero-padded last frame where it has one and must be reset on the clock before they take samples again.
     -> (features (B, tmax, F) with tmax = max(frames) and zeros behind a row's frames, frames per row (list)).
+    ``return_spec``: -> (features, frames, spec (B, tmax, F, 2)), the complex spectrum (re, im) of the samples / peak that
+    the same launch holds anyway (zeros behind a row's frames); the features keep their bits.  What ``istft_stream`` takes.
     Every argument is checked before the clock or a state changes.  Any split of a stream into calls gives the same bits."""
     chunk = _dev(chunk, "chunk")
     if chunk.dim() != 2 or chunk.shape[0] < 1:
@@ -1000,13 +1002,98 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
     new = torch.empty_like(state) if in_place else out_state
     src = chunk if n > 0 else chunk.new_zeros(B, 1)
     d = L.StftStreamDesc(B, max(n, 1), n_fft, hop, tmax, sum(frames), float(eps), float(norm_eps))
+    spec = torch.empty(B, tmax, F, 2, dtype=torch.float32, device=chunk.device) if return_spec else None
     with torch.cuda.device(chunk.device):
-        L.check(L.lib().avvad_stft_stream_fwd(L.ptr(src), L.ptr(counts[0]), L.ptr(counts[1]), L.ptr(counts[2]), L.ptr(counts[3]),
-                                              L.ptr(pk), L.ptr(state), L.ptr(new), L.ptr(basis), L.ptr(mean), L.ptr(std),
-                                              L.ptr(out) if tmax else None, C.byref(d), _stream()), "avvad_stft_stream_fwd")
+        args = (L.ptr(src), L.ptr(counts[0]), L.ptr(counts[1]), L.ptr(counts[2]), L.ptr(counts[3]), L.ptr(pk), L.ptr(state),
+                L.ptr(new), L.ptr(basis), L.ptr(mean), L.ptr(std), L.ptr(out) if tmax else None)
+        if return_spec:
+            L.check(L.lib().avvad_stft_stream_fwd_spec(*args, L.ptr(spec) if tmax else None, C.byref(d), _stream()),
+                    "avvad_stft_stream_fwd_spec")
+        else:
+            L.check(L.lib().avvad_stft_stream_fwd(*args, C.byref(d), _stream()), "avvad_stft_stream_fwd")
     if in_place:
         state.copy_(new)
-    return out, frames
+    return (out, frames, spec) if return_spec else (out, frames)
+
+
+# --------------------------------------------------------------------------- streaming masked inverse (csrc/istft_stream.hip)
+def istft_stream_basis(n_fft, device):
+    """The windowed inverse-DFT basis of ``istft`` in the streaming kernel's packed layout, with the squared window behind
+    it (an opaque float tensor): built once, reused by every ``istft_stream`` call with that ``n_fft``."""
+    n_fft = _n_fft_check(n_fft)
+    out = torch.empty(L.lib().avvad_istft_stream_basis_bytes(n_fft) // 4, dtype=torch.float32, device=device)
+    if not out.is_cuda:
+        raise L.AvvadError("the basis lives on the GPU: no CPU fallback")
+    with torch.cuda.device(out.device):
+        L.check(L.lib().avvad_istft_stream_basis(n_fft, L.ptr(out), _stream()), "avvad_istft_stream_basis")
+    return out
+
+
+def istft_stream_state(B, n_fft, device):
+    """Zeroed overlap-add state (B, n_fft) -- each row's unfinished sums of the samples later frames still cover; all
+    zeros (a fresh ``OlaClock``) is "start of utterance"."""
+    if int(B) < 1:
+        raise L.AvvadError("B must be >= 1")
+    return torch.zeros(int(B), _n_fft_check(n_fft), dtype=torch.float32, device=device)
+
+
+def istft_stream(spec, frames, clock, state, basis, mask=None, mask_mode=None, scale=None, final_samples=None, out_state=None):
+    """The next frames of ``B`` rows through the masked inverse STFT (inference only): the samples no later frame can
+    cover any more, at a cost that does not depend on the position in the stream.
+
+    spec (B, T, F, 2) float32 on the GPU as ``stft_stream(return_spec=True)`` returns it, of which row b's first
+    ``frames[b]`` frames are real; ``mask`` (B, T, F) with ``mask_mode`` as in ``istft`` (modes 2 and 3 take logits).
+    ``clock`` is the rows' :class:`avvad.stream.OlaClock` (n_fft, hop and the per-row counts); it is advanced by this call.
+    ``state`` (B, n_fft) from ``istft_stream_state``; the new sums go to ``out_state`` -- a spare tensor the caller swaps
+    with ``state`` -- or, with ``out_state`` None or ``state`` itself, back into ``state``.  ``scale`` (B,) multiplies each
+    row (the peak the forward divided by).  ``final_samples``: {row: N} (or a list with None for rows that go on) -- the
+    row's stream ends with this call and held N samples: it returns what is left of them, cropped or zero-filled like
+    ``resynth``'s rows, and must be reset on the clock before it takes frames again.
+    A row that goes on returns ``frames[b] * hop`` samples: a sample comes out up to ``n_fft - 1`` samples after it went in.
+    -> (samples (B, nmax) with zeros behind a row's count, samples per row (list)).
+    Every argument is checked before the clock or a state changes.  Any split of a stream into calls gives the same bits."""
+    if not isinstance(spec, torch.Tensor) or not spec.is_cuda:
+        raise L.AvvadError("spec must be a GPU tensor: the streaming inverse STFT has no CPU fallback")
+    n_fft, hop = _n_fft_check(clock.n_fft), int(clock.hop)
+    F = n_fft // 2 + 1
+    if spec.dtype != torch.float32 or spec.dim() != 4 or spec.shape[0] < 1 or tuple(spec.shape[2:]) != (F, 2):
+        raise L.AvvadError("spec must be float32 (B, T, %d, 2), got %s %s" % (F, spec.dtype, tuple(spec.shape)))
+    spec = spec.contiguous()
+    B, T = spec.shape[0], spec.shape[1]
+    nf = _ints(frames, B, T, "frames must hold %d counts within 0..%d" % (B, T))
+    if T > 0:
+        m, mode = _mask_args(mask, mask_mode, B, T, F)
+    else:
+        m, mode = None, 0                                         # no row has a frame: there is nothing to mask
+
+    def st(t, what):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
+                tuple(t.shape) != (B, n_fft) or t.device != spec.device:
+            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of istft_stream_state(%d, %d, device)" % (what, B, n_fft))
+        return t
+    state = st(state, "state")
+    if out_state is not None and out_state is not state:
+        st(out_state, "out_state")
+    in_place = out_state is None or out_state.data_ptr() == state.data_ptr()
+    if not isinstance(basis, torch.Tensor) or not basis.is_cuda or basis.dtype != torch.float32 or \
+            basis.numel() * 4 != L.lib().avvad_istft_stream_basis_bytes(n_fft) or basis.device != spec.device:
+        raise L.AvvadError("basis must be istft_stream_basis(%d, device)" % n_fft)
+    sc = None if scale is None else _row_vector(scale, B, "scale")
+    n_before, n_out = clock.advance(nf, final_samples)           # raises before it changes anything
+    nmax = max(n_out)
+    counts = torch.tensor([nf, n_before, n_out], dtype=torch.int32).to(spec.device, non_blocking=False)
+    out = torch.empty(B, nmax, dtype=torch.float32, device=spec.device)
+    new = torch.empty_like(state) if in_place else out_state
+    d = L.IstftStreamDesc(B, T, n_fft, hop, nmax, sum(nf), mode)
+    with torch.cuda.device(spec.device):
+        ws = _ws(L.lib().avvad_istft_stream_workspace(C.byref(d)), spec.device)
+        L.check(L.lib().avvad_istft_stream(L.ptr(spec) if T else None, L.ptr(m), L.ptr(counts[0]), L.ptr(counts[1]),
+                                           L.ptr(counts[2]), L.ptr(sc), L.ptr(state), L.ptr(new), L.ptr(basis),
+                                           L.ptr(out) if nmax else None, C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()),
+                "avvad_istft_stream")
+    if in_place:
+        state.copy_(new)
+    return out, n_out
 
 
 # --------------------------------------------------------------------------- train-set statistics (no gradient)

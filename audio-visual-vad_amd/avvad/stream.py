@@ -135,6 +135,72 @@ class SampleClock:
         return frames, used, pad
 
 
+class OlaClock:
+    """Host-side bookkeeping of the streaming overlap-add (``ops.istft_stream``), per row, beside :class:`SampleClock`:
+    ``emitted`` frames taken and ``written`` samples returned since the reset.  A row that goes on writes
+    ``frames[b] * hop`` samples per call -- those no later frame can cover -- so ``written = emitted * hop``.  A row that
+    ends with N input samples (``final_totals``) writes the ``N - written[b]`` that are left: a stream of N samples
+    yields exactly N, as ``ops.resynth`` returns exactly L_b, and a row that never completes a frame yields N zeros at
+    its end.  It must be ``reset`` before it takes frames again."""
+
+    def __init__(self, batch, n_fft=1024, hop=256):
+        if int(batch) < 1 or int(n_fft) < 1 or int(hop) < 1 or int(hop) > int(n_fft):
+            raise L.AvvadError("OlaClock needs batch >= 1 and 1 <= hop <= n_fft")
+        self.n_fft, self.hop = int(n_fft), int(hop)
+        self.emitted = [0] * int(batch)
+        self.written = [0] * int(batch)
+        self.ended = [False] * int(batch)
+
+    def reset(self, rows=None):
+        for b in (range(len(self.emitted)) if rows is None else rows):
+            self.emitted[b] = self.written[b] = 0
+            self.ended[b] = False
+
+    def _plan(self, frames, final_totals):
+        B = len(self.emitted)
+        frames = ops._ints(frames)
+        if len(frames) != B:
+            raise L.AvvadError("one frame count per row expected (%d), got %d" % (B, len(frames)))
+        if final_totals is None:
+            final_totals = {}
+        elif not isinstance(final_totals, dict):
+            if len(final_totals) != B:
+                raise L.AvvadError("final_totals must be {row: samples} or hold one entry (None: the row goes on) per row")
+            final_totals = {b: n for b, n in enumerate(final_totals) if n is not None}
+        final_totals = {int(b): int(n) for b, n in final_totals.items()}
+        if any(b < 0 or b >= B for b in final_totals):
+            raise L.AvvadError("final rows must be in [0, %d)" % B)
+        n_out = []
+        for b, f in enumerate(frames):
+            if f < 0:
+                raise L.AvvadError("row %d: negative frame count" % b)
+            if self.ended[b] and (f > 0 or b in final_totals):
+                raise L.AvvadError("row %d ended with a final call: reset it before it takes frames again" % b)
+            if b in final_totals:
+                if final_totals[b] < self.written[b]:
+                    raise L.AvvadError("row %d: a stream of %d samples cannot end after %d were written"
+                                       % (b, final_totals[b], self.written[b]))
+                n_out.append(final_totals[b] - self.written[b])
+            else:
+                n_out.append(f * self.hop)
+        return frames, list(self.emitted), n_out, final_totals
+
+    def plan(self, frames, final_totals=None):
+        """-> (frames each row has behind it, samples each row writes) for a call with ``frames[b]`` more frames, rows in
+        ``final_totals`` ({row: N input samples}, or a list with None for rows that go on) ending with it; raises
+        :class:`AvvadError` when a count is negative or a row that ended is fed again.  Changes nothing."""
+        return self._plan(frames, final_totals)[1:3]
+
+    def advance(self, frames, final_totals=None):
+        """``plan`` and then consume: -> (n_before, n_out)."""
+        frames, before, n_out, fin = self._plan(frames, final_totals)
+        for b, f in enumerate(frames):
+            self.emitted[b] += f
+            self.written[b] += n_out[b]
+            self.ended[b] = self.ended[b] or b in fin
+        return before, n_out
+
+
 def _int_list(v, B, what, hi):
     if v is None:
         return [hi] * B
@@ -185,9 +251,13 @@ class Session:
         # the waveform front-end of the spectrogram models (step_wave), built on first use
         # (sample_clock is host bookkeeping and exists from the start; the GPU side is built by prepare_frontend)
         self.sample_clock = self.stft_state = self._stft_spare = self._basis = None
+        # the streaming resynthesis (step_enhance): overlap-add state, its spare and the inverse basis, built with the front-end
+        self.ola_clock = self.ola_state = self._ola_spare = self._inv_basis = None
+        self._route = [None] * self.batch          # per row: "wave" / "enhance" once it has taken samples since its reset
         self._frontend = dict(stats=None, eps=1e-8, n_fft=1024, hop=256)
         if self.kind != "video" and self.enc is None:
             self.sample_clock = SampleClock(self.batch, 1024, 256)
+            self.ola_clock = OlaClock(self.batch, 1024, 256)
         self.peak = torch.ones(self.batch, dtype=torch.float32, device=dev)
         if self.enc is not None:
             self.clock = FrameClock(self.batch, self.enc.receptive_field, samples_per_frame)
@@ -209,6 +279,12 @@ class Session:
             self.sample_clock.reset(rows)
         if self.stft_state is not None:
             self.stft_state.index_fill_(0, idx, 0.0)
+        if self.ola_clock is not None:
+            self.ola_clock.reset(rows)
+        if self.ola_state is not None:
+            self.ola_state.index_fill_(0, idx, 0.0)
+        for r in rows:
+            self._route[r] = None
 
     # ------------------------------------------------------------------ waveform front-end (csrc/stft_stream.hip)
     def _wave_check(self):
@@ -226,18 +302,26 @@ class Session:
             raise L.AvvadError("hop must be in [1, n_fft]")
         if (n_fft, hop) != (self.sample_clock.n_fft, self.sample_clock.hop):
             self.stft_state = self._stft_spare = self._basis = None
+            self.ola_state = self._ola_spare = self._inv_basis = None
             self.sample_clock = SampleClock(self.batch, n_fft, hop)
+            self.ola_clock = OlaClock(self.batch, n_fft, hop)
+            self._route = [None] * self.batch
         self._frontend = dict(stats=stats, eps=float(eps), n_fft=n_fft, hop=hop)
 
     def prepare_frontend(self):
         """Builds what ``step_wave`` needs on the GPU -- the windowed basis, ``stft_state`` and its spare -- if it is not
-        there yet (``step_wave`` does it on first use; a caller that restores a saved ``stft_state`` does it first)."""
+        there yet (``step_wave`` does it on first use; a caller that restores a saved ``stft_state`` does it first).  For a
+        model that predicts a mask over the bins (``step_enhance``) also the inverse basis, ``ola_state`` and its spare."""
         self._wave_check()
+        f = self._frontend
         if self.stft_state is None:
-            f = self._frontend
             self._basis = ops.stft_stream_basis(f["n_fft"], self.device)
             self.stft_state = ops.stft_stream_state(self.batch, f["n_fft"], self.device)
             self._stft_spare = torch.zeros_like(self.stft_state)
+        if self.ola_state is None and self.linear.out_features == f["n_fft"] // 2 + 1:
+            self._inv_basis = ops.istft_stream_basis(f["n_fft"], self.device)
+            self.ola_state = ops.istft_stream_state(self.batch, f["n_fft"], self.device)
+            self._ola_spare = torch.zeros_like(self.ola_state)
 
     def step_wave(self, wave, samples=None, video=None, final=None):
         """The next SAMPLES of every row of a spectrogram model: wave (B, n) float32 on the GPU, of which row b's first
@@ -247,8 +331,28 @@ class Session:
         ``reset`` them before they take samples again).  For the AV model ``video`` must hold exactly
         ``max(self.sample_clock.plan(samples, final))`` lip frames (None when that is 0).
         -> (logits (B, tmax, y_dim), frames per row); (B, 0, y_dim) when no row completes a frame."""
+        return self._step_samples(wave, samples, video, final, None)
+
+    def step_enhance(self, wave, samples=None, video=None, final=None, hard=True):
+        """``step_wave`` for a model that predicts a mask over the bins (``y_dim == n_fft // 2 + 1``), which also returns
+        the ENHANCED samples: the logits of the frames the samples complete mask those frames' spectrum (``hard``: logit > 0,
+        the evaluators' sigmoid > 0.5; else ``sigmoid(logit)``), and the streaming inverse STFT (``ops.istft_stream``) turns
+        it back into samples, multiplied by ``self.peak[b]``.  A sample comes out once no later frame can cover it, up to
+        ``n_fft - 1`` samples after it went in; a row in ``final`` returns all that is left, so a stream of N samples
+        returns exactly N.  The cost of a call does not depend on the position in the utterance, and any split of a stream
+        into packets gives the same samples bit for bit (given the same logits).  A row goes through ONE of ``step_wave`` /
+        ``step_enhance`` from its reset to its end.
+        -> (logits (B, tmax, y_dim), frames per row, enhanced (B, nmax) with zeros behind a row's count, samples per row)."""
+        return self._step_samples(wave, samples, video, final, bool(hard))
+
+    def _step_samples(self, wave, samples, video, final, hard):
+        """the body of ``step_wave`` (``hard`` None) and ``step_enhance``"""
         self._wave_check()
         B = self.batch
+        enhance = hard is not None
+        if enhance and self.linear.out_features != self._frontend["n_fft"] // 2 + 1:
+            raise L.AvvadError("step_enhance needs a model that predicts a mask over the %d bins, this one has y_dim = %d"
+                               % (self._frontend["n_fft"] // 2 + 1, self.linear.out_features))
         if not isinstance(wave, torch.Tensor) or not wave.is_cuda:
             raise L.AvvadError("wave must be a GPU tensor: no CPU fallback")
         if wave.dtype != torch.float32 or wave.dim() != 2 or wave.shape[0] != B:
@@ -258,6 +362,16 @@ class Session:
         final = () if final is None else final
         frames = self.sample_clock.plan(n, final)
         tmax = max(frames)
+        route = "enhance" if enhance else "wave"
+        fin = set(ops._ints(final))
+        live = [b for b in range(B) if n[b] > 0 or b in fin]
+        for b in live:
+            if self._route[b] not in (None, route):
+                raise L.AvvadError("row %d went through step_%s since its reset: a row stays with one of step_wave / "
+                                   "step_enhance until its end" % (b, self._route[b]))
+        totals = {b: self.sample_clock.total[b] + n[b] for b in fin}
+        if enhance:
+            self.ola_clock.plan(frames, totals)
         with torch.no_grad():
             vfeats = None
             if self.kind == "av":
@@ -271,18 +385,30 @@ class Session:
             mean = std = None
             if f["stats"] is not None:
                 mean, std = f["stats"].get("audio_mean", self.device), f["stats"].get("audio_std", self.device)
-            x, frames = ops.stft_stream(wave, n, self.sample_clock, self.stft_state, self._basis, self.peak, mean, std, final,
-                                        self._stft_spare, eps=f["eps"],
-                                        norm_eps=f["stats"].eps if f["stats"] is not None else f["eps"])
+            res = ops.stft_stream(wave, n, self.sample_clock, self.stft_state, self._basis, self.peak, mean, std, final,
+                                  self._stft_spare, eps=f["eps"],
+                                  norm_eps=f["stats"].eps if f["stats"] is not None else f["eps"], return_spec=enhance)
+            x, frames = res[0], res[1]
             self.stft_state, self._stft_spare = self._stft_spare, self.stft_state
+            for b in live:
+                self._route[b] = route
             if tmax == 0:
-                return torch.zeros(B, 0, self.linear.out_features, dtype=torch.float32, device=self.device), frames
-            if vfeats is not None:
-                x = ops.ConcatColsFn.apply(x, vfeats)
-            old = (self.h, self.c)
-            y, (self.h, self.c) = ops.lstm_stack_state(x, frames, self.lstm, state=old, out=self._spare)
-            self._spare = old
-            return ops.LinearFn.apply(y, self.linear.weight, self.linear.bias), frames
+                logits = torch.zeros(B, 0, self.linear.out_features, dtype=torch.float32, device=self.device)
+            else:
+                if vfeats is not None:
+                    x = ops.ConcatColsFn.apply(x, vfeats)
+                old = (self.h, self.c)
+                y, (self.h, self.c) = ops.lstm_stack_state(x, frames, self.lstm, state=old, out=self._spare)
+                self._spare = old
+                logits = ops.LinearFn.apply(y, self.linear.weight, self.linear.bias)
+            if not enhance:
+                return logits, frames
+            if tmax == 0 and not fin:                   # no row has a frame or ends: nothing comes out, no state moves
+                return logits, frames, torch.zeros(B, 0, dtype=torch.float32, device=self.device), [0] * B
+            enhanced, n_out = ops.istft_stream(res[2], frames, self.ola_clock, self.ola_state, self._inv_basis,
+                                               logits if tmax else None, 3 if hard else 2, self.peak, totals, self._ola_spare)
+            self.ola_state, self._ola_spare = self._ola_spare, self.ola_state
+            return logits, frames, enhanced, n_out
 
     def _audio_frames(self, audio, lengths, samples, video=None, with_video=False):
         """-> (audio features (B, T, F), frames per row, video features (B, T, 512) or None).  Every argument is checked
@@ -467,4 +593,37 @@ def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=25
             if f:
                 out[b, done[b]:done[b] + f] = y[b, :f]
                 done[b] += f
+    return out
+
+
+def enhance_wave_chunked(model, wave, lengths=None, chunk_samples=256, stats=None, peak=None, hard=True, eps=1e-8, n_fft=1024,
+                         hop=256):
+    """The twin of ``forward_wave_chunked`` for a mask-predicting ``DeepVAD_audio(y_dim=n_fft // 2 + 1)``: wave (B, Lmax) on
+    the GPU, row b's first ``lengths[b]`` samples real, fed through ``Session.step_enhance`` in packets of ``chunk_samples``
+    with each row's last packet ``final``.  ``peak`` (B,): what every sample is divided by on the way in and multiplied by
+    on the way out (None: 1).  -> enhanced samples (B, Lmax), row b's first ``lengths[b]`` real, zeros behind them."""
+    c = int(chunk_samples)
+    if c < 1:
+        raise L.AvvadError("chunk_samples must be >= 1")
+    w = ops._wave2d(wave)[1]
+    if w.dim() != 2:
+        raise L.AvvadError("wave must be (B, L) samples, got %s" % (tuple(w.shape),))
+    B, Lmax = w.shape
+    lens = _int_list(lengths, B, "lengths", Lmax)
+    sess = open(model, B)
+    sess.set_frontend(stats, eps, n_fft, hop)
+    sess.prepare_frontend()
+    if peak is not None:
+        sess.peak.copy_(ops._row_vector(peak, B, "peak"))
+    out = w.new_zeros(B, Lmax)
+    done, ended = [0] * B, set()
+    for s0 in range(0, max(max(lens), 1), c):
+        n = [min(max(l - s0, 0), c) for l in lens]
+        fin = [b for b in range(B) if b not in ended and s0 + c >= lens[b]]
+        ended.update(fin)
+        _, _, y, n_out = sess.step_enhance(w[:, s0:s0 + c].contiguous(), n, None, fin, hard)
+        for b, k in enumerate(n_out):
+            if k:
+                out[b, done[b]:done[b] + k] = y[b, :k]
+                done[b] += k
     return out

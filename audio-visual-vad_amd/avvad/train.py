@@ -573,17 +573,22 @@ def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, ep
     return soft, (soft > 0.5).int()
 
 
-def resynth_utt(classifier, x_t, stats=None, hard=True, eps=EPS, std_norm=True):
+def resynth_utt(classifier, x_t, stats=None, hard=True, eps=EPS, std_norm=True, chunk_samples=None):
     """Enhanced waveform of one utterance from a mask-predicting audio model (``y_dim = n_fft/2 + 1 = 513``): peak
     normalisation -> features -> model as in ``process_utt``, then the logits go straight in as the mask of
     ``ops.resynth`` on the peak-normalised wave -- ``hard``: ``logit > 0`` (the evaluator's ``sigmoid > 0.5``), else
     ``sigmoid(logit)`` -- with the peak as the output scale, so the result is in the input's scale.  x_t (L,) on the GPU
-    -> (L,) on the GPU."""
+    -> (L,) on the GPU.  ``chunk_samples``: the raw samples go through a streaming session in packets of that many and the
+    enhanced samples come out of it per packet (``stream.enhance_wave_chunked``) -- the same values up to summation order
+    (with ``hard``, a logit next to 0 may fall on the other side)."""
     n_fft = 1024
     if getattr(classifier, "y_dim", None) != n_fft // 2 + 1:
         raise ValueError("resynthesis needs a model that predicts a %d-bin mask (y_dim = %d), got y_dim = %r"
                          % (n_fft // 2 + 1, n_fft // 2 + 1, getattr(classifier, "y_dim", None)))
     w = x_t.reshape(1, -1)
+    if chunk_samples is not None:
+        return stream.enhance_wave_chunked(classifier, w, None, chunk_samples, stats if std_norm else None, ops.peak(w), hard,
+                                           eps, n_fft, 256).view(-1)
     x = audio_features(x_t, stats, None, eps=eps, std_norm=std_norm)
     logits = classifier(x, [x.shape[1]]).detach().contiguous()
     out = ops.resynth(ops.peak_normalize(w), logits, mask_mode=3 if hard else 2, n_fft=n_fft, hop=256, scale=ops.peak(w))
@@ -592,7 +597,7 @@ def resynth_utt(classifier, x_t, stats=None, hard=True, eps=EPS, std_norm=True):
 
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
                   stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None, chunk_samples=None,
-                  resynth_dir=None, resynth_hard=True):
+                  resynth_dir=None, resynth_hard=True, resynth_chunked=False):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
@@ -613,8 +618,11 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
 
     ``resynth_dir`` (``wav_list`` with a 513-output audio model): every utterance is also resynthesised from the model's
     mask (``resynth_utt``; ``resynth_hard``: binary mask, else the soft one) and written there as ``<base>_enhanced.wav``
-    -- float32, 16 kHz, as many samples as the input.  ``None`` writes nothing."""
+    -- float32, 16 kHz, as many samples as the input.  ``None`` writes nothing.  ``resynth_chunked`` (with ``resynth_dir``
+    and ``chunk_samples``): the enhanced samples come out of the streaming session, packet by packet."""
     _one_chunking(chunk_frames, chunk_samples)
+    if resynth_chunked and (resynth_dir is None or chunk_samples is None):
+        raise ValueError("resynth_chunked streams the resynthesis: it needs resynth_dir and chunk_samples")
     model = None
     if resynth_dir is not None:
         if wav_list is None or kind != "audio":
@@ -683,7 +691,8 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                     torch.save(y.int().cpu(), base + "_label.pt")
                 if resynth_dir is not None:
                     from scipy.io import wavfile
-                    enhanced = resynth_utt(model, x_t.to(device), stats, hard=resynth_hard)
+                    enhanced = resynth_utt(model, x_t.to(device), stats, hard=resynth_hard,
+                                           chunk_samples=chunk_samples if resynth_chunked else None)
                     wavfile.write(os.path.join(resynth_dir, os.path.basename(base) + "_enhanced.wav"), 16000,
                                   enhanced.cpu().numpy())
     else:

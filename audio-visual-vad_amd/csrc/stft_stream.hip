@@ -1,7 +1,8 @@
 // stft_stream.hip -- the STFT front-end on a stream of samples: each row carries the samples that did not yet complete a
 // frame (or that later frames still overlap) across calls, and a call emits the log-power (optionally standardised)
 // features of exactly the frames its new samples complete.  One launch per call: framing, peak division, windowed real
-// DFT on fp32 MFMA, |X|^2 -> log -> standardisation, the new tail.
+// DFT on fp32 MFMA, |X|^2 -> log -> standardisation, the new tail.  avvad_stft_stream_fwd_spec is the same launch with the
+// complex spectrum stored beside the features (what the streaming inverse, istft_stream.hip, takes).
 //
 // The shape is M = a few frames (1 .. a few hundred) against K = n_fft, N = 2 (n_fft/2 + 1): a basis-streaming product, not
 // a tile GEMM.  Workgroup blockIdx.x owns 16 bins; it reads its slab of the basis (2 x 16 x K floats, packed so that a
@@ -31,6 +32,7 @@ struct SsArgs {
   int B, L, K, hop, T, F;
   int tab;                  // float offset of the per-frame tables in LDS (behind the frames / partial sums)
   float eps, norm_eps;
+  float* spec;              // [B][T][F][2] (re, im) of the same frames: only the SPEC instantiations read it
 };
 
 // k index that lane-quarter q reads in MFMA j of sample group kk: both operands use it, so the product is a plain sum over k
@@ -76,7 +78,9 @@ __device__ __forceinline__ float ss_sample(const SsArgs& a, int b, const SsRow& 
   return s < r.nv ? a.chunk[(long)b * a.L + s] : 0.f;
 }
 
-template <int NG>
+// SPEC: the epilogue also stores (re, im), the complex spectrum of the samples / peak, for the streaming inverse
+// (istft_stream.hip).  A template parameter, so that the instantiations behind avvad_stft_stream_fwd stay what they were.
+template <int NG, bool SPEC>
 __global__ void __launch_bounds__(SS_NT) ss_fwd_kernel(const SsArgs a) {
   // All LDS is the dynamic region, so that its base is offset 0 and every 16-byte access below is aligned: frames
   // [16 NG][K + 4], afterwards the waves' partial sums; behind them (a.tab floats in) the pass's per-frame tables.
@@ -182,6 +186,7 @@ __global__ void __launch_bounds__(SS_NT) ss_fwd_kernel(const SsArgs a) {
         float v = logf(fmaf(re, re, im * im) + a.eps);
         if (a.mean) v = (v - a.mean[f]) / (a.stdv[f] + a.norm_eps);
         a.out[((long)fb[fr] * a.T + ft[fr]) * a.F + f] = v;
+        if constexpr (SPEC) *reinterpret_cast<float2*>(a.spec + (((long)fb[fr] * a.T + ft[fr]) * a.F + f) * 2) = float2{re, im};
       }
     }
     __syncthreads();                             // the partial sums are read before the next pass stages over them
@@ -192,7 +197,10 @@ __global__ void __launch_bounds__(SS_NT) ss_fwd_kernel(const SsArgs a) {
   for (int b = blockIdx.y * (SS_NT / 16) + (tid >> 4); b < a.B; b += gridDim.y * (SS_NT / 16)) {   // 16 lanes per row
     const int nf = ss_row(a, b).nf;
     if ((tid & 15) < fw)
-      for (int t = nf; t < a.T; ++t) a.out[((long)b * a.T + t) * a.F + f0 + (tid & 15)] = 0.f;
+      for (int t = nf; t < a.T; ++t) {
+        a.out[((long)b * a.T + t) * a.F + f0 + (tid & 15)] = 0.f;
+        if constexpr (SPEC) *reinterpret_cast<float2*>(a.spec + (((long)b * a.T + t) * a.F + f0 + (tid & 15)) * 2) = float2{0.f, 0.f};
+      }
   }
   // ---- the new tail of the rows this workgroup looks after: the stream from the start of the next frame on
   for (int b = blockIdx.y * gridDim.x + nb; b < a.B; b += gridDim.x * gridDim.y) {
@@ -222,10 +230,34 @@ size_t ss_lds_bytes(int K, int NG) {
 size_t ss_tab_bytes(int NG) { return align_up((size_t)(5 * 16 * NG + 1) * sizeof(float), 16); }
 inline int ss_bin_blocks(int n_fft) { return (n_fft / 2 + 1 + 15) / 16; }
 
-template <int NG>
+template <int NG, bool SPEC>
 int ss_launch(const SsArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (int rc = allow_large_lds<ss_fwd_kernel<NG>>(lds, SS_LDS_MAX)) return rc;
-  hipLaunchKernelGGL(ss_fwd_kernel<NG>, grid, dim3(SS_NT), lds, s, a);
+  if (int rc = allow_large_lds<ss_fwd_kernel<NG, SPEC>>(lds, SS_LDS_MAX)) return rc;
+  hipLaunchKernelGGL((ss_fwd_kernel<NG, SPEC>), grid, dim3(SS_NT), lds, s, a);
+  return AVVAD_OK;
+}
+
+template <bool SPEC>
+int ss_forward(const float* chunk, const int* n_valid, const int* n_pending, const int* n_frames, const int* pad_frames,
+               const float* peak, const float* state_in, float* state_out, const float* basis, const float* mean,
+               const float* stdv, float* out, float* spec, const avvad_stft_stream_desc* d, hipStream_t s) {
+  if (!chunk || !n_valid || !n_pending || !n_frames || !pad_frames || !state_in || !state_out || !basis || !ss_desc_ok(d) ||
+      state_in == state_out || (d->T > 0 && !out) || (SPEC && ((d->T > 0 && !spec) || ((uintptr_t)spec & 7))) || !mean != !stdv || ws_misaligned(basis))
+    return AVVAD_EINVAL;
+  const int K = d->n_fft;
+  const long hint = d->M > 0 ? d->M : (long)d->B * d->T;
+  int NG = hint > 16 ? 2 : 1;
+  if (NG == 2 && ss_lds_bytes(K, 2) + ss_tab_bytes(2) > SS_LDS_MAX) NG = 1;
+  if (ss_lds_bytes(K, NG) + ss_tab_bytes(NG) > SS_LDS_MAX) return AVVAD_EINVAL;
+  long ny = (hint + 16 * NG - 1) / (16 * NG);
+  ny = ny < 1 ? 1 : (ny > 16 ? 16 : ny);         // the passes beyond walk the grid's second dimension
+  SsArgs a{chunk, n_valid, n_pending, n_frames, pad_frames, peak, state_in, state_out, basis, mean, stdv, out,
+           d->B, d->L, K, d->hop, d->T, K / 2 + 1, (int)(ss_lds_bytes(K, NG) / sizeof(float)), d->eps, d->norm_eps, spec};
+  const dim3 grid(ss_bin_blocks(K), (int)ny);
+  const int rc = NG == 2 ? ss_launch<2, SPEC>(a, grid, ss_lds_bytes(K, 2) + ss_tab_bytes(2), s)
+                         : ss_launch<1, SPEC>(a, grid, ss_lds_bytes(K, 1) + ss_tab_bytes(1), s);
+  if (rc) return rc;
+  AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
 
@@ -250,22 +282,15 @@ extern "C" int avvad_stft_stream_fwd(const float* chunk, const int* n_valid, con
                                      const float* basis, const float* mean, const float* stdv, float* out,
                                      const avvad_stft_stream_desc* d, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!chunk || !n_valid || !n_pending || !n_frames || !pad_frames || !state_in || !state_out || !basis || !ss_desc_ok(d) ||
-      state_in == state_out || (d->T > 0 && !out) || !mean != !stdv || ((uintptr_t)basis & 15))
-    return AVVAD_EINVAL;
-  const int K = d->n_fft;
-  const long hint = d->M > 0 ? d->M : (long)d->B * d->T;
-  int NG = hint > 16 ? 2 : 1;
-  if (NG == 2 && ss_lds_bytes(K, 2) + ss_tab_bytes(2) > SS_LDS_MAX) NG = 1;
-  if (ss_lds_bytes(K, NG) + ss_tab_bytes(NG) > SS_LDS_MAX) return AVVAD_EINVAL;
-  long ny = (hint + 16 * NG - 1) / (16 * NG);
-  ny = ny < 1 ? 1 : (ny > 16 ? 16 : ny);         // the passes beyond walk the grid's second dimension
-  SsArgs a{chunk, n_valid, n_pending, n_frames, pad_frames, peak, state_in, state_out, basis, mean, stdv, out,
-           d->B, d->L, K, d->hop, d->T, K / 2 + 1, (int)(ss_lds_bytes(K, NG) / sizeof(float)), d->eps, d->norm_eps};
-  const dim3 grid(ss_bin_blocks(K), (int)ny);
-  const int rc = NG == 2 ? ss_launch<2>(a, grid, ss_lds_bytes(K, 2) + ss_tab_bytes(2), (hipStream_t)sv)
-                         : ss_launch<1>(a, grid, ss_lds_bytes(K, 1) + ss_tab_bytes(1), (hipStream_t)sv);
-  if (rc) return rc;
-  AVVAD_LAUNCH_CHECK();
-  return AVVAD_OK;
+  return ss_forward<false>(chunk, n_valid, n_pending, n_frames, pad_frames, peak, state_in, state_out, basis, mean, stdv, out,
+                           nullptr, d, (hipStream_t)sv);
+}
+
+extern "C" int avvad_stft_stream_fwd_spec(const float* chunk, const int* n_valid, const int* n_pending, const int* n_frames,
+                                          const int* pad_frames, const float* peak, const float* state_in, float* state_out,
+                                          const float* basis, const float* mean, const float* stdv, float* out, float* spec,
+                                          const avvad_stft_stream_desc* d, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  return ss_forward<true>(chunk, n_valid, n_pending, n_frames, pad_frames, peak, state_in, state_out, basis, mean, stdv, out,
+                          spec, d, (hipStream_t)sv);
 }

@@ -37,6 +37,8 @@
  *           float64 statistics accumulator  8 bytes
  *           int64 / int32 index arrays      their natural alignment
  *           bf16 operands, avvad_lip_decode's coef, the avvad_stft_stream basis,
+ *           (checked by avvad_stft_stream_fwd / _fwd_spec), the avvad_istft_stream
+ *           basis (checked by avvad_istft_stream),
  *           activations, weights, outputs and gradients of the encoder, the
  *           trunk, the convolutions and the fusion: 16 bytes (the base address
  *           of any allocation; not checked unless the entry point says so)
@@ -447,6 +449,14 @@ int avvad_stft_stream_fwd(const float* chunk, const int* n_valid, const int* n_p
                           const int* pad_frames, const float* peak, const float* state_in, float* state_out,
                           const float* basis, const float* mean, const float* std_, float* out,
                           const avvad_stft_stream_desc* d, avvad_stream_t s);
+/* The same call, which also hands out the complex spectrum it holds anyway: spec [B][T][F][2], (re, im) adjacent, of the
+ * samples divided by peak[b]; frames a row does not fill are zero, like out.  Written in the epilogue that writes out, in the
+ * forward's summation order, so it is bit-identical for every split of a stream; out has the bits of avvad_stft_stream_fwd.
+ * spec: plain float, 8-byte aligned (AVVAD_EINVAL otherwise), may be NULL when d->T == 0.  What avvad_istft_stream takes. */
+int avvad_stft_stream_fwd_spec(const float* chunk, const int* n_valid, const int* n_pending, const int* n_frames,
+                               const int* pad_frames, const float* peak, const float* state_in, float* state_out,
+                               const float* basis, const float* mean, const float* std_, float* out, float* spec,
+                               const avvad_stft_stream_desc* d, avvad_stream_t s);
 /* ------------------------------------------------------------------------
  * Masked inverse STFT: mask x spectrum -> waveform
  * Replaces: istft packages/processing/stft.py:63-99 (librosa.core.istft: per-frame irfft, periodic Hann, overlap-add,
@@ -486,6 +496,41 @@ size_t avvad_resynth_workspace(const avvad_stft_desc* sd, const avvad_istft_desc
 int avvad_resynth(const float* wave, const float* mask, const int* n_frames, const int* out_len, const float* scale,
                   float* out, const avvad_stft_desc* sd, const avvad_istft_desc* d, void* ws, size_t ws_bytes,
                   avvad_stream_t s);
+/* The masked inverse on a STREAM of frames (inference; center = False, no start trim, like the streaming forward).  Row b
+ * has n_before[b] frames behind it; the call takes its next n_frames[b] frames, spec / mask [B][T][F]([2]) as
+ * avvad_stft_stream_fwd_spec and the model hand them out (mask_mode as for avvad_istft; modes 2 and 3 take logits), and
+ * writes n_out[b] samples: out[b][p], p < n_out[b], is the absolute sample s' = n_before[b] hop + p,
+ *   out[b][p] = scale[b] * (state_in[b][p] + sum_i Y[b,i][p - i hop]) / wss(s'),   i ascending over the call's frames,
+ * wss(s') the double sum of hann^2 over the absolute frames t < n_before[b] + n_frames[b] that cover s', ascending (the
+ * division only where (float)wss > 1.17549435e-38); a sample no frame covers is +0, and out [B][L] is zero from n_out[b] on.
+ * state_out[b][q] is the partial sum of the absolute sample (n_before[b] + n_frames[b]) hop + q (zero for q >= n_fft - hop).
+ * A row that goes on emits n_out[b] = n_frames[b] hop samples -- those no later frame can cover: a sample leaves up to
+ * n_fft - 1 samples after it came in.  A row with n_out[b] != n_frames[b] hop ENDS with this call (the final flush: a
+ * stream of N samples has written n_before[b] hop so far and takes n_out[b] = N - that, cropped or zero-filled like
+ * avvad_resynth's rows); its new state is all zero.  A row with n_frames[b] == 0 and n_out[b] == 0 keeps its state bit for
+ * bit.  The sum of a sample is the ascending chain of avvad_istft's overlap-add cut at the call boundaries, and Y is summed
+ * in an order that depends on (n_fft, n) alone, so ANY split of a stream into calls gives the same bits.
+ * n_frames / n_before / n_out: device int32 [B], clamped in the kernel (to T, to >= 0, to L) so that wrong counts cannot
+ * leave a buffer.  state_in / state_out: plain float [B][n_fft], different buffers; all zeros is "start of utterance".
+ * basis: avvad_istft_stream_basis_bytes(n_fft) bytes filled ONCE by avvad_istft_stream_basis (16-byte aligned): the basis
+ * of avvad_istft with the contraction packed to K = n_fft rows (re[0], re[n_fft/2], then re[f], im[f]), per block of 16
+ * samples, and hann^2 in double behind it.  n_fft % 32 == 0, 32 <= n_fft <= 2048, 1 <= hop <= n_fft.  T == 0 (no row has
+ * a frame; spec and mask may be NULL) with L > 0 is the final flush of rows that complete no frame; L == 0: out may be
+ * NULL.  d->M: the host's sum of n_frames (0: unknown); it sizes the grid and selects nothing that changes a value.
+ * ws: avvad_istft_stream_workspace(d) bytes, 16-byte aligned (the per-frame inverses Y). */
+typedef struct {
+  int B, T;        /* rows, frame pitch of spec / mask                       */
+  int n_fft, hop;
+  int L;           /* floats per row of out (>= every n_out[b])              */
+  int M;           /* host's sum of n_frames, or 0                           */
+  int mask_mode;   /* 0 .. 3                                                 */
+} avvad_istft_stream_desc;
+size_t avvad_istft_stream_basis_bytes(int n_fft);          /* 0 on an unsupported n_fft */
+int avvad_istft_stream_basis(int n_fft, float* out, avvad_stream_t s);
+size_t avvad_istft_stream_workspace(const avvad_istft_stream_desc* d);   /* 0 on a bad descriptor */
+int avvad_istft_stream(const float* spec, const float* mask, const int* n_frames, const int* n_before, const int* n_out,
+                       const float* scale, const float* state_in, float* state_out, const float* basis, float* out,
+                       const avvad_istft_stream_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
 /* The batched complex spectrum of avvad_stft's DFT: out [B][T][F][2] = (re, im).  ws: avvad_stft_workspace(d). */
 int avvad_stft_complex(const float* wave, float* out, const avvad_stft_desc* d, void* ws, size_t ws_bytes,
                        avvad_stream_t s);
