@@ -926,24 +926,51 @@ def peak(wave):
     return out
 
 
-def stft_stream_basis(n_fft, device):
-    """The windowed DFT basis of ``stft`` in the streaming kernel's packed layout (an opaque float tensor): built once,
-    reused by every ``stft_stream`` call with that ``n_fft``."""
+def _stream_basis(which, n_fft, device):
+    """the packed basis of ``avvad_<which>_basis``, sized by ``avvad_<which>_basis_bytes``"""
     n_fft = _n_fft_check(n_fft)
-    out = torch.empty(L.lib().avvad_stft_stream_basis_bytes(n_fft) // 4, dtype=torch.float32, device=device)
+    out = torch.empty(getattr(L.lib(), "avvad_%s_basis_bytes" % which)(n_fft) // 4, dtype=torch.float32, device=device)
     if not out.is_cuda:
         raise L.AvvadError("the basis lives on the GPU: no CPU fallback")
     with torch.cuda.device(out.device):
-        L.check(L.lib().avvad_stft_stream_basis(n_fft, L.ptr(out), _stream()), "avvad_stft_stream_basis")
+        L.check(getattr(L.lib(), "avvad_%s_basis" % which)(n_fft, L.ptr(out), _stream()), "avvad_%s_basis" % which)
     return out
+
+
+def _stream_state(B, n_fft, device):
+    if int(B) < 1:
+        raise L.AvvadError("B must be >= 1")
+    return torch.zeros(int(B), _n_fft_check(n_fft), dtype=torch.float32, device=device)
+
+
+def _stream_buffers(which, state, out_state, basis, B, n_fft, device):
+    """Checks ``state`` / ``out_state`` / ``basis`` of ``<which>`` (stft_stream / istft_stream).  -> (in_place, the tensor
+    the kernel writes the new state to): with ``out_state`` None or ``state`` itself a temporary, which the caller copies
+    back into ``state`` after the launch."""
+    def st(t, what):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
+                tuple(t.shape) != (B, n_fft) or t.device != device:
+            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of %s_state(%d, %d, device)" % (what, which, B, n_fft))
+    st(state, "state")
+    if out_state is not None and out_state is not state:
+        st(out_state, "out_state")
+    in_place = out_state is None or out_state.data_ptr() == state.data_ptr()
+    if not isinstance(basis, torch.Tensor) or not basis.is_cuda or basis.dtype != torch.float32 or \
+            basis.numel() * 4 != getattr(L.lib(), "avvad_%s_basis_bytes" % which)(n_fft) or basis.device != device:
+        raise L.AvvadError("basis must be %s_basis(%d, device)" % (which, n_fft))
+    return in_place, torch.empty_like(state) if in_place else out_state
+
+
+def stft_stream_basis(n_fft, device):
+    """The windowed DFT basis of ``stft`` in the streaming kernel's packed layout (an opaque float tensor): built once,
+    reused by every ``stft_stream`` call with that ``n_fft``."""
+    return _stream_basis("stft_stream", n_fft, device)
 
 
 def stft_stream_state(B, n_fft, device):
     """Zeroed front-end state (B, n_fft) -- each row's pending samples; all zeros with a count of 0 (a fresh
     ``SampleClock``) is "start of utterance"."""
-    if int(B) < 1:
-        raise L.AvvadError("B must be >= 1")
-    return torch.zeros(int(B), _n_fft_check(n_fft), dtype=torch.float32, device=device)
+    return _stream_state(B, n_fft, device)
 
 
 def _row_vector(v, B, name):
@@ -977,19 +1004,7 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
     nv = [n] * B if n_valid is None else _ints(n_valid)
     if len(nv) != B or any(x < 0 or x > n for x in nv):
         raise L.AvvadError("n_valid must hold one count in [0, %d] per row (%d rows), got %s" % (n, B, nv))
-
-    def st(t, what):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
-                tuple(t.shape) != (B, n_fft) or t.device != chunk.device:
-            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of stft_stream_state(%d, %d, device)" % (what, B, n_fft))
-        return t
-    state = st(state, "state")
-    if out_state is not None and out_state is not state:
-        st(out_state, "out_state")
-    in_place = out_state is None or out_state.data_ptr() == state.data_ptr()
-    if not isinstance(basis, torch.Tensor) or not basis.is_cuda or basis.dtype != torch.float32 or \
-            basis.numel() * 4 != L.lib().avvad_stft_stream_basis_bytes(n_fft) or basis.device != chunk.device:
-        raise L.AvvadError("basis must be stft_stream_basis(%d, device)" % n_fft)
+    in_place, new = _stream_buffers("stft_stream", state, out_state, basis, B, n_fft, chunk.device)
     pk = None if peak is None else _row_vector(peak, B, "peak")
     if (mean is None) != (std is None):
         raise L.AvvadError("standardisation needs both mean and std")
@@ -999,7 +1014,6 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
     tmax = max(frames)
     counts = torch.tensor([nv, pending, frames, pad], dtype=torch.int32).to(chunk.device, non_blocking=False)
     out = torch.empty(B, tmax, F, dtype=torch.float32, device=chunk.device)
-    new = torch.empty_like(state) if in_place else out_state
     src = chunk if n > 0 else chunk.new_zeros(B, 1)
     d = L.StftStreamDesc(B, max(n, 1), n_fft, hop, tmax, sum(frames), float(eps), float(norm_eps))
     spec = torch.empty(B, tmax, F, 2, dtype=torch.float32, device=chunk.device) if return_spec else None
@@ -1020,21 +1034,13 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
 def istft_stream_basis(n_fft, device):
     """The windowed inverse-DFT basis of ``istft`` in the streaming kernel's packed layout, with the squared window behind
     it (an opaque float tensor): built once, reused by every ``istft_stream`` call with that ``n_fft``."""
-    n_fft = _n_fft_check(n_fft)
-    out = torch.empty(L.lib().avvad_istft_stream_basis_bytes(n_fft) // 4, dtype=torch.float32, device=device)
-    if not out.is_cuda:
-        raise L.AvvadError("the basis lives on the GPU: no CPU fallback")
-    with torch.cuda.device(out.device):
-        L.check(L.lib().avvad_istft_stream_basis(n_fft, L.ptr(out), _stream()), "avvad_istft_stream_basis")
-    return out
+    return _stream_basis("istft_stream", n_fft, device)
 
 
 def istft_stream_state(B, n_fft, device):
     """Zeroed overlap-add state (B, n_fft) -- each row's unfinished sums of the samples later frames still cover; all
     zeros (a fresh ``OlaClock``) is "start of utterance"."""
-    if int(B) < 1:
-        raise L.AvvadError("B must be >= 1")
-    return torch.zeros(int(B), _n_fft_check(n_fft), dtype=torch.float32, device=device)
+    return _stream_state(B, n_fft, device)
 
 
 def istft_stream(spec, frames, clock, state, basis, mask=None, mask_mode=None, scale=None, final_samples=None, out_state=None):
@@ -1065,25 +1071,12 @@ def istft_stream(spec, frames, clock, state, basis, mask=None, mask_mode=None, s
         m, mode = _mask_args(mask, mask_mode, B, T, F)
     else:
         m, mode = None, 0                                         # no row has a frame: there is nothing to mask
-
-    def st(t, what):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
-                tuple(t.shape) != (B, n_fft) or t.device != spec.device:
-            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of istft_stream_state(%d, %d, device)" % (what, B, n_fft))
-        return t
-    state = st(state, "state")
-    if out_state is not None and out_state is not state:
-        st(out_state, "out_state")
-    in_place = out_state is None or out_state.data_ptr() == state.data_ptr()
-    if not isinstance(basis, torch.Tensor) or not basis.is_cuda or basis.dtype != torch.float32 or \
-            basis.numel() * 4 != L.lib().avvad_istft_stream_basis_bytes(n_fft) or basis.device != spec.device:
-        raise L.AvvadError("basis must be istft_stream_basis(%d, device)" % n_fft)
+    in_place, new = _stream_buffers("istft_stream", state, out_state, basis, B, n_fft, spec.device)
     sc = None if scale is None else _row_vector(scale, B, "scale")
     n_before, n_out = clock.advance(nf, final_samples)           # raises before it changes anything
     nmax = max(n_out)
     counts = torch.tensor([nf, n_before, n_out], dtype=torch.int32).to(spec.device, non_blocking=False)
     out = torch.empty(B, nmax, dtype=torch.float32, device=spec.device)
-    new = torch.empty_like(state) if in_place else out_state
     d = L.IstftStreamDesc(B, T, n_fft, hop, nmax, sum(nf), mode)
     with torch.cuda.device(spec.device):
         ws = _ws(L.lib().avvad_istft_stream_workspace(C.byref(d)), spec.device)

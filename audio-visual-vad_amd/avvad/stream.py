@@ -541,15 +541,9 @@ def forward_chunked(model, audio=None, video=None, lengths=None, chunk_frames=1,
     return torch.cat(outs, dim=1)
 
 
-def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=256, stats=None, peak=None, eps=1e-8,
-                         n_fft=1024, hop=256, max_frames=None):
-    """A spectrogram model (``DeepVAD_audio`` / concat ``DeepVAD_AV`` without the encoder, in ``eval()`` mode) scored
-    from RAW SAMPLES through a session: wave (B, Lmax) on the GPU, row b's first ``lengths[b]`` samples real, fed in
-    packets of ``chunk_samples`` with each row's last packet ``final``.  ``peak`` (B,) is what every sample is divided by
-    (``ops.peak(wave)`` reproduces the evaluators' x / max|x|; None: 1), ``stats`` standardises the features, ``video``
-    (B, T, 67, 67) holds the lip frames already decoded and standardised.  ``max_frames[b]`` ends row b after that many
-    frames (the evaluators' crop to the label length).  -> logits (B, T, y_dim), T = the longest row's frame count
-    (``ops.n_frames``, capped by ``max_frames``); positions behind a row's frames hold the Linear layer's bias."""
+def _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop):
+    """the shared opening of ``forward_wave_chunked`` / ``enhance_wave_chunked``: the arguments checked, a session with its
+    front-end built and ``peak`` set.  -> (chunk_samples, wave (B, Lmax), lengths (list), session)"""
     c = int(chunk_samples)
     if c < 1:
         raise L.AvvadError("chunk_samples must be >= 1")
@@ -563,6 +557,20 @@ def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=25
     sess.prepare_frontend()
     if peak is not None:
         sess.peak.copy_(ops._row_vector(peak, B, "peak"))
+    return c, w, lens, sess
+
+
+def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=256, stats=None, peak=None, eps=1e-8,
+                         n_fft=1024, hop=256, max_frames=None):
+    """A spectrogram model (``DeepVAD_audio`` / concat ``DeepVAD_AV`` without the encoder, in ``eval()`` mode) scored
+    from RAW SAMPLES through a session: wave (B, Lmax) on the GPU, row b's first ``lengths[b]`` samples real, fed in
+    packets of ``chunk_samples`` with each row's last packet ``final``.  ``peak`` (B,) is what every sample is divided by
+    (``ops.peak(wave)`` reproduces the evaluators' x / max|x|; None: 1), ``stats`` standardises the features, ``video``
+    (B, T, 67, 67) holds the lip frames already decoded and standardised.  ``max_frames[b]`` ends row b after that many
+    frames (the evaluators' crop to the label length).  -> logits (B, T, y_dim), T = the longest row's frame count
+    (``ops.n_frames``, capped by ``max_frames``); positions behind a row's frames hold the Linear layer's bias."""
+    c, w, lens, sess = _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop)
+    B, Lmax = w.shape
     total = [max(ops.n_frames(l, n_fft, hop), 0) for l in lens]
     ends = [True] * B                                   # the row ends with its last sample (and may owe the padded frame)
     if max_frames is not None:
@@ -602,19 +610,8 @@ def enhance_wave_chunked(model, wave, lengths=None, chunk_samples=256, stats=Non
     the GPU, row b's first ``lengths[b]`` samples real, fed through ``Session.step_enhance`` in packets of ``chunk_samples``
     with each row's last packet ``final``.  ``peak`` (B,): what every sample is divided by on the way in and multiplied by
     on the way out (None: 1).  -> enhanced samples (B, Lmax), row b's first ``lengths[b]`` real, zeros behind them."""
-    c = int(chunk_samples)
-    if c < 1:
-        raise L.AvvadError("chunk_samples must be >= 1")
-    w = ops._wave2d(wave)[1]
-    if w.dim() != 2:
-        raise L.AvvadError("wave must be (B, L) samples, got %s" % (tuple(w.shape),))
+    c, w, lens, sess = _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop)
     B, Lmax = w.shape
-    lens = _int_list(lengths, B, "lengths", Lmax)
-    sess = open(model, B)
-    sess.set_frontend(stats, eps, n_fft, hop)
-    sess.prepare_frontend()
-    if peak is not None:
-        sess.peak.copy_(ops._row_vector(peak, B, "peak"))
     out = w.new_zeros(B, Lmax)
     done, ended = [0] * B, set()
     for s0 in range(0, max(max(lens), 1), c):

@@ -89,6 +89,8 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 // every sub-buffer on a 256-byte multiple of the base and the kernels read them 16 bytes at a time, so an entry point
 // refuses (AVVAD_EINVAL) a workspace that is not, before anything is launched.  A null pointer is not misaligned.
 static inline bool ws_misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
+// a count read from device memory, as a kernel uses it: within [0, hi], so that a wrong one cannot reach outside a buffer
+__device__ __forceinline__ int clamp_count(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // fp32-input MFMA 32x32x2: D(32x32) += A(32x2) . B(2x32).
 //   lane l supplies A[i = l&31][k = l>>5] and B[k = l>>5][j = l&31];

@@ -1,7 +1,8 @@
-// frames.h -- what the STFT family (stft.hip, stft_stream.hip, target.hip, stats.hip, istft.hip) shares about the framed,
-// windowed DFT: the descriptor rule, the basis formula, the spectrum workspace and the transform itself.  A real DFT of
-// every frame of a [B][L] batch is ONE fp32-MFMA GEMM, S[(b,t)][2f + {re,im}] = sum_k wave[b][t*hop + k] basis[k][2f + {re,im}],
-// run through igemm::launch; it is compiled once, in stft.hip.
+// frames.h -- what the STFT family (stft.hip, stft_stream.hip, target.hip, stats.hip, istft.hip, istft_stream.hip) shares
+// about the framed, windowed DFT: the descriptor rule, the basis formula, the inverse's formulae, the spectrum workspace and
+// the transform itself.  A real DFT of every frame of a [B][L] batch is ONE fp32-MFMA GEMM,
+// S[(b,t)][2f + {re,im}] = sum_k wave[b][t*hop + k] basis[k][2f + {re,im}], run through igemm::launch; it is compiled once, in
+// stft.hip.
 #pragma once
 #include "igemm.h"
 
@@ -25,6 +26,35 @@ struct Phase {
 __device__ __forceinline__ Phase phase(int f, int k, int N) {
   const long fk = ((long)f * k) % N;                                              // exact phase reduction
   return Phase{2.0 * (double)fk / (double)N};
+}
+
+// ---- the inverse's formulae (istft.hip, istft_stream.hip)
+// element (f, re | im, n) of the windowed inverse real DFT: hann[n] w_f/N cos(2 pi f n / N) | -hann[n] w_f/N sin(2 pi f n / N),
+// w_f = 1 for DC and Nyquist, else 2 (irfft of a half spectrum, then the synthesis window)
+__device__ __forceinline__ float idft_element(int f, bool imag, int n, int N) {
+  const double win = hann(n, N);
+  const double wf = (f == 0 || 2 * f == N) ? 1.0 : 2.0;
+  const Phase ph = phase(f, n, N);
+  return (float)(imag ? -win * (wf / (double)N) * ph.sin() : win * (wf / (double)N) * ph.cos());
+}
+// spectrum value v under mask value g, mode 1 .. 3: the mask itself, sigmoid(logit) or logit > 0.  SIG: mode 2, its own
+// instantiation of whatever calls this, so that the exponential's registers do not weigh on the other modes.
+template <bool SIG>
+__device__ __forceinline__ float apply_mask(float v, float g, int mode) {
+  if constexpr (SIG) return v * (1.f / (1.f + expf(-g)));
+  else return v * (mode == 1 ? g : (g > 0.f ? 1.f : 0.f));
+}
+// the frames t0 .. t1 that cover sample sp of a stream whose last frame is `last` (none when t0 > t1)
+struct Cover { long t0, t1; };
+__device__ __forceinline__ Cover covering(long sp, int N, int hop, long last) {
+  const long lo = sp - N + 1, hi = sp / hop;
+  return Cover{lo > 0 ? (lo + hop - 1) / hop : 0, hi > last ? last : hi};
+}
+// librosa's normalisation of an overlap-add sum by the window sum of squares, where that exceeds float32 tiny
+constexpr float F32_TINY = 1.17549435e-38f;
+__device__ __forceinline__ float ola_normalise(float acc, double wss) {
+  const float w = (float)wss;
+  return w > F32_TINY ? acc / w : acc;
 }
 
 static inline int grid1(long n) { long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }

@@ -12,28 +12,19 @@
 
 namespace {
 
-// Winv[c][n]: row 2f = hann[n] w_f/N cos(2 pi f n / N), row 2f+1 = -hann[n] w_f/N sin(2 pi f n / N), w_f = 1 for DC and
-// Nyquist, else 2 (irfft of a half spectrum, then the synthesis window); rows >= 2F are zero.  win2[n] = hann[n]^2 as doubles.
+// Winv[c][n]: rows 2f, 2f + 1 = frames::idft_element (f, re | im, n); rows >= 2F are zero.  win2[n] = hann[n]^2 as doubles.
 __global__ void idft_basis(float* __restrict__ W, double* __restrict__ win2, int N, int F, int rows) {
   const long n_el = (long)rows * N;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i / N), n = (int)(i % N);
     const double win = frames::hann(n, N);
-    float v = 0.f;
-    if (c < 2 * F) {
-      const int f = c >> 1;
-      const double wf = (f == 0 || 2 * f == N) ? 1.0 : 2.0;
-      const frames::Phase ph = frames::phase(f, n, N);
-      v = (float)((c & 1) ? -win * (wf / (double)N) * ph.sin() : win * (wf / (double)N) * ph.cos());
-    }
-    W[i] = v;
+    W[i] = c < 2 * F ? frames::idft_element(c >> 1, c & 1, n, N) : 0.f;
     if (c == 0) win2[n] = win * win;
   }
 }
 
 // A[m = (b,t)][c] = S[b,t,c] * m(b,t,c>>1)  (zero for c >= 2F); S through element strides, (re, im) adjacent.  Offsets are
-// 32-bit (the entry points check that the last element of spec and mask lies below 2^31).  SIG: the mask is sigmoid(logit)
-// (mode 2; its own instantiation, so that the exponential's registers do not weigh on the other modes).
+// 32-bit (the entry points check that the last element of spec and mask lies below 2^31).  SIG: frames::apply_mask's.
 template <bool SIG>
 struct MaskedSpec {
   static constexpr bool KCONTIG = true;
@@ -52,17 +43,11 @@ struct MaskedSpec {
     if (x < X && c < 2 * F) {
       const unsigned b = (unsigned)x / (unsigned)T, t = (unsigned)x - b * (unsigned)T, f = (unsigned)c >> 1;
       r = S[b * sb + t * st + f * sf + (c & 1)];
-      if (mode) {
-        const float g = mask[(unsigned)x * (unsigned)F + f];
-        if constexpr (SIG) r *= 1.f / (1.f + expf(-g));
-        else r *= mode == 1 ? g : (g > 0.f ? 1.f : 0.f);
-      }
+      if (mode) r = frames::apply_mask<SIG>(r, mask[(unsigned)x * (unsigned)F + f], mode);
     }
     v[0] = r;
   }
 };
-
-constexpr float F32_TINY = 1.17549435e-38f;
 
 // out[b][s] = scale[b] * (sum_t Y[b,t][s' - t hop]) / wss(s'),  s' = s + start, t ascending over the frames that cover s';
 // no atomics: one thread gathers one sample.  Exact zeros at and beyond out_len[b] and the row's natural length.
@@ -72,27 +57,22 @@ __global__ void overlap_add(const float* __restrict__ Y, const double* __restric
   const long n_el = (long)B * pitch;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
     const int b = (int)(i / pitch), s = (int)(i % pitch);
-    int nf = n_frames ? n_frames[b] : T;
-    nf = nf < 0 ? 0 : (nf > T ? T : nf);
+    const int nf = n_frames ? clamp_count(n_frames[b], T) : T;
     int len = out_len ? out_len[b] : pitch;
     len = len > pitch ? pitch : len;
     const long natural = nf > 0 ? (long)N + (long)hop * (nf - 1) - start : 0;
     float y = 0.f;
     if (s < len && s < natural) {
       const long sp = (long)s + start;
-      const long lo = sp - N + 1;
-      int t0 = lo > 0 ? (int)((lo + hop - 1) / hop) : 0;
-      long t1 = sp / hop;
-      if (t1 > nf - 1) t1 = nf - 1;
+      const frames::Cover c = frames::covering(sp, N, hop, nf - 1);
       float acc = 0.f;
       double wss = 0.0;
-      for (int t = t0; t <= (int)t1; ++t) {
+      for (int t = (int)c.t0; t <= (int)c.t1; ++t) {
         const int n = (int)(sp - (long)t * hop);
         acc += Y[((long)b * T + t) * N + n];
         wss += win2[n];
       }
-      const float w = (float)wss;
-      y = w > F32_TINY ? acc / w : acc;
+      y = frames::ola_normalise(acc, wss);
       if (scale) y *= scale[b];
     }
     out[i] = y;

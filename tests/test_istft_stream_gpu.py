@@ -464,3 +464,27 @@ def test_evaluator_writes_the_streamed_enhanced_utterance(tmp_path):
     assert whole.shape == direct.shape
     print("istft stream: enhanced utt_sa1 peak %.3f, max|streamed - whole utterance| = %.3e away from the ends"
           % (np.abs(y).max(), float((direct - whole)[1024:-1024].abs().max())))
+
+
+@pytest.mark.parametrize("n_fft", [32, 64])
+def test_streaming_inverse_basis_is_the_whole_utterance_basis(n_fft):
+    """Frame c of the spectrum is a unit impulse at packed contraction row c of the streaming kernel (c = 0: re[0], c = 1:
+    re[n_fft/2], c = 2f, 2f + 1: re[f], im[f] for 1 <= f < n_fft/2; never im[0] or im[n_fft/2]) and hop = n_fft, so no two
+    frames overlap: every sum of the whole-utterance inverse and of the streaming one is one product 1.0 * W plus exact
+    zeros, divided by the same (float) hann^2[n] (or not at all where that is not above FLT_MIN, n = 0).  The two hold the
+    same basis floats exactly when the two outputs are the same bits."""
+    from avvad import ops
+    from avvad.stream import OlaClock
+    N, F = n_fft, n_fft // 2 + 1
+    spec = torch.zeros(1, N, F, 2, device=DEV)
+    spec[0, 0, 0, 0] = 1.0
+    spec[0, 1, N // 2, 0] = 1.0
+    for f in range(1, N // 2):
+        spec[0, 2 * f, f, 0] = 1.0
+        spec[0, 2 * f + 1, f, 1] = 1.0
+    assert int(spec.count_nonzero()) == N and not spec[0, :, 0, 1].any() and not spec[0, :, N // 2, 1].any()
+    whole = ops.istft(spec, N, N, center=False)
+    stream, n_out = ops.istft_stream(spec, [N], OlaClock(1, N, N), ops.istft_stream_state(1, N, DEV), ops.istft_stream_basis(N, DEV))
+    assert n_out == [N * N] and whole.shape == stream.shape == (1, N * N)
+    assert whole.any()
+    assert torch.equal(whole, stream)
