@@ -40,10 +40,15 @@ struct AvvadTune {
   int wn_no_fused_wgrad;    // unfused encoder block backward (dz, weight gradients as separate kernels)
   int no_fixup1;             // tuning aid: always the four-wave fix-up kernel
   int no_buf;                // convolution gathers with flat addressing + validity selects (the form operands >= 2 GiB use)
-  int wn_flat;               // residual-block forward: 0 by size, 1 flat dword kernel, 2 dword buffer kernel, 3 wide (dwordx4) buffer kernel
-  int wn_dx;                 // dx kernel: 0 by the descriptor's shared_device hint, 1 resident weights + cross-tile prefetch, 2 high occupancy, 3 round 1's flat kernel
-  int wn_grid;               // tuning aid: workgroup cap of the wide residual-block kernels (0 = default)
-  int wn_bwd_t;             // fused block backward: 0 by the descriptor's shared_device hint, 1 transposed products, 2 high occupancy, 3 resident weights
+  // (the next four as in include/avvad.h)
+  int wn_flat;               // encoder block forward: 0 by plane length -- the wide kernel from 8192 samples, else the high-occupancy
+                             // kernel; 1 flat dword kernel, which also makes the input gradient flat; 2 buffer dword kernel with resident weights and
+                             // cross-tile prefetch; 3 wide dwordx4 kernel; 4 high-occupancy kernel; 5 LDS-DMA kernel
+  int wn_dx;                 // encoder block input gradient: 0 and 2 high-occupancy kernel; 1 resident weights and cross-tile prefetch;
+                             // 3 flat kernel
+  int wn_grid;               // workgroup cap of the encoder block forward kernels
+  int wn_bwd_t;              // encoder block dz + weight gradients in one pass: 0 by the descriptor's shared_device hint -- 3 beside
+                             // another stream's kernels, else 2; 1 transposed products; 2 high occupancy; 3 resident weights
   int bf16;                 // bf16-input MFMA (fp32 accumulate) for the convolutions and dense GEMMs: BASELINE config 5's arithmetic
   int stagger;              // the engine's 8-wave kernels WITH the half-tile stagger of waves 4-7 (measured: step +0.14 ms; off)
   int cls_cap;              // tuning aid: most tiles a position-class product may have (0 = two per CU)
@@ -147,25 +152,32 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
 }
 
-// XCD-aware walk of a persistent grid of 4-wave workgroups over `ntiles` wave-tiles.  Workgroups are dealt round-robin to
+// XCD-aware walk of a persistent grid of `waves`-wave workgroups over `ntiles` wave-tiles.  Workgroups are dealt round-robin to
 // the 8 XCDs (each with its own L2), so XCD x takes the contiguous eighth [x*ntiles/8, (x+1)*ntiles/8) and its waves sweep it
 // side by side: tile j + d (the other tap, the residual, the neighbouring halo) is then a line that a wave of the SAME XCD
 // fetched a moment ago.  Dealt out by raw wave id, neighbouring tiles sat in different XCDs and every activation plane
 // crossed the fabric ~1.4-1.7 times (FETCH_SIZE: 117 -> 94 MB per encoder-layer launch for 86 MB algorithmic).  Falls back
 // to the plain strided walk when the grid is not a whole number of XCD groups.  Speed only: every tile is visited once.
 struct TileWalk { long first, last, stride; };
-__device__ __forceinline__ TileWalk xcd_walk(long ntiles) {
+__device__ __forceinline__ TileWalk xcd_walk(long ntiles, int waves = 4) {
   TileWalk w;
   w.first = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   w.last = ntiles;
   w.stride = ((long)gridDim.x * blockDim.x) >> 6;
-  if ((gridDim.x & 7) == 0 && blockDim.x == 256) {
+  if ((gridDim.x & 7) == 0 && blockDim.x == 64 * waves) {
     const int xcd = blockIdx.x & 7;
-    w.first = ntiles * xcd / 8 + ((blockIdx.x >> 3) * 4 + (threadIdx.x >> 6));
+    w.first = ntiles * xcd / 8 + ((blockIdx.x >> 3) * waves + (threadIdx.x >> 6));
     w.last = ntiles * (xcd + 1) / 8;
-    w.stride = (gridDim.x >> 3) * 4;
+    w.stride = (gridDim.x >> 3) * waves;
   }
   return w;
+}
+// The same walk for kernels that count tiles in an int (buffer addressing: < 2^31 tiles); `first` is wave-uniform and
+// handed over in an SGPR, so that everything derived from the tile index (descriptors, row offsets) is scalar work.
+struct TileWalkI { int first, last, stride; };
+__device__ __forceinline__ TileWalkI xcd_walk_i(int ntiles, int waves = 4) {
+  const TileWalk w = xcd_walk(ntiles, waves);
+  return {__builtin_amdgcn_readfirstlane((int)w.first), (int)w.last, (int)w.stride};
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }

@@ -23,6 +23,7 @@
 // Any other (R, D, filter_width) runs generic direct kernels.
 // Weight gradients contract over (sequence, time) on the igemm engine.
 #include "gemm_api.h"
+#include "wn_block.h"
 
 namespace {
 
@@ -187,38 +188,36 @@ __global__ void tail_bwd_dz_generic(const float* __restrict__ s, const float* __
 }
 
 // ------------------------------------------------------------------ fused MFMA residual block (R = D = 32, fw = 2)
-// MODE 0: write s_out only; MODE 1: write s_out and z (pre-ReLU dilation output); MODE 2: write z only
+// The device toolkit every block kernel below stands on -- the LDS weight image and its stagers, the tile decode, the
+// ping-pong loop -- is wn_block.h; the tile walk is xcd_walk in common.h.
+// FLAT-ADDRESSED form (round 1; the fallback for planes of >= 2 GiB).  MODE 0: write s_out; MODE 2: write z (the pre-ReLU
+// dilation output) only, for the unfused backward.
 template <int MODE>
 __global__ void __launch_bounds__(256)
     wn_block_fwd_mfma(const float* __restrict__ s_in, const float* __restrict__ w_dil, const float* __restrict__ b_dil,
                       const float* __restrict__ w_dense, const float* __restrict__ b_dense, float* __restrict__ s_out,
                       float* __restrict__ z_out, int B, int Lin, int dil) {
+  static_assert(MODE == 0 || MODE == 2, "s_out only, or z only");
   const int lane = threadIdx.x & 63;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lo);
   const long ntiles = (long)B * tiles_per_seq;
   const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
 
-  // A operands, resident for the whole kernel.  The per-lane fragment pattern is a 256-byte-strided gather, so
-  // the block first copies the 3072 weights coalesced into (padded, conflict-free) LDS and picks them from there.
-  __shared__ float wl[32 * 65 + 32 * 33 + 64];
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  for (int i = threadIdx.x; i < 1024; i += 256) wl[2080 + (i >> 5) * 33 + (i & 31)] = w_dense[i];
-  if (threadIdx.x < 32) {   // biases stay in LDS and seed the accumulators per tile (32 registers saved)
-    wl[3136 + threadIdx.x] = b_dil ? b_dil[threadIdx.x] : 0.f;
-    wl[3168 + threadIdx.x] = b_dense ? b_dense[threadIdx.x] : 0.f;
-  }
+  // A operands, resident for the whole kernel, picked from the LDS weight image
+  __shared__ float wl[WIMG_SIZE];
+  stage_block_weights(wl, w_dil, b_dil, w_dense, b_dense, threadIdx.x, 256);
   __syncthreads();
   float wd[32];   // W_dil[d = li][c = s][tap = lh]
 #pragma unroll
-  for (int s = 0; s < 32; ++s) wd[s] = wl[li * 65 + s * 2 + lh];
+  for (int s = 0; s < 32; ++s) wd[s] = wl[WIMG_DIL + li * WIMG_DIL_PITCH + s * 2 + lh];
   float we[16];   // W_dense[r = li][d = row(r', lh)]
 #pragma unroll
-  for (int r = 0; r < 16; ++r) we[r] = wl[2080 + li * 33 + mfma32_row(r, lh)];
-  const float* bzl = wl + 3136;
-  const float* bsl = wl + 3168;
+  for (int r = 0; r < 16; ++r) we[r] = wl[WIMG_DENSE + li * WIMG_DENSE_PITCH + mfma32_row(r, lh)];
+  const float* bzl = wl + WIMG_BDIL;
+  const float* bsl = wl + WIMG_BDENSE;
 
   // Software pipeline across tiles: the NEXT tile's 48 loads are issued before the current tile's 48 MFMAs, so
   // HBM latency hides under the matrix work inside one wave (the kernel is balanced HBM <-> MFMA).
@@ -226,14 +225,12 @@ __global__ void __launch_bounds__(256)
   // "ok ? load : 0" makes hipcc branch around every load and wait for each one (32 serial round trips).
   float xn[32], rn[16];
   auto issue = [&](long tile) {
-    const long tl = tile < ntiles ? tile : ntiles - 1;
-    const int b = (int)(tl / tiles_per_seq);
-    const int t = (int)(tl - (long)b * tiles_per_seq) * 32 + li;
-    const int tcl = t < Lo ? t : 0;
+    const TilePos p = tile_pos(tile < ntiles ? tile : ntiles - 1, tiles_per_seq, li, Lo);
+    const int b = p.b, tcl = p.ok ? p.t : 0;
     const float* xp = s_in + (long)b * 32 * Lin + tcl + lh * dil;
 #pragma unroll
     for (int c = 0; c < 32; ++c) xn[c] = xp[(long)c * Lin];
-    if (MODE <= 1) {
+    if (MODE == 0) {
       const float* rp = s_in + (long)b * 32 * Lin + tcl + dil;
 #pragma unroll
       for (int r = 0; r < 16; ++r) rn[r] = rp[(long)mfma32_row(r, lh) * Lin];
@@ -241,27 +238,27 @@ __global__ void __launch_bounds__(256)
   };
   if (wave0 < ntiles) issue(wave0);
   for (long tile = wave0; tile < ntiles; tile += nwaves) {
-    const int b = (int)(tile / tiles_per_seq);
-    const int t = (int)(tile - (long)b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lo;
+    const TilePos p = tile_pos(tile, tiles_per_seq, li, Lo);
+    const int b = p.b, t = p.t;
+    const bool ok = p.ok;
     float x[32], rv[16];
 #pragma unroll
     for (int c = 0; c < 32; ++c) x[c] = ok ? xn[c] : 0.f;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) rv[r] = (MODE <= 1 && ok) ? rn[r] : 0.f;
+    for (int r = 0; r < 16; ++r) rv[r] = (MODE == 0 && ok) ? rn[r] : 0.f;
     issue(tile + nwaves);     // in flight during the MFMAs below (clamped to the last tile when there is none)
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = bzl[mfma32_row(r, lh)];
 #pragma unroll
     for (int s = 0; s < 32; ++s) acc = mfma32(wd[s], relu1(x[s]), acc);
-    if (MODE >= 1) {
+    if (MODE == 2) {
       float* zp = z_out + (long)b * 32 * Lo + t;
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         if (ok) zp[(long)mfma32_row(r, lh) * Lo] = acc[r];
     }
-    if (MODE <= 1) {
+    if (MODE == 0) {
       f32x16 acc2;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[r] = bsl[mfma32_row(r, lh)] + rv[r];
@@ -276,7 +273,7 @@ __global__ void __launch_bounds__(256)
 }
 
 
-// BUFFER-ADDRESSED form of the same block (the default; option "wn_flat" selects the kernel above).  On this chip the fp32
+// BUFFER-ADDRESSED forms of the same block (option "wn_flat" selects the kernel above).  On this chip the fp32
 // MFMA runs on the vector lanes: every VALU instruction costs ~4 matrix-pipe cycles whatever the occupancy (tools/lab/
 // mfvar_lab.py: a wave's MFMA chain at 0.90 of the pipe with ~50 VALU per tile, 0.71 with ~220, the same at 1, 2 and 3
 // waves/SIMD).  The flat kernel above carries 718 VALU instructions per 48 MFMAs -- 139 64-bit address adds, 96 v_max (two
@@ -284,171 +281,97 @@ __global__ void __launch_bounds__(256)
 //   * one buffer descriptor per tensor and tile (SALU), ONE per-lane byte offset, the row in the instruction's scalar offset;
 //   * lanes past the end of a sequence carry an out-of-range offset: their loads return 0 and their stores are dropped by
 //     the bounds check, so no select touches the data;
-//   * ReLU is one integer max (relu1);
-//   * the cross-tile prefetch alternates between two register sets instead of copying.
-template <int MODE>
-__global__ void __launch_bounds__(256)
-    wn_block_fwd_buf(const float* __restrict__ s_in, const float* __restrict__ w_dil, const float* __restrict__ b_dil,
-                     const float* __restrict__ w_dense, const float* __restrict__ b_dense, float* __restrict__ s_out,
-                     float* __restrict__ z_out, int B, int Lin, int dil) {
+//   * ReLU is one integer max (relu1).
+// ONE body, two schedules of it (wn_block_fwd_buf and wn_block_fwd_occ below):
+//   RESIDENT   the 48 weight fragments live in registers and the cross-tile prefetch alternates between two register sets
+//              (instead of copying): a tile's memory latency hides under this wave's own MFMAs;
+//   otherwise  nothing is held across tiles -- weights read from LDS per MFMA, no prefetch registers -- so the kernel fits
+//              4 waves per SIMD (< 128 VGPRs) and the latency hides under the OTHER waves' MFMAs.
+// The tiles are walked XCD-aware (xcd_walk, common.h): the second tap and the residual of a tile (the same plane, `dil`
+// samples later) are then lines that a neighbouring wave of the SAME XCD fetched a moment ago.
+struct FwdTile { float x[32], r[16]; };      // a tile's 32 operand rows (tap lh) and 16 residual rows, as requested
+template <bool RESIDENT>
+__device__ __forceinline__ void wn_block_fwd_body(float* wl, const float* __restrict__ s_in, const float* __restrict__ w_dil,
+                                                  const float* __restrict__ b_dil, const float* __restrict__ w_dense,
+                                                  const float* __restrict__ b_dense, float* __restrict__ s_out, int B, int Lin,
+                                                  int dil) {
   const int lane = threadIdx.x & 63;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lo);
   const int ntiles = B * tiles_per_seq;
-  const int wave0 = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-  const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
-  __shared__ float wl[32 * 65 + 32 * 33 + 64];
-  float wd[32];   // W_dil[d = li][c = s][tap = lh]
-  float we[16];   // W_dense[r = li][d = row(r', lh)]
-  const float* bzl = wl + 3136 + 4 * lh;
-  const float* bsl = wl + 3168 + 4 * lh;
+  const float* wdl = wl + WIMG_DIL + li * WIMG_DIL_PITCH + lh;             // W_dil[d = li][c = s][tap = lh] at wdl[2 s]
+  const float* wel = wl + WIMG_DENSE + li * WIMG_DENSE_PITCH + 4 * lh;     // W_dense[r = li][d = row(r', lh)] at wel[row(r', 0)]
+  const float* bzl = wl + WIMG_BDIL + 4 * lh;
+  const float* bsl = wl + WIMG_BDENSE + 4 * lh;
   const int rowL = Lin * 4, rowO = Lo * 4;     // bytes per row of the input / output tensors
+  float wd[32], we[16];                        // RESIDENT: the fragments themselves
 
-  // request tile `tile`'s 48 values (clamped to the last tile when there is none: the values are then never used)
-  auto issue = [&](int tile, float (&xn)[32], float (&rn)[16]) {
-    const int tl = tile < ntiles ? tile : ntiles - 1;
-    const int b = tl / tiles_per_seq;
-    const int t = (tl - b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lo;
-    const __amdgpu_buffer_rsrc_t rx = brsrc(s_in + (long)b * 32 * Lin, 32 * rowL);
-    const int offx = ok ? (t + lh * dil) * 4 : BUF_OOB;
+  // request tile `tile`'s 48 values (the prefetch clamps to the last tile when there is none: the values are then never used)
+  auto issue = [&](int tile, FwdTile& n) __attribute__((always_inline)) {
+    const TilePos p = tile_pos(RESIDENT && tile >= ntiles ? ntiles - 1 : tile, tiles_per_seq, li, Lo);
+    const __amdgpu_buffer_rsrc_t rx = brsrc(s_in + (long)p.b * 32 * Lin, 32 * rowL);
+    const int offx = p.ok ? (p.t + lh * dil) * 4 : BUF_OOB;
 #pragma unroll
-    for (int c = 0; c < 32; ++c) xn[c] = bload(rx, offx, c * rowL);
-    if (MODE <= 1) {
-      const int offr = ok ? (t + dil) * 4 + 4 * lh * rowL : BUF_OOB;
+    for (int c = 0; c < 32; ++c) n.x[c] = bload(rx, offx, c * rowL);
+    const int offr = p.ok ? (p.t + dil) * 4 + 4 * lh * rowL : BUF_OOB;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) rn[r] = bload(rx, offr, mfma32_row(r, 0) * rowL);
-    }
+    for (int r = 0; r < 16; ++r) n.r[r] = bload(rx, offr, mfma32_row(r, 0) * rowL);
   };
-  auto compute = [&](int tile, const float (&x)[32], const float (&rv)[16]) {
-    const int b = tile / tiles_per_seq;
-    const int t = (tile - b * tiles_per_seq) * 32 + li;
-    const int offo = t < Lo ? t * 4 + 4 * lh * rowO : BUF_OOB;
+  auto compute = [&](int tile, const FwdTile& c) __attribute__((always_inline)) {
+    const TilePos p = tile_pos(tile, tiles_per_seq, li, Lo);
+    const int offo = p.ok ? p.t * 4 + 4 * lh * rowO : BUF_OOB;
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = bzl[mfma32_row(r, 0)];
 #pragma unroll
-    for (int s = 0; s < 32; ++s) acc = mfma32(wd[s], relu1(x[s]), acc);
-    if (MODE >= 1) {
-      const __amdgpu_buffer_rsrc_t rz = brsrc(z_out + (long)b * 32 * Lo, 32 * rowO);
+    for (int s = 0; s < 32; ++s) acc = mfma32(RESIDENT ? wd[s] : wdl[2 * s], relu1(c.x[s]), acc);
+    f32x16 acc2;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) bstore(acc[r], rz, offo, mfma32_row(r, 0) * rowO);
-    }
-    if (MODE <= 1) {
-      f32x16 acc2;
+    for (int r = 0; r < 16; ++r) acc2[r] = bsl[mfma32_row(r, 0)] + c.r[r];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[r] = bsl[mfma32_row(r, 0)] + rv[r];
+    for (int r = 0; r < 16; ++r) acc2 = mfma32(RESIDENT ? we[r] : wel[mfma32_row(r, 0)], relu1(acc[r]), acc2);
+    const __amdgpu_buffer_rsrc_t ro = brsrc(s_out + (long)p.b * 32 * Lo, 32 * rowO);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc2 = mfma32(we[r], relu1(acc[r]), acc2);
-      const __amdgpu_buffer_rsrc_t ro = brsrc(s_out + (long)b * 32 * Lo, 32 * rowO);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bstore(acc2[r], ro, offo, mfma32_row(r, 0) * rowO);
-    }
+    for (int r = 0; r < 16; ++r) bstore(acc2[r], ro, offo, mfma32_row(r, 0) * rowO);
   };
-  // XCD-aware walk: workgroups are dealt round-robin to the 8 XCDs (each with its own L2), so XCD x takes the contiguous
-  // eighth [lo, hi) of the tiles and its waves sweep it side by side -- the second tap and the residual of a tile (the
-  // same plane, `dil` samples later) are then lines that a neighbouring wave of the SAME XCD fetched a moment ago.  Dealt
-  // out by raw wave id, tile j's neighbours j + dil/32 sat in other XCDs and every plane crossed the fabric ~1.7 times.
-  int first = wave0, last = ntiles, stride = nwaves;
-  if ((gridDim.x & 7) == 0) {
-    const int xcd = blockIdx.x & 7, nbx = gridDim.x >> 3;
-    first = (int)((long)ntiles * xcd / 8) + ((blockIdx.x >> 3) * 4 + (int)(threadIdx.x >> 6));
-    last = (int)((long)ntiles * (xcd + 1) / 8);
-    stride = nbx * 4;
-  }
-  first = __builtin_amdgcn_readfirstlane(first);
-  float xa[32], ra[16], xb[32], rb[16];
-  if (first < last) issue(first, xa, ra);
-  // the first tile's requests are on their way while the block's weights make their own round trip (global -> LDS ->
-  // registers): at the bench shape a launch lasts ~37 us and each of the two latencies is ~2 us of it
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  for (int i = threadIdx.x; i < 1024; i += 256) wl[2080 + (i >> 5) * 33 + (i & 31)] = w_dense[i];
-  if (threadIdx.x < 32) {
-    wl[3136 + threadIdx.x] = b_dil ? b_dil[threadIdx.x] : 0.f;
-    wl[3168 + threadIdx.x] = b_dense ? b_dense[threadIdx.x] : 0.f;
-  }
+  const TileWalkI w = xcd_walk_i(ntiles);
+  FwdTile ta, tb;
+  // RESIDENT: the first tile's requests are on their way while the block's weights make their own round trip (global -> LDS
+  // -> registers): at the bench shape a launch lasts ~37 us and each of the two latencies is ~2 us of it
+  if (RESIDENT && w.first < w.last) issue(w.first, ta);
+  stage_block_weights(wl, w_dil, b_dil, w_dense, b_dense, threadIdx.x, 256);
   __syncthreads();
+  if (RESIDENT) {
 #pragma unroll
-  for (int s = 0; s < 32; ++s) wd[s] = wl[li * 65 + s * 2 + lh];
+    for (int s = 0; s < 32; ++s) wd[s] = wdl[2 * s];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) we[r] = wl[2080 + li * 33 + mfma32_row(r, lh)];
-  for (int tile = first; tile < last; tile += 2 * stride) {
-    issue(tile + stride, xb, rb);          // in flight during the MFMAs below (a tile past `last` is fetched, never used)
-    compute(tile, xa, ra);
-    if (tile + stride >= last) break;
-    issue(tile + 2 * stride, xa, ra);
-    compute(tile + stride, xb, rb);
+    for (int r = 0; r < 16; ++r) we[r] = wel[mfma32_row(r, 0)];
+    pingpong_tiles<false>(w, ta, tb, issue, compute);
+  } else {
+    plain_tiles<false, FwdTile>(w, issue, compute);
   }
 }
 
-// HIGH-OCCUPANCY form (the default for planes shorter than 8192 samples): the same block with nothing held across tiles
-// -- weights read from LDS per MFMA instead of 48 resident registers, no cross-tile prefetch registers -- so the kernel
-// fits 4 waves per SIMD (< 128 VGPRs) and the memory latency of a tile hides under the OTHER waves' MFMAs instead of under
-// this wave's own.  Measured (tools/lab/clk_lab2.py, same body): bench-shape layer 28.4 us at 4 waves/SIMD, 28.5 at 3,
-// 31.0 at 2; C2-shape layer 273 / 303 / 380 us.  Earlier attempts at this shape (round 2, first half) ran the flat
-// addressing: with ~700 VALU instructions per tile the extra waves only queued for the vector ALUs.
-template <int MODE>
+// resident weights + cross-tile prefetch: the form picked beside another stream's kernels (wn_flat = 2)
+__global__ void __launch_bounds__(256)
+    wn_block_fwd_buf(const float* __restrict__ s_in, const float* __restrict__ w_dil, const float* __restrict__ b_dil,
+                     const float* __restrict__ w_dense, const float* __restrict__ b_dense, float* __restrict__ s_out, int B,
+                     int Lin, int dil) {
+  __shared__ float wl[WIMG_SIZE];
+  wn_block_fwd_body<true>(wl, s_in, w_dil, b_dil, w_dense, b_dense, s_out, B, Lin, dil);
+}
+
+// HIGH-OCCUPANCY form (the default for planes shorter than 8192 samples).  Measured (tools/lab/clk_lab2.py, same body):
+// bench-shape layer 28.4 us at 4 waves/SIMD, 28.5 at 3, 31.0 at 2; C2-shape layer 273 / 303 / 380 us.  Earlier attempts at
+// this shape (round 2, first half) ran the flat addressing: with ~700 VALU instructions per tile the extra waves only queued
+// for the vector ALUs.
 __global__ void __launch_bounds__(256, 4)
     wn_block_fwd_occ(const float* __restrict__ s_in, const float* __restrict__ w_dil, const float* __restrict__ b_dil,
-                     const float* __restrict__ w_dense, const float* __restrict__ b_dense, float* __restrict__ s_out,
-                     float* __restrict__ z_out, int B, int Lin, int dil) {
-  const int lane = threadIdx.x & 63;
-  const int li = lane & 31, lh = lane >> 5;
-  const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 31) >> 5;
-  const int ntiles = B * tiles_per_seq;
-  __shared__ float wl[32 * 65 + 32 * 33 + 64];
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  for (int i = threadIdx.x; i < 1024; i += 256) wl[2080 + (i >> 5) * 33 + (i & 31)] = w_dense[i];
-  if (threadIdx.x < 32) {
-    wl[3136 + threadIdx.x] = b_dil ? b_dil[threadIdx.x] : 0.f;
-    wl[3168 + threadIdx.x] = b_dense ? b_dense[threadIdx.x] : 0.f;
-  }
-  __syncthreads();
-  const float* wdl = wl + li * 65 + lh;              // W_dil[d = li][c = s][tap = lh] at wdl[2 s]
-  const float* wel = wl + 2080 + li * 33 + 4 * lh;   // W_dense[r = li][d = row(r', lh)] at wel[row(r', 0)]
-  const float* bzl = wl + 3136 + 4 * lh;
-  const float* bsl = wl + 3168 + 4 * lh;
-  const int rowL = Lin * 4, rowO = Lo * 4;
-  const TileWalk tw = xcd_walk(ntiles);
-  const int first = __builtin_amdgcn_readfirstlane((int)tw.first), last = (int)tw.last, stride = (int)tw.stride;
-  for (int tile = first; tile < last; tile += stride) {
-    const int b = tile / tiles_per_seq;
-    const int t = (tile - b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lo;
-    const __amdgpu_buffer_rsrc_t rx = brsrc(s_in + (long)b * 32 * Lin, 32 * rowL);
-    const int offx = ok ? (t + lh * dil) * 4 : BUF_OOB;
-    float x[32], rv[16];
-#pragma unroll
-    for (int c = 0; c < 32; ++c) x[c] = bload(rx, offx, c * rowL);
-    if (MODE <= 1) {
-      const int offr = ok ? (t + dil) * 4 + 4 * lh * rowL : BUF_OOB;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) rv[r] = bload(rx, offr, mfma32_row(r, 0) * rowL);
-    }
-    const int offo = ok ? t * 4 + 4 * lh * rowO : BUF_OOB;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = bzl[mfma32_row(r, 0)];
-#pragma unroll
-    for (int s = 0; s < 32; ++s) acc = mfma32(wdl[2 * s], relu1(x[s]), acc);
-    if (MODE >= 1) {
-      const __amdgpu_buffer_rsrc_t rz = brsrc(z_out + (long)b * 32 * Lo, 32 * rowO);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bstore(acc[r], rz, offo, mfma32_row(r, 0) * rowO);
-    }
-    if (MODE <= 1) {
-      f32x16 acc2;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[r] = bsl[mfma32_row(r, 0)] + rv[r];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc2 = mfma32(wel[mfma32_row(r, 0)], relu1(acc[r]), acc2);
-      const __amdgpu_buffer_rsrc_t ro = brsrc(s_out + (long)b * 32 * Lo, 32 * rowO);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bstore(acc2[r], ro, offo, mfma32_row(r, 0) * rowO);
-    }
-  }
+                     const float* __restrict__ w_dense, const float* __restrict__ b_dense, float* __restrict__ s_out, int B,
+                     int Lin, int dil) {
+  __shared__ float wl[WIMG_SIZE];
+  wn_block_fwd_body<false>(wl, s_in, w_dil, b_dil, w_dense, b_dense, s_out, B, Lin, dil);
 }
 
 // LDS-DMA form.  What bounds the dword kernels above is the CU's ADDRESS unit, shared by the four SIMDs: a wave memory
@@ -469,39 +392,26 @@ __global__ void __launch_bounds__(512, 4)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lo);
   const int ntiles = B * tiles_per_seq;
-  __shared__ __attribute__((aligned(16))) float wl[8 * 2048 + 32 * 65 + 32 * 33 + 64];     // wave tiles first (16-byte aligned DMA targets)
+  __shared__ __attribute__((aligned(16))) float wl[8 * 2048 + WIMG_SIZE];     // wave tiles first (16-byte aligned DMA targets)
   float* const wts = wl + 8 * 2048;
-  for (int i = threadIdx.x; i < 2048; i += 512) wts[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  for (int i = threadIdx.x; i < 1024; i += 512) wts[2080 + (i >> 5) * 33 + (i & 31)] = w_dense[i];
-  if (threadIdx.x < 32) {
-    wts[3136 + threadIdx.x] = b_dil ? b_dil[threadIdx.x] : 0.f;
-    wts[3168 + threadIdx.x] = b_dense ? b_dense[threadIdx.x] : 0.f;
-  }
+  stage_block_weights(wts, w_dil, b_dil, w_dense, b_dense, threadIdx.x, 512);
   __syncthreads();
-  const float* wdl = wts + li * 65 + lh;              // W_dil[d = li][c = s][tap = lh] at wdl[2 s]
-  const float* wel = wts + 2080 + li * 33 + 4 * lh;   // W_dense[r = li][d = row(r', lh)] at wel[row(r', 0)]
-  const float* bzl = wts + 3136 + 4 * lh;
-  const float* bsl = wts + 3168 + 4 * lh;
+  const float* wdl = wts + WIMG_DIL + li * WIMG_DIL_PITCH + lh;             // W_dil[d = li][c = s][tap = lh] at wdl[2 s]
+  const float* wel = wts + WIMG_DENSE + li * WIMG_DENSE_PITCH + 4 * lh;     // W_dense[r = li][d = row(r', lh)] at wel[row(r', 0)]
+  const float* bzl = wts + WIMG_BDIL + 4 * lh;
+  const float* bsl = wts + WIMG_BDENSE + 4 * lh;
   const int rowL = Lin * 4, rowO = Lo * 4;
   float* const tb = wl + __builtin_amdgcn_readfirstlane(wave) * 2048;        // this wave's tile: [tap][32 channels][32 samples]
   const float* const xs = tb + lh * 1024 + li;                               // B operand of k-step s: xs[32 s]
   const float* const rs = tb + 1024 + 4 * lh * 32 + li;                       // residual row (r, lh): rs[32 row(r, 0)]
   // the DMA's per-lane source: channel row (lane >> 3) of the instruction's 8, samples 4 (lane & 7) .. + 3
   const int dvo = (lane >> 3) * rowL + (lane & 7) * 16;
-  // tile walk: waves of one XCD sweep a contiguous eighth of the tiles (see xcd_walk; 8 waves per workgroup here)
-  int first = (int)(blockIdx.x * 8 + wave), last = ntiles, stride = (int)(gridDim.x * 8);
-  if ((gridDim.x & 7) == 0) {
-    const int xcd = blockIdx.x & 7;
-    first = (int)((long)ntiles * xcd / 8) + ((blockIdx.x >> 3) * 8 + wave);
-    last = (int)((long)ntiles * (xcd + 1) / 8);
-    stride = (gridDim.x >> 3) * 8;
-  }
-  first = __builtin_amdgcn_readfirstlane(first);
-  for (int tile = first; tile < last; tile += stride) {
-    const int b = tile / tiles_per_seq;
-    const int t0 = (tile - b * tiles_per_seq) * 32;
+  const TileWalkI w = xcd_walk_i(ntiles, 8);             // 8 waves per workgroup here
+  for (int tile = w.first; tile < w.last; tile += w.stride) {
+    const TilePos p = tile_pos(tile, tiles_per_seq, li, Lo);
+    const int b = p.b, t0 = p.t0;
     const __amdgpu_buffer_rsrc_t rx = brsrc(s_in + (long)b * 32 * Lin, 32 * rowL);
     // samples past the end of a row read into the next row, past the slab nothing is written: garbage COLUMNS, whose
     // results are never stored (an output column depends on its own input columns only)
@@ -513,9 +423,7 @@ __global__ void __launch_bounds__(512, 4)
     for (int q = 0; q < 4; ++q)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(tb + 1024 + q * 256), 16,
                                                dvo + (t0 + dil) * 4, 8 * q * rowL, 0, 0);
-    const int t = t0 + li;
-    const bool ok = t < Lo;
-    const int offo = ok ? t * 4 + 4 * lh * rowO : BUF_OOB;
+    const int offo = p.ok ? p.t * 4 + 4 * lh * rowO : BUF_OOB;
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = bzl[mfma32_row(r, 0)];
@@ -569,35 +477,21 @@ __global__ void __launch_bounds__(256, 2)
   const int lane = threadIdx.x & 63;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 127) >> 7;
+  const int tiles_per_seq = tiles_per_sequence<128>(Lo);
   const int ntiles = B * tiles_per_seq;
-  __shared__ float wl[32 * 65 + 32 * 33 + 64];
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  for (int i = threadIdx.x; i < 1024; i += 256) wl[2080 + (i >> 5) * 33 + (i & 31)] = w_dense[i];
-  if (threadIdx.x < 32) {
-    wl[3136 + threadIdx.x] = b_dil ? b_dil[threadIdx.x] : 0.f;
-    wl[3168 + threadIdx.x] = b_dense ? b_dense[threadIdx.x] : 0.f;
-  }
+  __shared__ float wl[WIMG_SIZE];
+  stage_block_weights(wl, w_dil, b_dil, w_dense, b_dense, threadIdx.x, 256);
   __syncthreads();
-  const float* wdl = wl + li * 65 + lh;            // W_dil[d = li][c = s][tap = lh] at wdl[2 s]
-  const float* wel = wl + 2080 + li * 33 + 4 * lh; // W_dense[r = li][d = row(r', lh)] at wel[row(r', 0)]
-  const float* bzl = wl + 3136 + 4 * lh;
-  const float* bsl = wl + 3168 + 4 * lh;
+  const float* wdl = wl + WIMG_DIL + li * WIMG_DIL_PITCH + lh;             // W_dil[d = li][c = s][tap = lh] at wdl[2 s]
+  const float* wel = wl + WIMG_DENSE + li * WIMG_DENSE_PITCH + 4 * lh;     // W_dense[r = li][d = row(r', lh)] at wel[row(r', 0)]
+  const float* bzl = wl + WIMG_BDIL + 4 * lh;
+  const float* bsl = wl + WIMG_BDENSE + 4 * lh;
   const int rowL = Lin * 4, rowO = Lo * 4;
 
-  // XCD-aware walk (see wn_block_fwd_buf)
-  int first = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), last = ntiles, stride = (int)((gridDim.x * blockDim.x) >> 6);
-  if ((gridDim.x & 7) == 0) {
-    const int xcd = blockIdx.x & 7, nbx = gridDim.x >> 3;
-    first = (int)((long)ntiles * xcd / 8) + ((blockIdx.x >> 3) * 4 + (int)(threadIdx.x >> 6));
-    last = (int)((long)ntiles * (xcd + 1) / 8);
-    stride = nbx * 4;
-  }
-  first = __builtin_amdgcn_readfirstlane(first);
-  for (int tile = first; tile < last; tile += stride) {
-    const int b = tile / tiles_per_seq;
-    const int t0 = (tile - b * tiles_per_seq) * 128;
-    const int t = t0 + 4 * li;                     // this lane's first sample
+  const TileWalkI w = xcd_walk_i(ntiles);
+  for (int tile = w.first; tile < w.last; tile += w.stride) {
+    const TilePos p = tile_pos<128>(tile, tiles_per_seq, 4 * li, Lo);
+    const int b = p.b, t0 = p.t0, t = p.t;         // t: this lane's first sample
     const __amdgpu_buffer_rsrc_t rx = brsrc(s_in + (long)b * 32 * Lin, 32 * rowL);
     const __amdgpu_buffer_rsrc_t ro = brsrc(s_out + (long)b * 32 * Lo, 32 * rowO);
     // samples past the end of a row read into the next row (or return 0 past the slab): garbage columns, never stored
@@ -686,20 +580,20 @@ __global__ void __launch_bounds__(256)
                          float* __restrict__ DZ, int B, int Lo) {
   const int lane = threadIdx.x & 63;
   const int li = lane & 31, lh = lane >> 5;
-  const int tiles_per_seq = (Lo + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lo);
   const long ntiles = (long)B * tiles_per_seq;
   const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-  __shared__ float wl[32 * 33];
-  for (int i = threadIdx.x; i < 1024; i += 256) wl[(i >> 5) * 33 + (i & 31)] = w_dense[i];
+  __shared__ float wl[WIMG_DENSE_SIZE];
+  stage_w_dense(wl, w_dense, threadIdx.x, 256);
   __syncthreads();
   float wt[16];  // A[i = d = li][k = r = 2s+lh] = W_dense[r][d]
 #pragma unroll
-  for (int s = 0; s < 16; ++s) wt[s] = wl[(2 * s + lh) * 33 + li];
+  for (int s = 0; s < 16; ++s) wt[s] = wl[(2 * s + lh) * WIMG_DENSE_PITCH + li];
   for (long tile = wave0; tile < ntiles; tile += nwaves) {
-    const int b = (int)(tile / tiles_per_seq);
-    const int t = (int)(tile - (long)b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lo;
+    const TilePos p = tile_pos(tile, tiles_per_seq, li, Lo);
+    const int b = p.b, t = p.t;
+    const bool ok = p.ok;
     const long base = (long)b * 32 * Lo + (ok ? t : 0);   // clamped: loads are unconditional, masked below
     float g[16], z[16];
 #pragma unroll
@@ -727,23 +621,20 @@ __global__ void __launch_bounds__(256)
   const int lane = threadIdx.x & 63;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lin + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lin);
   const long ntiles = (long)B * tiles_per_seq;
-  const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-  __shared__ float wl[32 * 65];
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
+  __shared__ float wl[WIMG_DIL_SIZE];
+  stage_w_dil(wl, w_dil, threadIdx.x, 256);
   __syncthreads();
   float wt[32];  // A[i = c = li][k = (d = s, tap = lh)] = W_dil[d][c][tap]
 #pragma unroll
-  for (int s = 0; s < 32; ++s) wt[s] = wl[s * 65 + li * 2 + lh];
+  for (int s = 0; s < 32; ++s) wt[s] = wl[s * WIMG_DIL_PITCH + li * 2 + lh];
   // software pipeline across tiles (see wn_block_fwd_mfma): next tile's loads fly under this tile's MFMAs
   float dzn[32], svn[16], rvn[16];
   auto issue = [&](long tile) {
-    const long tl = tile < ntiles ? tile : ntiles - 1;
-    const int b = (int)(tl / tiles_per_seq);
-    const int t = (int)(tl - (long)b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lin;
+    const TilePos p = tile_pos(tile < ntiles ? tile : ntiles - 1, tiles_per_seq, li, Lin);
+    const int b = p.b, t = p.t;
+    const bool ok = p.ok;
     const int to = t - lh * dil;
     const bool okz = ok && to >= 0 && to < Lo;
     const float* zp = DZ + (long)b * 32 * Lo + (okz ? to : 0);
@@ -758,9 +649,9 @@ __global__ void __launch_bounds__(256)
   const TileWalk tw = xcd_walk(ntiles);
   if (tw.first < tw.last) issue(tw.first);
   for (long tile = tw.first; tile < tw.last; tile += tw.stride) {
-    const int b = (int)(tile / tiles_per_seq);
-    const int t = (int)(tile - (long)b * tiles_per_seq) * 32 + li;   // t' (input time)
-    const bool ok = t < Lin;
+    const TilePos p = tile_pos(tile, tiles_per_seq, li, Lin);
+    const int b = p.b, t = p.t;                                       // t' (input time)
+    const bool ok = p.ok;
     const int to = t - lh * dil;                                      // dz time of this lane half's tap
     const bool okz = ok && to >= 0 && to < Lo;
     const bool okr = ok && t >= dil;                                  // residual: dS_out[c][t' - dil]
@@ -782,114 +673,80 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// BUFFER-ADDRESSED form of (B) with the weights resident and the next tile's requests in flight under this tile's MFMAs:
-// the low-occupancy form picked beside another stream's kernels (descriptor hint shared_device), where the flat kernel
-// above ran until now -- 720 VALU instructions per 32 MFMAs, most of them 64-bit address arithmetic and validity selects.
-__global__ void __launch_bounds__(256)
-    wn_block_bwd_dx_buf(const float* __restrict__ DZ, const float* __restrict__ s_in, const float* __restrict__ dS_out,
-                        const float* __restrict__ w_dil, float* __restrict__ dS_in, int B, int Lin, int dil) {
+// BUFFER-ADDRESSED forms of (B): ONE body, the two schedules of the forward pair (see wn_block_fwd_body).  Same arithmetic,
+// same summation order as the flat kernel above -- which carries 720 VALU instructions per 32 MFMAs, most of them 64-bit
+// address arithmetic and validity selects.
+struct DxTile { float dz[32], sv[16], rv[16]; };   // dz rows (tap lh), s_in rows (the ReLU mask), dS_out rows (the residual)
+template <bool RESIDENT>
+__device__ __forceinline__ void wn_block_bwd_dx_body(float* wl, const float* __restrict__ DZ, const float* __restrict__ s_in,
+                                                     const float* __restrict__ dS_out, const float* __restrict__ w_dil,
+                                                     float* __restrict__ dS_in, int B, int Lin, int dil) {
   const int lane = threadIdx.x & 63;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lin + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lin);
   const int ntiles = B * tiles_per_seq;
-  __shared__ float wl[32 * 65];
+  const float* wtl = wl + li * 2 + lh;   // A[i = c = li][k = (d = s, tap = lh)] = W_dil[d][c][tap] at wtl[65 s]
   const int rowL = Lin * 4, rowO = Lo * 4;
-  // request tile `tile` (clamped to the last tile when there is none: the values are then never used)
-  auto issue = [&](int tile, float (&dzn)[32], float (&svn)[16], float (&rvn)[16]) {
-    const int tc = tile < ntiles ? tile : ntiles - 1;
-    const int b = tc / tiles_per_seq;
-    const int t = (tc - b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lin;
-    const int to = t - lh * dil;
-    const bool okz = ok && to >= 0 && to < Lo;
-    const bool okr = ok && t >= dil;
-    const __amdgpu_buffer_rsrc_t rz = brsrc(DZ + (long)b * 32 * Lo, 32 * rowO);
-    const __amdgpu_buffer_rsrc_t rs = brsrc(s_in + (long)b * 32 * Lin, 32 * rowL);
-    const __amdgpu_buffer_rsrc_t rg = brsrc(dS_out + (long)b * 32 * Lo, 32 * rowO);
+  float wt[32];                          // RESIDENT: the fragment itself
+  // request tile `tile` (the prefetch clamps to the last tile when there is none: the values are then never used)
+  auto issue = [&](int tile, DxTile& n) __attribute__((always_inline)) {
+    const TilePos p = tile_pos(RESIDENT && tile >= ntiles ? ntiles - 1 : tile, tiles_per_seq, li, Lin);
+    const int t = p.t;                                    // t' (input time)
+    const int to = t - lh * dil;                          // dz time of this lane half's tap
+    const bool okz = p.ok && to >= 0 && to < Lo;
+    const bool okr = p.ok && t >= dil;                    // residual: dS_out[c][t' - dil]
+    const __amdgpu_buffer_rsrc_t rz = brsrc(DZ + (long)p.b * 32 * Lo, 32 * rowO);
+    const __amdgpu_buffer_rsrc_t rs = brsrc(s_in + (long)p.b * 32 * Lin, 32 * rowL);
+    const __amdgpu_buffer_rsrc_t rg = brsrc(dS_out + (long)p.b * 32 * Lo, 32 * rowO);
     const int offz = okz ? to * 4 : BUF_OOB;
-    const int offs = ok ? t * 4 + 4 * lh * rowL : BUF_OOB;
+    const int offs = p.ok ? t * 4 + 4 * lh * rowL : BUF_OOB;
     const int offg = okr ? (t - dil) * 4 + 4 * lh * rowO : BUF_OOB;
 #pragma unroll
-    for (int s = 0; s < 32; ++s) dzn[s] = bload(rz, offz, s * rowO);
+    for (int s = 0; s < 32; ++s) n.dz[s] = bload(rz, offz, s * rowO);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { svn[r] = bload(rs, offs, mfma32_row(r, 0) * rowL); rvn[r] = bload(rg, offg, mfma32_row(r, 0) * rowO); }
+    for (int r = 0; r < 16; ++r) { n.sv[r] = bload(rs, offs, mfma32_row(r, 0) * rowL); n.rv[r] = bload(rg, offg, mfma32_row(r, 0) * rowO); }
   };
-  const TileWalk tw = xcd_walk(ntiles);
-  const int first = __builtin_amdgcn_readfirstlane((int)tw.first), last = (int)tw.last, stride = (int)tw.stride;
-  float dza[32], sva[16], rva[16], dzb[32], svb[16], rvb[16];
-  if (first < last) issue(first, dza, sva, rva);
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  __syncthreads();
-  float wt[32];  // A[i = c = li][k = (d = s, tap = lh)] = W_dil[d][c][tap]
-#pragma unroll
-  for (int s = 0; s < 32; ++s) wt[s] = wl[s * 65 + li * 2 + lh];
-  auto compute = [&](int tile, const float (&dz)[32], const float (&sv)[16], const float (&rv)[16]) {
-    const int b = tile / tiles_per_seq;
-    const int t = (tile - b * tiles_per_seq) * 32 + li;
-    const __amdgpu_buffer_rsrc_t ro = brsrc(dS_in + (long)b * 32 * Lin, 32 * rowL);
-    const int offs = t < Lin ? t * 4 + 4 * lh * rowL : BUF_OOB;
+  auto compute = [&](int tile, const DxTile& c) __attribute__((always_inline)) {
+    const TilePos p = tile_pos(tile, tiles_per_seq, li, Lin);
+    const __amdgpu_buffer_rsrc_t ro = brsrc(dS_in + (long)p.b * 32 * Lin, 32 * rowL);
+    const int offs = p.ok ? p.t * 4 + 4 * lh * rowL : BUF_OOB;
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-    for (int s = 0; s < 32; ++s) acc = mfma32(wt[s], dz[s], acc);
+    for (int s = 0; s < 32; ++s) acc = mfma32(RESIDENT ? wt[s] : wtl[WIMG_DIL_PITCH * s], c.dz[s], acc);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) bstore((sv[r] > 0.f ? acc[r] : 0.f) + rv[r], ro, offs, mfma32_row(r, 0) * rowL);
+    for (int r = 0; r < 16; ++r) bstore((c.sv[r] > 0.f ? acc[r] : 0.f) + c.rv[r], ro, offs, mfma32_row(r, 0) * rowL);
   };
-  for (int tile = first; tile < last; tile += 2 * stride) {
-    issue(tile + stride, dzb, svb, rvb);
-    compute(tile, dza, sva, rva);
-    if (tile + stride >= last) break;
-    issue(tile + 2 * stride, dza, sva, rva);
-    compute(tile + stride, dzb, svb, rvb);
+  const TileWalkI w = xcd_walk_i(ntiles);
+  DxTile ta, tb;                                             // (RESIDENT only)
+  if (RESIDENT && w.first < w.last) issue(w.first, ta);      // in flight while the weights are staged
+  stage_w_dil(wl, w_dil, threadIdx.x, 256);
+  __syncthreads();
+  if (RESIDENT) {
+#pragma unroll
+    for (int s = 0; s < 32; ++s) wt[s] = wtl[WIMG_DIL_PITCH * s];
+    pingpong_tiles<false>(w, ta, tb, issue, compute);
+  } else {
+    plain_tiles<false, DxTile>(w, issue, compute);
   }
 }
 
-// HIGH-OCCUPANCY form of (B), the default (see wn_block_fwd_occ): buffer addressing, weights read from LDS per MFMA,
-// nothing held across tiles -> < 128 VGPRs, 4 waves per SIMD.  Same arithmetic, same summation order.
+// resident weights, the next tile's requests in flight under this tile's MFMAs (option wn_dx = 1)
+__global__ void __launch_bounds__(256)
+    wn_block_bwd_dx_buf(const float* __restrict__ DZ, const float* __restrict__ s_in, const float* __restrict__ dS_out,
+                        const float* __restrict__ w_dil, float* __restrict__ dS_in, int B, int Lin, int dil) {
+  __shared__ float wl[WIMG_DIL_SIZE];
+  wn_block_bwd_dx_body<true>(wl, DZ, s_in, dS_out, w_dil, dS_in, B, Lin, dil);
+}
+
+// HIGH-OCCUPANCY form, the default (see wn_block_fwd_occ): nothing held across tiles -> < 128 VGPRs, 4 waves per SIMD
 __global__ void __launch_bounds__(256, 4)
     wn_block_bwd_dx_occ(const float* __restrict__ DZ, const float* __restrict__ s_in, const float* __restrict__ dS_out,
                         const float* __restrict__ w_dil, float* __restrict__ dS_in, int B, int Lin, int dil) {
-  const int lane = threadIdx.x & 63;
-  const int li = lane & 31, lh = lane >> 5;
-  const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lin + 31) >> 5;
-  const int ntiles = B * tiles_per_seq;
-  __shared__ float wl[32 * 65];
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  __syncthreads();
-  const float* wtl = wl + li * 2 + lh;   // A[i = c = li][k = (d = s, tap = lh)] = W_dil[d][c][tap] at wtl[65 s]
-  const int rowL = Lin * 4, rowO = Lo * 4;
-  const TileWalk tw = xcd_walk(ntiles);
-  const int first = __builtin_amdgcn_readfirstlane((int)tw.first), last = (int)tw.last, stride = (int)tw.stride;
-  for (int tile = first; tile < last; tile += stride) {
-    const int b = tile / tiles_per_seq;
-    const int t = (tile - b * tiles_per_seq) * 32 + li;   // t' (input time)
-    const bool ok = t < Lin;
-    const int to = t - lh * dil;                          // dz time of this lane half's tap
-    const bool okz = ok && to >= 0 && to < Lo;
-    const bool okr = ok && t >= dil;                      // residual: dS_out[c][t' - dil]
-    const __amdgpu_buffer_rsrc_t rz = brsrc(DZ + (long)b * 32 * Lo, 32 * rowO);
-    const __amdgpu_buffer_rsrc_t rs = brsrc(s_in + (long)b * 32 * Lin, 32 * rowL);
-    const __amdgpu_buffer_rsrc_t rg = brsrc(dS_out + (long)b * 32 * Lo, 32 * rowO);
-    const __amdgpu_buffer_rsrc_t ro = brsrc(dS_in + (long)b * 32 * Lin, 32 * rowL);
-    const int offz = okz ? to * 4 : BUF_OOB;
-    const int offs = ok ? t * 4 + 4 * lh * rowL : BUF_OOB;
-    const int offg = okr ? (t - dil) * 4 + 4 * lh * rowO : BUF_OOB;
-    float dz[32], sv[16], rv[16];
-#pragma unroll
-    for (int s = 0; s < 32; ++s) dz[s] = bload(rz, offz, s * rowO);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { sv[r] = bload(rs, offs, mfma32_row(r, 0) * rowL); rv[r] = bload(rg, offg, mfma32_row(r, 0) * rowO); }
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 32; ++s) acc = mfma32(wtl[65 * s], dz[s], acc);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bstore((sv[r] > 0.f ? acc[r] : 0.f) + rv[r], ro, offs, mfma32_row(r, 0) * rowL);
-  }
+  __shared__ float wl[WIMG_DIL_SIZE];
+  wn_block_bwd_dx_body<false>(wl, DZ, s_in, dS_out, w_dil, dS_in, B, Lin, dil);
 }
 
 // ------------------------------------------------------------------ MFMA bottleneck + ReLU + adaptive average pool (R = 32, Bn % 32 == 0)
@@ -1383,16 +1240,16 @@ __global__ void __launch_bounds__(256)
     wn_block_wgrad_mfma(const float* __restrict__ dS, const float* __restrict__ Z, const float* __restrict__ DZ,
                         const float* __restrict__ s_in, float* __restrict__ slab, int B, int Lin, int dil) {
   __shared__ float tile[4][32 * 33];
-  __shared__ float red[3 * 1024 + 64];
+  __shared__ float red[WG_SLAB];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lo);
   const long ntiles = (long)B * tiles_per_seq;
   const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
   float* T = tile[wave];
-  for (int i = threadIdx.x; i < 3 * 1024 + 64; i += 256) red[i] = 0.f;
+  for (int i = threadIdx.x; i < WG_SLAB; i += 256) red[i] = 0.f;
 
   f32x16 acc0, acc1, acc2;
 #pragma unroll
@@ -1419,9 +1276,9 @@ __global__ void __launch_bounds__(256)
   };
 
   for (long tl = wave0; tl < ntiles; tl += nwaves) {
-    const int b = (int)(tl / tiles_per_seq);
-    const int t = (int)(tl - (long)b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lo;
+    const TilePos p = tile_pos(tl, tiles_per_seq, li, Lo);
+    const int b = p.b, t = p.t;
+    const bool ok = p.ok;
     const long oo = (long)b * 32 * Lo + (ok ? t : 0);
     const long oi = (long)b * 32 * Lin + (ok ? t : 0);
     float v0[16], v1[16], v2[16], v3[16], v4[16];   // all five operand tiles in flight at once
@@ -1473,39 +1330,46 @@ __global__ void __launch_bounds__(256)
 // transposes into the three resident weight-gradient accumulators.  Per layer this replaces 350 MB of HBM traffic
 // (z written by the forward, dS + Z read twice, DZ re-read) by 150 MB; the encoder shares HBM with the trunk's
 // convolutions running on the other stream, so the bytes matter beyond this kernel's own time.
-__global__ void __launch_bounds__(256)
-    wn_block_bwd_dz_wgrad_mfma(const float* __restrict__ dS, const float* __restrict__ w_dil, const float* __restrict__ b_dil,
-                               const float* __restrict__ w_dense, const float* __restrict__ s_in, float* __restrict__ DZ,
-                               float* __restrict__ slab, int B, int Lin, int dil) {
-  __shared__ float tile[4][2][32 * 33];
-  __shared__ float red[3 * 1024 + 64];
-  __shared__ float wl[32 * 65 + 32];
+// ONE body, two schedules (wn_block_bwd_dz_wgrad_mfma and wn_block_bwd_dz_wgrad_occ below):
+//   RESIDENT   both weight fragments in registers (W_dense reaches its transposed fragment through the wave's own transpose
+//              tile), the next tile's 48 loads in flight under this tile's 96 MFMAs: one wave per SIMD;
+//   otherwise  weights read from LDS per MFMA (W_dense from an image of its own, `wtl`), no cross-tile prefetch -> under
+//              256 registers, two waves per SIMD (two workgroups per CU).  (Tried for the beside-the-trunk case: this schedule
+//              WITH the cross-tile prefetch, 243 registers and no AGPR shuffling, one workgroup per CU -- 0.2-0.5 ms/step
+//              slower than the resident-weights form.)
+struct DzwTile { float g[16], x[32]; };      // dS rows 2q + lh, s_in rows of tap lh
+template <bool RESIDENT>
+__device__ __forceinline__ void wn_block_bwd_dz_wgrad_body(float* tiles, float* red, float* wl, float* wtl,
+                                                           const float* __restrict__ dS, const float* __restrict__ w_dil,
+                                                           const float* __restrict__ b_dil, const float* __restrict__ w_dense,
+                                                           const float* __restrict__ s_in, float* __restrict__ DZ,
+                                                           float* __restrict__ slab, int B, int Lin, int dil) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lo);
   const int ntiles = B * tiles_per_seq;
-  float* T = tile[wave][0];
-  float* Th = tile[wave][lh];           // this lane half's tile for the two-tap transpose
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  if (threadIdx.x < 32) wl[2080 + threadIdx.x] = b_dil ? b_dil[threadIdx.x] : 0.f;
-  // W_dense through this wave's transpose tile: A[i = d = li][k = r = 2s+lh] = W_dense[r][d]
-  {
-    float wv[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) wv[u] = w_dense[lane + 64 * u];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) { const int i = lane + 64 * u; T[(i >> 5) * 33 + (i & 31)] = wv[u]; }
-  }
-  for (int i = threadIdx.x; i < 3 * 1024 + 64; i += 256) red[i] = 0.f;
+  float* T = tiles + wave * 2 * 1056;   // this wave's two 32 x 33 transpose tiles
+  float* T1 = T + 1056;
+  float* Th = T + lh * 1056;            // this lane half's tile for the two-tap transpose
+  stage_w_dil(wl, w_dil, threadIdx.x, 256);
+  stage_bias(wl + WIMG_DIL_SIZE, b_dil, threadIdx.x);       // (no dense part in this image: b_dil follows W_dil)
+  // W_dense[r][d], padded rows: A[i = d = li][k = r = 2s+lh] = image[(2s+lh)*33 + li].  RESIDENT: through this wave's
+  // transpose tile into registers
+  if (RESIDENT) stage_w_dense(T, w_dense, lane, 64);
+  else stage_w_dense(wtl, w_dense, threadIdx.x, 256);
+  for (int i = threadIdx.x; i < WG_SLAB; i += 256) red[i] = 0.f;
   __syncthreads();
-  float wt[16];
+  const float* wtp = (RESIDENT ? T : wtl) + lh * WIMG_DENSE_PITCH + li;   // + 66 s
+  const float* wdp = wl + li * WIMG_DIL_PITCH + lh;                        // + 2 s: W_dil[d = li][c = s][tap = lh]  (the forward's fragment)
+  const float* bzl = wl + WIMG_DIL_SIZE + 4 * lh;
+  float wt[16], wd[32];
+  if (RESIDENT) {
 #pragma unroll
-  for (int s = 0; s < 16; ++s) wt[s] = T[(2 * s + lh) * 33 + li];
-  float wd[32];   // W_dil[d = li][c = s][tap = lh]  (the forward's fragment)
+    for (int s = 0; s < 16; ++s) wt[s] = wtp[2 * WIMG_DENSE_PITCH * s];
 #pragma unroll
-  for (int s = 0; s < 32; ++s) wd[s] = wl[li * 65 + s * 2 + lh];
-  const float* bzl = wl + 2080 + 4 * lh;
+    for (int s = 0; s < 32; ++s) wd[s] = wdp[2 * s];
+  }
   __builtin_amdgcn_wave_barrier();
 
   f32x16 acc0, acc1, acc2;
@@ -1514,46 +1378,42 @@ __global__ void __launch_bounds__(256)
   float bs_dz = 0.f, bs_ds = 0.f;
   const int rowL = Lin * 4, rowO = Lo * 4;
 
-  // One wave per SIMD is resident (368 registers), so VALU instructions add to the 96 MFMAs of a tile one for one (~4
-  // cycles each): the flat-addressed version of this kernel carried 1225 of them per tile -- 64-bit address arithmetic
+  // One wave per SIMD is resident (RESIDENT; two otherwise), so VALU instructions add to the 96 MFMAs of a tile one for one
+  // (~4 cycles each): the flat-addressed version of this kernel carried 1225 of them per tile -- 64-bit address arithmetic
   // for 64 memory instructions, a validity select on every loaded value, two-instruction ReLUs.  Buffer addressing
   // (common.h): samples past the end of a sequence carry an out-of-range offset, their loads return 0 and their stores are
   // dropped; a zero dS column makes every product of that column zero, so nothing downstream needs masking.
-  // Software pipeline across tiles: the NEXT tile's 48 loads are issued before this tile's 96 MFMAs and LDS transposes
-  // (nothing else hides their latency), alternating between two register sets instead of copying.
-  auto issue = [&](int tile, float (&gn)[16], float (&xn)[32]) {
-    const int tc = tile < ntiles ? tile : ntiles - 1;
-    const int b = tc / tiles_per_seq;
-    const int t = (tc - b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lo;
-    const __amdgpu_buffer_rsrc_t rg = brsrc(dS + (long)b * 32 * Lo, 32 * rowO);
-    const __amdgpu_buffer_rsrc_t rx = brsrc(s_in + (long)b * 32 * Lin, 32 * rowL);
-    const int offg = ok ? t * 4 + lh * rowO : BUF_OOB;
-    const int offx = ok ? (t + lh * dil) * 4 : BUF_OOB;
+  // RESIDENT, software pipeline across tiles: the NEXT tile's 48 loads are issued before this tile's 96 MFMAs and LDS
+  // transposes (nothing else hides their latency), alternating between two register sets instead of copying.
+  auto issue = [&](int tile, DzwTile& n) __attribute__((always_inline)) {
+    const TilePos p = tile_pos(tile < ntiles ? tile : ntiles - 1, tiles_per_seq, li, Lo);
+    const __amdgpu_buffer_rsrc_t rg = brsrc(dS + (long)p.b * 32 * Lo, 32 * rowO);
+    const __amdgpu_buffer_rsrc_t rx = brsrc(s_in + (long)p.b * 32 * Lin, 32 * rowL);
+    const int offg = p.ok ? p.t * 4 + lh * rowO : BUF_OOB;
+    const int offx = p.ok ? (p.t + lh * dil) * 4 : BUF_OOB;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) gn[q] = bload(rg, offg, 2 * q * rowO);
+    for (int q = 0; q < 16; ++q) n.g[q] = bload(rg, offg, 2 * q * rowO);
 #pragma unroll
-    for (int c = 0; c < 32; ++c) xn[c] = bload(rx, offx, c * rowL);
+    for (int c = 0; c < 32; ++c) n.x[c] = bload(rx, offx, c * rowL);
   };
-  auto compute = [&](int tidx, const float (&g)[16], const float (&xraw)[32]) {
-    const int b = tidx / tiles_per_seq;
-    const int t = (tidx - b * tiles_per_seq) * 32 + li;
-    const int offo = t < Lo ? t * 4 + 4 * lh * rowO : BUF_OOB;
-    const __amdgpu_buffer_rsrc_t rz = brsrc(DZ + (long)b * 32 * Lo, 32 * rowO);
+  auto compute = [&](int tidx, const DzwTile& c) __attribute__((always_inline)) {
+    const TilePos p = tile_pos(tidx, tiles_per_seq, li, Lo);
+    const int offo = p.ok ? p.t * 4 + 4 * lh * rowO : BUF_OOB;
+    const __amdgpu_buffer_rsrc_t rz = brsrc(DZ + (long)p.b * 32 * Lo, 32 * rowO);
     float x[32];
 #pragma unroll
-    for (int c = 0; c < 32; ++c) x[c] = relu1(xraw[c]);      // relu(s tap lh); 0 outside the sequence
+    for (int s = 0; s < 32; ++s) x[s] = relu1(c.x[s]);      // relu(s tap lh); 0 outside the sequence
     // z exactly as the forward builds it
     f32x16 z;
 #pragma unroll
     for (int r = 0; r < 16; ++r) z[r] = bzl[mfma32_row(r, 0)];
 #pragma unroll
-    for (int s = 0; s < 32; ++s) z = mfma32(wd[s], x[s], z);
+    for (int s = 0; s < 32; ++s) z = mfma32(RESIDENT ? wd[s] : wdp[2 * s], x[s], z);
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) acc = mfma32(wt[q], g[q], acc);
+    for (int q = 0; q < 16; ++q) acc = mfma32(RESIDENT ? wt[q] : wtp[2 * WIMG_DENSE_PITCH * q], c.g[q], acc);
     float f0[16], f1[16];
     // ---- dz (D layout: rows mfma32_row(r, lh), column = time li) -> store, transpose
     __builtin_amdgcn_wave_barrier();
@@ -1569,52 +1429,48 @@ __global__ void __launch_bounds__(256)
     __builtin_amdgcn_wave_barrier();
     // ---- both taps of relu(s): lane half h writes its 32 channels into tile h
 #pragma unroll
-    for (int c = 0; c < 32; ++c) Th[c * 33 + li] = x[c];
+    for (int s = 0; s < 32; ++s) Th[s * 33 + li] = x[s];
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int q = 0; q < 16; ++q) f1[q] = tile[wave][0][li * 33 + 2 * q + lh];
+    for (int q = 0; q < 16; ++q) f1[q] = T[li * 33 + 2 * q + lh];
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc0 = mfma32(f0[q], f1[q], acc0);
 #pragma unroll
-    for (int q = 0; q < 16; ++q) f1[q] = tile[wave][1][li * 33 + 2 * q + lh];
+    for (int q = 0; q < 16; ++q) f1[q] = T1[li * 33 + 2 * q + lh];
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc1 = mfma32(f0[q], f1[q], acc1);
     __builtin_amdgcn_wave_barrier();
     // ---- dS (channel 2q+lh on register q) and relu(z) (D layout; multiplied by dS = 0 past the sequence)
 #pragma unroll
-    for (int q = 0; q < 16; ++q) T[(2 * q + lh) * 33 + li] = g[q];
+    for (int q = 0; q < 16; ++q) T[(2 * q + lh) * 33 + li] = c.g[q];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tile[wave][1][mfma32_row(r, lh) * 33 + li] = relu1(z[r]);
+    for (int r = 0; r < 16; ++r) T1[mfma32_row(r, lh) * 33 + li] = relu1(z[r]);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int q = 0; q < 16; ++q) { f0[q] = T[li * 33 + 2 * q + lh]; bs_ds += f0[q]; }
 #pragma unroll
-    for (int q = 0; q < 16; ++q) f1[q] = tile[wave][1][li * 33 + 2 * q + lh];
+    for (int q = 0; q < 16; ++q) f1[q] = T1[li * 33 + 2 * q + lh];
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc2 = mfma32(f0[q], f1[q], acc2);
     __builtin_amdgcn_wave_barrier();
   };
-  const TileWalk tw = xcd_walk(ntiles);
-  const int first = __builtin_amdgcn_readfirstlane((int)tw.first), last = (int)tw.last, stride = (int)tw.stride;
-  float ga[16], xa[32], gb[16], xb[32];
-  if (first < last) issue(first, ga, xa);
-  for (int tl = first; tl < last; tl += 2 * stride) {
-    issue(tl + stride, gb, xb);
-    // pin the 48 loads HERE: left alone hipcc sinks each one down to its consumer (load, wait, mfma, load, wait, ...),
-    // 32 serial memory round trips per tile -- the kernel ran 2.5x slower than the two it replaces
-    __builtin_amdgcn_sched_barrier(0);
-    compute(tl, ga, xa);
-    if (tl + stride >= last) break;
-    issue(tl + 2 * stride, ga, xa);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(tl + stride, gb, xb);
+  const TileWalkI w = xcd_walk_i(ntiles);
+  DzwTile ta, tb;
+  // the loads are PINNED in front of the compute (both schedules): left alone hipcc sinks each one down to its consumer
+  // (load, wait, mfma, load, wait, ...), 32 serial memory round trips per tile -- the kernel ran 2.5x slower than the two
+  // it replaces
+  if (RESIDENT) {
+    if (w.first < w.last) issue(w.first, ta);
+    pingpong_tiles<true>(w, ta, tb, issue, compute);
+  } else {
+    plain_tiles<true, DzwTile>(w, issue, compute);    // nothing held across tiles: the other wave of the SIMD hides the loads
   }
 
   // the four waves' sums meet in LDS in WAVE ORDER (plain adds between barriers: float atomics here added them in
   // arrival order, the one place left where this kernel's result could differ in the last bit from run to run)
-  for (int w = 0; w < 4; ++w) {
+  for (int wv = 0; wv < 4; ++wv) {
     __syncthreads();
-    if (wave == w) {
+    if (wave == wv) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = mfma32_row(r, lh);
@@ -1633,150 +1489,27 @@ __global__ void __launch_bounds__(256)
   for (int i = threadIdx.x; i < WG_SLAB; i += 256) out[i] = red[i];
 }
 
-// HIGH-OCCUPANCY form of the fused pass (option wn_bwd_t = 2): weights read from LDS per MFMA, no cross-tile prefetch -> under
-// 256 registers, two waves per SIMD (two workgroups per CU).  (Tried for the beside-the-trunk case: this body WITH the cross-tile
-// prefetch, 243 registers and no AGPR shuffling, one workgroup per CU -- 0.2-0.5 ms/step slower than the resident-weights form.)
+// resident weights + cross-tile prefetch (option wn_bwd_t = 3; the default beside another stream's kernels)
+__global__ void __launch_bounds__(256)
+    wn_block_bwd_dz_wgrad_mfma(const float* __restrict__ dS, const float* __restrict__ w_dil, const float* __restrict__ b_dil,
+                               const float* __restrict__ w_dense, const float* __restrict__ s_in, float* __restrict__ DZ,
+                               float* __restrict__ slab, int B, int Lin, int dil) {
+  __shared__ float tile[4 * 2 * 32 * 33];
+  __shared__ float red[WG_SLAB];
+  __shared__ float wl[WIMG_DIL_SIZE + 32];
+  wn_block_bwd_dz_wgrad_body<true>(tile, red, wl, nullptr, dS, w_dil, b_dil, w_dense, s_in, DZ, slab, B, Lin, dil);
+}
+
+// HIGH-OCCUPANCY form of the fused pass (option wn_bwd_t = 2; the default alone on the device)
 __global__ void __launch_bounds__(256, 2)
     wn_block_bwd_dz_wgrad_occ(const float* __restrict__ dS, const float* __restrict__ w_dil, const float* __restrict__ b_dil,
                                const float* __restrict__ w_dense, const float* __restrict__ s_in, float* __restrict__ DZ,
                                float* __restrict__ slab, int B, int Lin, int dil) {
-  __shared__ float tile[4][2][32 * 33];
-  __shared__ float red[3 * 1024 + 64];
-  __shared__ float wl[32 * 65 + 32];
-  __shared__ float wtl[32 * 33];        // W_dense[r][d], padded rows: A[i = d = li][k = r = 2s+lh] = wtl[(2s+lh)*33 + li]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 31) >> 5;
-  const int ntiles = B * tiles_per_seq;
-  float* T = tile[wave][0];
-  float* Th = tile[wave][lh];           // this lane half's tile for the two-tap transpose
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  if (threadIdx.x < 32) wl[2080 + threadIdx.x] = b_dil ? b_dil[threadIdx.x] : 0.f;
-  for (int i = threadIdx.x; i < 1024; i += 256) wtl[(i >> 5) * 33 + (i & 31)] = w_dense[i];
-  for (int i = threadIdx.x; i < 3 * 1024 + 64; i += 256) red[i] = 0.f;
-  __syncthreads();
-  const float* wtp = wtl + lh * 33 + li;       // + 66 s
-  const float* wdp = wl + li * 65 + lh;        // + 2 s: W_dil[d = li][c = s][tap = lh]  (the forward's fragment)
-  const float* bzl = wl + 2080 + 4 * lh;
-  __builtin_amdgcn_wave_barrier();
-
-  f32x16 acc0, acc1, acc2;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; acc2[r] = 0.f; }
-  float bs_dz = 0.f, bs_ds = 0.f;
-  const int rowL = Lin * 4, rowO = Lo * 4;
-
-  // One wave per SIMD is resident (368 registers), so VALU instructions add to the 96 MFMAs of a tile one for one (~4
-  // cycles each): the flat-addressed version of this kernel carried 1225 of them per tile -- 64-bit address arithmetic
-  // for 64 memory instructions, a validity select on every loaded value, two-instruction ReLUs.  Buffer addressing
-  // (common.h): samples past the end of a sequence carry an out-of-range offset, their loads return 0 and their stores are
-  // dropped; a zero dS column makes every product of that column zero, so nothing downstream needs masking.
-  // Software pipeline across tiles: the NEXT tile's 48 loads are issued before this tile's 96 MFMAs and LDS transposes
-  // (nothing else hides their latency), alternating between two register sets instead of copying.
-  auto issue = [&](int tile, float (&gn)[16], float (&xn)[32]) {
-    const int tc = tile < ntiles ? tile : ntiles - 1;
-    const int b = tc / tiles_per_seq;
-    const int t = (tc - b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lo;
-    const __amdgpu_buffer_rsrc_t rg = brsrc(dS + (long)b * 32 * Lo, 32 * rowO);
-    const __amdgpu_buffer_rsrc_t rx = brsrc(s_in + (long)b * 32 * Lin, 32 * rowL);
-    const int offg = ok ? t * 4 + lh * rowO : BUF_OOB;
-    const int offx = ok ? (t + lh * dil) * 4 : BUF_OOB;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) gn[q] = bload(rg, offg, 2 * q * rowO);
-#pragma unroll
-    for (int c = 0; c < 32; ++c) xn[c] = bload(rx, offx, c * rowL);
-  };
-  auto compute = [&](int tidx, const float (&g)[16], const float (&xraw)[32]) {
-    const int b = tidx / tiles_per_seq;
-    const int t = (tidx - b * tiles_per_seq) * 32 + li;
-    const int offo = t < Lo ? t * 4 + 4 * lh * rowO : BUF_OOB;
-    const __amdgpu_buffer_rsrc_t rz = brsrc(DZ + (long)b * 32 * Lo, 32 * rowO);
-    float x[32];
-#pragma unroll
-    for (int c = 0; c < 32; ++c) x[c] = relu1(xraw[c]);      // relu(s tap lh); 0 outside the sequence
-    // z exactly as the forward builds it
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = bzl[mfma32_row(r, 0)];
-#pragma unroll
-    for (int s = 0; s < 32; ++s) z = mfma32(wdp[2 * s], x[s], z);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc = mfma32(wtp[66 * q], g[q], acc);
-    float f0[16], f1[16];
-    // ---- dz (D layout: rows mfma32_row(r, lh), column = time li) -> store, transpose
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float dz = z[r] > 0.f ? acc[r] : 0.f;            // (a column past the sequence has dS = 0, so acc = 0)
-      bstore(dz, rz, offo, mfma32_row(r, 0) * rowO);
-      T[mfma32_row(r, lh) * 33 + li] = dz;
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { f0[q] = T[li * 33 + 2 * q + lh]; bs_dz += f0[q]; }   // f0 = dz[d = li][t = 2q+lh]
-    __builtin_amdgcn_wave_barrier();
-    // ---- both taps of relu(s): lane half h writes its 32 channels into tile h
-#pragma unroll
-    for (int c = 0; c < 32; ++c) Th[c * 33 + li] = x[c];
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) f1[q] = tile[wave][0][li * 33 + 2 * q + lh];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc0 = mfma32(f0[q], f1[q], acc0);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) f1[q] = tile[wave][1][li * 33 + 2 * q + lh];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc1 = mfma32(f0[q], f1[q], acc1);
-    __builtin_amdgcn_wave_barrier();
-    // ---- dS (channel 2q+lh on register q) and relu(z) (D layout; multiplied by dS = 0 past the sequence)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) T[(2 * q + lh) * 33 + li] = g[q];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tile[wave][1][mfma32_row(r, lh) * 33 + li] = relu1(z[r]);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { f0[q] = T[li * 33 + 2 * q + lh]; bs_ds += f0[q]; }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) f1[q] = tile[wave][1][li * 33 + 2 * q + lh];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc2 = mfma32(f0[q], f1[q], acc2);
-    __builtin_amdgcn_wave_barrier();
-  };
-  const TileWalk tw = xcd_walk(ntiles);
-  const int first = __builtin_amdgcn_readfirstlane((int)tw.first), last = (int)tw.last, stride = (int)tw.stride;
-  for (int tl = first; tl < last; tl += stride) {       // nothing held across tiles: the other wave of the SIMD hides the loads
-    float ga[16], xa[32];
-    issue(tl, ga, xa);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(tl, ga, xa);
-  }
-
-  // the four waves' sums meet in LDS in WAVE ORDER (plain adds between barriers: float atomics here added them in
-  // arrival order, the one place left where this kernel's result could differ in the last bit from run to run)
-  for (int w = 0; w < 4; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = mfma32_row(r, lh);
-        red[row * 32 + li] += acc0[r];
-        red[1024 + row * 32 + li] += acc1[r];
-        red[2048 + row * 32 + li] += acc2[r];
-      }
-      // the bias sums: both lane halves hold partial sums of the same 32 channels -> half 0 first, then half 1
-      if (lh == 0) { red[3072 + li] += bs_dz; red[3104 + li] += bs_ds; }
-      __builtin_amdgcn_wave_barrier();
-      if (lh == 1) { red[3072 + li] += bs_dz; red[3104 + li] += bs_ds; }
-    }
-  }
-  __syncthreads();
-  float* out = slab + (long)blockIdx.x * WG_SLAB;
-  for (int i = threadIdx.x; i < WG_SLAB; i += 256) out[i] = red[i];
+  __shared__ float tile[4 * 2 * 32 * 33];
+  __shared__ float red[WG_SLAB];
+  __shared__ float wl[WIMG_DIL_SIZE + 32];
+  __shared__ float wtl[WIMG_DENSE_SIZE];
+  wn_block_bwd_dz_wgrad_body<false>(tile, red, wl, wtl, dS, w_dil, b_dil, w_dense, s_in, DZ, slab, B, Lin, dil);
 }
 
 // ------------------------------------------------------------------ the same pass with TRANSPOSED products: no LDS transposes
@@ -1800,28 +1533,28 @@ __global__ void __launch_bounds__(256, 2)
     wn_block_bwd_dzw_t(const float* __restrict__ dS, const float* __restrict__ w_dil, const float* __restrict__ b_dil,
                        const float* __restrict__ w_dense, const float* __restrict__ s_in, float* __restrict__ DZ,
                        float* __restrict__ slab, int B, int Lin, int dil) {
-  __shared__ float red[3 * 1024 + 64];
-  __shared__ float wl[32 * 65 + 32 * 33 + 32];
+  __shared__ float red[WG_SLAB];
+  __shared__ float wl[WIMG_BDENSE];          // the image without b_dense
   const int lane = threadIdx.x & 63;
   const int li = lane & 31, lh = lane >> 5;
   const int Lo = Lin - dil;
-  const int tiles_per_seq = (Lo + 31) >> 5;
+  const int tiles_per_seq = tiles_per_sequence<32>(Lo);
   const long ntiles = (long)B * tiles_per_seq;
   const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-  for (int i = threadIdx.x; i < 2048; i += 256) wl[(i >> 6) * 65 + (i & 63)] = w_dil[i];
-  for (int i = threadIdx.x; i < 1024; i += 256) wl[2080 + (i >> 5) * 33 + (i & 31)] = w_dense[i];
-  if (threadIdx.x < 32) wl[3136 + threadIdx.x] = b_dil ? b_dil[threadIdx.x] : 0.f;
-  for (int i = threadIdx.x; i < 3 * 1024 + 64; i += 256) red[i] = 0.f;
+  stage_w_dil(wl + WIMG_DIL, w_dil, threadIdx.x, 256);
+  stage_w_dense(wl + WIMG_DENSE, w_dense, threadIdx.x, 256);
+  stage_bias(wl + WIMG_BDIL, b_dil, threadIdx.x);
+  for (int i = threadIdx.x; i < WG_SLAB; i += 256) red[i] = 0.f;
   __syncthreads();
   // The weight fragments stay in LDS and are read per k-step (one conflict-free ds_read_b32 each, 48 per tile against 96
   // MFMAs of 64 cycles): 48 registers less than keeping them resident -- that is what brings the kernel under the 256
   // registers of two waves per SIMD.
   //   wdp[2s]  : B[k = (c = s, tap = lh)][j = d = li] = W_dil[d][c][tap]   (the forward's A fragment)
   //   wtp[66s] : B[k = r = 2s+lh][j = d = li]         = W_dense[r][d]
-  const float* wdp = wl + li * 65 + lh;
-  const float* wtp = wl + 2080 + lh * 33 + li;
-  const float bz = wl[3136 + li];
+  const float* wdp = wl + WIMG_DIL + li * WIMG_DIL_PITCH + lh;
+  const float* wtp = wl + WIMG_DENSE + lh * WIMG_DENSE_PITCH + li;
+  const float bz = wl[WIMG_BDIL + li];
 
   f32x16 acc0, acc1, acc2;
 #pragma unroll
@@ -1829,10 +1562,9 @@ __global__ void __launch_bounds__(256, 2)
   float bs_dz = 0.f, bs_ds = 0.f;
 
   for (long tl = wave0; tl < ntiles; tl += nwaves) {
-    const int b = (int)(tl / tiles_per_seq);
-    const int t0 = (int)(tl - (long)b * tiles_per_seq) * 32;
-    const int t = t0 + li;
-    const bool ok = t < Lo;
+    const TilePos p = tile_pos(tl, tiles_per_seq, li, Lo);
+    const int b = p.b, t0 = p.t0, t = p.t;
+    const bool ok = p.ok;
     const int tcl = ok ? t : 0;
     const bool full = t0 + 32 <= Lo;                        // wave-uniform: every sample of the tile exists
     // ---- time on the lane (coalesced; unconditional loads from a clamped address, masked below)
@@ -2013,60 +1745,115 @@ static int make_plan(const avvad_wavenet_desc* d, Plan* p) {
 }
 
 static inline bool mfma_shape(const avvad_wavenet_desc* d) { return d->R == 32 && d->D == 32 && d->fw == 2; }
-// forward of one residual block, MFMA shape: wide kernel when the plane has >= 128 output samples, else the dword forms
-static void launch_block_fwd(const float* s_in, const float* wd, const float* bd, const float* we, const float* be, float* s_out,
-                             int B, int Lin, int dil, hipStream_t s);
 // the buffer-addressed block kernels index a sequence's [32][L] slab with 31-bit byte offsets and count tiles in an int
 static inline bool buf_ok(int B, int Lin) {
   return avvad_tune().wn_flat != 1 && (long)Lin * 32 * 4 + 4096 < (1L << 31) && (long)B * cdiv(Lin, 32) < (1L << 31);
 }
-// option "wn_flat": 0 by plane length (wide dwordx4 kernel from 8192 samples, else the high-occupancy dword kernel),
-// 1 flat dword kernel, 2 dword buffer kernel with resident weights and cross-tile prefetch, 3 wide kernel, 4 high-occupancy kernel
+
+// ------------------------------------------------------------------ kernel-form choice: one per product and call
+// Which form of a product runs, and on how many workgroups, is decided HERE and nowhere else: pure functions of the
+// shape, the descriptor's shared_device hint, the gradients wanted and the options table (the only readers of avvad_tune()
+// in this file, with buf_ok).  The launchers switch on the result.  Options (common.h / include/avvad.h): wn_flat, wn_dx,
+// wn_bwd_t, wn_grid, wn_no_fused_wgrad, wn_no_fused_tail, wn_no_tail_pair.
+enum class FwdForm { FLAT, BUF, OCC, WIDE, DMA };
+enum class DxForm { FLAT, BUF, OCC };
+enum class BwdForm { RESIDENT, OCC, TRANSPOSED, UNFUSED };
+enum class TailBwdForm { PAIR, FUSED, MFMA, GENERIC };
+struct FwdChoice { FwdForm form; int grid; };
+struct DxChoice { DxForm form; int grid; };
+struct BwdChoice { BwdForm form; int grid; int grid_z, grid_dz; };   // grid: weight-gradient workgroups = slabs; UNFUSED also runs z and dz
+struct TailBwdChoice { TailBwdForm form; int grid; };
+
+// Workgroups of a persistent grid: `per_wg` tiles' worth of waves per workgroup, at most `cap` (and at most wn_grid when
+// that tuning option is set), then whole XCD groups of 8 for the XCD-aware walk.  Rounding UP leaves surplus waves that
+// find no tile; the fused backward rounds DOWN because its workgroup count is its slab count (the summation order).
+enum class XcdRound { NONE, UP, UP_FROM_8, DOWN_FROM_8 };
+static int wn_grid_size(long tiles, int per_wg, long cap, int wn_grid, XcdRound r) {
+  long g = (tiles + per_wg - 1) / per_wg;
+  if (g > cap) g = cap;
+  if (wn_grid > 0 && g > wn_grid) g = wn_grid;
+  if (r == XcdRound::UP || (r == XcdRound::UP_FROM_8 && g >= 8)) g = (g + 7) / 8 * 8;
+  if (r == XcdRound::DOWN_FROM_8 && g >= 8) g = g / 8 * 8;
+  return (int)(g < 1 ? 1 : g);
+}
+
 constexpr int WIDE_FROM = 8192;    // plane length from which the dwordx4 kernel runs
+// Forward of one block.  Wide kernel for long planes (C2's one-second chunks: 290 vs 363 us per layer); at the bench shape
+// (64 planes of ~6000 samples, 3008 super-tiles) the dword kernel's finer tiles balance better and the two time the same
+// (37-38 us).  The choice depends on the plane LENGTH only: the two forms round the residual add differently (last bit),
+// and a sequence's result must not depend on how many others share its batch.
+static FwdChoice fwd_form(int B, int Lin, int dil) {
+  const AvvadTune& t = avvad_tune();
+  const int Lo = Lin - dil;
+  const bool buf = buf_ok(B, Lin);
+  if (buf && (t.wn_flat == 0 || t.wn_flat == 3) && Lo >= 128 && (Lo >= WIDE_FROM || t.wn_flat == 3))     // wn_grid REPLACES this cap
+    return {FwdForm::WIDE, wn_grid_size((long)B * cdiv(Lo, 128), 4, t.wn_grid > 0 ? t.wn_grid : 1024, 0, XcdRound::UP)};
+  const long ntiles = (long)B * cdiv(Lo, 32);
+  if (buf && t.wn_flat == 5 && Lo >= 32)            // 8 waves per workgroup, two workgroups per CU
+    return {FwdForm::DMA, wn_grid_size(ntiles, 8, 512, t.wn_grid, XcdRound::UP_FROM_8)};
+  if (buf && (t.wn_flat == 0 || t.wn_flat == 4))    // 4 waves per SIMD resident: 1024 workgroups
+    return {FwdForm::OCC, wn_grid_size(ntiles, 4, 1024, t.wn_grid, XcdRound::UP_FROM_8)};
+  // 2 waves per SIMD resident; each wave walks >= 5 tiles at the bench shape
+  return {buf ? FwdForm::BUF : FwdForm::FLAT, wn_grid_size(ntiles, 4, 512, t.wn_grid, XcdRound::NONE)};
+}
+
+// Input gradient of one block: the high-occupancy kernel everywhere.  (Round 2 measured it 0.16 ms/step SLOWER beside the
+// trunk's backward on another stream, and the shared_device hint picked the resident-weights form there; with round 3's
+// trunk kernels -- layer 1 off the persistent engine, fewer and longer class launches -- the same A/B reads 0.06 ms FASTER:
+// bench.py --ab wn_dx=1.)
+static DxChoice dx_form(int B, int Lin) {
+  const AvvadTune& t = avvad_tune();
+  const long ntiles = (long)B * cdiv(Lin, 32);
+  if (buf_ok(B, Lin) && (t.wn_dx == 0 || t.wn_dx == 2))      // 4 waves per SIMD resident
+    return {DxForm::OCC, wn_grid_size(ntiles, 4, 1024, 0, XcdRound::UP_FROM_8)};
+  return {buf_ok(B, Lin) && t.wn_dx != 3 ? DxForm::BUF : DxForm::FLAT, wn_grid_size(ntiles, 4, 512, 0, XcdRound::NONE)};
+}
+
+// dz + the four parameter gradients of one block (Lo output samples per sequence).  Alone on the device the
+// two-waves-per-SIMD form wins (encoder fwd+bwd 3.09 -> 2.90 ms); beside the trunk's backward on the other stream it costs
+// the STEP 0.25 ms (same-process A/B), hence the descriptor's shared_device hint.  >= 4 tiles per wave in every form.
+static BwdChoice bwd_form(int B, int Lo, bool shared_device, bool any_grad) {
+  const AvvadTune& t = avvad_tune();
+  const long ntiles = (long)B * cdiv(Lo, 32);
+  if (!any_grad || t.wn_no_fused_wgrad)     // frozen weights / tuning switch: z, dz and the weight gradients as separate kernels
+    return {BwdForm::UNFUSED, wn_grid_size(ntiles, 16, WG_MAXBLK, 0, XcdRound::NONE), wn_grid_size(ntiles, 4, 512, 0, XcdRound::NONE),
+            wn_grid_size(ntiles, 4, 768, 0, XcdRound::NONE)};
+  switch (t.wn_bwd_t == 0 ? (shared_device ? 3 : 2) : t.wn_bwd_t) {
+    case 3:
+      // one workgroup per CU is resident: ONE round of 256, not two of 512 -- every workgroup pays a weight staging
+      // prologue and a 12.5 KB slab epilogue (step 22.57 -> 22.06 ms; 128..256 workgroups time the same)
+      return {BwdForm::RESIDENT, wn_grid_size(ntiles, 16, 256, 0, XcdRound::NONE), 0, 0};
+    case 2:
+      return {BwdForm::OCC, wn_grid_size(ntiles, 16, WG_MAXBLK, 0, XcdRound::DOWN_FROM_8), 0, 0};
+    default:    // under 256 registers, two workgroups per CU (one wave per SIMD each)
+      return {BwdForm::TRANSPOSED, wn_grid_size(ntiles, 16, WG_MAXBLK, 0, XcdRound::NONE), 0, 0};
+  }
+}
+
+// backward of the tail (bottleneck + ReLU + pool) over Lv samples per sequence
+static TailBwdChoice tail_bwd_form(int B, int Lv, int R, int Bn, bool any_grad) {
+  const AvvadTune& t = avvad_tune();
+  const long ntiles = (long)B * cdiv(Lv, 32);
+  if (!(R == 32 && Bn % 32 == 0 && Bn <= 1024)) return {TailBwdForm::GENERIC, 0};
+  if (Bn == 256 && any_grad && !t.wn_no_fused_tail)        // 1 workgroup / CU is resident: one round
+    return {t.wn_no_tail_pair ? TailBwdForm::FUSED : TailBwdForm::PAIR, wn_grid_size(ntiles, 4, 256, 0, XcdRound::NONE)};
+  return {TailBwdForm::MFMA, wn_grid_size(ntiles, 4, 2048, 0, XcdRound::NONE)};
+}
+
+// forward of one residual block, MFMA shape
 static void launch_block_fwd(const float* s_in, const float* wd, const float* bd, const float* we, const float* be, float* s_out,
                              int B, int Lin, int dil, hipStream_t s) {
-  const int Lo = Lin - dil;
-  // wide kernel for long planes (C2's one-second chunks: 290 vs 363 us per layer); at the bench shape (64 planes of ~6000
-  // samples, 3008 super-tiles) the dword kernel's finer tiles balance better and the two time the same (37-38 us).  The
-  // choice depends on the plane LENGTH only: the two forms round the residual add differently (last bit), and a sequence's
-  // result must not depend on how many others share its batch.
-  if (buf_ok(B, Lin) && (avvad_tune().wn_flat == 0 || avvad_tune().wn_flat == 3) && Lo >= 128 &&
-      (Lo >= WIDE_FROM || avvad_tune().wn_flat == 3)) {
-    const long ntiles = (long)B * cdiv(Lo, 128);
-    long blocks = (ntiles + 3) / 4;
-    const long cap = avvad_tune().wn_grid > 0 ? avvad_tune().wn_grid : 1024;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;                  // whole XCD groups (surplus waves find no tile)
-    hipLaunchKernelGGL(wn_block_fwd_w4, dim3((int)blocks), dim3(256), 0, s, s_in, wd, bd, we, be, s_out, B, Lin, dil);
-    return;
+  const FwdChoice c = fwd_form(B, Lin, dil);
+  const dim3 grid(c.grid);
+  switch (c.form) {
+    case FwdForm::WIDE: hipLaunchKernelGGL(wn_block_fwd_w4, grid, dim3(256), 0, s, s_in, wd, bd, we, be, s_out, B, Lin, dil); break;
+    case FwdForm::DMA: hipLaunchKernelGGL(wn_block_fwd_dma, grid, dim3(512), 0, s, s_in, wd, bd, we, be, s_out, B, Lin, dil); break;
+    case FwdForm::OCC: hipLaunchKernelGGL(wn_block_fwd_occ, grid, dim3(256), 0, s, s_in, wd, bd, we, be, s_out, B, Lin, dil); break;
+    case FwdForm::BUF: hipLaunchKernelGGL(wn_block_fwd_buf, grid, dim3(256), 0, s, s_in, wd, bd, we, be, s_out, B, Lin, dil); break;
+    case FwdForm::FLAT:
+      hipLaunchKernelGGL(wn_block_fwd_mfma<0>, grid, dim3(256), 0, s, s_in, wd, bd, we, be, s_out, (float*)nullptr, B, Lin, dil);
+      break;
   }
-  const long ntiles = (long)B * cdiv(Lo, 32);
-  long blocks = (ntiles + 3) / 4;
-  if (blocks > 512) blocks = 512;    // 2 waves per SIMD resident; each wave walks >= 5 tiles at the bench shape
-  if (avvad_tune().wn_grid > 0 && blocks > avvad_tune().wn_grid) blocks = avvad_tune().wn_grid;
-  if (buf_ok(B, Lin) && avvad_tune().wn_flat == 5 && Lo >= 32) {       // LDS-DMA form
-    long wb = (ntiles + 7) / 8;                       // 8 waves per workgroup, two workgroups per CU
-    if (wb > 512) wb = 512;
-    if (avvad_tune().wn_grid > 0 && wb > avvad_tune().wn_grid) wb = avvad_tune().wn_grid;
-    if (wb >= 8) wb = wb / 8 * 8 + ((wb & 7) ? 8 : 0);
-    hipLaunchKernelGGL(wn_block_fwd_dma, dim3((int)wb), dim3(512), 0, s, s_in, wd, bd, we, be, s_out, B, Lin, dil);
-    return;
-  }
-  if (buf_ok(B, Lin) && (avvad_tune().wn_flat == 0 || avvad_tune().wn_flat == 4)) {
-    long ob = (ntiles + 3) / 4;                       // 4 waves per SIMD resident: 1024 workgroups
-    if (ob > 1024) ob = 1024;
-    if (avvad_tune().wn_grid > 0 && ob > avvad_tune().wn_grid) ob = avvad_tune().wn_grid;
-    if (ob >= 8) ob = ob / 8 * 8 + ((ob & 7) ? 8 : 0);
-    hipLaunchKernelGGL(wn_block_fwd_occ<0>, dim3((int)ob), dim3(256), 0, s, s_in, wd, bd, we, be, s_out, (float*)nullptr, B, Lin,
-                       dil);
-    return;
-  }
-  if (buf_ok(B, Lin))
-    hipLaunchKernelGGL(wn_block_fwd_buf<0>, dim3((int)blocks), dim3(256), 0, s, s_in, wd, bd, we, be, s_out, (float*)nullptr, B, Lin,
-                       dil);
-  else
-    hipLaunchKernelGGL(wn_block_fwd_mfma<0>, dim3((int)blocks), dim3(256), 0, s, s_in, wd, bd, we, be, s_out, (float*)nullptr, B, Lin,
-                       dil);
 }
 
 // dw[co][ci][k] += sum_{b,t} dy[b][co][t] * f(x[b][ci][t + k*dil])  for every tap, on the engine
@@ -2176,40 +1963,42 @@ extern "C" int avvad_wavenet_bwd(const float* wave, const avvad_wavenet_params* 
   float* GB = ws + p.gb;  // d s_i
   // ---- tail: dz_t = relu'(z) * pooled-grad ; d s_N = Wb^T dz_t
   float* DZT = ws + p.dzt;
-  const bool tail_mfma = (R == 32 && Bn % 32 == 0 && Bn <= 1024);
-  const bool tail_fused = tail_mfma && Bn == 256 && (g->bott_w || (d->use_bias && g->bott_b)) && !avvad_tune().wn_no_fused_tail;
-  if (tail_fused) {
-    // d s_N and the bottleneck's weight + bias gradients in one pass; dz_t is never materialised
-    long blocks = ((long)B * cdiv(Lv, 32) + 3) / 4;
-    if (blocks > 256) blocks = 256;        // 1 workgroup / CU is resident: one round
-    if (!avvad_tune().wn_no_tail_pair) {
-      // two waves per time tile, 8 waves per workgroup (tail_bwd_wgrad_pair)
+  const float* bbp = d->use_bias ? prm->bott_b : (const float*)nullptr;
+  const TailBwdChoice tc = tail_bwd_form(B, Lv, R, Bn, g->bott_w || (d->use_bias && g->bott_b));
+  const bool tail_fused = tc.form == TailBwdForm::PAIR || tc.form == TailBwdForm::FUSED;
+  switch (tc.form) {
+    case TailBwdForm::PAIR: {
+      // d s_N and the bottleneck's weight + bias gradients in one pass, two waves per time tile; dz_t is never materialised
       const size_t lds = ((size_t)Bn * 33 + (size_t)Bn * 33 + 16 * 1056 + 4 * 1056) * sizeof(float);
       if ((rc = allow_large_lds<tail_bwd_wgrad_pair<8>>(lds, lds))) return rc;
-      hipLaunchKernelGGL(tail_bwd_wgrad_pair<8>, dim3((int)blocks), dim3(512), lds, s, ws + p.s[p.n], prm->bott_w,
-                         d->use_bias ? prm->bott_b : (const float*)nullptr, dout, GA, ws + p.slab, B, Lv, d->P);
-    } else {
-    const size_t lds = ((size_t)Bn * 33 + (size_t)Bn * 33 + 8 * 1056) * sizeof(float);
-    if ((rc = allow_large_lds<tail_bwd_wgrad_mfma<8>>(lds, lds))) return rc;
-    hipLaunchKernelGGL(tail_bwd_wgrad_mfma<8>, dim3((int)blocks), dim3(256), lds, s, ws + p.s[p.n], prm->bott_w,
-                       d->use_bias ? prm->bott_b : (const float*)nullptr, dout, GA, ws + p.slab, B, Lv, d->P);
+      hipLaunchKernelGGL(tail_bwd_wgrad_pair<8>, dim3(tc.grid), dim3(512), lds, s, ws + p.s[p.n], prm->bott_w, bbp, dout, GA,
+                         ws + p.slab, B, Lv, d->P);
+      break;
     }
-    hipLaunchKernelGGL(tail_wgrad_reduce, dim3(cdiv(Bn * 33, 32)), dim3(256), 0, s, ws + p.slab, (int)blocks, Bn, g->bott_w,
-                       d->use_bias ? g->bott_b : (float*)nullptr);
-  } else if (tail_mfma) {
-    long blocks = ((long)B * cdiv(Lv, 32) + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(tail_bwd_mfma, dim3((int)blocks), dim3(256), (size_t)Bn * 33 * sizeof(float), s, ws + p.s[p.n], prm->bott_w,
-                       d->use_bias ? prm->bott_b : (const float*)nullptr, dout, DZT, GA, B, Bn, Lv, d->P);
-  } else {
-    hipLaunchKernelGGL(tail_bwd_dz_generic, dim3(grid1((long)B * Bn * Lv)), dim3(256), 0, s, ws + p.s[p.n], prm->bott_w,
-                       d->use_bias ? prm->bott_b : (const float*)nullptr, dout, DZT, B, R, Bn, Lv, d->P);
+    case TailBwdForm::FUSED: {
+      const size_t lds = ((size_t)Bn * 33 + (size_t)Bn * 33 + 8 * 1056) * sizeof(float);
+      if ((rc = allow_large_lds<tail_bwd_wgrad_mfma<8>>(lds, lds))) return rc;
+      hipLaunchKernelGGL(tail_bwd_wgrad_mfma<8>, dim3(tc.grid), dim3(256), lds, s, ws + p.s[p.n], prm->bott_w, bbp, dout, GA,
+                         ws + p.slab, B, Lv, d->P);
+      break;
+    }
+    case TailBwdForm::MFMA:
+      hipLaunchKernelGGL(tail_bwd_mfma, dim3(tc.grid), dim3(256), (size_t)Bn * 33 * sizeof(float), s, ws + p.s[p.n], prm->bott_w,
+                         bbp, dout, DZT, GA, B, Bn, Lv, d->P);
+      break;
+    case TailBwdForm::GENERIC:
+      hipLaunchKernelGGL(tail_bwd_dz_generic, dim3(grid1((long)B * Bn * Lv)), dim3(256), 0, s, ws + p.s[p.n], prm->bott_w, bbp,
+                         dout, DZT, B, R, Bn, Lv, d->P);
+      break;
   }
-  if (!tail_fused) {
+  if (tail_fused) {
+    hipLaunchKernelGGL(tail_wgrad_reduce, dim3(cdiv(Bn * 33, 32)), dim3(256), 0, s, ws + p.slab, tc.grid, Bn, g->bott_w,
+                       d->use_bias ? g->bott_b : (float*)nullptr);
+  } else {
     if (g->bott_w && (rc = wgrad_conv1d(DZT, ws + p.s[p.n], g->bott_w, B, Bn, R, Lv, Lv, 1, 1, 0, s, ws + p.gslab))) return rc;
     if (d->use_bias) bias_grad(DZT, g->bott_b, B, Bn, Lv, s);
   }
-  if (!tail_mfma)
+  if (tc.form == TailBwdForm::GENERIC)
     hipLaunchKernelGGL(conv1d_bwd_data_generic, dim3(grid1((long)B * R * Lv)), dim3(256), 0, s, DZT, prm->bott_w,
                        (const float*)nullptr, (const float*)nullptr, GA, B, R, Bn, Lv, Lv, 1, 1, 0, 0);
   // ---- residual blocks, last to first
@@ -2219,8 +2008,8 @@ extern "C" int avvad_wavenet_bwd(const float* wave, const avvad_wavenet_params* 
     wtab.slab[l] = nullptr; wtab.nslab[l] = 0;
     wtab.dW_dil[l] = wtab.db_dil[l] = wtab.dW_dense[l] = wtab.db_dense[l] = nullptr;
   }
-  auto note_slabs = [&](int i, float* slab_i, long wb) {
-    wtab.slab[i] = slab_i; wtab.nslab[i] = (int)wb;
+  auto note_slabs = [&](int i, float* slab_i, int wb) {
+    wtab.slab[i] = slab_i; wtab.nslab[i] = wb;
     wtab.dW_dil[i] = g->dil_w_h[i]; wtab.dW_dense[i] = g->dense_w_h[i];
     wtab.db_dil[i] = d->use_bias ? g->dil_b_h[i] : (float*)nullptr;
     wtab.db_dense[i] = d->use_bias ? g->dense_b_h[i] : (float*)nullptr;
@@ -2238,73 +2027,44 @@ extern "C" int avvad_wavenet_bwd(const float* wave, const avvad_wavenet_params* 
       hipLaunchKernelGGL(conv1d_fwd_generic, dim3(grid1((long)B * D * Lo)), dim3(256), 0, s, si, prm->dil_w_h[i], bd,
                          (const float*)nullptr, Zi, B, R, D, Li, Lo, fw, dil, 1, 0, 0);
     if (fast) {
-      // dz = (z>0) * W_dense^T dS ; then all four parameter gradients in one pass ; then d s_i
-      long blocks = ((long)B * cdiv(Lo, 32) + 3) / 4;
-      // a block's four parameter gradients are wanted independently (partially frozen blocks): the fused kernel always
-      // forms all four sums, the reduce skips the NULL destinations
+      // dz = (z>0) * W_dense^T dS and all four parameter gradients (one pass, or three kernels) ; then d s_i.
+      // A block's four parameter gradients are wanted independently (partially frozen blocks): the fused kernels always
+      // form all four sums, the reduce skips the NULL destinations
       const bool any_grad = g->dil_w_h[i] || g->dense_w_h[i] || (d->use_bias && (g->dil_b_h[i] || g->dense_b_h[i]));
-      if (any_grad && !avvad_tune().wn_no_fused_wgrad) {
-        // dz AND the four parameter gradients in one pass over dS, Z and the two shifted s_i tiles
-        long wb = ((long)B * cdiv(Lo, 32) + 15) / 16;   // >= 4 tiles per wave
-        // one workgroup per CU is resident (368 VGPRs): ONE round of 256, not two of 512 -- every workgroup pays a weight
-        // staging prologue and a 12.5 KB slab epilogue (step 22.57 -> 22.06 ms; 128..256 workgroups time the same)
-        if (wb > 256) wb = 256;
-        if (wb > WG_MAXBLK) wb = WG_MAXBLK;
-        if (wb < 1) wb = 1;
-        // option wn_bwd_t: 0 by the descriptor's shared_device hint, 1 transposed-product alternate, 2 high-occupancy form,
-        // 3 resident-weights form.  Alone on the device the two-waves-per-SIMD form wins (encoder fwd+bwd 3.09 -> 2.90 ms);
-        // beside the trunk's backward on the other stream it costs the STEP 0.25 ms (same-process A/B), like the dx kernel.
-        const int bt = avvad_tune().wn_bwd_t == 0 ? (d->shared_device ? 3 : 2) : avvad_tune().wn_bwd_t;
-        if (bt == 3) {
-          hipLaunchKernelGGL(wn_block_bwd_dz_wgrad_mfma, dim3((int)wb), dim3(256), 0, s, GA, prm->dil_w_h[i], bd,
+      const BwdChoice bc = bwd_form(B, Lo, d->shared_device != 0, any_grad);
+      switch (bc.form) {
+        case BwdForm::RESIDENT:
+          hipLaunchKernelGGL(wn_block_bwd_dz_wgrad_mfma, dim3(bc.grid), dim3(256), 0, s, GA, prm->dil_w_h[i], bd,
                              prm->dense_w_h[i], si, DZ, slab_i, B, Li, dil);
-        } else if (bt == 2) {
-          wb = ((long)B * cdiv(Lo, 32) + 15) / 16;
-          if (wb > 512) wb = 512;
-          if (wb >= 8) wb = wb / 8 * 8;
-          if (wb < 1) wb = 1;
-          hipLaunchKernelGGL(wn_block_bwd_dz_wgrad_occ, dim3((int)wb), dim3(256), 0, s, GA, prm->dil_w_h[i], bd,
+          break;
+        case BwdForm::OCC:
+          hipLaunchKernelGGL(wn_block_bwd_dz_wgrad_occ, dim3(bc.grid), dim3(256), 0, s, GA, prm->dil_w_h[i], bd,
                              prm->dense_w_h[i], si, DZ, slab_i, B, Li, dil);
-        } else {
-          // alternate: transposed-product form, under 256 registers, two workgroups per CU (one wave per SIMD each)
-          wb = ((long)B * cdiv(Lo, 32) + 15) / 16;
-          if (wb > 512) wb = 512;
-          if (wb < 1) wb = 1;
-          hipLaunchKernelGGL(wn_block_bwd_dzw_t, dim3((int)wb), dim3(256), 0, s, GA, prm->dil_w_h[i], bd, prm->dense_w_h[i], si,
+          break;
+        case BwdForm::TRANSPOSED:
+          hipLaunchKernelGGL(wn_block_bwd_dzw_t, dim3(bc.grid), dim3(256), 0, s, GA, prm->dil_w_h[i], bd, prm->dense_w_h[i], si,
                              DZ, slab_i, B, Li, dil);
-        }
-        note_slabs(i, slab_i, wb);
-      } else {
-        // (frozen weights / tuning switch) separate kernels: z is not kept by the forward -> rebuild it first
-        long fb = blocks > 512 ? 512 : blocks;
-        hipLaunchKernelGGL(wn_block_fwd_mfma<2>, dim3((int)fb), dim3(256), 0, s, si, prm->dil_w_h[i], bd, prm->dense_w_h[i],
-                           (const float*)nullptr, (float*)nullptr, Zi, B, Li, dil);
-        if (blocks > 768) blocks = 768;
-        hipLaunchKernelGGL(wn_block_bwd_dz_mfma, dim3((int)blocks), dim3(256), 0, s, GA, Zi, prm->dense_w_h[i], DZ, B, Lo);
-        if (any_grad) {
-          long wb = ((long)B * cdiv(Lo, 32) + 15) / 16;   // >= 4 tiles per wave
-          if (wb > WG_MAXBLK) wb = WG_MAXBLK;
-          if (wb < 1) wb = 1;
-          hipLaunchKernelGGL(wn_block_wgrad_mfma, dim3((int)wb), dim3(256), 0, s, GA, Zi, DZ, si, slab_i, B, Li, dil);
-          note_slabs(i, slab_i, wb);
-        }
+          break;
+        case BwdForm::UNFUSED:      // z is not kept by the forward -> rebuild it first
+          hipLaunchKernelGGL(wn_block_fwd_mfma<2>, dim3(bc.grid_z), dim3(256), 0, s, si, prm->dil_w_h[i], bd, prm->dense_w_h[i],
+                             (const float*)nullptr, (float*)nullptr, Zi, B, Li, dil);
+          hipLaunchKernelGGL(wn_block_bwd_dz_mfma, dim3(bc.grid_dz), dim3(256), 0, s, GA, Zi, prm->dense_w_h[i], DZ, B, Lo);
+          if (any_grad)
+            hipLaunchKernelGGL(wn_block_wgrad_mfma, dim3(bc.grid), dim3(256), 0, s, GA, Zi, DZ, si, slab_i, B, Li, dil);
+          break;
       }
-      blocks = ((long)B * cdiv(Li, 32) + 3) / 4;
-      // The high-occupancy dx kernel everywhere.  (Round 2 measured it 0.16 ms/step SLOWER beside the trunk's backward on another
-      // stream, and the shared_device hint picked the resident-weights form there; with this round's trunk kernels -- layer 1 off
-      // the persistent engine, fewer and longer class launches -- the same A/B reads 0.06 ms FASTER: bench.py --ab wn_dx=1.)
-      // Option wn_dx: 1 forces the resident-weights kernel, 2 the high-occupancy one.
-      const bool dx_occ = avvad_tune().wn_dx == 2 || avvad_tune().wn_dx == 0;
-      if (buf_ok(B, Li) && avvad_tune().wn_flat != 1 && dx_occ) {
-        if (blocks > 1024) blocks = 1024;                 // 4 waves per SIMD resident
-        if (blocks >= 8) blocks = (blocks + 7) / 8 * 8;
-        hipLaunchKernelGGL(wn_block_bwd_dx_occ, dim3((int)blocks), dim3(256), 0, s, DZ, si, GA, prm->dil_w_h[i], GB, B, Li, dil);
-      } else if (buf_ok(B, Li) && avvad_tune().wn_flat != 1 && avvad_tune().wn_dx != 3) {     // (wn_dx = 3: the flat kernel)
-        if (blocks > 512) blocks = 512;
-        hipLaunchKernelGGL(wn_block_bwd_dx_buf, dim3((int)blocks), dim3(256), 0, s, DZ, si, GA, prm->dil_w_h[i], GB, B, Li, dil);
-      } else {
-        if (blocks > 512) blocks = 512;
-        hipLaunchKernelGGL(wn_block_bwd_dx_mfma, dim3((int)blocks), dim3(256), 0, s, DZ, si, GA, prm->dil_w_h[i], GB, B, Li, dil);
+      if (any_grad) note_slabs(i, slab_i, bc.grid);
+      const DxChoice dc = dx_form(B, Li);
+      switch (dc.form) {
+        case DxForm::OCC:
+          hipLaunchKernelGGL(wn_block_bwd_dx_occ, dim3(dc.grid), dim3(256), 0, s, DZ, si, GA, prm->dil_w_h[i], GB, B, Li, dil);
+          break;
+        case DxForm::BUF:
+          hipLaunchKernelGGL(wn_block_bwd_dx_buf, dim3(dc.grid), dim3(256), 0, s, DZ, si, GA, prm->dil_w_h[i], GB, B, Li, dil);
+          break;
+        case DxForm::FLAT:
+          hipLaunchKernelGGL(wn_block_bwd_dx_mfma, dim3(dc.grid), dim3(256), 0, s, DZ, si, GA, prm->dil_w_h[i], GB, B, Li, dil);
+          break;
       }
     } else {
       // dense (1x1) layer: d W_dense = GA . relu(z)^T ; d b ; dz = (z>0) * W_dense^T GA

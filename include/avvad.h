@@ -87,10 +87,15 @@ int avvad_abi_version(void);
 /* Schedule options (tuning / debugging; production leaves them alone).  Names:
  *   "no_streamk" (1 = whole-tile GEMM schedule), "igemm_variant", "kmajor", "no_tall", "no_stem_kernel",
  *   "no_fixup1" (1 = always the four-wave fix-up kernel), "no_buf" (1 = convolution gathers with flat addressing + validity selects, the form operands >= 2 GiB use),
- *   "lstm_no_fused_step", "lstm_no_persistent", "wn_no_fused_tail", "wn_no_fused_wgrad", "wn_bwd_t",
- *   "wn_flat" (encoder block forward: 0 by plane length, 1 flat dword kernel, 2 buffer dword kernel with resident
- *   weights, 3 dwordx4 kernel, 4 high-occupancy kernel), "wn_dx" / "wn_bwd_t" (0 by the descriptor's shared_device hint, other values force
- *   a form), "wn_grid" (workgroup cap of the encoder block kernels),
+ *   "lstm_no_fused_step", "lstm_no_persistent", "wn_no_fused_tail", "wn_no_fused_wgrad",
+ *   "wn_flat" (encoder block forward: 0 by plane length -- the wide kernel from 8192 samples, else the high-occupancy
+ *   kernel; 1 flat dword kernel, which also makes the input gradient flat; 2 buffer dword kernel with resident weights and
+ *   cross-tile prefetch; 3 wide dwordx4 kernel; 4 high-occupancy kernel; 5 LDS-DMA kernel),
+ *   "wn_dx" (encoder block input gradient: 0 and 2 high-occupancy kernel; 1 resident weights and cross-tile prefetch;
+ *   3 flat kernel),
+ *   "wn_bwd_t" (encoder block dz + weight gradients in one pass: 0 by the descriptor's shared_device hint -- 3 beside
+ *   another stream's kernels, else 2; 1 transposed products; 2 high occupancy; 3 resident weights),
+ *   "wn_grid" (workgroup cap of the encoder block forward kernels),
  *   "bf16" (BASELINE config 5's mixed precision, never the default.  1: the trunk runs its bf16 DATA PATH -- activations
  *   between convolutions, the gradients that feed convolutions and the packed weights are stored as bf16, the convolutions
  *   run on the bf16 engine -- and the dense GEMMs of the heads round their fp32 operands to bf16 on their way into LDS;

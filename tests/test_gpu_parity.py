@@ -261,6 +261,68 @@ def test_wavenet_backward_is_bit_reproducible():
             assert torch.equal(a, b)
 
 
+def _max_rel_l2(a, b):
+    return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30))
+
+
+@pytest.mark.parametrize("shape", [(7, 1, 700), (2, 1, 300)])
+def test_wavenet_backward_forms_agree(shape, lib_options):
+    """The backward counterpart of test_wavenet_block_kernel_forms_agree: one forward + backward of a five-block encoder
+    (R = D = 32; dilations 1, 2, 64, 3, 32: a tap that crosses tiles, ragged last tiles in every layer) in every form of
+    the input-gradient kernel (wn_dx 1 resident weights, 2 high occupancy, 3 flat with wn_flat = 1) and of the dz +
+    weight-gradient pass (wn_bwd_t 1 transposed, 2 high occupancy, 3 resident weights; wn_no_fused_wgrad).
+    (7, 1, 700): 699 -> 597 samples, >= 133 tiles per layer -- the rounded grids take the XCD walk with surplus waves and
+    the fused backward's round-down is exercised; (2, 1, 300): 14 tiles, the plain strided walk and a one-workgroup
+    fused backward.
+    * wn_bwd_t fixed: every gradient is bit-identical across wn_dx (same arithmetic, same summation order) -- except
+      the blocks' parameter gradients under wn_bwd_t = 1, whose kernel adds its waves' sums with LDS float atomics in
+      arrival order (not bit-reproducible from run to run): those are held to the relative bound below;
+    * wn_dx fixed: the input gradient is bit-identical across the dz forms (z and dz are the same sums in every form);
+    * the parameter gradients agree with the wn_bwd_t = 2 run within test_wavenet_golden's bound for these gradients
+      (relative L2 <= 2e-3: the slab count, hence the summation order, differs between the forms)."""
+    from packages.models.wavenet_autoencoder import wavenet_autoencoder
+    cfg = dict(filter_width=2, quantization_channel=1, dilations=[1, 2, 64, 3, 32], en_residual_channel=32,
+               en_dilation_channel=32, en_bottleneck_width=256, en_pool_kernel_size=7, use_bias=True)
+    torch.manual_seed(11)
+    m = wavenet_autoencoder(**cfg).to(DEV)
+    x = (torch.rand(*shape, device=DEV) * 2 - 1).requires_grad_(True)
+    Gd = torch.randn(shape[0], 256, 7, device=DEV)
+    names = ["x"] + [k for k, _ in m.named_parameters()]
+
+    def run(bwd_t, dx, unfused=0):
+        lib_options("wn_bwd_t", bwd_t)
+        lib_options("wn_no_fused_wgrad", unfused)
+        lib_options("wn_dx", dx)
+        lib_options("wn_flat", 1 if dx == 3 else 0)
+        for p in m.parameters():
+            p.grad = None
+        x.grad = None
+        (m(x) * Gd).sum().backward()
+        torch.cuda.synchronize()
+        got = [x.grad.clone()] + [p.grad.clone() for p in m.parameters()]
+        assert all(torch.isfinite(g).all() for g in got)
+        return got
+
+    by_form = {}
+    for key, bwd_t, unfused in (("t1", 1, 0), ("t2", 2, 0), ("t3", 3, 0), ("unfused", 2, 1)):
+        by_form[key] = run(bwd_t, 2, unfused)
+        if unfused:
+            continue
+        for dx in (1, 3):
+            for n, a, b in zip(names, by_form[key], run(bwd_t, dx)):
+                if bwd_t == 1 and "_layer_stack" in n:
+                    assert _max_rel_l2(a, b) <= 2e-3, (bwd_t, dx, n)
+                else:
+                    assert torch.equal(a, b), "wn_bwd_t=%d: %s differs between wn_dx=2 and wn_dx=%d" % (bwd_t, n, dx)
+    ref = by_form["t2"]
+    for key, got in by_form.items():
+        assert torch.equal(got[0], ref[0]), "x.grad of form %s differs from wn_bwd_t=2" % key
+        for n, a, b in zip(names[1:], got[1:], ref[1:]):
+            rel = _max_rel_l2(a, b)
+            print("%-8s d/d%-28s relL2 vs wn_bwd_t=2: %.2e" % (key, n, rel))
+            assert rel <= 2e-3, (key, n, rel)
+
+
 def test_wavenet_batch_and_tails():
     """ragged tile tails (L not a multiple of 32) and B>1 on the MFMA block path vs the oracle."""
     from oracle import wavenet as ow

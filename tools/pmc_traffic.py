@@ -26,7 +26,7 @@ def traffic(k):
 
 conv = find("kernel<128, 128, true, 512", "Im2colFwdCls", "false>")         # position-class forward (stages 2-4: 8 launches / step)
 conv_plain = find("kernel<128, 128, true, 512", "Im2colFwd<true>", "false>")   # dense schedule (stride-2 / 1x1 convolutions)
-wn = find("wn_block_fwd_occ<0>")
+wn = find("wn_block_fwd_occ")
 print(json.dumps({
     "conv_fwd": traffic(conv), "conv_fwd_kernel": conv,
     "conv_fwd_dense_schedule": traffic(conv_plain), "conv_fwd_dense_schedule_kernel": conv_plain,
