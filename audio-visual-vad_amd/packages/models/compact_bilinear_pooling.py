@@ -5,11 +5,24 @@ input channel) / ``s`` (+-1 sign) and sub-module names ``sketch1`` / ``sketch2``
 ``avvad_mcb_fwd/bwd``: csrc/mcb.hip -- the FFT product of the reference is evaluated as the circular
 convolution it equals) and returns the raw sketch / pooled vector like the reference; inside ``DeepVAD_AV``
 the same arithmetic runs fused with the signed sqrt, L2 norm and BatchNorm1d (``ops.McbFusionFn``).
-GPU tensors only: there is no PyTorch fallback."""
+GPU tensors only: there is no PyTorch fallback.
+The kernels index with ``h`` unchecked (a global read at ``dout[row * D + h[c]]``, an LDS index ``D - h``), and a buffer
+comes from wherever a checkpoint comes from: ``CountSketch`` validates it on the host where it receives it -- the
+constructor and ``load_state_dict`` -- and ``forward`` stays free of any device synchronisation."""
 import torch
 import torch.nn as nn
 
-from avvad import ops
+from avvad import AvvadError, ops
+
+
+def _check_hashes(h, input_size, output_size, name="h"):
+    """int64, shape (input_size,), every value in [0, output_size): or AvvadError"""
+    if not isinstance(h, torch.Tensor) or h.dtype != torch.long:
+        raise AvvadError("%s must be an int64 tensor, got %s" % (name, h.dtype if isinstance(h, torch.Tensor) else type(h).__name__))
+    if tuple(h.shape) != (input_size,):
+        raise AvvadError("%s must have shape (%d,), got %s" % (name, input_size, tuple(h.shape)))
+    if input_size and (int(h.min()) < 0 or int(h.max()) >= output_size):
+        raise AvvadError("%s must lie in [0, %d): found values from %d to %d" % (name, output_size, int(h.min()), int(h.max())))
 
 
 class CountSketch(nn.Module):
@@ -21,6 +34,7 @@ class CountSketch(nn.Module):
             h = torch.randint(0, output_size, (input_size,), dtype=torch.long)
         if s is None:
             s = 2.0 * torch.randint(0, 2, (input_size,)).float() - 1.0
+        _check_hashes(h, input_size, output_size)
         self.register_buffer("h", h)
         self.register_buffer("s", s)
 
@@ -31,6 +45,11 @@ class CountSketch(nn.Module):
         if self.h.dtype != torch.long:
             self.h = h.to(self.h.device)
         return self
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        if prefix + "h" in state_dict:
+            _check_hashes(state_dict[prefix + "h"], self.input_size, self.output_size, prefix + "h")
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def forward(self, x):
         assert x.shape[-1] == self.input_size
