@@ -1164,6 +1164,129 @@ def finalize_stats(acc):
     return mean, std
 
 
+# --------------------------------------------------------------------------- scores (no gradient)
+SCORE_CHUNK = L.SCORE_CHUNK      # samples of one partial of the energy-ratio pass (include/avvad.h AVVAD_SCORE_CHUNK)
+_THIRD = {None: 0, "none": 0, "noise": 1, "mixture": 2, 0: 0, 1: 1, 2: 2}
+
+
+def score_state(B, device):
+    """A zeroed score accumulator: float64 (B, 6) on the GPU, per row the inner products
+    ``(e.e, e.r, e.n, r.r, n.n, r.n)`` of estimate, clean reference and noise (include/avvad.h, avvad_score_*)."""
+    if int(B) < 1:
+        raise L.AvvadError("B must be positive, got %r" % (B,))
+    if torch.device(device).type != "cuda":
+        raise L.AvvadError("the scores accumulate on the GPU: the AV-VAD hot path has no CPU fallback")
+    return torch.zeros(int(B), 6, dtype=torch.float64, device=device)
+
+
+def _score_acc(acc):
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.dtype != torch.float64 or acc.dim() != 2 \
+            or acc.shape[1] != 6 or not acc.is_contiguous():
+        raise L.AvvadError("acc must be a contiguous float64 GPU tensor (B, 6) (ops.score_state)")
+    return acc.shape[0]
+
+
+def _score_rows(t, name, B, Ls):
+    """(tensor to read in place, row pitch in floats) of a (B, >= Ls) or (>= Ls,) float32 GPU signal: read through its
+    strides; only a last axis that is not unit-stride (or rows that overlap) is copied."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise L.AvvadError("%s must be a GPU tensor: the AV-VAD hot path has no CPU fallback" % name)
+    if t.dtype != torch.float32:
+        raise L.AvvadError("%s must be float32, got %s" % (name, t.dtype))
+    if t.dim() == 1:
+        t = t.view(1, -1)
+    if t.dim() != 2 or t.shape[0] != B or t.shape[1] < Ls:
+        raise L.AvvadError("%s must hold %d rows of at least %d samples, got shape %s" % (name, B, Ls, tuple(t.shape)))
+    t = t[:, :Ls]
+    if t.stride(1) != 1 or (B > 1 and t.stride(0) < Ls):
+        t = t.contiguous()
+    return t, (t.stride(0) if B > 1 else Ls)
+
+
+def score_accumulate(acc, est, ref, noise=None, mixture=None, lengths=None):
+    """Adds the inner products of a ragged batch to ``acc`` (avvad_score_accumulate): est (B, L) (or (L,)) the enhanced
+    signal, ref the clean one, and as the third signal either ``noise`` or the noisy ``mixture`` (the kernel then forms
+    ``noise = mixture - ref`` in double), or neither (SI-SDR alone).  ref / noise / mixture may have longer rows than est:
+    their first L samples count.  Samples at or behind ``lengths[b]`` are not read.  Returns ``acc``."""
+    B = _score_acc(acc)
+    if noise is not None and mixture is not None:
+        raise L.AvvadError("score_accumulate: give the noise or the mixture, not both")
+    if not isinstance(est, torch.Tensor) or est.dim() not in (1, 2):
+        raise L.AvvadError("est must be a (B, L) or (L,) GPU tensor")
+    Ls = est.shape[-1]
+    e, ld_e = _score_rows(est, "est", B, Ls)
+    r, ld_r = _score_rows(ref, "ref", B, Ls)
+    third, mode = (noise, 1) if noise is not None else (mixture, 2) if mixture is not None else (None, 0)
+    t, ld_t = _score_rows(third, "noise" if mode == 1 else "mixture", B, Ls) if mode else (None, 0)
+    lens32 = None
+    if lengths is not None:
+        lens32 = lengths_i32(lengths, e.device)
+        if lens32.numel() != B:
+            raise L.AvvadError("lengths must hold %d values" % B)
+    ws = _ws(L.lib().avvad_score_workspace(B, Ls), e.device)
+    L.check(L.lib().avvad_score_accumulate(L.ptr(e), ld_e, L.ptr(r), ld_r, L.ptr(t), ld_t, mode, L.ptr(lens32), L.ptr(acc), B, Ls,
+                                           L.ptr(ws), ws.numel() * 4, _stream()), "avvad_score_accumulate")
+    return acc
+
+
+def score_finalize(acc, third, return_alpha=False):
+    """(B, 3) float64 on the GPU: ``si_sdr, si_sir, si_sar`` in dB from a score accumulator (avvad_score_finalize).
+    ``third``: what the accumulate calls were given -- "noise", "mixture" or "none" (None); with "none" only SI-SDR is
+    defined and the other two are NaN.  An empty row is NaN.  ``return_alpha``: also (B, 2) ``alpha_s, alpha_n``."""
+    B = _score_acc(acc)
+    if third not in _THIRD:
+        raise L.AvvadError("third must be 'none', 'noise' or 'mixture', got %r" % (third,))
+    ratios = torch.empty((B, 3), dtype=torch.float64, device=acc.device)
+    alpha = torch.empty((B, 2), dtype=torch.float64, device=acc.device) if return_alpha else None
+    L.check(L.lib().avvad_score_finalize(L.ptr(acc), B, _THIRD[third], L.ptr(ratios), L.ptr(alpha), _stream()), "avvad_score_finalize")
+    return (ratios, alpha) if return_alpha else ratios
+
+
+def energy_ratios(est, ref, noise=None, mixture=None, lengths=None, return_alpha=False):
+    """``packages/metrics.py energy_ratios`` of a ragged batch in one call: (B, 3) float64 ``si_sdr, si_sir, si_sar`` on
+    the GPU (and (B, 2) ``alpha_s, alpha_n`` with ``return_alpha``).  Arguments as for ``score_accumulate``."""
+    if not isinstance(est, torch.Tensor) or not est.is_cuda:
+        raise L.AvvadError("est must be a GPU tensor: the AV-VAD hot path has no CPU fallback")
+    acc = score_state(1 if est.dim() == 1 else est.shape[0], est.device)
+    score_accumulate(acc, est, ref, noise, mixture, lengths)
+    return score_finalize(acc, "noise" if noise is not None else "mixture" if mixture is not None else "none", return_alpha)
+
+
+def confusion_counts(pred, target, lengths=None, logits=False, counts=None):
+    """(B, 4) int64 ``tp, tn, fp, fn`` per row of pred / target (B, T, Y) (or (B, T)), the four sums of ``f1_loss``
+    (avvad_confusion_accumulate).  ``pred`` holds 0 / 1, or with ``logits`` the logits (prediction: ``logit > 0``, the
+    evaluator's ``sigmoid > 0.5``); frames t >= lengths[b] are not read.  ``counts`` (from an earlier call) is added to."""
+    p, y = _dev(pred, "pred"), _dev(target, "target")
+    if p.shape != y.shape or p.dim() not in (2, 3):
+        raise L.AvvadError("pred and target must both be (B, T, Y) or (B, T), got %s and %s" % (tuple(p.shape), tuple(y.shape)))
+    B, T = p.shape[:2]
+    Y = p.shape[2] if p.dim() == 3 else 1
+    if counts is None:
+        counts = torch.zeros(B, 4, dtype=torch.int64, device=p.device)
+    elif not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.dtype != torch.int64 \
+            or tuple(counts.shape) != (B, 4) or not counts.is_contiguous():
+        raise L.AvvadError("counts must be a contiguous int64 GPU tensor (%d, 4)" % B)
+    lens32 = None
+    if lengths is not None:
+        lens32 = lengths_i32(lengths, p.device)
+        if lens32.numel() != B:
+            raise L.AvvadError("lengths must hold %d values" % B)
+    L.check(L.lib().avvad_confusion_accumulate(L.ptr(p), 1 if logits else 0, L.ptr(y), L.ptr(lens32), L.ptr(counts), B, T, Y,
+                                               _stream()), "avvad_confusion_accumulate")
+    return counts
+
+
+def f1_from_counts(counts, eps=1e-8):
+    """(B, 4) float32 ``accuracy, precision, recall, f1`` from (B, 4) ``tp, tn, fp, fn``: ``f1_loss``'s own float32
+    expressions (packages/models/utils.py:191-200) on the counts, row by row the values ``f1_loss`` returns."""
+    tp, tn, fp, fn = (counts[..., k].to(torch.float32) for k in range(4))
+    accuracy = (tp + tn) / (tp + tn + fp + fn + eps)
+    precision = tp / (tp + fp + eps)
+    recall = tp / (tp + fn + eps)
+    f1 = 2 * (precision * recall) / (precision + recall + eps)
+    return torch.stack([accuracy, precision, recall, f1], dim=-1)
+
+
 # --------------------------------------------------------------------------- training labels from clean speech (no gradient)
 _CENTER = {"reflect": 1, "constant": 2}
 

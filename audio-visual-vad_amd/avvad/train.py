@@ -544,6 +544,14 @@ def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, ep
     many frames per step; the features are still formed from the whole utterance.  ``chunk_samples``: the RAW samples go
     through the session in packets of that many (``stream.forward_wave_chunked``): the peak -- the one statistic of the
     whole utterance -- is one reduction up front, everything behind it is streamed."""
+    soft = torch.sigmoid(utt_logits(classifier, x_t, stats, n_label_frames, video, eps, std_norm, chunk_frames,
+                                    chunk_samples)[..., 0].detach().cpu())
+    return soft, (soft > 0.5).int()
+
+
+def utt_logits(classifier, x_t, stats=None, n_label_frames=None, video=None, eps=EPS, std_norm=True, chunk_frames=None,
+               chunk_samples=None):
+    """The logits (1, T, y_dim) of ``process_utt``, on the GPU (arguments as there)."""
     _one_chunking(chunk_frames, chunk_samples)
     if chunk_samples is not None:
         w = x_t.reshape(1, -1)
@@ -553,10 +561,8 @@ def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, ep
         if video is not None:
             v = video[None, :T].contiguous()
             v = stats.video(v) if (stats is not None and std_norm) else v
-        y = stream.forward_wave_chunked(classifier, w, None, v, chunk_samples, stats if std_norm else None, ops.peak(w),
-                                        eps=eps, max_frames=[T])
-        soft = torch.sigmoid(y[..., 0].detach().cpu())
-        return soft, (soft > 0.5).int()
+        return stream.forward_wave_chunked(classifier, w, None, v, chunk_samples, stats if std_norm else None, ops.peak(w),
+                                           eps=eps, max_frames=[T])
     x = audio_features(x_t, stats, n_label_frames, eps=eps, std_norm=std_norm)
     lengths = [x.shape[1]]
     v = None
@@ -569,8 +575,7 @@ def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, ep
         y = classifier(x, lengths)
     else:
         y = classifier(x, v, lengths)
-    soft = torch.sigmoid(y[..., 0].detach().cpu())
-    return soft, (soft > 0.5).int()
+    return y
 
 
 def resynth_utt(classifier, x_t, stats=None, hard=True, eps=EPS, std_norm=True, chunk_samples=None):
@@ -595,9 +600,23 @@ def resynth_utt(classifier, x_t, stats=None, hard=True, eps=EPS, std_norm=True, 
     return out.view(-1)
 
 
+def score_utt(enhanced, clean, noisy):
+    """Enhancement scores of one utterance on the GPU: a dict of Python floats ``si_sdr``, ``si_sir``, ``si_sar`` (the
+    enhanced signal against the clean one, the noise being ``noisy - clean``) and ``input_si_sdr`` (the noisy signal
+    itself against the clean one).  One two-row ``ops.energy_ratios`` call: rows ``enhanced`` and ``noisy``, both scored
+    against ``clean`` with ``mixture = noisy``.  The three (L,) GPU signals are cropped to their common length."""
+    n = min(enhanced.numel(), clean.numel(), noisy.numel())
+    e, c, x = (t.reshape(-1)[:n] for t in (enhanced, clean, noisy))
+    r = ops.energy_ratios(torch.stack([e, x]), torch.stack([c, c]), mixture=torch.stack([x, x])).tolist()
+    return {"si_sdr": r[0][0], "si_sir": r[0][1], "si_sar": r[0][2], "input_si_sdr": r[1][0]}
+
+
+SCORE_KEYS = ("si_sdr", "si_sir", "si_sar", "input_si_sdr")
+
+
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
                   stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None, chunk_samples=None,
-                  resynth_dir=None, resynth_hard=True, resynth_chunked=False):
+                  resynth_dir=None, resynth_hard=True, resynth_chunked=False, score_dir=None):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
@@ -619,7 +638,14 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
     ``resynth_dir`` (``wav_list`` with a 513-output audio model): every utterance is also resynthesised from the model's
     mask (``resynth_utt``; ``resynth_hard``: binary mask, else the soft one) and written there as ``<base>_enhanced.wav``
     -- float32, 16 kHz, as many samples as the input.  ``None`` writes nothing.  ``resynth_chunked`` (with ``resynth_dir``
-    and ``chunk_samples``): the enhanced samples come out of the streaming session, packet by packet."""
+    and ``chunk_samples``): the enhanced samples come out of the streaming session, packet by packet.
+
+    ``score_dir`` (``wav_list`` with ``clean_of``): every utterance is scored on the GPU and ``<base>_scores.pt`` is
+    written there, a dict of Python numbers: the classifier's ``tp, tn, fp, fn`` (``ops.confusion_counts`` on the logits
+    the predictions come from and the GPU labels) and, with ``resynth_dir``, ``score_utt`` of the enhanced waveform
+    against the clean file cropped to the common length.  ``None`` writes nothing and changes nothing."""
+    if score_dir is not None and (wav_list is None or clean_of is None):
+        raise ValueError("score_dir scores the utterances of wav_list against their clean files: it needs clean_of")
     _one_chunking(chunk_frames, chunk_samples)
     if resynth_chunked and (resynth_dir is None or chunk_samples is None):
         raise ValueError("resynth_chunked streams the resynthesis: it needs resynth_dir and chunk_samples")
@@ -648,6 +674,8 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
     os.makedirs(out_dir, exist_ok=True)
     if resynth_dir is not None:
         os.makedirs(resynth_dir, exist_ok=True)
+    if score_dir is not None:
+        os.makedirs(score_dir, exist_ok=True)
     t0 = time.perf_counter()
     if av_files is not None:
         if kind.lower() not in ("video", "av") or waveform or wav_list is not None:
@@ -682,8 +710,16 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                     y = clean_vad_labels(clean_of[wav_list[i]], x_t.numel(), device)
                 else:
                     y = labels.get(wav_list[i]) if labels else None
-                soft, hard = process_utt(model, x_t.to(device), stats, None if y is None else y.shape[-1],
-                                         chunk_frames=chunk_frames, chunk_samples=chunk_samples)
+                logits = utt_logits(model, x_t.to(device), stats, None if y is None else y.shape[-1],
+                                    chunk_frames=chunk_frames, chunk_samples=chunk_samples)
+                soft = torch.sigmoid(logits[..., 0].detach().cpu())                      # process_utt's outputs
+                hard = (soft > 0.5).int()
+                scores = None
+                if score_dir is not None:
+                    Tn = min(logits.shape[1], y.shape[-1])
+                    counts = ops.confusion_counts(logits[:, :Tn, 0].detach().contiguous(), y[:, :Tn].float().contiguous(),
+                                                  logits=True)[0].tolist()
+                    scores = dict(zip(("tp", "tn", "fp", "fn"), counts))
                 base = os.path.join(out_dir, os.path.splitext(os.path.basename(wav_list[i]))[0])
                 torch.save(hard, base + "_y_hat_hard.pt")
                 torch.save(soft, base + "_y_hat_soft.pt")
@@ -695,6 +731,11 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                                            chunk_samples=chunk_samples if resynth_chunked else None)
                     wavfile.write(os.path.join(resynth_dir, os.path.basename(base) + "_enhanced.wav"), 16000,
                                   enhanced.cpu().numpy())
+                    if scores is not None:
+                        clean, _ = load_waveform(clean_of[wav_list[i]])
+                        scores.update(score_utt(enhanced, clean.to(device), x_t.to(device)))
+                if scores is not None:
+                    torch.save(scores, os.path.join(score_dir, os.path.basename(base) + "_scores.pt"))
     else:
         ds = SyntheticAV(n_items, kind, waveform=waveform, seed=7)
         collate = pick_collate(kind, waveform)
@@ -710,10 +751,13 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
         print("Finished in {:.2f} seconds".format(time.perf_counter() - t0))
 
 
-def metrics_main(out_dir="eval_out", confidence=0.95, eps=1e-8):
+def metrics_main(out_dir="eval_out", confidence=0.95, eps=1e-8, score_dir=None):
     """The body of ``scripts/run_metrics_dnn_classif.py`` (``:102-300``) for the classifier outputs: per utterance
     ``f1_loss(y_hat_hard, y)`` -> (accuracy, precision, recall, F1), then ``compute_stats`` tables with Student-t
-    confidence intervals.  Reads the ``*_y_hat_hard.pt`` / ``*_label.pt`` pairs that ``evaluate_main`` wrote."""
+    confidence intervals.  Reads the ``*_y_hat_hard.pt`` / ``*_label.pt`` pairs that ``evaluate_main`` wrote.
+    ``score_dir``: a second table over the four enhancement scores of the ``*_scores.pt`` files that
+    ``evaluate_main(resynth_dir=..., score_dir=...)`` wrote there; both tables are then returned as
+    ``{"classifier": ..., "enhancement": ...}``."""
     import glob
     from packages.metrics import compute_stats
     from packages.models.utils import f1_loss
@@ -724,5 +768,13 @@ def metrics_main(out_dir="eval_out", confidence=0.95, eps=1e-8):
         rows.append(tuple(float(v) for v in f1_loss(y_hat, y.long(), eps)))
     if len(rows) < 2:
         raise SystemExit("need at least two evaluated utterances in %s (run scripts/evaluate_*_net.py first)" % out_dir)
-    return compute_stats(metrics_keys=["accuracy", "precision", "recall", "f1score"], all_metrics=rows, model_data_dir=out_dir,
-                         confidence=confidence)
+    table = compute_stats(metrics_keys=["accuracy", "precision", "recall", "f1score"], all_metrics=rows, model_data_dir=out_dir,
+                          confidence=confidence)
+    if score_dir is None:
+        return table
+    scored = [torch.load(path, weights_only=True) for path in sorted(glob.glob(os.path.join(score_dir, "*_scores.pt")))]
+    scored = [tuple(d[k] for k in SCORE_KEYS) for d in scored if all(k in d for k in SCORE_KEYS)]
+    if len(scored) < 2:
+        raise SystemExit("need at least two scored utterances in %s (evaluate_main with resynth_dir and score_dir)" % score_dir)
+    return {"classifier": table, "enhancement": compute_stats(metrics_keys=list(SCORE_KEYS), all_metrics=scored,
+                                                              model_data_dir=score_dir, confidence=confidence)}

@@ -1,0 +1,248 @@
+// scores.hip -- scores of the enhanced speech and of the classifier on the GPU: the scale-invariant energy ratios
+// SI-SDR / SI-SIR / SI-SAR of a ragged batch of waveforms, and the confusion counts (tp, tn, fp, fn) of a ragged batch of
+// frame labels.
+//
+// Replaces the host-side scoring of the reference:
+//   packages/metrics.py:12-60            si_sdr_components (alpha_s, alpha_n, the three planes s_target / e_noise / e_art) and
+//                                        energy_ratios (10 log10 of |s_target|^2 over |e_noise + e_art|^2, |e_noise|^2, |e_art|^2)
+//   packages/models/utils.py:164-203     f1_loss's four sums tp / tn / fp / fn
+//
+// Energy ratios.  Every norm the reference takes is a quadratic form of six inner products of the estimate e, the clean
+// reference r and the noise n (the Gram matrix of the three signals):
+//   G = (e.e, e.r, e.n, r.r, n.n, r.n),   a_s = e.r / r.r,   a_n = e.n / n.n
+//   |s_target|^2 = a_s e.r      |e_noise + e_art|^2 = e.e - a_s e.r      |e_noise|^2 = a_n e.n
+//   |e_art|^2 = e.e - a_s e.r - a_n e.n + 2 a_s a_n r.n
+// so ONE pass over the three signals (12 bytes per sample) is all the data traffic; the planes are never written.  Every
+// value is widened to double before it is multiplied.  third_mode 2 reads the noisy mixture x and forms n = (double)x -
+// (double)r itself.
+//
+// An accumulator is [B][6] doubles in caller-owned device memory; calls ADD to it, so an utterance may arrive in packets.
+//
+// Kernel forms (memory-bound, and at an utterance's size launch-bound):
+//   gram_partials<MODE>: rows are cut into chunks of AVVAD_SCORE_CHUNK samples; workgroup (chunk, row) has four waves whose
+//        256 lanes stride over the chunk (a wave reads 256 consecutive bytes per signal and load, UN samples of each signal
+//        in flight per lane: plain dword loads, since the three row bases are only 4-byte aligned and differently so);
+//        cross-lane sums by a fixed butterfly, the four waves added in wave order; the workgroup stores one 6-double partial.
+//        A workgroup whose chunk lies past the row's length exits and stores nothing.
+//   gram_add: acc[row][c] += the row's partials in ascending chunk order (lane c < 6 of one wave per row); only the
+//        chunks below the row's length are read.
+//   gram_finalize: one thread per row, acc -> the three ratios in dB (and the two alpha).
+//   confusion_partials: workgroup (chunk of the row's len * Y values, row) counts in integers and adds its four counts to
+//        counts[row][0..3] with 64-bit integer atomics (exact in any order: no workspace).
+// No floating-point atomics, and the chunking depends on the row length alone: bit-identical run to run and whatever the
+// CU cap.  Nothing at or behind lengths[b] (clamped to [0, L]) is read.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int CHUNK = AVVAD_SCORE_CHUNK;   // samples of one partial
+constexpr int UN = 8;                      // samples of each signal in flight per lane (measured: tools/lab/score_lab.hip)
+constexpr int CONF_CHUNK = 4096;           // values of one confusion workgroup
+static_assert(CHUNK % (256 * UN) == 0, "a chunk is a whole number of unrolled workgroup strides");
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// part[row][chunk][6], chunk < nchunks(L).  MODE 0: no third signal (its three products stay 0), 1: noise, 2: mixture.
+template <int MODE>
+__global__ void __launch_bounds__(256)
+    gram_partials(const float* __restrict__ est, long ld_est, const float* __restrict__ ref, long ld_ref,
+                  const float* __restrict__ third, long ld_third, const int* __restrict__ lengths, long L,
+                  double* __restrict__ part) {
+  __shared__ double red[6][4];
+  const int b = blockIdx.y;
+  long len = L;
+  if (lengths) {
+    const int v = lengths[b];
+    len = v < 0 ? 0 : (v > L ? L : v);
+  }
+  const long i0 = (long)blockIdx.x * CHUNK;
+  if (i0 >= len) return;                  // (uniform for the workgroup: nothing is waiting at the barrier below)
+  const long i1 = min(len, i0 + CHUNK);
+  const float* e = est + b * ld_est;
+  const float* r = ref + b * ld_ref;
+  const float* t = MODE ? third + b * ld_third : nullptr;
+  double g[6] = {};
+  for (long i = i0 + threadIdx.x; i < i1; i += 256 * UN) {
+    float ve[UN] = {}, vr[UN] = {}, vt[UN] = {};
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const long j = i + u * 256;
+      if (j < i1) {
+        ve[u] = e[j], vr[u] = r[j];
+        if (MODE) vt[u] = t[j];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {         // (a lane past the end adds exact zeros)
+      const double de = (double)ve[u], dr = (double)vr[u];
+      g[0] += de * de;
+      g[1] += de * dr;
+      g[3] += dr * dr;
+      if (MODE) {
+        const double dn = MODE == 2 ? (double)vt[u] - dr : (double)vt[u];
+        g[2] += de * dn;
+        g[4] += dn * dn;
+        g[5] += dr * dn;
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const double s = wave_sum_d(g[c]);
+    if (lane == 0) red[c][wv] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const int c = threadIdx.x;
+    part[((long)b * gridDim.x + blockIdx.x) * 6 + c] = ((red[c][0] + red[c][1]) + red[c][2]) + red[c][3];
+  }
+}
+
+// acc[row][c] += partials of the chunks below the row's length, ascending
+__global__ void __launch_bounds__(64)
+    gram_add(const double* __restrict__ part, int nchunks, const int* __restrict__ lengths, long L, double* __restrict__ acc) {
+  const int b = blockIdx.x, c = threadIdx.x;
+  if (c >= 6) return;
+  long len = L;
+  if (lengths) {
+    const int v = lengths[b];
+    len = v < 0 ? 0 : (v > L ? L : v);
+  }
+  const int n = (int)((len + CHUNK - 1) / CHUNK);      // <= nchunks
+  const double* p = part + (long)b * nchunks * 6 + c;
+  double a = acc[b * 6 + c];
+  int k = 0;
+  for (; k + 8 <= n; k += 8) {
+    double t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[u] = p[(long)(k + u) * 6];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a += t[u];
+  }
+  for (; k < n; ++k) a += p[(long)k * 6];
+  acc[b * 6 + c] = a;
+}
+
+// 10 log10(num / den) with the reference's IEEE behaviour: den == 0 gives inf (0 / 0: NaN), and a den that cancellation
+// drove slightly negative counts as 0 (stats.hip's variance clamp); a NaN den stays a NaN
+__device__ __forceinline__ double ratio_db(double num, double den) {
+  if (den < 0.0) den = 0.0;
+  return 10.0 * log10(num / den);
+}
+
+__global__ void gram_finalize(const double* __restrict__ acc, int B, int mode, double* __restrict__ ratios,
+                              double* __restrict__ alpha) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const double* g = acc + (long)b * 6;
+  const double ee = g[0], er = g[1], en = g[2], rr = g[3], nn = g[4], rn = g[5];
+  const double nan = __builtin_nan("");
+  const double a_s = er / rr;              // an empty row: 0 / 0
+  const double target = a_s * er;
+  const double a_n = mode ? en / nn : nan;
+  const double noise = a_n * en;
+  ratios[b * 3 + 0] = ratio_db(target, ee - target);
+  ratios[b * 3 + 1] = mode ? ratio_db(target, noise) : nan;
+  ratios[b * 3 + 2] = mode ? ratio_db(target, ee - target - noise + 2.0 * a_s * a_n * rn) : nan;
+  if (alpha) alpha[b * 2 + 0] = a_s, alpha[b * 2 + 1] = a_n;
+}
+
+// counts[row] += (tp, tn, fp, fn) over the row's first len * Y values; a value is "1" when > 0.5 (logits: > 0)
+__global__ void __launch_bounds__(256)
+    confusion_partials(const float* __restrict__ pred, int logits, const float* __restrict__ target,
+                       const int* __restrict__ lengths, int T, int Y, unsigned long long* __restrict__ counts) {
+  __shared__ int red[4][4];
+  const int b = blockIdx.y;
+  const long n = (long)(lengths ? clamp_count(lengths[b], T) : T) * Y;
+  const long i0 = (long)blockIdx.x * CONF_CHUNK;
+  if (i0 >= n) return;
+  const long i1 = min(n, i0 + CONF_CHUNK);
+  const float* p = pred + (long)b * T * Y;
+  const float* y = target + (long)b * T * Y;
+  const float thr = logits ? 0.f : 0.5f;
+  int c[4] = {};
+  for (long i = i0 + threadIdx.x; i < i1; i += 256) {
+    const int hp = p[i] > thr, hy = y[i] > 0.5f;
+    c[0] += hp & hy;
+    c[1] += (hp | hy) ^ 1;
+    c[2] += hp & (hy ^ 1);
+    c[3] += (hp ^ 1) & hy;
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int v = c[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) red[k][wv] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    const int v = red[k][0] + red[k][1] + red[k][2] + red[k][3];
+    if (v) atomicAdd(counts + (long)b * 4 + k, (unsigned long long)v);
+  }
+}
+
+inline long n_chunks(long L) { return (L + CHUNK - 1) / CHUNK; }
+inline bool ok_shape(int B, long L) {
+  return B > 0 && B <= 65535 && L > 0 && L < (1L << 40) && n_chunks(L) * B < (1L << 31) / 6;
+}
+inline size_t partial_bytes(int B, long L) { return align_up((size_t)B * n_chunks(L) * 6 * sizeof(double), 256); }
+
+template <int MODE>
+void launch_partials(const float* est, long ld_est, const float* ref, long ld_ref, const float* third, long ld_third,
+                     const int* lengths, int B, long L, double* part, hipStream_t s) {
+  hipLaunchKernelGGL(gram_partials<MODE>, dim3((unsigned)n_chunks(L), B), dim3(256), 0, s, est, ld_est, ref, ld_ref, third,
+                     ld_third, lengths, L, part);
+}
+
+}  // namespace
+
+extern "C" size_t avvad_score_workspace(int B, long L) { return ok_shape(B, L) ? partial_bytes(B, L) : 0; }
+
+extern "C" int avvad_score_accumulate(const float* est, long ld_est, const float* ref, long ld_ref, const float* third,
+                                      long ld_third, int third_mode, const int* lengths, double* acc, int B, long L, void* ws,
+                                      size_t ws_bytes, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!est || !ref || !acc || !ws || third_mode < 0 || third_mode > 2 || (third_mode != 0) != (third != nullptr)) return AVVAD_EINVAL;
+  if (!ok_shape(B, L) || ld_est < L || ld_ref < L || (third_mode && ld_third < L)) return AVVAD_EINVAL;
+  if (((uintptr_t)ws & 255) || ((uintptr_t)acc & 7)) return AVVAD_EINVAL;
+  if (ws_bytes < partial_bytes(B, L)) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  double* part = (double*)ws;
+  if (third_mode == 0) launch_partials<0>(est, ld_est, ref, ld_ref, third, ld_third, lengths, B, L, part, s);
+  else if (third_mode == 1) launch_partials<1>(est, ld_est, ref, ld_ref, third, ld_third, lengths, B, L, part, s);
+  else launch_partials<2>(est, ld_est, ref, ld_ref, third, ld_third, lengths, B, L, part, s);
+  hipLaunchKernelGGL(gram_add, dim3(B), dim3(64), 0, s, part, (int)n_chunks(L), lengths, L, acc);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+extern "C" int avvad_score_finalize(const double* acc, int B, int third_mode, double* ratios, double* alpha, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!acc || !ratios || B <= 0 || third_mode < 0 || third_mode > 2) return AVVAD_EINVAL;
+  if (((uintptr_t)acc & 7) || ((uintptr_t)ratios & 7) || ((uintptr_t)alpha & 7)) return AVVAD_EINVAL;
+  hipLaunchKernelGGL(gram_finalize, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)sv, acc, B, third_mode, ratios, alpha);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+extern "C" int avvad_confusion_accumulate(const float* pred, int pred_mode, const float* target, const int* lengths,
+                                          long long* counts, int B, int T, int Y, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!pred || !target || !counts || pred_mode < 0 || pred_mode > 1 || B <= 0 || B > 65535 || T <= 0 || Y <= 0) return AVVAD_EINVAL;
+  const long chunks = ((long)T * Y + CONF_CHUNK - 1) / CONF_CHUNK;
+  if (chunks >= (1L << 31) || ((uintptr_t)counts & 7)) return AVVAD_EINVAL;
+  hipLaunchKernelGGL(confusion_partials, dim3((unsigned)chunks, B), dim3(256), 0, (hipStream_t)sv, pred, pred_mode, target, lengths,
+                     T, Y, (unsigned long long*)counts);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}

@@ -4,10 +4,55 @@
 the per-utterance scores, overall and per input SNR / noise type / speaker, printed as the reference's
 ``METRIC / AVERAGE / CONF. INT.`` tables (and returned, which the reference does not do).
 
-The speech-enhancement metrics of that file (SI-SDR components, energy ratios) belong to a different
-pipeline and are not part of this build."""
+The speech-enhancement metrics of that file, ``si_sdr_components`` (``:12-37``) and ``energy_ratios`` (``:39-60``),
+run on the GPU: one pass over the three signals sums six inner products in double (``avvad.ops.energy_ratios``,
+csrc/scores.hip) and the ratios and the two ``alpha`` follow in closed form.  Signatures are the reference's; numpy
+arrays in give numpy arrays / floats out, tensors in give tensors out.  The kernel reads float32 samples (what a wav
+file holds); float64 input is rounded to float32 first."""
 import numpy as np
 import scipy.stats
+
+
+def _on_gpu(*signals):
+    """the 1-D signals as float32 GPU tensors (on the device of the first tensor among them, else the current one)"""
+    import torch
+    dev = next((x.device for x in signals if isinstance(x, torch.Tensor) and x.is_cuda), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    out = []
+    for x in signals:
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        out.append(t.detach().to(device=dev, dtype=torch.float32).reshape(-1))
+    return out
+
+
+def si_sdr_components(s_hat, s, n):
+    """``s_hat = alpha_s s + alpha_n n + e_art`` -> (s_target, e_noise, e_art): the two projections' coefficients come
+    from the GPU's inner products, the three planes are formed elementwise from them on the inputs as given."""
+    from avvad import ops
+    e, r, v = _on_gpu(s_hat, s, n)
+    _, alpha = ops.energy_ratios(e, r, noise=v, return_alpha=True)
+    if all(isinstance(x, np.ndarray) for x in (s_hat, s, n)):
+        a_s, a_n = (float(a) for a in alpha[0].tolist())
+    else:
+        import torch
+        s_hat, s, n = (x if isinstance(x, torch.Tensor) else torch.as_tensor(x) for x in (s_hat, s, n))
+        a_s, a_n = alpha[0, 0].to(s.device), alpha[0, 1].to(n.device)
+    s_target = a_s * s
+    e_noise = a_n * n
+    return s_target, e_noise, s_hat - s_target - e_noise
+
+
+def energy_ratios(s_hat, s, n):
+    """(si_sdr, si_sir, si_sar) in dB (``si_sir`` is the reference's name for the SI-SNR: noise is the only interferer):
+    floats for numpy input, 0-dim float64 tensors on the GPU for tensor input."""
+    import torch
+    from avvad import ops
+    e, r, v = _on_gpu(s_hat, s, n)
+    ratios = ops.energy_ratios(e, r, noise=v)[0]
+    if any(isinstance(x, torch.Tensor) for x in (s_hat, s, n)):
+        return ratios[0], ratios[1], ratios[2]
+    return tuple(float(x) for x in ratios.tolist())
 
 
 def mean_confidence_interval(data, confidence=0.95, round=3):

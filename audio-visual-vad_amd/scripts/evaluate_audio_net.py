@@ -29,6 +29,9 @@ stats_dir = None          # directory holding trainset_audio_mean.npy / trainset
 wav_list = None           # e.g. sorted(glob.glob('data/subset/processed/ntcd_timit/Noisy/*/*/test/*/*.wav'))
 wav_pairs = None          # text file with one "noisy.wav clean.wav" pair per line: evaluates the noisy files and scores them
                           # against the clean files' VAD, computed on the GPU (takes the place of wav_list)
+resynth_dir = None        # y_dim = 513 with wav_list / wav_pairs: write every utterance's enhanced waveform there (<base>_enhanced.wav)
+score_dir = None          # wav_pairs: write <base>_scores.pt there -- the classifier's tp / tn / fp / fn and, with resynth_dir, SI-SDR /
+                          # SI-SIR / SI-SAR of the enhanced file and the input SI-SDR, all computed on the GPU
 WAVENET = False           # True: raw waveforms through the WaveNet encoder (the hook the reference left commented out)
 wavenet_params = dict(filter_width=2, quantization_channel=1, dilations=[2 ** i for i in range(10)] * 2,
                       en_residual_channel=32, en_dilation_channel=32, en_bottleneck_width=256,
@@ -46,4 +49,4 @@ if __name__ == '__main__':
         pairs = read_wav_pairs(wav_pairs)
         wav_list, clean_of = [n for n, _ in pairs], dict(pairs)
     evaluate_main('audio', make_model, checkpoint=classif_dir, waveform=WAVENET, out_dir=classif_data_dir, wav_list=wav_list, stats=stats,
-                  clean_of=clean_of)
+                  clean_of=clean_of, resynth_dir=resynth_dir, score_dir=score_dir)

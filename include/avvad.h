@@ -33,8 +33,8 @@
  *         copied as a whole; it may overwrite it (one backward per forward);
  *       * alignment is per pointer class, checked before anything is launched
  *         where a wrong one would be an error (AVVAD_EINVAL):
- *           workspace                      16 bytes, every entry point
- *           float64 statistics accumulator  8 bytes
+ *           workspace                      16 bytes, every entry point (avvad_score_accumulate: 256)
+ *           float64 statistics and score accumulators, score ratios, int64 confusion counts  8 bytes
  *           int64 / int32 index arrays      their natural alignment
  *           bf16 operands, avvad_lip_decode's coef, the avvad_stft_stream basis,
  *           (checked by avvad_stft_stream_fwd / _fwd_spec), the avvad_istft_stream
@@ -80,7 +80,8 @@ typedef void* avvad_stream_t; /* hipStream_t */
  * 2 = (ws, ws_bytes) in front of the stream of avvad_gemm_f32 / avvad_conv2d_*, avvad_wavenet_desc.shared_device). */
 #define AVVAD_ABI_VERSION 3   /* 3 = + avvad_conv2d_*_bf16.  Added entry points alone (the avvad_target_* labels) change no
                                  existing signature, so they keep the version: a version-3 binding still describes the
-                                 library exactly for every symbol it binds.  The avvad_stats_* section is such an addition. */
+                                 library exactly for every symbol it binds.  The avvad_stats_* section is such an addition, and so
+                                 are the avvad_score_* / avvad_confusion_* scores. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -586,6 +587,46 @@ int avvad_stft_stats(const float* wave, const int* n_frames, double* acc, const 
  * computed in double and written as float [nstat].  The clamp keeps constant data (where the difference can round to a
  * tiny negative number) from producing a NaN; n < 2 gives NaN as numpy would. */
 int avvad_stats_finalize(const double* acc, int nstat, float* mean, float* std_, avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Scores: SI-SDR / SI-SIR / SI-SAR of the enhanced speech, confusion counts of the classifier
+ * Replaces: packages/metrics.py:12-60 (si_sdr_components, energy_ratios: numpy on the host, three planes per utterance)
+ *   and the four sums of f1_loss, packages/models/utils.py:191-194.
+ * With the estimate e, the clean reference r and the noise n, every norm the reference takes is a quadratic form of six
+ * inner products G = (e.e, e.r, e.n, r.r, n.n, r.n); a_s = e.r / r.r, a_n = e.n / n.n:
+ *   |s_target|^2 = a_s e.r    |e_noise + e_art|^2 = e.e - a_s e.r    |e_noise|^2 = a_n e.n
+ *   |e_art|^2 = e.e - a_s e.r - a_n e.n + 2 a_s a_n r.n
+ *   si_sdr, si_sir, si_sar = 10 log10(|s_target|^2 / |e_noise + e_art|^2, / |e_noise|^2, / |e_art|^2)
+ * One pass reads the three signals (12 bytes per sample), widens every value to double before it is multiplied and sums
+ * G; the planes n, s_target, e_noise, e_art are never written.  An accumulator is caller-owned device memory of [B][6]
+ * doubles in the order of G.  The caller zeroes it; every call ADDS to it, so an utterance may arrive in packets.
+ * Rows are cut into chunks of AVVAD_SCORE_CHUNK samples (a function of the row length alone), per-chunk double partials
+ * go to the workspace in a fixed cross-lane and cross-wave order and are added to the accumulator in ascending chunk
+ * order: no floating-point atomics, bit-identical run to run and independent of the "max_cus" option.
+ * ---------------------------------------------------------------------- */
+#define AVVAD_SCORE_CHUNK 4096
+/* Bytes of workspace of avvad_score_accumulate; 0 on a bad shape (B outside 1..65535, L < 1). */
+size_t avvad_score_workspace(int B, long L);                       /* 0 on a bad shape */
+/* est / ref / third: B rows of L samples, each with its own row pitch in floats (ld_* >= L), so a column slice of a wider
+ * tensor is read in place; any 4-byte aligned float pointer.  third_mode 0: third must be NULL, only SI-SDR is defined;
+ * 1: third is the noise n; 2: third is the noisy mixture x and n = (double)x - (double)r is formed in the kernel.
+ * lengths: device int32 [B], clamped to [0, L]; nothing at or behind a row's length is read (NULL: L each).
+ * ws: 256-byte aligned, acc: 8-byte aligned. */
+int avvad_score_accumulate(const float* est, long ld_est, const float* ref, long ld_ref,
+                           const float* third, long ld_third, int third_mode /* 0 none, 1 noise, 2 mixture */,
+                           const int* lengths /* NULL: L each */, double* acc /* [B][6], added to */,
+                           int B, long L, void* ws, size_t ws_bytes, avvad_stream_t s);
+/* ratios[b] = (si_sdr, si_sir, si_sar) in dB, alpha[b] = (a_s, a_n), with the reference's IEEE behaviour: an empty row
+ * gives NaN, a zero denominator inf, and a denominator that cancellation drove slightly negative counts as 0.
+ * third_mode 0: si_sir, si_sar and a_n are NaN.  ratios / alpha: 8-byte aligned. */
+int avvad_score_finalize(const double* acc, int B, int third_mode, double* ratios /* [B][3] */,
+                         double* alpha /* [B][2] or NULL */, avvad_stream_t s);
+/* pred, target [B][T][Y] contiguous; target values are 0 / 1; pred_mode 0: pred values are 0 / 1, 1: pred values are
+ * logits and the prediction is logit > 0 (sigmoid > 0.5).  counts[b] = (tp, tn, fp, fn) as int64, ADDED to (64-bit
+ * integer atomics: exact in any order, no workspace); values at t >= lengths[b] (clamped to [0, T]; NULL: T each) are
+ * not read. */
+int avvad_confusion_accumulate(const float* pred, int pred_mode, const float* target, const int* lengths,
+                               long long* counts /* [B][4], added to */, int B, int T, int Y, avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Training labels from clean speech: framed-energy VAD and ideal binary mask (IBM)

@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by RUNNING THE REFERENCE in the build container.
 
     python tools/gen_golden.py [group ...]   # needs /root/reference (absent on the GPU box); groups: wavenet audio
-                                             # video av misc metrics eval targets (default: all)
+                                             # video av misc metrics eval targets scores (default: all)
 
 The reference's own classes/functions are imported from /root/reference and run
 on seeded inputs; only inputs, (small) weights and outputs are written -- data,
@@ -363,7 +363,36 @@ def gen_targets():
     save("targets", **arrs)
 
 
+# ------------------------------------------------------------------ scores (packages/metrics.py:12-60, f1_loss): the
+# reference's own functions on seeded signals s_hat = 0.7 s + g n + e (float32 samples, handed over as float64) and on
+# two small ragged label grids, row by row over the frames below each row's length.  Writes scores.npz only.
+SCORE_CASES = ((2, 1.0, 0.0, 11), (63, 0.1, 20.0, 12), (257, 1e-3, 40.0, 13), (1200, 0.1, 40.0, 14))   # L, g, artefact dB, seed
+LABEL_GRIDS = (((3, 7, 1), [7, 1, 0], 21), ((3, 5, 13), [5, 1, 0], 22))                                 # (B, T, Y), lengths, seed
+
+
+def gen_scores():
+    from packages import metrics as ref_metrics
+    import score_ref
+    arrs = {}
+    for k, (L, g, art_db, seed) in enumerate(SCORE_CASES):
+        s_hat, s, n = score_ref.mix(np.random.default_rng(seed), L, g, art_db)
+        e64, s64, n64 = (x.astype(np.float64) for x in (s_hat, s, n))
+        arrs["c%d_s_hat" % k], arrs["c%d_s" % k], arrs["c%d_n" % k] = s_hat, s, n
+        arrs["c%d_ratios" % k] = np.array(ref_metrics.energy_ratios(e64, s64, n64), dtype=np.float64)
+        arrs["c%d_components" % k] = np.stack(ref_metrics.si_sdr_components(e64, s64, n64)).astype(np.float64)
+    for k, (shape, lengths, seed) in enumerate(LABEL_GRIDS):
+        rng = np.random.default_rng(seed)
+        pred = (rng.random(shape) > 0.5).astype(np.int64)
+        target = (rng.random(shape) > 0.4).astype(np.int64)
+        f1 = np.stack([np.array([float(v) for v in ref_mutils.f1_loss(torch.from_numpy(pred[b, :n].reshape(-1)),
+                                                                       torch.from_numpy(target[b, :n].reshape(-1)))],
+                                dtype=np.float32) for b, n in enumerate(lengths)])
+        arrs["g%d_pred" % k], arrs["g%d_target" % k] = pred.astype(np.uint8), target.astype(np.uint8)
+        arrs["g%d_lengths" % k], arrs["g%d_f1" % k] = np.array(lengths, dtype=np.int32), f1
+    save("scores", **arrs)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["wavenet", "audio", "video", "av", "misc", "metrics", "eval", "targets"]
+    which = sys.argv[1:] or ["wavenet", "audio", "video", "av", "misc", "metrics", "eval", "targets", "scores"]
     for w in which:
         globals()["gen_" + w]()
