@@ -158,6 +158,11 @@ SIGNATURES = {
     "avvad_istft": (C.c_int, [FP, C.c_long, C.c_long, C.c_long, FP, FP, FP, FP, FP, C.POINTER(IstftDesc), FP, C.c_size_t, FP]),
     "avvad_resynth_workspace": (C.c_size_t, [C.POINTER(StftDesc), C.POINTER(IstftDesc)]),
     "avvad_resynth": (C.c_int, [FP, FP, FP, FP, FP, FP, C.POINTER(StftDesc), C.POINTER(IstftDesc), FP, C.c_size_t, FP]),
+    "avvad_istft_bwd_workspace": (C.c_size_t, [C.POINTER(IstftDesc)]),
+    "avvad_istft_bwd": (C.c_int, [FP, C.c_long, C.c_long, C.c_long, FP, FP, FP, FP, FP, FP, C.POINTER(IstftDesc), FP, C.c_size_t,
+                                  FP]),
+    "avvad_resynth_bwd_workspace": (C.c_size_t, [C.POINTER(StftDesc), C.POINTER(IstftDesc)]),
+    "avvad_resynth_bwd": (C.c_int, [FP, FP, FP, FP, FP, FP, FP, C.POINTER(StftDesc), C.POINTER(IstftDesc), FP, C.c_size_t, FP]),
     "avvad_stft_complex": (C.c_int, [FP, FP, C.POINTER(StftDesc), FP, C.c_size_t, FP]),
     "avvad_stats_workspace": (C.c_size_t, [C.c_size_t, C.c_int]),
     "avvad_stats_accumulate": (C.c_int, [FP, FP, FP, C.c_int, C.c_int, C.c_int, C.c_int, FP, C.c_size_t, FP]),
@@ -168,6 +173,8 @@ SIGNATURES = {
     "avvad_score_accumulate": (C.c_int, [FP, C.c_long, FP, C.c_long, FP, C.c_long, C.c_int, FP, FP, C.c_int, C.c_long, FP,
                                          C.c_size_t, FP]),
     "avvad_score_finalize": (C.c_int, [FP, C.c_int, C.c_int, FP, FP, FP]),
+    "avvad_si_sdr_loss_workspace": (C.c_size_t, [C.c_int, C.c_long]),
+    "avvad_si_sdr_loss": (C.c_int, [FP, C.c_long, FP, C.c_long, FP, FP, FP, FP, C.c_long, C.c_int, C.c_long, FP, C.c_size_t, FP]),
     "avvad_confusion_accumulate": (C.c_int, [FP, C.c_int, FP, FP, FP, C.c_int, C.c_int, C.c_int, FP]),
     "avvad_target_workspace": (C.c_size_t, [C.POINTER(TargetDesc)]),
     "avvad_target_vad": (C.c_int, [FP, FP, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),

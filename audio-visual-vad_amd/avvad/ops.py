@@ -780,7 +780,7 @@ def standardize(x, mean, std, eps=1e-8):
     return out
 
 
-# --------------------------------------------------------------------------- masked inverse STFT (csrc/istft.hip, no gradient)
+# --------------------------------------------------------------------------- masked inverse STFT (csrc/istft.hip)
 def istft_length(T, n_fft, hop, center=False):
     """Samples librosa's ``istft`` returns for T frames when no ``length`` is given: ``n_fft + hop (T - 1)``, less
     ``n_fft/2`` at either end when ``center``."""
@@ -826,6 +826,31 @@ def _row_counts(v, B, hi, name, device):
     return torch.tensor(vals, dtype=torch.int32).to(device), vals
 
 
+class MaskedInverseFn(torch.autograd.Function):
+    """The graph node of ``istft`` / ``resynth`` for a mask (mode 1) or its logits (mode 2) that require a gradient.
+    ``fwd(mask)`` is the very call the graph-less path makes, so the output keeps its bits; ``bwd(mask, dout)`` calls the
+    ``_bwd`` entry point.  The spectrum / waveform is data: no gradient for it, and no double backward."""
+
+    @staticmethod
+    def forward(ctx, mask, fwd, bwd):
+        ctx.bwd = bwd
+        ctx.save_for_backward(mask)
+        return fwd(mask)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        (mask,) = ctx.saved_tensors
+        return ctx.bwd(mask, _dev(dout, "dout")).view(mask.shape), None, None
+
+
+def _masked_inverse(mask, mode, fwd, bwd):
+    """``fwd(mask)``, with a graph when the mask asks for one (modes 1 and 2 only: 0 has no mask, 3 no derivative)"""
+    if mode in (1, 2) and mask.requires_grad and torch.is_grad_enabled():
+        return MaskedInverseFn.apply(mask, fwd, bwd)
+    return fwd(mask)
+
+
 def istft(spec, n_fft=1024, hop=256, mask=None, mask_mode=None, n_frames=None, length=None, center=False, scale=None):
     """Masked inverse STFT on the GPU (librosa's ``istft``: Hann synthesis window, overlap-add, window sum-of-squares
     normalisation).  ``spec``: (B,T,F,2) (re, im), or ONE utterance in the legacy (F,T,2) layout ``stft_pytorch`` returns,
@@ -833,7 +858,8 @@ def istft(spec, n_fft=1024, hop=256, mask=None, mask_mode=None, n_frames=None, l
     the default when a mask is given), 2 (``sigmoid(mask)``) or 3 (``mask > 0``); the product is formed while the spectrum
     is loaded.  ``n_frames``: frames per row (default T); ``length``: output samples, one value or one per row (default
     ``istft_length`` of the row's frames); ``center`` trims ``n_fft/2`` at the start; ``scale`` (B,) multiplies each row.
-    Returns (B, Lout); samples past a row's length are zero."""
+    Returns (B, Lout); samples past a row's length are zero.  A mask (mode 1) or logits (mode 2) that require a gradient
+    get one (avvad_istft_bwd); the spectrum is data and gets none."""
     legacy = False
     if isinstance(spec, torch.Tensor) and spec.is_complex():
         if spec.dtype != torch.complex64 or spec.dim() != 2:
@@ -873,12 +899,25 @@ def istft(spec, n_fft=1024, hop=256, mask=None, mask_mode=None, n_frames=None, l
     len_dev = None if min(lens) == Lout else torch.tensor(lens, dtype=torch.int32).to(spec.device)
     sc = None if scale is None else _row_vector(scale, B, "scale")
     d = L.IstftDesc(B, T, n_fft, hop, n_fft // 2 if center else 0, Lout, mode)
-    out = torch.empty(B, Lout, dtype=torch.float32, device=spec.device)
-    with torch.cuda.device(spec.device):
-        ws = _ws(L.lib().avvad_istft_workspace(C.byref(d)), spec.device)
-        L.check(L.lib().avvad_istft(L.ptr(spec), strides[0], strides[1], strides[2], L.ptr(m), L.ptr(nf_dev), L.ptr(len_dev),
-                                    L.ptr(sc), L.ptr(out), C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()), "avvad_istft")
-    return out
+
+    def fwd(m):
+        m = None if m is None else m.detach()
+        out = torch.empty(B, Lout, dtype=torch.float32, device=spec.device)
+        with torch.cuda.device(spec.device):
+            ws = _ws(L.lib().avvad_istft_workspace(C.byref(d)), spec.device)
+            L.check(L.lib().avvad_istft(L.ptr(spec), strides[0], strides[1], strides[2], L.ptr(m), L.ptr(nf_dev), L.ptr(len_dev),
+                                        L.ptr(sc), L.ptr(out), C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()), "avvad_istft")
+        return out
+
+    def bwd(m, dout):
+        dmask = torch.empty(B, T, F, dtype=torch.float32, device=spec.device)
+        with torch.cuda.device(spec.device):
+            ws = _ws(L.lib().avvad_istft_bwd_workspace(C.byref(d)), spec.device)
+            L.check(L.lib().avvad_istft_bwd(L.ptr(spec), strides[0], strides[1], strides[2], L.ptr(m), L.ptr(nf_dev), L.ptr(len_dev),
+                                            L.ptr(sc), L.ptr(dout), L.ptr(dmask), C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()),
+                    "avvad_istft_bwd")
+        return dmask
+    return _masked_inverse(m, mode, fwd, bwd)
 
 
 def resynth(wave, mask, mask_mode=1, n_fft=1024, hop=256, sample_lengths=None, pad_at_end=True, fs=16e3, scale=None):
@@ -887,7 +926,8 @@ def resynth(wave, mask, mask_mode=1, n_fft=1024, hop=256, sample_lengths=None, p
     B real lengths (default L); ``mask`` (B,T,F) with T = ``n_frames(L)``, read by ``mask_mode`` as in ``istft`` (``None``
     with mode 0).  Row b uses its own ``n_frames(L_b)`` frames and comes back with exactly L_b samples, zero behind them
     (cropped where the frames run past the utterance -- the end pad -- and zero-filled where they stop short of it).
-    Returns (B, L)."""
+    Returns (B, L).  A mask (mode 1) or logits (mode 2) that require a gradient get one (avvad_resynth_bwd, which
+    transforms the wave again); the wave is data and gets none."""
     w, w2 = _wave2d(wave)
     B, Ls = w2.shape
     n_fft, hop = int(n_fft), int(hop)
@@ -903,11 +943,22 @@ def resynth(wave, mask, mask_mode=1, n_fft=1024, hop=256, sample_lengths=None, p
     sc = None if scale is None else _row_vector(scale, B, "scale")
     sd = L.StftDesc(B, Ls, n_fft, hop, T, 0.0)
     d = L.IstftDesc(B, T, n_fft, hop, 0, Ls, mode)
-    ws = _ws(L.lib().avvad_resynth_workspace(C.byref(sd), C.byref(d)), w.device)
-    out = torch.empty(B, Ls, dtype=torch.float32, device=w.device)
-    L.check(L.lib().avvad_resynth(L.ptr(w2), L.ptr(m), L.ptr(nf_dev), L.ptr(len_dev), L.ptr(sc), L.ptr(out), C.byref(sd), C.byref(d),
-                                  L.ptr(ws), ws.numel() * 4, _stream()), "avvad_resynth")
-    return out
+
+    def fwd(m):
+        m = None if m is None else m.detach()
+        ws = _ws(L.lib().avvad_resynth_workspace(C.byref(sd), C.byref(d)), w.device)
+        out = torch.empty(B, Ls, dtype=torch.float32, device=w.device)
+        L.check(L.lib().avvad_resynth(L.ptr(w2), L.ptr(m), L.ptr(nf_dev), L.ptr(len_dev), L.ptr(sc), L.ptr(out), C.byref(sd),
+                                      C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()), "avvad_resynth")
+        return out
+
+    def bwd(m, dout):
+        ws = _ws(L.lib().avvad_resynth_bwd_workspace(C.byref(sd), C.byref(d)), w.device)
+        dmask = torch.empty(B, T, F, dtype=torch.float32, device=w.device)
+        L.check(L.lib().avvad_resynth_bwd(L.ptr(w2), L.ptr(m), L.ptr(nf_dev), L.ptr(len_dev), L.ptr(sc), L.ptr(dout), L.ptr(dmask),
+                                          C.byref(sd), C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()), "avvad_resynth_bwd")
+        return dmask
+    return _masked_inverse(m, mode, fwd, bwd)
 
 
 # --------------------------------------------------------------------------- streaming STFT front-end (csrc/stft_stream.hip)
@@ -1250,6 +1301,64 @@ def energy_ratios(est, ref, noise=None, mixture=None, lengths=None, return_alpha
     acc = score_state(1 if est.dim() == 1 else est.shape[0], est.device)
     score_accumulate(acc, est, ref, noise, mixture, lengths)
     return score_finalize(acc, "noise" if noise is not None else "mixture" if mixture is not None else "none", return_alpha)
+
+
+# --------------------------------------------------------------------------- SI-SDR loss (csrc/scores.hip)
+class SiSdrLossFn(torch.autograd.Function):
+    """-sum_b SI-SDR_b over each row's window, and its gradient in the estimate from the same call (avvad_si_sdr_loss)."""
+
+    @staticmethod
+    def forward(ctx, est, ld_est, ref, ld_ref, lens32, head, Lw):
+        B, Ls = est.shape
+        e, r = est.detach()[:, head:head + Lw], ref[:, head:head + Lw]
+        loss = torch.empty(1, dtype=torch.float32, device=est.device)
+        ratios = torch.empty(B, dtype=torch.float64, device=est.device)
+        dest = torch.empty(B, Ls, dtype=torch.float32, device=est.device)
+        ws = _ws(L.lib().avvad_si_sdr_loss_workspace(B, Lw), est.device)
+        L.check(L.lib().avvad_si_sdr_loss(L.ptr(e), ld_est, L.ptr(r), ld_ref, L.ptr(lens32), L.ptr(loss), L.ptr(ratios),
+                                          L.ptr(dest[:, head:]), Ls, B, Lw, L.ptr(ws), ws.numel() * 4, _stream()), "avvad_si_sdr_loss")
+        if head:
+            dest[:, :head].zero_()                      # (the call wrote columns head .. L - 1)
+        ctx.save_for_backward(dest)
+        ctx.mark_non_differentiable(ratios)
+        return loss.view(()), ratios
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss, _dratios):
+        (dest,) = ctx.saved_tensors
+        g = dest.clone()
+        L.check(L.lib().avvad_scale_by_device_scalar(L.ptr(g), L.ptr(_dev(dloss, "dloss").view(1)), g.numel(), _stream()),
+                "avvad_scale_by_device_scalar")
+        return g, None, None, None, None, None, None
+
+
+def si_sdr_loss(est, ref, lengths=None, skip_head=0, skip_tail=0, return_ratios=False):
+    """``-sum_b SI-SDR_b`` of a ragged batch as a float32 scalar, differentiable in ``est``: est, ref (B, L) (or (L,)),
+    ref rows may be longer.  Row b's window is samples ``[skip_head, lengths[b] - skip_tail)`` (``lengths`` default L);
+    the gradient is zero outside it and a row whose window is empty adds nothing.  The trainers skip ``n_fft - hop``
+    samples at either end, where ``center=False`` resynthesis divides by a window sum that falls to 1e-10.  The sums are
+    those of ``energy_ratios`` (double, fixed order): bit-identical run to run.  ``return_ratios``: also the (B,) float64
+    SI-SDR per row in dB (NaN for an empty window)."""
+    if not isinstance(est, torch.Tensor) or not est.is_cuda or est.dim() not in (1, 2):
+        raise L.AvvadError("est must be a (B, L) or (L,) GPU tensor: the AV-VAD hot path has no CPU fallback")
+    e = est.view(1, -1) if est.dim() == 1 else est
+    if e.dtype != torch.float32:
+        raise L.AvvadError("est must be float32, got %s" % e.dtype)
+    if e.stride(1) != 1 or (e.shape[0] > 1 and e.stride(0) < e.shape[1]):
+        e = e.contiguous()
+    B, Ls = e.shape
+    r, ld_r = _score_rows(ref.detach() if isinstance(ref, torch.Tensor) else ref, "ref", B, Ls)
+    head, tail = int(skip_head), int(skip_tail)
+    if head < 0 or tail < 0:
+        raise L.AvvadError("skip_head / skip_tail must not be negative, got %d / %d" % (head, tail))
+    lens = [Ls] * B if lengths is None else _ints(lengths, B, Ls, "lengths must hold %d values within 0..%d" % (B, Ls))
+    win = [max(0, n - tail - head) for n in lens]
+    head = min(head, Ls - 1)
+    Lw = Ls - head
+    lens32 = torch.tensor(win, dtype=torch.int32).to(e.device)
+    loss, ratios = SiSdrLossFn.apply(e, e.stride(0) if B > 1 else Ls, r, ld_r, lens32, head, Lw)
+    return (loss, ratios) if return_ratios else loss
 
 
 def confusion_counts(pred, target, lengths=None, logits=False, counts=None):

@@ -8,7 +8,8 @@ reference's Python loops over the batch replaced by single fused calls, ``nn.Dat
 GPU + bucketed RCCL all-reduce, and a synthetic data source for training (the reference's HDF5 readers are out of scope,
 SURVEY.md 2.1; h5py and torchaudio are not installed in this image), (noisy, clean) wav pairs whose labels are computed
 on the GPU from the clean files (``WavPairs``, ``wav_pair_step``), or such pairs with the utterance's lip-region DCT
-coefficients, decoded to video frames on the GPU (``AVFiles``, ``av_file_step``).  The per-utterance evaluator of the audio network
+coefficients, decoded to video frames on the GPU (``AVFiles``, ``av_file_step``).  On wav pairs a 513-bin mask model can
+be trained on the SI-SDR of its resynthesised waveform instead of the BCE (``objective="si_sdr"``, ``SiSdrObjective``).  The per-utterance evaluator of the audio network
 (``process_utt``, ``evaluate_audio_net.py:107-180``) runs the reference's whole chain on real waveforms: peak
 normalisation -> STFT -> power -> log -> crop to the label length -> standardise -> classifier -> sigmoid -> threshold."""
 import os
@@ -167,12 +168,13 @@ def labels_for_ydim(y_dim):
     raise ValueError("y_dim %d: wav-pair labels are VAD (y_dim 1) or IBM (y_dim 513)" % y_dim)
 
 
-def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS):
+def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS, waves=False):
     """A ``WavPairs.collate`` batch -> (frame lengths, features (B, T, 513), target (B, T, y_dim)) on the GPU: every file
     peak-normalised on its own (``x / max|x|``, as the reference normalises each file it reads), log-power STFT features of
     the noisy file (standardised when ``stats`` hold the train-set statistics), labels of the clean file with the training
     pipeline's settings (64 ms, hop 0.25, ``center=False``, end pad; create_audio_train_files.py:44-60) and the same
-    frame counts."""
+    frame counts.  ``waves``: a fourth value, (peak-normalised noisy (B, L), clean (B, L), sample lengths), what a loss on
+    the resynthesised waveform needs."""
     lens, noisy, clean = batch
     noisy = ops.peak_normalize(noisy.to(device, non_blocking=True))
     clean = ops.peak_normalize(clean.to(device, non_blocking=True))
@@ -187,7 +189,52 @@ def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, ho
     T = target.shape[1]
     if x.shape[1] != T:                 # the longest row's frame count on both sides (same lengths, same rule)
         raise RuntimeError("feature frames %d != label frames %d" % (x.shape[1], T))
+    if waves:
+        return frames.to(device), x, target, (noisy, clean, [int(n) for n in lens])
     return frames.to(device), x, target
+
+
+OBJECTIVES = ("bce", "si_sdr")
+
+
+def check_objective(objective, kind, waveform, wav_pairs, y_dim=None):
+    """``objective`` "si_sdr" trains a 513-bin mask model of the audio network on wav pairs; anything else is a
+    ValueError (``y_dim`` None: not known yet)."""
+    if objective not in OBJECTIVES:
+        raise ValueError("objective %r: one of %s" % (objective, ", ".join(OBJECTIVES)))
+    if objective == "si_sdr":
+        if kind != "audio" or waveform or wav_pairs is None:
+            raise ValueError("objective 'si_sdr' trains the audio network on spectrograms of wav_pairs: it resynthesises "
+                             "the noisy file through the model's mask")
+        if y_dim is not None and y_dim != 513:
+            raise ValueError("objective 'si_sdr' needs a 513-bin mask head (y_dim 513), got y_dim %d" % y_dim)
+
+
+class SiSdrObjective:
+    """The step of ``objective="si_sdr"``: ``prepare`` is ``wav_pair_step`` and keeps the batch's waves, ``loss`` resynthesises
+    the noisy wave through sigmoid(logits) (``ops.resynth``, mask_mode 2) and returns minus the summed SI-SDR against the
+    clean wave (``ops.si_sdr_loss``) -- summed over the batch like the BCE -- and the batch's mean SI-SDR for the log line.
+    The first and last ``n_fft - hop`` samples of every utterance stay out of the loss: with ``center=False`` they divide by
+    a window sum of squares that falls to 1e-10, and a masked estimate there would own it."""
+
+    def __init__(self, device, labels, stats, fs=16e3, wlen_sec=64e-3, hop_percent=0.25):
+        self.device, self.labels, self.stats = device, labels, stats      # stats: a callable, read at every step
+        self.fs, self.wlen_sec, self.hop_percent = fs, wlen_sec, hop_percent
+        self.n_fft = int(wlen_sec * fs)
+        self.hop = int(hop_percent * self.n_fft)
+        self.waves = None
+
+    def prepare(self, batch):
+        frames, x, target, self.waves = wav_pair_step(batch, self.device, self.labels, self.stats(), self.fs, self.wlen_sec,
+                                                      self.hop_percent, waves=True)
+        return frames, x, target
+
+    def loss(self, logits, y, lengths):
+        noisy, clean, lens = self.waves
+        est = ops.resynth(noisy, logits, mask_mode=2, n_fft=self.n_fft, hop=self.hop, sample_lengths=lens, pad_at_end=True, fs=self.fs)
+        skip = self.n_fft - self.hop
+        loss, ratios = ops.si_sdr_loss(est, clean, lens, skip, skip, return_ratios=True)
+        return loss, "  si-sdr %.2f dB" % float(torch.nanmean(ratios))
 
 
 def rank_shard(n, rank, world):
@@ -348,9 +395,11 @@ def forward_batch(model, kind, batch, device, waveform, stats=None, chunk_frames
     return lengths, model(a, v, lengths), y
 
 
-def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log=None, log_interval=10, stats=None, prepare=None):
+def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log=None, log_interval=10, stats=None, prepare=None,
+              loss_fn=None):
     """``prepare`` (wav pairs, av files): batch -> (lengths, the model's inputs ..., target) on the GPU, the model's forward
-    follows."""
+    follows.  ``loss_fn`` (logits, target, lengths) -> (loss summed over the batch, text for the log line); without one
+    the summed masked BCE."""
     from packages.models.utils import batch_binary_cross_entropy, batch_f1
     train = opt is not None
     model.train(train)
@@ -361,7 +410,11 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
         else:
             lengths, *x, y = prepare(batch)
             logits = model(*x, lengths)
-        loss = batch_binary_cross_entropy(logits, y, lengths, EPS)       # sum over sequences (train_AV_net.py:298-302)
+        note = ""
+        if loss_fn is None:
+            loss = batch_binary_cross_entropy(logits, y, lengths, EPS)       # sum over sequences (train_AV_net.py:298-302)
+        else:
+            loss, note = loss_fn(logits, y, lengths)
         if train:
             loss.backward()
             if reducer is not None:
@@ -374,14 +427,15 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
             tot[k] += float(v)
         tot["n"] += 1
         if log and i % log_interval == 0:
-            log("%s batch %4d  loss %.3f  acc %.3f  prec %.3f  rec %.3f  f1 %.3f"
-                % ("train" if train else "valid", i, float(loss.detach()), float(acc), float(prec), float(rec), float(f1)))
+            log("%s batch %4d  loss %.3f  acc %.3f  prec %.3f  rec %.3f  f1 %.3f%s"
+                % ("train" if train else "valid", i, float(loss.detach()), float(acc), float(prec), float(rec), float(f1), note))
     n = max(tot.pop("n"), 1)
     return {k: v / n for k, v in tot.items()}
 
 
 def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_size=16, n_items=64, lr=1e-4,
-               freeze_features=False, out_dir=None, stats=None, wav_pairs=None, compute_stats=False, av_files=None):
+               freeze_features=False, out_dir=None, stats=None, wav_pairs=None, compute_stats=False, av_files=None,
+               objective="bce"):
     """The body of ``scripts/train_{audio,video,AV}_net.py``; settings come from the caller's module-level constants
     (the reference's "config system") and may be overridden by AVVAD_* environment variables.
 
@@ -395,7 +449,13 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
 
     ``av_files`` (video and AV networks, ``kind`` "video" / "AV", spectrogram input): a list of (noisy wav, clean wav,
     coefficient .npy) triples or a text file of them (``AVFiles``); the lip frames are decoded on the GPU in the step
-    (``av_file_step``).  ``compute_stats`` then also fills the video scalars (``av_file_stats``)."""
+    (``av_file_step``).  ``compute_stats`` then also fills the video scalars (``av_file_stats``).
+
+    ``objective``: "bce" (the summed masked BCE against the labels) or, with ``wav_pairs`` and a y_dim 513 head, "si_sdr":
+    minus the SI-SDR of the noisy file resynthesised through sigmoid(logits) against the clean file (``SiSdrObjective``);
+    the F1 figures against the IBM label stay in the log.  AVVAD_OBJECTIVE overrides it."""
+    objective = os.environ.get("AVVAD_OBJECTIVE", objective)
+    check_objective(objective, kind, waveform, wav_pairs)
     if av_files is not None and (kind.lower() not in ("video", "av") or waveform or wav_pairs is not None):
         raise ValueError("av_files trains the video or the AV network on spectrograms and lip coefficients; give either "
                          "wav_pairs (audio) or av_files, and no WaveNet waveform input")
@@ -410,6 +470,7 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     torch.cuda.set_device(device)
     torch.manual_seed(0)
     model = make_model().to(device)
+    check_objective(objective, kind, waveform, wav_pairs, getattr(model, "y_dim", None))
     if freeze_features:                      # train_AV_net.py:241-245
         for name, child in model.named_children():
             if name == "features":
@@ -418,7 +479,7 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     opt = FlatAdam(model.parameters(), lr=lr, betas=(0.9, 0.999))
     reducer = avd.BucketReducer(opt.params, opt.flat_grad, opt.offsets,
                                 names=[n for n, q in model.named_parameters() if q.requires_grad]) if world > 1 else None
-    prepare = None
+    prepare = loss_fn = None
     if av_files is not None:
         pairs = AVFiles(av_files)
         labels = labels_for_ydim(model.y_dim)
@@ -439,6 +500,9 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         collate = WavPairs.collate
         ds_train = ds_valid = torch.utils.data.Subset(pairs, range(rank, len(pairs), world))
         prepare = lambda batch: wav_pair_step(batch, device, labels, stats)   # noqa: E731
+        if objective == "si_sdr":
+            step = SiSdrObjective(device, labels, lambda: stats)
+            prepare, loss_fn = step.prepare, step.loss
     mk = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=batch_size // world or 1, shuffle=sh, collate_fn=collate)
     out_dir = out_dir or os.path.join("models", model_name)
     if rank == 0:
@@ -474,9 +538,10 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         log("- Train-set statistics over {} utterances in {:.1f} s, saved in {}".format(len(pairs), time.perf_counter() - t0, out_dir))
     for epoch in range(1, epochs + 1):
         t0 = time.perf_counter()
-        tr = run_epoch(model, kind, mk(ds_train, True), device, waveform, opt, reducer, log, stats=stats, prepare=prepare)
+        tr = run_epoch(model, kind, mk(ds_train, True), device, waveform, opt, reducer, log, stats=stats, prepare=prepare,
+                       loss_fn=loss_fn)
         with torch.no_grad():
-            va = run_epoch(model, kind, mk(ds_valid, False), device, waveform, stats=stats, prepare=prepare)
+            va = run_epoch(model, kind, mk(ds_valid, False), device, waveform, stats=stats, prepare=prepare, loss_fn=loss_fn)
         log("====> Epoch: {:2d}  train loss {:.3f} f1 {:.3f} | valid loss {:.3f} f1 {:.3f} | {:.1f} s".format(
             epoch, tr["loss"], tr["f1"], va["loss"], va["f1"], time.perf_counter() - t0))
         if rank == 0:                       # same checkpoint naming as train_AV_net.py:443-448

@@ -8,6 +8,10 @@
 // count as the forward transform.  The mask (given, sigmoid of a logit, or logit > 0) is applied while the A operand is
 // loaded, so the masked spectrum never exists in memory; the spectrum is read through element strides, so the STFT's own
 // workspace rows, a batched (B,T,F,2) tensor and the legacy (F,T,2) view all go in as they are.
+//
+// For training (avvad_istft_bwd, avvad_resynth_bwd): the adjoint with respect to the mask or its logits.  The inverse basis is
+// w_f / N times the forward one, so the adjoint of the inverse GEMM is frames::framed_dft applied to the normalised cotangent
+// q (overlap_add_adjoint), followed by one epilogue pass (mask_gradient); the spectrum is data and has no gradient.
 #include "frames.h"
 
 namespace {
@@ -79,6 +83,70 @@ __global__ void overlap_add(const float* __restrict__ Y, const double* __restric
   }
 }
 
+// ---- the adjoint of the masked inverse with respect to the mask (avvad_istft_bwd, avvad_resynth_bwd)
+// win2[n] = hann[n]^2 as doubles, idft_basis's own values
+__global__ void hann_squares(double* __restrict__ win2, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n < N) {
+    const double win = frames::hann(n, N);
+    win2[n] = win * win;
+  }
+}
+
+// The adjoint of overlap_add: q[b][s'] = scale[b] dout[b][s' - start] / w(s') where the forward wrote a sum, w the float
+// overlap_add divides by (the same ascending double sum over the row's own frames); exactly 0 everywhere else, so nothing
+// of dout at or behind the row's length is read.  One thread per sample of q [B][Lq], Lq = (T - 1) hop + n_fft.
+__global__ void overlap_add_adjoint(const float* __restrict__ dout, const double* __restrict__ win2,
+                                    const int* __restrict__ n_frames, const int* __restrict__ out_len,
+                                    const float* __restrict__ scale, float* __restrict__ q, int B, int T, int N, int hop, int start,
+                                    int pitch, long Lq) {
+  const long n_el = (long)B * Lq;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / Lq);
+    const long sp = i % Lq, s = sp - start;
+    const int nf = n_frames ? clamp_count(n_frames[b], T) : T;
+    int len = out_len ? out_len[b] : pitch;
+    len = len > pitch ? pitch : len;
+    const long natural = nf > 0 ? (long)N + (long)hop * (nf - 1) - start : 0;
+    float g = 0.f;
+    if (s >= 0 && s < len && s < natural) {
+      const frames::Cover c = frames::covering(sp, N, hop, nf - 1);
+      double wss = 0.0;
+      for (int t = (int)c.t0; t <= (int)c.t1; ++t) wss += win2[(int)(sp - (long)t * hop)];
+      g = dout[(long)b * pitch + s];
+      if (scale) g *= scale[b];
+      g = frames::ola_normalise(g, wss);
+    }
+    q[i] = g;
+  }
+}
+
+// dmask[b,t,f] = (w_f / N) (G_re S_re + G_im S_im), G = framed_dft(q): the adjoint of A = S g(mask) under Y = A Winv, whose
+// basis is (w_f / N) times the forward transform's.  SIG (mode 2): times sigmoid'(logit).  Frames t >= n_frames[b] are
+// exact zeros and neither their spectrum nor their mask is read (q is not zero under them; they may hold anything).
+template <bool SIG>
+__global__ void mask_gradient(const float* __restrict__ G, int ld, const float* __restrict__ S, unsigned sb, unsigned st, unsigned sf,
+                              const float* __restrict__ mask, const int* __restrict__ n_frames, float* __restrict__ dmask, int B,
+                              int T, int F, int N) {
+  const long n_el = (long)B * T * F;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
+    const unsigned f = (unsigned)(i % F), x = (unsigned)(i / F), b = x / (unsigned)T, t = x - b * (unsigned)T;
+    const int nf = n_frames ? clamp_count(n_frames[b], T) : T;
+    float r = 0.f;
+    if ((int)t < nf) {
+      const float2 g = *reinterpret_cast<const float2*>(G + (long)x * ld + 2 * f);
+      const float* sp = S + (b * sb + t * st + f * sf);
+      const float wf = (float)(((f == 0 || 2 * (int)f == N) ? 1.0 : 2.0) / (double)N);
+      r = wf * (g.x * sp[0] + g.y * sp[1]);
+      if constexpr (SIG) {
+        const float sg = 1.f / (1.f + expf(-mask[i]));
+        r *= sg * (1.f - sg);
+      }
+    }
+    dmask[i] = r;
+  }
+}
+
 using frames::grid1;
 
 static bool ok_desc(const avvad_istft_desc* d) {
@@ -127,6 +195,54 @@ static int inverse(const float* spec, long sb, long st, long sf, const float* ma
   if (rc) return rc;
   hipLaunchKernelGGL(overlap_add, dim3(grid1((long)d->B * d->out_pitch)), dim3(256), 0, s, Y, win2, n_frames, out_len, scale, out,
                      d->B, d->T, N, d->hop, d->start, d->out_pitch);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+// workspace of the adjoint: [W n_fft x ld][G B*T x ld][q B x Lq][win2 n_fft doubles][slab]; `W`: a forward basis the
+// caller's own carve-up already holds (avvad_resynth_bwd), else it comes first
+struct BwdCarve {
+  frames::SpecWs g;
+  size_t q, win2, total;
+  long Lq;
+};
+static BwdCarve bwd_carve(const avvad_istft_desc* d, size_t base, const frames::SpecWs* fwd) {
+  BwdCarve c;
+  c.Lq = (long)(d->T - 1) * d->hop + d->n_fft;
+  c.g = frames::spec_ws(d->n_fft, (size_t)d->B * d->T, base);
+  if (fwd) {
+    c.g.W = fwd->W;
+    c.g.S_end -= c.g.S - base;
+    c.g.S = base;
+  }
+  c.q = c.g.S_end;
+  c.win2 = c.q + align_up((size_t)d->B * c.Lq, 64);
+  c.g.slab = c.win2 + align_up((size_t)2 * d->n_fft, 64);
+  c.total = c.g.total = c.g.slab + igemm::SLAB_FLOATS;
+  return c;
+}
+static bool ok_bwd(const avvad_istft_desc* d) {
+  return ok_desc(d) && (d->mask_mode == 1 || d->mask_mode == 2) &&
+         (long)d->B * ((long)(d->T - 1) * d->hop + d->n_fft) < (1L << 31);
+}
+static int adjoint(const float* spec, long sb, long st, long sf, const float* mask, const int* n_frames, const int* out_len,
+                   const float* scale, const float* dout, float* dmask, const avvad_istft_desc* d, float* ws, const BwdCarve& c,
+                   hipStream_t s) {
+  const int N = d->n_fft, F = N / 2 + 1;
+  float* q = ws + c.q;
+  double* win2 = reinterpret_cast<double*>(ws + c.win2);
+  hipLaunchKernelGGL(hann_squares, dim3((N + 255) / 256), dim3(256), 0, s, win2, N);
+  hipLaunchKernelGGL(overlap_add_adjoint, dim3(grid1((long)d->B * c.Lq)), dim3(256), 0, s, dout, win2, n_frames, out_len, scale, q,
+                     d->B, d->T, N, d->hop, d->start, d->out_pitch, c.Lq);
+  const int rc = frames::framed_dft(q, c.Lq, d->B, d->T, N, d->hop, ws, c.g, s);
+  if (rc) return rc;
+  const dim3 grid(grid1((long)d->B * d->T * F));
+  if (d->mask_mode == 2)
+    hipLaunchKernelGGL(mask_gradient<true>, grid, dim3(256), 0, s, ws + c.g.S, c.g.ld, spec, (unsigned)sb, (unsigned)st, (unsigned)sf,
+                       mask, n_frames, dmask, d->B, d->T, F, N);
+  else
+    hipLaunchKernelGGL(mask_gradient<false>, grid, dim3(256), 0, s, ws + c.g.S, c.g.ld, spec, (unsigned)sb, (unsigned)st, (unsigned)sf,
+                       mask, n_frames, dmask, d->B, d->T, F, N);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
@@ -182,4 +298,51 @@ extern "C" int avvad_resynth(const float* wave, const float* mask, const int* n_
   const int rc = frames::framed_dft(wave, sd->L, sd->B, sd->T, sd->n_fft, sd->hop, ws, f, s);
   if (rc) return rc;
   return inverse(ws + f.S, (long)sd->T * f.ld, f.ld, 2, mask, n_frames, out_len, scale, out, d, ws, c, s);
+}
+
+extern "C" size_t avvad_istft_bwd_workspace(const avvad_istft_desc* d) {
+  if (!ok_bwd(d)) return 0;
+  return bwd_carve(d, 0, nullptr).total * sizeof(float);
+}
+
+extern "C" int avvad_istft_bwd(const float* spec, long stride_b, long stride_t, long stride_f, const float* mask,
+                               const int* n_frames, const int* out_len, const float* scale, const float* dout, float* dmask,
+                               const avvad_istft_desc* d, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!spec || !mask || !dout || !dmask || !wsv || !ok_bwd(d) || !ok_strides(d, stride_b, stride_t, stride_f) ||
+      ws_misaligned(wsv))
+    return AVVAD_EINVAL;
+  if (ws_bytes < avvad_istft_bwd_workspace(d)) return AVVAD_EWORKSPACE;
+  return adjoint(spec, stride_b, stride_t, stride_f, mask, n_frames, out_len, scale, dout, dmask, d, (float*)wsv,
+                 bwd_carve(d, 0, nullptr), (hipStream_t)sv);
+}
+
+// the fused adjoint's workspace: the forward transform's [W][S] of the wave, then the adjoint's carve-up, which shares W
+static BwdCarve fused_bwd(const avvad_istft_desc* d, frames::SpecWs* f) {
+  *f = frames::spec_ws(d->n_fft, (size_t)d->B * d->T);
+  const BwdCarve c = bwd_carve(d, f->S_end, f);
+  f->slab = c.g.slab;
+  return c;
+}
+
+extern "C" size_t avvad_resynth_bwd_workspace(const avvad_stft_desc* sd, const avvad_istft_desc* d) {
+  if (!ok_pair(sd, d) || !ok_bwd(d)) return 0;
+  frames::SpecWs f;
+  return fused_bwd(d, &f).total * sizeof(float);
+}
+
+// framed_dft(wave) again (the forward kept no spectrum), then the adjoint: two forward-size GEMMs
+extern "C" int avvad_resynth_bwd(const float* wave, const float* mask, const int* n_frames, const int* out_len,
+                                 const float* scale, const float* dout, float* dmask, const avvad_stft_desc* sd,
+                                 const avvad_istft_desc* d, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!wave || !mask || !dout || !dmask || !wsv || !ok_pair(sd, d) || !ok_bwd(d) || ws_misaligned(wsv)) return AVVAD_EINVAL;
+  if (ws_bytes < avvad_resynth_bwd_workspace(sd, d)) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  float* ws = (float*)wsv;
+  frames::SpecWs f;
+  const BwdCarve c = fused_bwd(d, &f);
+  const int rc = frames::framed_dft(wave, sd->L, sd->B, sd->T, sd->n_fft, sd->hop, ws, f, s);
+  if (rc) return rc;
+  return adjoint(ws + f.S, (long)sd->T * f.ld, f.ld, 2, mask, n_frames, out_len, scale, dout, dmask, d, ws, c, s);
 }

@@ -27,6 +27,10 @@
 //   gram_add: acc[row][c] += the row's partials in ascending chunk order (lane c < 6 of one wave per row); only the
 //        chunks below the row's length are read.
 //   gram_finalize: one thread per row, acc -> the three ratios in dB (and the two alpha).
+//   sisdr_coefficients, sisdr_gradient (avvad_si_sdr_loss, training): gram_partials<0> and gram_add as above into a zeroed
+//        accumulator of the workspace, then one workgroup turns each row's three sums into SI-SDR and the two coefficients
+//        of its gradient (double, rounded once) and sums the loss in ascending row order; the gradient c1 ref + c2 est is
+//        one pass on gram_partials' grid (chunk, row), exact zeros behind the row's length.
 //   confusion_partials: workgroup (chunk of the row's len * Y values, row) counts in integers and adds its four counts to
 //        counts[row][0..3] with 64-bit integer atomics (exact in any order: no workspace).
 // No floating-point atomics, and the chunking depends on the row length alone: bit-identical run to run and whatever the
@@ -191,6 +195,62 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// ---- the SI-SDR loss (avvad_si_sdr_loss): gram_partials<0> / gram_add's sums, then two coefficients per row and one pass
+__global__ void zero_doubles(double* __restrict__ p, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = 0.0;
+}
+
+// One workgroup.  Per row, with a = e.r, r = r.r, e = e.e, P = a^2 / r, D = e - P: sdr[b] = gram_finalize's SI-SDR, and the
+// gradient of -SI-SDR in the estimate is c1 ref + c2 est, c2 = (20 / ln 10) / D, c1 = -(20 / ln 10) (1 / a + a / (r D)),
+// formed in double and rounded once each.  A row with an empty window: sdr NaN (as gram_finalize), coefficients 0, nothing
+// added to the loss.  loss = -(sum_b sdr[b]) in ascending row order by one thread.
+__global__ void __launch_bounds__(256)
+    sisdr_coefficients(const double* __restrict__ acc, const int* __restrict__ lengths, long L, int B, double* __restrict__ sdr,
+                       double* __restrict__ ratios, float* __restrict__ coef, float* __restrict__ loss) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    long len = L;
+    if (lengths) {
+      const int v = lengths[b];
+      len = v < 0 ? 0 : (v > L ? L : v);
+    }
+    const double ee = acc[b * 6 + 0], er = acc[b * 6 + 1], rr = acc[b * 6 + 3];
+    const double target = (er / rr) * er, D = ee - target;
+    const double k = 20.0 / log(10.0);
+    const double v = ratio_db(target, D);
+    sdr[b] = v;
+    if (ratios) ratios[b] = v;
+    coef[2 * b + 0] = len > 0 ? (float)(-k * (1.0 / er + er / (rr * D))) : 0.f;
+    coef[2 * b + 1] = len > 0 ? (float)(k / D) : 0.f;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sum = 0.0;
+    for (int b = 0; b < B; ++b)
+      if (!lengths || lengths[b] > 0) sum += sdr[b];
+    loss[0] = (float)-sum;
+  }
+}
+
+// dest[b][i] = c1[b] ref[b][i] + c2[b] est[b][i] below the row's length, exact zeros from there to L; the grid of
+// gram_partials (chunk, row).  Nothing of est / ref at or behind the length is read.
+__global__ void __launch_bounds__(256)
+    sisdr_gradient(const float* __restrict__ est, long ld_est, const float* __restrict__ ref, long ld_ref,
+                   const int* __restrict__ lengths, long L, const float* __restrict__ coef, float* __restrict__ dest, long ld_dest) {
+  const int b = blockIdx.y;
+  long len = L;
+  if (lengths) {
+    const int v = lengths[b];
+    len = v < 0 ? 0 : (v > L ? L : v);
+  }
+  const long i0 = (long)blockIdx.x * CHUNK, i1 = min(L, i0 + CHUNK);
+  const float c1 = coef[2 * b], c2 = coef[2 * b + 1];
+  const float* e = est + b * ld_est;
+  const float* r = ref + b * ld_ref;
+  float* d = dest + b * ld_dest;
+  for (long i = i0 + threadIdx.x; i < i1; i += 256) d[i] = i < len ? c1 * r[i] + c2 * e[i] : 0.f;
+}
+
 inline long n_chunks(long L) { return (L + CHUNK - 1) / CHUNK; }
 inline bool ok_shape(int B, long L) {
   return B > 0 && B <= 65535 && L > 0 && L < (1L << 40) && n_chunks(L) * B < (1L << 31) / 6;
@@ -202,6 +262,17 @@ void launch_partials(const float* est, long ld_est, const float* ref, long ld_re
                      const int* lengths, int B, long L, double* part, hipStream_t s) {
   hipLaunchKernelGGL(gram_partials<MODE>, dim3((unsigned)n_chunks(L), B), dim3(256), 0, s, est, ld_est, ref, ld_ref, third,
                      ld_third, lengths, L, part);
+}
+
+// workspace of the loss: [partials][acc B x 6 doubles][sdr B doubles][coef B x 2 floats], byte offsets
+struct LossWs { size_t acc, sdr, coef, total; };
+inline LossWs loss_ws(int B, long L) {
+  LossWs w;
+  w.acc = partial_bytes(B, L);
+  w.sdr = w.acc + align_up((size_t)B * 6 * sizeof(double), 256);
+  w.coef = w.sdr + align_up((size_t)B * sizeof(double), 256);
+  w.total = w.coef + align_up((size_t)B * 2 * sizeof(float), 256);
+  return w;
 }
 
 }  // namespace
@@ -243,6 +314,31 @@ extern "C" int avvad_confusion_accumulate(const float* pred, int pred_mode, cons
   if (chunks >= (1L << 31) || ((uintptr_t)counts & 7)) return AVVAD_EINVAL;
   hipLaunchKernelGGL(confusion_partials, dim3((unsigned)chunks, B), dim3(256), 0, (hipStream_t)sv, pred, pred_mode, target, lengths,
                      T, Y, (unsigned long long*)counts);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+extern "C" size_t avvad_si_sdr_loss_workspace(int B, long L) { return ok_shape(B, L) ? loss_ws(B, L).total : 0; }
+
+extern "C" int avvad_si_sdr_loss(const float* est, long ld_est, const float* ref, long ld_ref, const int* lengths, float* loss,
+                                 double* ratios, float* dest, long ld_dest, int B, long L, void* ws, size_t ws_bytes,
+                                 avvad_stream_t sv) {
+  AVVAD_ENTER();
+  if (!est || !ref || !loss || !dest || !ws || !ok_shape(B, L) || ld_est < L || ld_ref < L || ld_dest < L) return AVVAD_EINVAL;
+  if (ws_misaligned(ws) || ((uintptr_t)ratios & 7)) return AVVAD_EINVAL;
+  const LossWs w = loss_ws(B, L);
+  if (ws_bytes < w.total) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  double* part = (double*)ws;
+  double* acc = (double*)((char*)ws + w.acc);
+  double* sdr = (double*)((char*)ws + w.sdr);
+  float* coef = (float*)((char*)ws + w.coef);
+  hipLaunchKernelGGL(zero_doubles, dim3((B * 6 + 255) / 256), dim3(256), 0, s, acc, B * 6);
+  launch_partials<0>(est, ld_est, ref, ld_ref, nullptr, 0, lengths, B, L, part, s);
+  hipLaunchKernelGGL(gram_add, dim3(B), dim3(64), 0, s, part, (int)n_chunks(L), lengths, L, acc);
+  hipLaunchKernelGGL(sisdr_coefficients, dim3(1), dim3(256), 0, s, acc, lengths, L, B, sdr, ratios, coef, loss);
+  hipLaunchKernelGGL(sisdr_gradient, dim3((unsigned)n_chunks(L), B), dim3(256), 0, s, est, ld_est, ref, ld_ref, lengths, L, coef,
+                     dest, ld_dest);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }

@@ -6,7 +6,9 @@ Inputs: 513-bin log-power spectrogram sequences (B,T,513) or, with WAVENET = Tru
 The loop body (standardise -> forward -> summed masked BCE -> backward -> Adam -> per-sequence F1 -> checkpoint
 ``Video_Net_epoch_XXX_vloss_Y.pt``) is ``avvad.train.train_main``; with ``wav_pairs`` it trains on (noisy, clean) wav pairs
 and computes the labels on the GPU, otherwise a synthetic ragged data source stands in for the reference's HDF5
-datasets (h5py is not installed in this image).  AVVAD_EPOCHS / AVVAD_ITEMS / AVVAD_BATCH override sizes."""
+datasets (h5py is not installed in this image).  With ``objective = 'si_sdr'`` (wav pairs, y_dim 513) the loss is the
+SI-SDR of the waveform resynthesised through the sigmoid mask instead of the BCE against the IBM label.
+AVVAD_EPOCHS / AVVAD_ITEMS / AVVAD_BATCH override sizes, AVVAD_OBJECTIVE the objective."""
 import sys
 sys.path.append('.')
 
@@ -28,6 +30,8 @@ wav_pairs = None          # text file with one "noisy.wav clean.wav" pair per li
                           # the GPU from the clean files (VAD for y_dim 1, IBM for y_dim 513); None: synthetic data
 compute_stats = False     # with wav_pairs and no trainset_audio_*.npy yet: compute the train-set mean / std over the pairs on
                           # the GPU before the first epoch and save them in models/<model_name> (the evaluate scripts' stats_dir)
+objective = 'bce'         # 'si_sdr' (wav_pairs, y_dim 513): minus the SI-SDR of the noisy file resynthesised through the
+                          # sigmoid of the logits, against the clean file; the F1 figures against the IBM stay in the log
 wavenet_params = dict(filter_width=2, quantization_channel=1, dilations=[2 ** i for i in range(10)] * 2,
                       en_residual_channel=32, en_dilation_channel=32, en_bottleneck_width=256,
                       en_pool_kernel_size=16, use_bias=True)
@@ -40,4 +44,5 @@ def make_model():
 if __name__ == '__main__':
     stats = Stats.load('models/' + model_name, eps) if std_norm else None
     train_main('audio', make_model, model_name, waveform=WAVENET, epochs=end_epoch, batch_size=batch_size,
-               lr=learning_rate, stats=stats, wav_pairs=wav_pairs, compute_stats=compute_stats and std_norm)
+               lr=learning_rate, stats=stats, wav_pairs=wav_pairs, compute_stats=compute_stats and std_norm,
+               objective=objective)

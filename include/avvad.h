@@ -81,7 +81,8 @@ typedef void* avvad_stream_t; /* hipStream_t */
 #define AVVAD_ABI_VERSION 3   /* 3 = + avvad_conv2d_*_bf16.  Added entry points alone (the avvad_target_* labels) change no
                                  existing signature, so they keep the version: a version-3 binding still describes the
                                  library exactly for every symbol it binds.  The avvad_stats_* section is such an addition, and so
-                                 are the avvad_score_* / avvad_confusion_* scores. */
+                                 are the avvad_score_* / avvad_confusion_* scores, and avvad_istft_bwd / avvad_resynth_bwd /
+                                 avvad_si_sdr_loss. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -502,6 +503,30 @@ size_t avvad_resynth_workspace(const avvad_stft_desc* sd, const avvad_istft_desc
 int avvad_resynth(const float* wave, const float* mask, const int* n_frames, const int* out_len, const float* scale,
                   float* out, const avvad_stft_desc* sd, const avvad_istft_desc* d, void* ws, size_t ws_bytes,
                   avvad_stream_t s);
+/* The adjoint of the masked inverse with respect to the mask (mode 1) or its logits (mode 2), for training on a loss
+ * of the waveform.  With a cotangent dout [B][out_pitch] of avvad_istft's out:
+ *   q[b][s']      = scale[b] dout[b][s' - start] / wss(s')   where the forward wrote a sum (0 <= s' - start below
+ *                   out_len[b] and the row's natural length; the division as in the forward), exactly 0 elsewhere;
+ *   G             = the framed DFT of q taken as a [B][(T - 1) hop + n_fft] waveform -- the inverse basis is w_f / N times
+ *                   the forward one, so the adjoint of the inverse GEMM IS the forward transform's GEMM (same M, N, K);
+ *   dmask[b,t,f]  = (w_f / N) (G_re S_re + G_im S_im), in mode 2 times sigmoid'(mask[b,t,f]);  w_f = 1 for DC and
+ *                   Nyquist, else 2.  Frames t >= n_frames[b] are written as exact zeros.
+ * dmask [B][T][F] is overwritten.  Nothing of dout at or behind a row's length, and neither spectrum nor mask of a frame
+ * t >= n_frames[b], is read: they may hold anything.  There is no gradient for spec (it is data) and no second derivative.
+ * mask_mode 0 and 3 have no gradient: AVVAD_EINVAL, as is B ((T - 1) hop + n_fft) >= 2^31.  Every other argument and
+ * limit as for avvad_istft; no float atomics, bit-identical run to run.  ws: 16-byte aligned; q, G and the basis live
+ * only there. */
+size_t avvad_istft_bwd_workspace(const avvad_istft_desc* d);   /* 0 on a bad descriptor or mask_mode 0 / 3 */
+int avvad_istft_bwd(const float* spec, long stride_b, long stride_t, long stride_f, const float* mask, const int* n_frames,
+                    const int* out_len, const float* scale, const float* dout, float* dmask, const avvad_istft_desc* d,
+                    void* ws, size_t ws_bytes, avvad_stream_t s);
+/* The same from the waveform: avvad_resynth keeps no spectrum, so this call transforms wave again into the workspace and
+ * proceeds as avvad_istft_bwd on those rows (bit for bit what avvad_stft_complex + avvad_istft_bwd give): two
+ * forward-size GEMMs. */
+size_t avvad_resynth_bwd_workspace(const avvad_stft_desc* sd, const avvad_istft_desc* d);
+int avvad_resynth_bwd(const float* wave, const float* mask, const int* n_frames, const int* out_len, const float* scale,
+                      const float* dout, float* dmask, const avvad_stft_desc* sd, const avvad_istft_desc* d, void* ws,
+                      size_t ws_bytes, avvad_stream_t s);
 /* The masked inverse on a STREAM of frames (inference; center = False, no start trim, like the streaming forward).  Row b
  * has n_before[b] frames behind it; the call takes its next n_frames[b] frames, spec / mask [B][T][F]([2]) as
  * avvad_stft_stream_fwd_spec and the model hand them out (mask_mode as for avvad_istft; modes 2 and 3 take logits), and
@@ -621,6 +646,24 @@ int avvad_score_accumulate(const float* est, long ld_est, const float* ref, long
  * third_mode 0: si_sir, si_sar and a_n are NaN.  ratios / alpha: 8-byte aligned. */
 int avvad_score_finalize(const double* acc, int B, int third_mode, double* ratios /* [B][3] */,
                          double* alpha /* [B][2] or NULL */, avvad_stream_t s);
+/* The SI-SDR loss of a ragged batch and its gradient in the estimate, for training.  Per row, over its first lengths[b]
+ * samples, with the sums a = e.r, r = r.r, e = e.e of avvad_score_accumulate's pass (third_mode 0: the same chunks, the
+ * same order, in double), P = a^2 / r and D = e - P:
+ *   SI-SDR_b = 10 log10(P / D)   (avvad_score_finalize's value, bit for bit)
+ *   loss[0]  = -sum_b SI-SDR_b   (summed in double in ascending row order, rounded once to float)
+ *   dest[b][i] = c1 ref[b][i] + c2 est[b][i],   c2 = (20 / ln 10) / D,   c1 = -(20 / ln 10) (1 / a + a / (r D))
+ * the two coefficients formed in double and rounded once each.  dest [B][ld_dest] is overwritten in columns 0 .. L - 1,
+ * with exact zeros at and behind lengths[b] (clamped to [0, L]; NULL: L each); nothing of est / ref there is read.
+ * ratios: NULL or [B] doubles (8-byte aligned), SI-SDR_b in dB.
+ * Degenerate rows: a row with an empty window (lengths[b] <= 0) adds 0 to the loss and has a zero gradient (its ratios
+ * entry is NaN, as avvad_score_finalize has it).  Any other non-finite value -- a silent reference (r = 0), an estimate
+ * orthogonal to it (a = 0) or a perfect one (D = 0) -- propagates to loss, ratios and dest as IEEE arithmetic gives it.
+ * The pass runs one workgroup per chunk of AVVAD_SCORE_CHUNK samples and row; no float atomics, bit-identical run to
+ * run.  est / ref / dest: any 4-byte aligned float pointers with their own row pitches (>= L).  ws: 16-byte aligned. */
+size_t avvad_si_sdr_loss_workspace(int B, long L);                 /* 0 on a bad shape */
+int avvad_si_sdr_loss(const float* est, long ld_est, const float* ref, long ld_ref, const int* lengths /* NULL: L each */,
+                      float* loss /* [1] */, double* ratios /* [B] or NULL */, float* dest, long ld_dest, int B, long L,
+                      void* ws, size_t ws_bytes, avvad_stream_t s);
 /* pred, target [B][T][Y] contiguous; target values are 0 / 1; pred_mode 0: pred values are 0 / 1, 1: pred values are
  * logits and the prediction is logit > 0 (sigmoid > 0.5).  counts[b] = (tp, tn, fp, fn) as int64, ADDED to (64-bit
  * integer atomics: exact in any order, no workspace); values at t >= lengths[b] (clamped to [0, T]; NULL: T each) are
