@@ -176,11 +176,13 @@ __global__ void tail_bwd_dz_generic(const float* __restrict__ s, const float* __
     for (int c = 0; c < R; ++c) z = fmaf(wb[(long)bn * R + c], sb[(long)c * Lv], z);
     float g = 0.f;
     if (z > 0.f) {
-      const int pc = (int)(((long)t * P) / Lv);
-      for (int p = max(0, pc - 1); p <= min(P - 1, pc + 1); ++p) {
+      // the bins that contain t are exactly floor(t P / Lv) .. ceil((t + 1) P / Lv) - 1: two at the most while P <= Lv,
+      // any number beyond (Lv = 3, P = 5: sample 1 is in bins 1, 2, 3)
+      const int p0 = (int)(((long)t * P) / Lv), p1 = (int)((((long)t + 1) * P + Lv - 1) / Lv);
+      for (int p = p0; p < p1; ++p) {
         int a, e;
         pool_bin(p, Lv, P, a, e);
-        if (t >= a && t < e) g += dout[((long)b * Bn + bn) * P + p] / (float)(e - a);
+        g += dout[((long)b * Bn + bn) * P + p] / (float)(e - a);
       }
     }
     dz[i] = g;
@@ -837,7 +839,7 @@ __global__ void __launch_bounds__(256)
     for (int k = 0; k < 16; ++k) x[k] = sp[(long)(2 * k + lh) * Lv];
 #pragma unroll
     for (int k = 0; k < 16; ++k) x[k] = ok ? x[k] : 0.f;
-    // pool bins that contain t (at most two adjacent ones overlap)
+    // pool bins that contain t: P <= Lv here (tail_bwd_form), so they are bin c0 = floor(t P / Lv) and at most its successor
     int pb[3];
     float pc[3];
     {
@@ -1830,11 +1832,15 @@ static BwdChoice bwd_form(int B, int Lo, bool shared_device, bool any_grad) {
   }
 }
 
-// backward of the tail (bottleneck + ReLU + pool) over Lv samples per sequence
-static TailBwdChoice tail_bwd_form(int B, int Lv, int R, int Bn, bool any_grad) {
+// backward of the tail (bottleneck + ReLU + pool) over Lv samples per sequence.  The three MFMA forms look for the bins of
+// sample t in the three-register window c0 - 1 .. c0 + 1, c0 = floor(t P / Lv); the bins that contain t are
+// c0 .. ceil((t + 1) P / Lv) - 1, which is inside the window exactly when P <= Lv ((t + 1) P / Lv <= t P / Lv + 1).  A pool
+// with more bins than samples (fewer than P samples per sequence: not a shape to tune for) takes the generic form, whose loop walks
+// the whole range.
+static TailBwdChoice tail_bwd_form(int B, int Lv, int R, int Bn, int P, bool any_grad) {
   const AvvadTune& t = avvad_tune();
   const long ntiles = (long)B * cdiv(Lv, 32);
-  if (!(R == 32 && Bn % 32 == 0 && Bn <= 1024)) return {TailBwdForm::GENERIC, 0};
+  if (!(R == 32 && Bn % 32 == 0 && Bn <= 1024) || P > Lv) return {TailBwdForm::GENERIC, 0};
   if (Bn == 256 && any_grad && !t.wn_no_fused_tail)        // 1 workgroup / CU is resident: one round
     return {t.wn_no_tail_pair ? TailBwdForm::FUSED : TailBwdForm::PAIR, wn_grid_size(ntiles, 4, 256, 0, XcdRound::NONE)};
   return {TailBwdForm::MFMA, wn_grid_size(ntiles, 4, 2048, 0, XcdRound::NONE)};
@@ -1964,7 +1970,7 @@ extern "C" int avvad_wavenet_bwd(const float* wave, const avvad_wavenet_params* 
   // ---- tail: dz_t = relu'(z) * pooled-grad ; d s_N = Wb^T dz_t
   float* DZT = ws + p.dzt;
   const float* bbp = d->use_bias ? prm->bott_b : (const float*)nullptr;
-  const TailBwdChoice tc = tail_bwd_form(B, Lv, R, Bn, g->bott_w || (d->use_bias && g->bott_b));
+  const TailBwdChoice tc = tail_bwd_form(B, Lv, R, Bn, d->P, g->bott_w || (d->use_bias && g->bott_b));
   const bool tail_fused = tc.form == TailBwdForm::PAIR || tc.form == TailBwdForm::FUSED;
   switch (tc.form) {
     case TailBwdForm::PAIR: {

@@ -193,7 +193,8 @@ size_t avvad_wavenet_workspace(const avvad_wavenet_desc* d);
 int avvad_wavenet_fwd(const float* wave, const avvad_wavenet_params* p, float* out,
                       const avvad_wavenet_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
 /* needs the workspace of a forward run with save_for_backward=1.
- * grads are ACCUMULATED (+=) into g; dwave may be NULL. */
+ * grads are ACCUMULATED (+=) into g; dwave may be NULL.  Every shape the forward accepts is supported, a pool with more
+ * bins than samples (P > Lv, a sample in more than two bins) included. */
 int avvad_wavenet_bwd(const float* wave, const avvad_wavenet_params* p, const float* dout,
                       const avvad_wavenet_grads* g, float* dwave, const avvad_wavenet_desc* d,
                       void* ws, size_t ws_bytes, avvad_stream_t s);
