@@ -10,6 +10,7 @@
 // pre-activations) + one fused gate kernel.  The activated gates overwrite the
 // pre-activations in the workspace and are what backward consumes.
 #include "gemm_api.h"
+#include "lstm_cell.h"
 #include <stdlib.h>
 
 namespace {
@@ -28,17 +29,10 @@ __global__ void lstm_gates_fwd(float* __restrict__ G, float* __restrict__ Cs, fl
   const int b = idx / H, j = idx - b * H;
   float* g = G + ((long)b * T + t) * 4 * H;
   const long o = ((long)b * T + t) * H + j;
-  if (t >= lengths[b]) {
-    g[j] = 0.f; g[H + j] = 0.f; g[2 * H + j] = 0.f; g[3 * H + j] = 0.f;
-    Cs[o] = 0.f; y[o] = 0.f;
-    return;
-  }
-  const float ig = sigmoidf_(g[j]), fg = sigmoidf_(g[H + j]), gg = tanhf(g[2 * H + j]), og = sigmoidf_(g[3 * H + j]);
-  const float cp = t > 0 ? Cs[o - H] : 0.f;
-  const float c = fg * cp + ig * gg;
-  g[j] = ig; g[H + j] = fg; g[2 * H + j] = gg; g[3 * H + j] = og;
-  Cs[o] = c;
-  y[o] = og * tanhf(c);
+  if (t >= lengths[b]) { lstm_cell::store_dead(g, Cs, y, H, j, o); return; }
+  float p[4];
+  lstm_cell::load_gates(g, H, j, p);      // all four first: see lstm_cell::fwd on what the staging decides
+  lstm_cell::store_live(g, Cs, y, H, j, o, lstm_cell::fwd([&](int e) { return p[e]; }, t > 0 ? Cs[o - H] : 0.f));
 }
 
 // ------------------------------------------------------------------ fused recurrent step (t >= 1), B % 16 == 0, H % 16 == 0
@@ -49,7 +43,7 @@ __global__ void lstm_gates_fwd(float* __restrict__ G, float* __restrict__ Cs, fl
 // from L2 (no LDS: nothing is shared between waves but the 64 KB weight slab, which L1 serves) and the 4 elements go to 4
 // MFMAs -- the k-slot q of MFMA e stands for k = 16*kk + 4*q + e on both operands, a permutation of the contraction
 // order only.  Row order 4*u + gate puts the four gate sums of unit q in the four accumulator registers of lane (b, q),
-// so the gate arithmetic (identical to lstm_gates_fwd) runs in registers.
+// so the gate arithmetic (lstm_cell::fwd, as in lstm_gates_fwd) runs in registers.
 // The workgroup always runs 16 waves: B/16 sequence blocks x KS = 16/(B/16) K-slices (the loads are L2-latency-bound, so
 // a wave keeps 16 float4 loads in flight over a short slice instead of walking all of K); the slices' partial sums meet
 // in LDS and the slice-0 waves finish the step.
@@ -62,7 +56,6 @@ __global__ void lstm_gates_fwd(float* __restrict__ G, float* __restrict__ Cs, fl
 //  step in this kernel's image -- W_hh transposed once, workgroup = 16 units x 64 sequences, dh in the accumulators, gate
 //  backward of step t-1 in registers: correct, one launch instead of three, but only H/16 = 64 workgroups each streaming
 //  1.25 MB of gate gradients: 1.3 ms/step SLOWER at the bench shape, 2.5 ms at C2.)
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 // blockIdx.y selects a group of BG = min(B, 64) sequences, blockIdx.x a run of 4*UB hidden units.  At B = 256 (BASELINE
 // config 1) the step is bound by L2 traffic: every workgroup re-reads h_{t-1} of its 64 sequences (256 KB) next to its
 // weight slab (64 KB per 4 units), 328 MB per step with UB = 1 -- 72 us.  UB = 4 shares one read of h between 16 units:
@@ -71,7 +64,7 @@ template <int UB>
 __global__ void __launch_bounds__(1024)
     lstm_step_fwd_mfma(float* __restrict__ G, float* __restrict__ Cs, float* __restrict__ y, const float* __restrict__ w_hh,
                        const int* __restrict__ lengths, int B, int T, int H, int t) {
-  __shared__ f32x4v part[UB][16][64];
+  __shared__ f32x4 part[UB][16][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int BG = B < 64 ? B : 64;                            // sequences per workgroup
   const int nb = BG >> 4, KS = 16 / nb;
@@ -81,11 +74,11 @@ __global__ void __launch_bounds__(1024)
   const int b = blockIdx.y * BG + wb * 16 + i;               // this lane's sequence (B operand column / D column)
   const int kspan = H / KS;                                  // host guarantees H % (16*KS) == 0
   // A row i = 4*u + gate of unit-quad ub: W_hh row gate*H + 4*(blk*UB + ub) + u
-  const float* wrow = w_hh + (long)((i & 3) * H + 4 * blk * UB + (i >> 2)) * H + ks * kspan + 4 * q;
+  const float* wrow = w_hh + (long)lstm_cell::whh_row(i, lstm_cell::quad_unit(i, blk * UB), H) * H + ks * kspan + 4 * q;
   const float* hrow = y + ((long)b * T + (t - 1)) * H + ks * kspan + 4 * q;
-  f32x4v acc[UB];
+  f32x4 acc[UB];
 #pragma unroll
-  for (int ub = 0; ub < UB; ++ub) acc[ub] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  for (int ub = 0; ub < UB; ++ub) acc[ub] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nk = kspan >> 4;
   for (int k0 = 0; k0 < nk; k0 += 8) {
     float4 h[8];
@@ -104,12 +97,7 @@ __global__ void __launch_bounds__(1024)
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        if (k0 + u < nk) {
-          acc[ub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].x, h[u].x, acc[ub], 0, 0, 0);
-          acc[ub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].y, h[u].y, acc[ub], 0, 0, 0);
-          acc[ub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].z, h[u].z, acc[ub], 0, 0, 0);
-          acc[ub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].w, h[u].w, acc[ub], 0, 0, 0);
-        }
+        if (k0 + u < nk) acc[ub] = lstm_cell::mfma4(a[u], h[u], acc[ub]);
       }
     }
   }
@@ -120,27 +108,15 @@ __global__ void __launch_bounds__(1024)
   const bool live = t < lengths[b];
 #pragma unroll
   for (int ub = 0; ub < UB; ++ub) {
-    f32x4v r = acc[ub];
-    for (int s2 = 1; s2 < KS; ++s2) {
-      const f32x4v p = part[ub][s2 * nb + wb][lane];
-      r[0] += p[0]; r[1] += p[1]; r[2] += p[2]; r[3] += p[3];
-    }
-    // r[gate] = recurrent part of the gate of unit j for sequence b
+    // r[gate] = recurrent part of the gate of unit j for sequence b: the slices' partial sums, wave ks * nb + wb's each
+    const f32x4 r = lstm_cell::add_slices(acc[ub], &part[ub][wb][lane], KS, nb * 64);
     const int j = 4 * (blk * UB + ub) + q;
     float* g = G + ((long)b * T + t) * 4 * H;
     const long o = ((long)b * T + t) * H + j;
-    if (!live) {
-      g[j] = 0.f; g[H + j] = 0.f; g[2 * H + j] = 0.f; g[3 * H + j] = 0.f;
-      Cs[o] = 0.f; y[o] = 0.f;
-      continue;
-    }
-    const float ig = sigmoidf_(g[j] + r[0]), fg = sigmoidf_(g[H + j] + r[1]), gg = tanhf(g[2 * H + j] + r[2]),
-                og = sigmoidf_(g[3 * H + j] + r[3]);
-    const float cp = Cs[o - H];
-    const float c = fg * cp + ig * gg;
-    g[j] = ig; g[H + j] = fg; g[2 * H + j] = gg; g[3 * H + j] = og;
-    Cs[o] = c;
-    y[o] = og * tanhf(c);
+    if (!live) { lstm_cell::store_dead(g, Cs, y, H, j, o); continue; }
+    float p[4];
+    lstm_cell::load_gates(g, H, j, p);
+    lstm_cell::store_live(g, Cs, y, H, j, o, lstm_cell::fwd([&](int e) { return p[e] + r[e]; }, Cs[o - H]));
   }
 }
 
@@ -165,7 +141,7 @@ template <int NK>   // H / 64: float4 fragments per lane and K quarter
 __global__ void __launch_bounds__(256)
     lstm_persistent_fwd(float* __restrict__ G, float* __restrict__ Cs, float* __restrict__ y, const float* __restrict__ w_hh,
                         const int* __restrict__ lengths, int B, int T, int H, unsigned* __restrict__ sync) {
-  __shared__ f32x4v part[4][4][64];      // [sequence group][K quarter][lane]
+  __shared__ f32x4 part[4][4][64];      // [sequence group][K quarter][lane]
   __shared__ int give_up;
   const int lane = threadIdx.x & 63, ks = threadIdx.x >> 6;
   const int i = lane & 15, q = lane >> 4;
@@ -174,13 +150,13 @@ __global__ void __launch_bounds__(256)
   const int kspan = H >> 2;
   if (threadIdx.x == 0) give_up = 0;
   // resident A fragments: row i = 4 u + gate  <->  W_hh row gate*H + 4 blk + u
-  f32x4v a[NK];
+  f32x4 a[NK];
   {
-    const float* wrow = w_hh + (long)((i & 3) * H + 4 * blk + (i >> 2)) * H + ks * kspan + 4 * q;
+    const float* wrow = w_hh + (long)lstm_cell::whh_row(i, lstm_cell::quad_unit(i, blk), H) * H + ks * kspan + 4 * q;
 #pragma unroll
     for (int kk = 0; kk < NK; ++kk) {
       const float4 v = *reinterpret_cast<const float4*>(wrow + 16 * kk);
-      a[kk] = f32x4v{v.x, v.y, v.z, v.w};
+      a[kk] = f32x4{v.x, v.y, v.z, v.w};
     }
   }
   // the finishing wave of sequence group sg is wave sg: lane (i, q) owns (sequence 16 sg + i, unit 4 blk + q)
@@ -198,20 +174,20 @@ __global__ void __launch_bounds__(256)
   float* const hb = reinterpret_cast<float*>(sync + 1024);
   const __amdgpu_buffer_rsrc_t rh = brsrc(hb, 2 * B * LDHB * 4);
   // h_{t-1} of sequence group sg, this wave's K quarter: NK 16-byte sc1 loads (step 1 reads y[:, 0], written before the launch)
-  auto hload = [&](int sg, int t, f32x4v (&h)[NK]) {
+  auto hload = [&](int sg, int t, f32x4 (&h)[NK]) {
     if (t == 1) {
       const int off = (int)((((long)(sg * 16 + i) * T) * H + ks * kspan + 4 * q) * 4);
 #pragma unroll
-      for (int kk = 0; kk < NK; ++kk) h[kk] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(ry, off, 64 * kk, 16));
+      for (int kk = 0; kk < NK; ++kk) h[kk] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, off, 64 * kk, 16));
     } else {
       const int off = ((((t - 1) & 1) * B + sg * 16 + i) * LDHB + ks * kspan + 4 * q) * 4;
 #pragma unroll
-      for (int kk = 0; kk < NK; ++kk) h[kk] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rh, off, 64 * kk, 16));
+      for (int kk = 0; kk < NK; ++kk) h[kk] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, off, 64 * kk, 16));
     }
   };
-  auto hmul = [&](const f32x4v (&h)[NK], int sg) {
+  auto hmul = [&](const f32x4 (&h)[NK], int sg) {
     // two accumulators: a dependent chain of this instruction issues every 40 cycles, independent ones every 32
-    f32x4v acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < NK; ++kk) {
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk][0], h[kk][0], acc, 0, 0, 0);
@@ -234,23 +210,17 @@ __global__ void __launch_bounds__(256)
     float* g = G + ((long)bfin * T + t) * 4 * H;
     // two register sets: group sg+1's requests are in flight under group sg's MFMAs (one wave per SIMD: nothing else
     // would hide them); sched_barriers keep hipcc from pairing each load with its four MFMAs
-    f32x4v h0[NK], h1[NK];
+    f32x4 h0[NK], h1[NK];
     hload(0, t, h0);
     __builtin_amdgcn_sched_barrier(0);
     for (int sg = 0; sg < nsg; sg += 2) {
       if (sg + 1 < nsg) hload(sg + 1, t, h1);
-      else if (fin) {       // last group: this step's pre-activations ride under its MFMAs
-#pragma unroll
-        for (int e = 0; e < 4; ++e) gin[e] = g[e * H + j];
-      }
+      else if (fin) lstm_cell::load_gates(g, H, j, gin);       // last group: this step's pre-activations ride under its MFMAs
       __builtin_amdgcn_sched_barrier(0);
       hmul(h0, sg);
       if (sg + 1 >= nsg) break;
       if (sg + 2 < nsg) hload(sg + 2, t, h0);
-      else if (fin) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) gin[e] = g[e * H + j];
-      }
+      else if (fin) lstm_cell::load_gates(g, H, j, gin);
       __builtin_amdgcn_sched_barrier(0);
       hmul(h1, sg + 1);
     }
@@ -259,30 +229,17 @@ __global__ void __launch_bounds__(256)
 #endif
     __syncthreads();
     if (fin) {
-      f32x4v r = part[ks][0][lane];
-#pragma unroll
-      for (int s2 = 1; s2 < 4; ++s2) {
-        const f32x4v pp = part[ks][s2][lane];
-        r[0] += pp[0]; r[1] += pp[1]; r[2] += pp[2]; r[3] += pp[3];
-      }
+      const f32x4 r = lstm_cell::add_slices(part[ks][0][lane], &part[ks][0][lane], 4, 64);
       const long o = ((long)bfin * T + t) * H + j;
-      float hv = 0.f;
+      // h_t first (sc1: for every workgroup), then the layer's output and the state the backward reads
       if (t < len) {
-        const float ig = sigmoidf_(gin[0] + r[0]), fg = sigmoidf_(gin[1] + r[1]), gg = tanhf(gin[2] + r[2]),
-                    og = sigmoidf_(gin[3] + r[3]);
-        const float c = fg * cprev + ig * gg;
-        hv = og * tanhf(c);
-        // h_t first (sc1: for every workgroup), then the layer's output and the state the backward reads
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, hv), rh, (((t & 1) * B + bfin) * LDHB + j) * 4, 0, 16);
-        y[o] = hv;
-        g[j] = ig; g[H + j] = fg; g[2 * H + j] = gg; g[3 * H + j] = og;
-        Cs[o] = c;
-        cprev = c;
+        const lstm_cell::Fwd c = lstm_cell::fwd([&](int e) { return gin[e] + r[e]; }, cprev);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, c.h), rh, (((t & 1) * B + bfin) * LDHB + j) * 4, 0, 16);
+        lstm_cell::store_live(g, Cs, y, H, j, o, c);
+        cprev = c.c;
       } else {
         __builtin_amdgcn_raw_buffer_store_b32(0, rh, (((t & 1) * B + bfin) * LDHB + j) * 4, 0, 16);
-        y[o] = 0.f;
-        g[j] = 0.f; g[H + j] = 0.f; g[2 * H + j] = 0.f; g[3 * H + j] = 0.f;
-        Cs[o] = 0.f;
+        lstm_cell::store_dead(g, Cs, y, H, j, o);
         cprev = 0.f;
       }
     }
@@ -327,14 +284,16 @@ __global__ void __launch_bounds__(256)
 // this falls back to the per-step kernels.  What the query cannot see is OTHER work on the device (a second process, RCCL's
 // kernels, the trunk's persistent grids on another stream): their workgroups retire on their own -- nothing they wait for
 // is behind this launch -- so the grid still becomes resident, late; the spins are bounded all the same.
-static int persistent_capacity(int NKp) {
+using PersistentKernel = void (*)(float*, float*, float*, const float*, const int*, int, int, int, unsigned*);
+static PersistentKernel persistent_kernel(int NK) {       // NK in {16, 8, 4} (fwd_form)
+  return NK == 16 ? lstm_persistent_fwd<16> : (NK == 8 ? lstm_persistent_fwd<8> : lstm_persistent_fwd<4>);
+}
+static int persistent_capacity(int NK) {
   static int cap[3] = {-1, -1, -1};
-  const int i = NKp == 16 ? 0 : (NKp == 8 ? 1 : 2);
+  const int i = NK == 16 ? 0 : (NK == 8 ? 1 : 2);
   if (cap[i] < 0) {
     int nb = 0, dev = 0, cus = 0;
-    hipError_t e = NKp == 16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, lstm_persistent_fwd<16>, 256, 0)
-                   : NKp == 8 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, lstm_persistent_fwd<8>, 256, 0)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, lstm_persistent_fwd<4>, 256, 0);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, persistent_kernel(NK), 256, 0);
     if (e != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
     cap[i] = (nb > 1 ? nb - 1 : nb) * cus;
@@ -361,26 +320,12 @@ __global__ void lstm_gates_bwd(float* __restrict__ G, const float* __restrict__ 
   const long o = ((long)b * T + t) * H + j;
   const float dhr = DH[idx];
   DH[idx] = 0.f;
-  if (t >= lengths[b]) {
-    g[j] = 0.f; g[H + j] = 0.f; g[2 * H + j] = 0.f; g[3 * H + j] = 0.f;
-    DC[idx] = 0.f;
-    return;
-  }
-  const float ig = g[j], fg = g[H + j], gg = g[2 * H + j], og = g[3 * H + j];
-  const float c = Cs[o], cp = t > 0 ? Cs[o - H] : 0.f;
-  const float tc = tanhf(c);
-  const float dh = dy[o] + dhr;
-  const float dc = DC[idx] + dh * og * (1.f - tc * tc);
-  g[j] = dc * gg * ig * (1.f - ig);
-  g[H + j] = dc * cp * fg * (1.f - fg);
-  g[2 * H + j] = dc * ig * (1.f - gg * gg);
-  g[3 * H + j] = dh * tc * og * (1.f - og);
-  DC[idx] = dc * fg;
+  lstm_cell::bwd(g, Cs, dy, DC, H, j, idx, o, t, t < lengths[b], dhr);
 }
 
 // Epilogue of the backward recurrent product DH = dG_t . W_hh (rows = sequences, columns = hidden units): the engine's
 // fix-up kernel, which is where a split tile's total exists, hands each finished dh to finish4(), and that runs the gate
-// backward of step t - 1 on the spot (lstm_gates_bwd's arithmetic) -- two launches per time step instead of three.
+// backward of step t - 1 on the spot (lstm_cell::bwd, as lstm_gates_bwd does) -- two launches per time step instead of three.
 struct EpiLstmBwd {
   static constexpr bool PLAIN = true;
   float* C;            // DH [B][H]
@@ -403,23 +348,7 @@ struct EpiLstmBwd {
     for (int e = 0; e < 4; ++e) {
       const int j = j0 + e;
       if (j >= N) continue;
-      const int idx = b * H + j;
-      const long o = ((long)b * T + t) * H + j;
-      if (!live) {
-        g[j] = 0.f; g[H + j] = 0.f; g[2 * H + j] = 0.f; g[3 * H + j] = 0.f;
-        DC[idx] = 0.f;
-        continue;
-      }
-      const float ig = g[j], fg = g[H + j], gg = g[2 * H + j], og = g[3 * H + j];
-      const float c = Cs[o], cp = t > 0 ? Cs[o - H] : 0.f;
-      const float tc = tanhf(c);
-      const float dh = dy[o] + dhr[e];
-      const float dc = DC[idx] + dh * og * (1.f - tc * tc);
-      g[j] = dc * gg * ig * (1.f - ig);
-      g[H + j] = dc * cp * fg * (1.f - fg);
-      g[2 * H + j] = dc * ig * (1.f - gg * gg);
-      g[3 * H + j] = dh * tc * og * (1.f - og);
-      DC[idx] = dc * fg;
+      lstm_cell::bwd(g, Cs, dy, DC, H, j, b * H + j, ((long)b * T + t) * H + j, t, live, dhr[e]);
     }
   }
 };
@@ -500,6 +429,52 @@ static inline int pick_split(int M, int N, int K) {
   return s < 1 ? 1 : s;
 }
 
+
+// ------------------------------------------------------------------ the form choices (restated by tests/head_ref.py)
+enum class FwdForm { PERSISTENT, STEP, GEMM };
+enum class BwdForm { FUSED, PLAIN };
+// PERSISTENT: n = NK, one launch of (gx) workgroups for steps 1 .. T-1; STEP: n = UB, a (gx, gy) grid per step t >= 1;
+// GEMM: the engine's product + lstm_gates_fwd per step.  Step 0 is lstm_gates_fwd in every form.
+struct FwdChoice { FwdForm form; int n, gx, gy; };
+
+// The per-step choice: lstm_step_fwd_mfma<UB> or GEMM + gates.  Sequences are handled in groups of BG = min(B, 64)
+// (blockIdx.y); a group's 16 waves are BG/16 sequence blocks x KS = 256/BG K-slices of a multiple of 16 floats.
+static FwdChoice step_form(const avvad_lstm_desc* d, const float* w_hh, const float* y) {
+  const int B = d->B, H = d->H, BG = B < 64 ? B : 64;
+  // (the fused step and the persistent kernel read rows of W_hh and of y 16 bytes at a time: a base pointer off that
+  //  boundary -- a contiguous slice of a larger buffer -- takes the GEMM + gate kernels, whose loads adapt)
+  if (!((B == 16 || B == 32 || (B % 64 == 0 && B <= 65535 * 64)) && H % (16 * (256 / BG)) == 0) ||
+      (((uintptr_t)w_hh | (uintptr_t)y) & 15) != 0 || avvad_tune().lstm_no_fused_step)
+    return {FwdForm::GEMM, 0, 0, 0};
+  // many sequences: one read of h_{t-1} serves 16 hidden units (B >= 128: BG = 64, so H % 64 == 0 and H / 16 is whole)
+  const int UB = B >= 128 ? 4 : 1;
+  return {FwdForm::STEP, UB, H / (4 * UB), B / BG};
+}
+
+// ONE persistent launch for steps 1 .. T-1 where the shape allows (option lstm_no_persistent: the per-step kernels).
+// Whether the device holds the grid (persistent_capacity) is not known here: the entry point falls back to step_form().
+static FwdChoice fwd_form(const avvad_lstm_desc* d, const float* w_hh, const float* y) {
+  const FwdChoice c = step_form(d, w_hh, y);
+  const int B = d->B, T = d->T, H = d->H, NK = H / 64;
+  // (a STEP form with B <= 64 has B in {16, 32, 64}: B % 16 == 0.  NK in {4, 8, 16} with H % 64 == 0 is H in
+  //  {256, 512, 1024}: H / 4 <= 256 workgroups, what one 16-byte poll per lane of the flag barrier covers.  The kernel's
+  //  byte offsets into y are 32-bit.)
+  if (c.form == FwdForm::STEP && !avvad_tune().lstm_no_persistent && B <= 64 && T > 1 && H % 64 == 0 &&
+      (NK == 16 || NK == 8 || NK == 4) && (long)B * T * H * 4 < (1L << 31))
+    return {FwdForm::PERSISTENT, NK, H / 4, 1};
+  return c;
+}
+
+// FUSED: the recurrent product's fix-up finishes step t - 1's gates (EpiLstmBwd); PLAIN: the engine's product, then
+// lstm_gates_bwd.  The fused form needs the 64x64 tile path with 16-byte rows of W_hh (H % 4 == 0, w_hh on a 16-byte
+// boundary) and the engine's 32-bit offsets into G.
+static BwdForm bwd_form(const avvad_lstm_desc* d, const float* w_hh) {
+  const int B = d->B, T = d->T, H = d->H;
+  const bool fused = (B <= 64 || H <= 64) && H % 4 == 0 && ((uintptr_t)w_hh % 16 == 0) && !avvad_tune().lstm_no_fused_step &&
+                     (long)B * T * 4 * H < (1L << 29) - 64;
+  return fused ? BwdForm::FUSED : BwdForm::PLAIN;
+}
+
 }  // namespace
 
 extern "C" size_t avvad_lstm_workspace(const avvad_lstm_desc* d) {
@@ -523,42 +498,31 @@ extern "C" int avvad_lstm_layer_fwd(const float* x, const float* w_ih, const flo
   avvad_gemm_desc gd = gemm_desc(B * T, 4 * H, In, In, In, 4 * H, 0, 1, 0, 1);
   if ((rc = avvad_gemm_impl(x, w_ih, w.bias, w.G, &gd, s, w.slab))) return rc;
   const int split = pick_split(B, 4 * H, H);
-  // sequences are handled in groups of BG = min(B, 64) (blockIdx.y); a group's 16 waves are BG/16 sequence blocks x KS K-slices
-  const int BG = B < 64 ? B : 64;
-  // (the fused step and the persistent kernel read rows of W_hh and of y 16 bytes at a time: a base pointer off that
-  //  boundary -- a contiguous slice of a larger buffer -- takes the GEMM + gate kernels, whose loads adapt)
-  const bool fused_step = (B == 16 || B == 32 || (B % 64 == 0 && B <= 65535 * 64)) && (H % (16 * (256 / BG)) == 0) &&
-                          !avvad_tune().lstm_no_fused_step && (((uintptr_t)w_hh | (uintptr_t)y) & 15) == 0;
-  // ONE persistent launch for steps 1 .. T-1 (option lstm_no_persistent: the per-step kernels)
-  const int NKp = H / 64;
-  const bool persistent = fused_step && !avvad_tune().lstm_no_persistent && B <= 64 && B % 16 == 0 && T > 1 &&
-                          (NKp == 16 || NKp == 8 || NKp == 4) && H % 64 == 0 && H / 4 <= 256 &&
-                          (long)B * T * H * 4 < (1L << 31);
-  if (persistent && H / 4 <= persistent_capacity(NKp)) {
-    hipLaunchKernelGGL(lstm_gates_fwd, dim3(cdiv(B * H, 256)), dim3(256), 0, s, w.G, w.Cs, y, d->lengths, B, T, H, 0);
-    unsigned* sync = reinterpret_cast<unsigned*>(w.slab);          // the engine scratch is idle during the time loop
-    if (hipMemsetAsync(sync, 0, 2048, s) != hipSuccess) return AVVAD_ELAUNCH;   // status words + one flag per workgroup
-    // (behind them, from word 1024: the two padded hand-off copies of h, 2 x B x (H + 32) floats)
-    if (NKp == 16) hipLaunchKernelGGL(lstm_persistent_fwd<16>, dim3(H / 4), dim3(256), 0, s, w.G, w.Cs, y, w_hh, d->lengths, B, T, H, sync);
-    else if (NKp == 8) hipLaunchKernelGGL(lstm_persistent_fwd<8>, dim3(H / 4), dim3(256), 0, s, w.G, w.Cs, y, w_hh, d->lengths, B, T, H, sync);
-    else hipLaunchKernelGGL(lstm_persistent_fwd<4>, dim3(H / 4), dim3(256), 0, s, w.G, w.Cs, y, w_hh, d->lengths, B, T, H, sync);
-    hipLaunchKernelGGL(lstm_persistent_check, dim3(64), dim3(256), 0, s, sync, y, (long)B * T * H);
-    AVVAD_LAUNCH_CHECK();
-    return AVVAD_OK;
-  }
-  for (int t = 0; t < T; ++t) {
-    if (t > 0 && fused_step) {
-      if (B >= 128 && H % 16 == 0)        // many sequences: one read of h_{t-1} serves 16 hidden units
-        hipLaunchKernelGGL(lstm_step_fwd_mfma<4>, dim3(H / 16, B / BG), dim3(1024), 0, s, w.G, w.Cs, y, w_hh, d->lengths, B, T, H, t);
-      else
-        hipLaunchKernelGGL(lstm_step_fwd_mfma<1>, dim3(H / 4, B / BG), dim3(1024), 0, s, w.G, w.Cs, y, w_hh, d->lengths, B, T, H, t);
-      continue;
+  FwdChoice c = fwd_form(d, w_hh, y);
+  // the grid barrier needs the whole grid resident: a device that cannot hold it takes the per-step form
+  if (c.form == FwdForm::PERSISTENT && c.gx > persistent_capacity(c.n)) c = step_form(d, w_hh, y);
+  hipLaunchKernelGGL(lstm_gates_fwd, dim3(cdiv(B * H, 256)), dim3(256), 0, s, w.G, w.Cs, y, d->lengths, B, T, H, 0);
+  switch (c.form) {
+    case FwdForm::PERSISTENT: {
+      unsigned* sync = reinterpret_cast<unsigned*>(w.slab);          // the engine scratch is idle during the time loop
+      if (hipMemsetAsync(sync, 0, 2048, s) != hipSuccess) return AVVAD_ELAUNCH;   // status words + one flag per workgroup
+      // (behind them, from word 1024: the two padded hand-off copies of h, 2 x B x (H + 32) floats)
+      hipLaunchKernelGGL(persistent_kernel(c.n), dim3(c.gx), dim3(256), 0, s, w.G, w.Cs, y, w_hh, d->lengths, B, T, H, sync);
+      hipLaunchKernelGGL(lstm_persistent_check, dim3(64), dim3(256), 0, s, sync, y, (long)B * T * H);
+      break;
     }
-    if (t > 0) {
-      avvad_gemm_desc rd = gemm_desc(B, 4 * H, H, T * H, H, T * 4 * H, 0, 1, 1, split);
-      if ((rc = avvad_gemm_impl(y + (long)(t - 1) * H, w_hh, nullptr, w.G + (long)t * 4 * H, &rd, s, w.slab))) return rc;
-    }
-    hipLaunchKernelGGL(lstm_gates_fwd, dim3(cdiv(B * H, 256)), dim3(256), 0, s, w.G, w.Cs, y, d->lengths, B, T, H, t);
+    case FwdForm::STEP:
+      for (int t = 1; t < T; ++t)
+        hipLaunchKernelGGL(c.n == 4 ? lstm_step_fwd_mfma<4> : lstm_step_fwd_mfma<1>, dim3(c.gx, c.gy), dim3(1024), 0, s, w.G,
+                           w.Cs, y, w_hh, d->lengths, B, T, H, t);
+      break;
+    case FwdForm::GEMM:
+      for (int t = 1; t < T; ++t) {
+        avvad_gemm_desc rd = gemm_desc(B, 4 * H, H, T * H, H, T * 4 * H, 0, 1, 1, split);
+        if ((rc = avvad_gemm_impl(y + (long)(t - 1) * H, w_hh, nullptr, w.G + (long)t * 4 * H, &rd, s, w.slab))) return rc;
+        hipLaunchKernelGGL(lstm_gates_fwd, dim3(cdiv(B * H, 256)), dim3(256), 0, s, w.G, w.Cs, y, d->lengths, B, T, H, t);
+      }
+      break;
   }
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
@@ -578,9 +542,7 @@ extern "C" int avvad_lstm_layer_bwd(const float* x, const float* w_ih, const flo
   hipLaunchKernelGGL(fill0, dim3(grid1(B * H)), dim3(256), 0, s, w.DH, (long)B * H);
   hipLaunchKernelGGL(fill0, dim3(grid1(B * H)), dim3(256), 0, s, w.DC, (long)B * H);
   const int split = pick_split(B, H, 4 * H);
-  // fused form: the product's fix-up finishes step t - 1's gates (EpiLstmBwd); needs the 64x64 tile path with 16-byte rows
-  const bool fuse = (B <= 64 || H <= 64) && H % 4 == 0 && ((uintptr_t)w_hh % 16 == 0) && !avvad_tune().lstm_no_fused_step &&
-                    (long)B * T * 4 * H < (1L << 29) - 64;
+  const BwdForm form = bwd_form(d, w_hh);
   bool gates_done = false;     // step t's gate backward already ran inside the previous product's fix-up
   for (int t = T - 1; t >= 0; --t) {
     if (!gates_done)
@@ -588,7 +550,7 @@ extern "C" int avvad_lstm_layer_bwd(const float* x, const float* w_ih, const flo
                          H, t);
     gates_done = false;
     if (t > 0) {  // DH = dG_t . W_hh   ([B][4H] x [4H][H])
-      if (fuse) {
+      if (form == BwdForm::FUSED) {
         igemm::RowVec4 a{w.G + (long)t * 4 * H, (long)T * 4 * H, B, 4 * H, 0};     // (4H % 4 == 0, rows 16-byte aligned)
         igemm::ColPlain<4> bop{w_hh, H, H, 4 * H, 0};
         EpiLstmBwd e{w.DH, H, nullptr, 0, 1, 0, w.G, w.Cs, dy, w.DC, d->lengths, T, H, t - 1};

@@ -7,6 +7,7 @@
 // trunk / concat fusion / final Linear are per frame, the LSTMs are unidirectional (Audio_Net.py:50-59,
 // Video_Net.py:102-116, AV_Net.py:124-140, wavenet_autoencoder.py:74-93).
 #include "gemm_api.h"
+#include "lstm_cell.h"
 #include <stdlib.h>
 
 namespace {
@@ -29,8 +30,8 @@ __device__ __forceinline__ float4 ld4(const float* __restrict__ p, int k, int K)
 }
 
 // One time step of one layer for the few-rows regime: a weight-streaming product, not a tile GEMM.  Workgroup blockIdx.x
-// owns hidden units 4 blk .. 4 blk + 3, i.e. the 16 rows {gate * H + unit} of W_hh in lstm_step_fwd_mfma's order
-// 4 * u + gate, and reads them ONCE per launch with 16-byte loads; blockIdx.y owns a run of 16 * NG batch rows ("columns"
+// owns hidden units 4 blk .. 4 blk + 3, i.e. the 16 rows {gate * H + unit} of W_hh in the order 4 * u + gate of
+// lstm_cell.h, and reads them ONCE per launch with 16-byte loads; blockIdx.y owns a run of 16 * NG batch rows ("columns"
 // of the product), each group of 16 one v_mfma_f32_16x16x4_f32 column block, padded by clamping.  The four waves take the
 // 16-float chunks of K round-robin; their partial sums meet in LDS and are added in wave order, then wave g finishes
 // column group g: gate arithmetic in registers on top of the input projection G, then c (in place: only this workgroup
@@ -48,9 +49,9 @@ __global__ void __launch_bounds__(256)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, q = lane >> 4;
   const int cb = blockIdx.y * (16 * NG);
-  int unit = 4 * blockIdx.x + (i >> 2);
+  int unit = lstm_cell::quad_unit(i, blockIdx.x);
   if (unit > H - 1) unit = H - 1;                            // H % 4 != 0: the surplus rows repeat the last unit, never stored
-  const float* wrow = w_hh + ((long)(i & 3) * H + unit) * H;
+  const float* wrow = w_hh + (long)lstm_cell::whh_row(i, unit, H) * H;
   const float* hrow[NG];
   f32x4 acc[NG];
 #pragma unroll
@@ -66,23 +67,15 @@ __global__ void __launch_bounds__(256)
     const float4 a = ld4<VEC>(wrow, k, H);
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-      const float4 h = ld4<VEC>(hrow[g], k, H);
-      acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, h.x, acc[g], 0, 0, 0);
-      acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, h.y, acc[g], 0, 0, 0);
-      acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, h.z, acc[g], 0, 0, 0);
-      acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, h.w, acc[g], 0, 0, 0);
+      acc[g] = lstm_cell::mfma4(a, ld4<VEC>(hrow[g], k, H), acc[g]);
     }
   }
 #pragma unroll
   for (int g = 0; g < NG; ++g) part[g][wave][lane] = acc[g];
   __syncthreads();
   if (wave >= NG) return;
-  f32x4 r = part[wave][0][lane];
-  for (int s2 = 1; s2 < 4; ++s2) {
-    const f32x4 p = part[wave][s2][lane];
-    r[0] += p[0]; r[1] += p[1]; r[2] += p[2]; r[3] += p[3];
-  }
   // r[gate] = recurrent part of the gate of unit j for batch row b
+  const f32x4 r = lstm_cell::add_slices(part[wave][0][lane], &part[wave][0][lane], 4, 64);
   const int b = cb + 16 * wave + i, j = 4 * blockIdx.x + q;
   if (b >= B || j >= H) return;
   const long o = (long)b * H + j, oy = ((long)b * T + t) * H + j;
@@ -94,13 +87,10 @@ __global__ void __launch_bounds__(256)
     return;
   }
   const float* g = G + ((long)b * T + t) * 4 * H;
-  const float ig = sigmoidf_(g[j] + (r[0] + b_hh[j])), fg = sigmoidf_(g[H + j] + (r[1] + b_hh[H + j])),
-              gg = tanhf(g[2 * H + j] + (r[2] + b_hh[2 * H + j])), og = sigmoidf_(g[3 * H + j] + (r[3] + b_hh[3 * H + j]));
-  const float cn = fg * cp + ig * gg;
-  const float hn = og * tanhf(cn);
-  cout[o] = cn;
-  hnext[o] = hn;
-  y[oy] = hn;
+  const lstm_cell::Fwd c = lstm_cell::fwd([&](int e) { return g[e * H + j] + (r[e] + b_hh[e * H + j]); }, cp);
+  cout[o] = c.c;
+  hnext[o] = c.h;
+  y[oy] = c.h;
 }
 
 struct LWs {
@@ -119,11 +109,19 @@ LWs lcarve(const avvad_lstm_desc* d, float* base) {
   return w;
 }
 
-template <int NG>
-void launch_step(bool vec, dim3 grid, hipStream_t s, const float* G, const float* w_hh, const float* b_hh, const float* hp,
-                 float* hn, const float* ci, float* co, float* y, const int* len, int B, int T, int H, int t) {
-  if (vec) hipLaunchKernelGGL((lstm_state_step<NG, true>), grid, dim3(256), 0, s, G, w_hh, b_hh, hp, hn, ci, co, y, len, B, T, H, t);
-  else hipLaunchKernelGGL((lstm_state_step<NG, false>), grid, dim3(256), 0, s, G, w_hh, b_hh, hp, hn, ci, co, y, len, B, T, H, t);
+// The form of lstm_state_step: NG groups of 16 batch rows per workgroup (as many as cover B, four at the most), and VEC,
+// 16-byte loads of W_hh and h: rows of H % 4 == 0 floats from 16-byte bases -- w_hh, h0 (read at step 0) and hT (read by
+// a later call); the workspace buffers between them are aligned by the entry point's check.
+struct StateChoice { int NG; bool vec; };
+StateChoice state_form(int B, int H, const float* w_hh, const float* h0, const float* hT) {
+  return {B <= 16 ? 1 : (B <= 32 ? 2 : 4),
+          H % 4 == 0 && ((uintptr_t)w_hh & 15) == 0 && (!h0 || ((uintptr_t)h0 & 15) == 0) && ((uintptr_t)hT & 15) == 0};
+}
+using StateKernel = void (*)(const float*, const float*, const float*, const float*, float*, const float*, float*, float*,
+                             const int*, int, int, int, int);
+template <bool VEC>
+StateKernel state_kernel(int NG) {
+  return NG == 1 ? lstm_state_step<1, VEC> : (NG == 2 ? lstm_state_step<2, VEC> : lstm_state_step<4, VEC>);
 }
 
 // ==================================================================== streaming encoder
@@ -398,9 +396,9 @@ extern "C" int avvad_lstm_layer_fwd_state(const float* x, const float* w_ih, con
   avvad_gemm_desc gd = gemm_desc(B * T, 4 * H, In, In, In, 4 * H, 0, 1, 0, 1);
   int rc;
   if ((rc = avvad_gemm_impl(x, w_ih, b_ih, w.G, &gd, s, w.slab))) return rc;
-  const bool vec = H % 4 == 0 && ((uintptr_t)w_hh & 15) == 0 && (!h0 || ((uintptr_t)h0 & 15) == 0) && ((uintptr_t)hT & 15) == 0;
-  const int NG = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-  const dim3 grid(cdiv(H, 4), cdiv(B, 16 * NG));
+  const StateChoice c = state_form(B, H, w_hh, h0, hT);
+  const StateKernel step = c.vec ? state_kernel<true>(c.NG) : state_kernel<false>(c.NG);
+  const dim3 grid(cdiv(H, 4), cdiv(B, 16 * c.NG));
   if (grid.y > 65535) return AVVAD_EINVAL;
   // step t reads h from where step t - 1 wrote it and writes somewhere else: the last step into hT, the others into the
   // two workspace buffers in turn.  Only a one-step call with hT == h0 needs a copy behind it.
@@ -410,9 +408,7 @@ extern "C" int avvad_lstm_layer_fwd_state(const float* x, const float* w_ih, con
     const bool staged = hn == hp;                        // T == 1 and in place
     if (staged) hn = hb[0];
     const float* ci = t == 0 ? c0 : cT;
-    if (NG == 1) launch_step<1>(vec, grid, s, w.G, w_hh, b_hh, hp, hn, ci, cT, y, d->lengths, B, T, H, t);
-    else if (NG == 2) launch_step<2>(vec, grid, s, w.G, w_hh, b_hh, hp, hn, ci, cT, y, d->lengths, B, T, H, t);
-    else launch_step<4>(vec, grid, s, w.G, w_hh, b_hh, hp, hn, ci, cT, y, d->lengths, B, T, H, t);
+    hipLaunchKernelGGL(step, grid, dim3(256), 0, s, w.G, w_hh, b_hh, hp, hn, ci, cT, y, d->lengths, B, T, H, t);
     if (staged) hipLaunchKernelGGL(st_copy, dim3(cdiv(BH, 256)), dim3(256), 0, s, hb[0], hT, BH);
     hp = hn;
   }

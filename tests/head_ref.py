@@ -360,9 +360,9 @@ def lstm_layer_mutable(x, lengths, w_ih, w_hh, b_ih, b_hh, mutant=None):
     return torch.stack(outs, dim=1)
 
 
-# In = 40 unless stated; lengths ragged with lens[0] = T and at least one length of 1.  The kernel forms follow from the
-# predicates of avvad_lstm_layer_fwd / avvad_lstm_layer_bwd (csrc/lstm.hip) and are stated by the tests of
-# tests/test_head_gpu.py.
+# In = 40 unless stated; lengths ragged with lens[0] = T and at least one length of 1.  The kernel form of each case is
+# what lstm_fwd_form / lstm_bwd_form below (csrc/lstm.hip's fwd_form / bwd_form, restated) give for it; the tests of
+# tests/test_head_gpu.py name it, and test_case_lists_reach_what_they_claim (tests/test_head_cpu.py) holds them to it.
 LSTM_CASES = {
     "L1": dict(B=16, H=256, T=60),
     "L1s": dict(B=16, H=256, T=60, no_persistent=True, same_as="L1"),
@@ -386,6 +386,26 @@ LSTM_SUBSETS = {            # what is frozen (of every layer); "x": the input ne
     "only_weight_ih": ("x", "weight_hh", "bias_ih", "bias_hh"),
 }
 LSTM_PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+
+
+# csrc/lstm.hip: step_form / fwd_form and bwd_form.  ``misalign``: weight_hh (or, forward, y) off a 16-byte boundary.
+def lstm_fwd_form(B, T, H, misalign=False, lstm_no_fused_step=0, lstm_no_persistent=0):
+    """(form, n, grid): ("PERSISTENT", NK, (H / 4, 1)) for steps 1 .. T-1 in one launch -- on a device that holds the grid;
+    ("STEP", UB, grid) per step; ("GEMM", 0, None).  Step 0 is lstm_gates_fwd in every form, so T = 1 runs nothing else."""
+    BG = min(B, 64)
+    if not ((B in (16, 32) or (B % 64 == 0 and B <= 65535 * 64)) and H % (16 * (256 // BG)) == 0) or misalign \
+            or lstm_no_fused_step:
+        return "GEMM", 0, None
+    if not lstm_no_persistent and B <= 64 and T > 1 and H % 64 == 0 and H // 64 in (4, 8, 16) and B * T * H * 4 < 1 << 31:
+        return "PERSISTENT", H // 64, (H // 4, 1)
+    UB = 4 if B >= 128 else 1
+    return "STEP", UB, (H // (4 * UB), B // BG)
+
+
+def lstm_bwd_form(B, T, H, misalign=False, lstm_no_fused_step=0):
+    fused = (B <= 64 or H <= 64) and H % 4 == 0 and not misalign and not lstm_no_fused_step \
+        and B * T * 4 * H < (1 << 29) - 64
+    return "FUSED" if fused else "PLAIN"
 
 
 @functools.lru_cache(maxsize=None)

@@ -886,7 +886,7 @@ def test_alignment_speech_targets_and_ibm_from_spectrum(monkeypatch):
 
 def test_alignment_lstm_w_hh(monkeypatch):
     """The recurrent weights 4 bytes off: the forward leaves its fused step / persistent kernels (they read W_hh rows 16
-    bytes at a time) for the GEMM + gate kernels, the backward its fused form (lstm.hip: ``fuse``), and the state layer
+    bytes at a time) for the GEMM + gate kernels, the backward its fused form (lstm.hip: ``bwd_form``), and the state layer
     takes its scalar form (stream.hip: ``vec``).  Each against the oracle / torch at the aligned form's bound."""
     import torch.nn as nn
     from oracle import head

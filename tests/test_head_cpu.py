@@ -90,7 +90,8 @@ def test_restatements_equal_the_oracle_in_float64():
 
 
 def test_case_lists_reach_what_they_claim():
-    """the host-side arithmetic of csrc/mcb.hip's chunks() on the fusion cases, and the shapes of the ragged inputs"""
+    """the host-side arithmetic of csrc/mcb.hip's chunks() on the fusion cases, the shapes of the ragged inputs, and the
+    kernel forms that the ``test_lstm_*`` docstrings of tests/test_head_gpu.py name (csrc/lstm.hip's fwd_form / bwd_form)"""
     def chunks(M, C):
         RL = max(256 // (C // 4), 1)
         per = max(-(-M // 512), 16 * RL)
@@ -112,6 +113,29 @@ def test_case_lists_reach_what_they_claim():
     l2 = R.lstm_inputs("L2-T3")
     assert l2.lens[:16] == [3] * 16 and l2.lens[16:] == [1] * 16
     assert torch.equal(R.lstm_inputs("L1").x, R.lstm_inputs("L1s").x)
+
+    def forms(name, **options):
+        li = R.lstm_inputs(name)
+        return (R.lstm_fwd_form(li.B, li.T, li.H, li.misalign, lstm_no_persistent=int(li.no_persistent), **options),
+                R.lstm_bwd_form(li.B, li.T, li.H, li.misalign, **options))
+    assert forms("L1") == (("PERSISTENT", 4, (64, 1)), "FUSED") and R.lstm_inputs("L1").T == 60
+    assert forms("L1s") == (("STEP", 1, (64, 1)), "FUSED") and R.lstm_inputs("L1s").no_persistent
+    assert forms("L1-T5") == (("PERSISTENT", 4, (64, 1)), "FUSED")
+    assert forms("L2-T2") == forms("L2-T3") == (("PERSISTENT", 4, (64, 1)), "FUSED")
+    assert forms("L3") == (("GEMM", 0, None), "FUSED") and R.lstm_inputs("L3").B == 48
+    assert forms("L3p") == (("PERSISTENT", 8, (128, 1)), "FUSED")
+    assert forms("L4") == (("PERSISTENT", 16, (256, 1)), "FUSED")               # exactly the 256 flags one poll covers
+    assert forms("L5") == (("STEP", 4, (4, 2)), "FUSED") and R.lstm_inputs("L5").B > 64 >= R.lstm_inputs("L5").H
+    assert forms("L6") == (("GEMM", 0, None), "FUSED")
+    assert forms("L7") == (("GEMM", 0, None), "PLAIN")
+    for name in ("L8-B16", "L8-B3"):                                             # T = 1: step 0 alone, no recurrent kernel
+        assert R.lstm_inputs(name).T == 1 and forms(name)[0][0] != "PERSISTENT"
+    l9 = R.lstm_inputs("L9")
+    assert forms("L9") == (("GEMM", 0, None), "PLAIN") and l9.misalign
+    assert (R.lstm_fwd_form(l9.B, l9.T, l9.H), R.lstm_bwd_form(l9.B, l9.T, l9.H)) == (("PERSISTENT", 4, (64, 1)), "FUSED")
+    assert {n.split("-")[0] for n in R.LSTM_CASES} == {"L%d" % i for i in range(1, 10)} | {"L1s", "L3p"}
+    for name in ("L1", "L5"):                                                    # what lstm_no_fused_step = 1 selects
+        assert forms(name, lstm_no_fused_step=1) == (("GEMM", 0, None), "PLAIN")
     m1 = R.masked_bce_inputs("M1")
     assert sorted(set(m1.lens)) == list(range(1, 61)) and m1.logits.numel() == 15360
     assert float(R.masked_bce_inputs("Msat").logits.abs().max()) > 39
