@@ -478,9 +478,8 @@ class TrunkFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads) + (None,) * (2 * n)
 
 
-def trunk_saved_activations(feat):
-    """Test support: the post-ReLU activations kept for backward by the TrunkFn node behind ``feat``, as a dict
-    name -> (N,C,H,W) view: ``pool``, ``<stage>.<block>.a1``, ``<stage>.<block>`` (the oracle's names)."""
+def _trunk_node(feat):
+    """the TrunkFn node behind ``feat`` -> (frames, workspace, descriptor)"""
     todo, seen, node = [feat.grad_fn], set(), None          # breadth-first over the autograd graph behind `feat`
     while todo:
         f = todo.pop(0)
@@ -496,16 +495,39 @@ def trunk_saved_activations(feat):
     frames, ws = node.saved_tensors[0], node.saved_tensors[1]
     N, H, W = frames.shape
     training, momentum, eps = node.cfg
-    d = L.TrunkDesc(N, H, W, training, momentum, eps, 1)
+    return frames, ws, L.TrunkDesc(N, H, W, training, momentum, eps, 1)
+
+
+def _trunk_slot(d, idx):
+    off, c, h, w = C.c_size_t(), C.c_int(), C.c_int(), C.c_int()
+    L.check(L.lib().avvad_trunk_activation(C.byref(d), idx, C.byref(off), C.byref(c), C.byref(h), C.byref(w)), "avvad_trunk_activation")
+    return off.value, c.value, h.value, w.value
+
+
+def trunk_saved_activations(feat):
+    """Test support: the post-ReLU activations kept for backward by the TrunkFn node behind ``feat``, as a dict
+    name -> (N,C,H,W) view: ``pool``, ``<stage>.<block>.a1``, ``<stage>.<block>`` (the oracle's names)."""
+    frames, ws, d = _trunk_node(feat)
+    N = frames.shape[0]
     out = {}
     for idx in range(17):
-        off, c, h, w = C.c_size_t(), C.c_int(), C.c_int(), C.c_int()
-        L.check(L.lib().avvad_trunk_activation(C.byref(d), idx, C.byref(off), C.byref(c), C.byref(h), C.byref(w)), "avvad_trunk_activation")
-        t = ws[off.value: off.value + N * h.value * w.value * c.value].view(N, h.value, w.value, c.value).permute(0, 3, 1, 2)
+        off, c, h, w = _trunk_slot(d, idx)
+        t = ws[off: off + N * h * w * c].view(N, h, w, c).permute(0, 3, 1, 2)
         k = (idx - 1) // 2
         name = "pool" if idx == 0 else "%d.%d%s" % (4 + k // 2, k % 2, ".a1" if (idx - 1) % 2 == 0 else "")
         out[name] = t
     return out
+
+
+def trunk_saved_pool_argmax(feat):
+    """Test support: the max pool's arg-max plane kept for backward by the TrunkFn node behind ``feat``: (N,64,h2,w2) uint8,
+    the window position dh*3+dw (first maximum in row-major scan order) of every pooled element.  Like the activations it
+    must be read before ``backward()``, which frees the workspace."""
+    frames, ws, d = _trunk_node(feat)
+    N = frames.shape[0]
+    off, c, h, w = _trunk_slot(d, 17)
+    words = ws[off: off + N * h * w * (c // 4)]
+    return words.view(torch.uint8).view(N, h, w, c).permute(0, 3, 1, 2)       # (little endian: byte k of word q = channel 4q+k)
 
 
 # --------------------------------------------------------------------------- MCB fusion

@@ -1152,12 +1152,15 @@ extern "C" size_t avvad_trunk_workspace(const avvad_trunk_desc* d) {
 // Where the post-ReLU activations a forward run with save_for_backward keeps in its workspace live (test support: the
 // parity tests compare their sign patterns with the oracle's to tell a flipped ReLU unit from an indexing error).
 // index 0: pooled stem output; 1 + 2k: block k's first activation (after bn1 + ReLU); 2 + 2k: block k's output. NHWC.
+// index 17: the pool's arg-max plane (N * H * W * 16 32-bit words, byte k of word q: window position dh*3+dw of channel 4q+k).
 extern "C" int avvad_trunk_activation(const avvad_trunk_desc* d, int index, size_t* offset_floats, int* C, int* H, int* W) {
-  if (!d || d->N <= 0 || d->H < 32 || d->W < 32 || index < 0 || index > 16 || !offset_floats || !C || !H || !W) return AVVAD_EINVAL;
+  if (!d || d->N <= 0 || d->H < 32 || d->W < 32 || index < 0 || index > 17 || !offset_floats || !C || !H || !W) return AVVAD_EINVAL;
+  if (index == 17 && !d->save_for_backward) return AVVAD_EINVAL;     // (the plane is written only for a backward)
   Plan p;
   make_plan(d, &p);
   const int widths[4] = {64, 128, 256, 512};
   if (index == 0) { *offset_floats = p.p0; *C = 64; *H = p.h[2]; *W = p.w[2]; return AVVAD_OK; }
+  if (index == 17) { *offset_floats = p.am; *C = 64; *H = p.h[2]; *W = p.w[2]; return AVVAD_OK; }
   const int k = (index - 1) / 2, st = k / 2;
   *offset_floats = p.blk[k][(index - 1) % 2 == 0 ? 1 : 4];
   *C = widths[st]; *H = p.h[st + 2]; *W = p.w[st + 2];

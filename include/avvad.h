@@ -278,7 +278,10 @@ int avvad_conv2d_wgrad_bf16(const void* x16, const void* dy16, float* dw_packed,
 size_t avvad_trunk_workspace(const avvad_trunk_desc* d);
 /* Test support: offset (floats), channels and spatial size of the post-ReLU activation `index` that a forward run with
  * save_for_backward keeps in its workspace, NHWC.  index 0: pooled stem output; 1 + 2k: block k's first activation
- * (bn1 + ReLU); 2 + 2k: block k's output (k = 0..7).  The parity tests compare sign patterns with the oracle's. */
+ * (bn1 + ReLU); 2 + 2k: block k's output (k = 0..7).  The parity tests compare sign patterns with the oracle's.
+ * index 17 (save_for_backward only): the max pool's arg-max plane, N*H*W*16 32-bit words at `offset_floats` (C = 64, H x W
+ * the pooled grid).  Byte k of word q of a pooled position is the window position dh*3+dw (0..8, the window starts one
+ * row and one column before 2*ph, 2*pw) that holds the maximum of channel 4q+k: the first one in row-major scan order. */
 int avvad_trunk_activation(const avvad_trunk_desc* d, int index, size_t* offset_floats, int* C, int* H, int* W);
 int avvad_trunk_fwd(const float* frames, const avvad_trunk_params* p, float* feat /* [N][512] */,
                     const avvad_trunk_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
