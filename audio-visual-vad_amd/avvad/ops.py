@@ -455,6 +455,7 @@ class TrunkFn(torch.autograd.Function):
         if save:
             ctx.save_for_backward(frames, ws, *ts)
             ctx.cfg = (int(training), float(momentum), float(eps))
+            ctx.bf16 = L.get_option("bf16") == 1          # the data path this forward ran (csrc/trunk.hip native_bf16)
             ctx.owners = owners
         return feat
 
@@ -479,7 +480,7 @@ class TrunkFn(torch.autograd.Function):
 
 
 def _trunk_node(feat):
-    """the TrunkFn node behind ``feat`` -> (frames, workspace, descriptor)"""
+    """the TrunkFn node behind ``feat`` -> (frames, workspace, descriptor, whether its forward ran the bf16 data path)"""
     todo, seen, node = [feat.grad_fn], set(), None          # breadth-first over the autograd graph behind `feat`
     while todo:
         f = todo.pop(0)
@@ -495,7 +496,7 @@ def _trunk_node(feat):
     frames, ws = node.saved_tensors[0], node.saved_tensors[1]
     N, H, W = frames.shape
     training, momentum, eps = node.cfg
-    return frames, ws, L.TrunkDesc(N, H, W, training, momentum, eps, 1)
+    return frames, ws, L.TrunkDesc(N, H, W, training, momentum, eps, 1), bool(node.bf16)
 
 
 def _trunk_slot(d, idx):
@@ -506,13 +507,18 @@ def _trunk_slot(d, idx):
 
 def trunk_saved_activations(feat):
     """Test support: the post-ReLU activations kept for backward by the TrunkFn node behind ``feat``, as a dict
-    name -> (N,C,H,W) view: ``pool``, ``<stage>.<block>.a1``, ``<stage>.<block>`` (the oracle's names)."""
-    frames, ws, d = _trunk_node(feat)
+    name -> (N,C,H,W) view: ``pool``, ``<stage>.<block>.a1``, ``<stage>.<block>`` (the oracle's names).  A forward that ran
+    the bf16 data path (option "bf16" = 1) keeps them as NHWC bf16 at the same offsets, in the first half of each slot: they
+    come back as exact float32 COPIES of the stored values."""
+    frames, ws, d, bf16 = _trunk_node(feat)
     N = frames.shape[0]
     out = {}
     for idx in range(17):
         off, c, h, w = _trunk_slot(d, idx)
-        t = ws[off: off + N * h * w * c].view(N, h, w, c).permute(0, 3, 1, 2)
+        if bf16:
+            t = ws[off: off + N * h * w * c // 2].view(torch.bfloat16).view(N, h, w, c).permute(0, 3, 1, 2).float()
+        else:
+            t = ws[off: off + N * h * w * c].view(N, h, w, c).permute(0, 3, 1, 2)
         k = (idx - 1) // 2
         name = "pool" if idx == 0 else "%d.%d%s" % (4 + k // 2, k % 2, ".a1" if (idx - 1) % 2 == 0 else "")
         out[name] = t
@@ -523,7 +529,7 @@ def trunk_saved_pool_argmax(feat):
     """Test support: the max pool's arg-max plane kept for backward by the TrunkFn node behind ``feat``: (N,64,h2,w2) uint8,
     the window position dh*3+dw (first maximum in row-major scan order) of every pooled element.  Like the activations it
     must be read before ``backward()``, which frees the workspace."""
-    frames, ws, d = _trunk_node(feat)
+    frames, ws, d, _ = _trunk_node(feat)
     N = frames.shape[0]
     off, c, h, w = _trunk_slot(d, 17)
     words = ws[off: off + N * h * w * (c // 4)]

@@ -31,7 +31,10 @@ Measured.  Decisions that differ from float64 per run: float32 CPU evaluation 0 
 (default options: T1 4, T1e 3, T2 3, T3 2, T4 0, T5 4, T6 9, T7 0, T7e 0, T8 8; T8 under no_streamk 10 of 25), all inside
 the rule; no pool position differed anywhere.  Worst error / bound, MI355X | float32 CPU: features 0.21 | 0.15, gradients
 0.070 | 0.069, running statistics 0.043 | 0.026.  (units counts the 17 saved tensors, as _relu_flips does: 8.4 M for
-130 x 35x43, cap 10.)"""
+130 x 35x43, cap 10.)
+
+The bf16 data path (option "bf16" = 1) has its own reference at the end of this module: a replay that is pinned to the
+implementation's stored bf16 VALUES, not only to its decisions (``trunk_restated(..., bf16=...)``, ``check_trunk_bf16``)."""
 import functools
 import types
 
@@ -167,12 +170,16 @@ MUTANTS = ("pool_second_best", "pool_hw_swapped", "pool_drops_last", "stats_skip
            "s2_dgrad_misses_last", "wgrad_short_of_last_image")
 
 
-def trunk_restated(sd, x, training, masks=None, argmax=None, mutant=None):
+def trunk_restated(sd, x, training, masks=None, argmax=None, mutant=None, bf16=None):
     """``oracle.resnet18.trunk_forward`` on gray frames x (N,H,W) with every ReLU as ``z * mask`` and the pool as a gather.
+    (``bf16``: the value-pinned replay of the bf16 data path, see ``trunk_restated_bf16`` at the end of this module.)
     sd: keys without prefix.  masks: name -> bool (N,C,H,W) for the 17 layers of NAMES; argmax: (N,64,Hp,Wp) window
     positions dh*3+dw.  Left out, they are this evaluation's own: z > 0 and the first maximum in scan order.
     -> namespace(feat, stats (updated running statistics, sd untouched), pre (the 17 pre-activations; "pool": the largest
     pre-activation of the window), z0 (the stem's pre-activation), masks, argmax)."""
+    if bf16 is not None:
+        assert masks is None
+        return trunk_restated_bf16(sd, x, training, bf16, argmax, mutant)
     assert mutant is None or mutant in MUTANTS, mutant
     dt = x.dtype
     N = x.shape[0]
@@ -606,4 +613,418 @@ VARIANTS = [
     ("cls_cap40", dict(cls_cap=40), ("T1", "T8"), {}),
     ("max_cus200", dict(max_cus=200), ("T1", "T8"), {}),
     ("bwd_max_cus8", dict(bwd_max_cus=8), ("T1", "T8"), {}),
+]
+
+
+# ========================================================================================== the bf16 data path (option "bf16" = 1)
+# A VALUE-PINNED replay.  Under option "bf16" = 1 csrc/trunk.hip keeps the 17 post-ReLU activations as bf16, and bf16
+# rounding is discontinuous: a free-running reference is a bf16 step away after one layer and 5 .. 9 % away in the deep
+# gradients.  So the float64 replay CONTINUES WITH THE IMPLEMENTATION'S STORED VALUES: at storage point k it computes its own
+# pre-store value v_k from the implementation's stored inputs of that layer, the stored value s_k is held to v_k by the
+# forward rule, and the next layer takes s_k (the gradient path goes through v_k, ``_mix``).  Every layer is compared given
+# exact inputs, nothing compounds, a failure names layer and index, and the backward is the exact backward of the network
+# the implementation ran.
+#
+# Where the implementation rounds (read from csrc/trunk.hip, bn_kernels.h, bgemm.h, conv64.h, igemm.h):
+# * weights: convolutions 1 .. 19 multiply rne_bf16(w) (pack_all's bf16 packs, forward and data gradient alike); their
+#   gradient goes straight through to the fp32 master weight;
+# * the stem (convolution 0) runs the fp32 entry points whatever the option: its LDS kernels (stem_fwd_mfma, stem_wgrad_mfma)
+#   are fp32, its engine fall-backs go through igemm::launch, which under the option rounds BOTH operands to bf16 while
+#   staging.  Per form (``stem_rounding``, asserted by the CPU test): forward STEM -> exact, ENGINE -> rne(x) * rne(sum_c w);
+#   weight gradient STEM -> exact, ENGINE -> rne(x) * rne(d c0); the stem has no data gradient.  T5 runs the forward on the
+#   stem kernel and the weight gradient on the engine;
+# * forward stores: the 17 activations are rne_bf16(relu(fp32 value)) (stem_bn_relu_pool<true>, bn_act<true, .>); raw
+#   convolution outputs, batch statistics, the downsample branch's identity (bn_act reads the raw fp32 output of the 1x1
+#   convolution) and the features are fp32; a block input that serves as identity is read back as the stored bf16 value;
+#   the byte mask (and the pool / a1 masks the backward rebuilds) is the sign of the fp32 value before the store, which is the
+#   sign of the stored value (rne keeps a positive fp32 positive);
+# * backward stores: bn_bwd_apply<true> stores d(raw convolution output) as bf16 for every convolution behind the stem, and
+#   that one value feeds the data gradient and the weight gradient (``_RoundGrad`` on each raw output: identity forward,
+#   rne in the backward); gout, the data-gradient outputs and the whole stem backward are fp32.
+#
+# THE FORWARD RULE, per element: rne(relu(v - d_k)) <= s <= rne(relu(v + d_k)): one or two adjacent bf16 values (all values
+# up to rne(2 d_k) where |v| < d_k: a ReLU unit within rounding of zero).  Round-toward-zero, a double rounding and a missing
+# ReLU fall outside.  d_k = D16[case][k] is 10 x the largest |v32 - v64| of the float32 stand-in at that layer under the same
+# pinning (tests/test_trunk_bf16_cpu.py asserts 8 .. 16 x, the margin and reason of TAU).  D16's first entry is the stem's
+# pre-activation z0 as it runs under the option: the pool-position rule's tau.
+# VALUES, element-wise, no aggregate: features against the mean of the implementation's last stored activation,
+# 2e-5 max(1, max|ref|); the 40 running statistics 1e-5 + 1e-5 |ref|; the 60 gradients B16 max(1, max|ref|) with
+# B16 = max(1e-4, 10 x E32), E32 the float32 stand-in's worst such distance over all cases and gradients: a cotangent that
+# fp32 noise puts on the other bf16 neighbour moves by 2^-8 relative.
+FAMILY16 = "trunk16"
+D_NAMES = ["z0"] + NAMES
+TWO_VALUE_CAP = 0.05          # most elements of a layer whose admissible set holds two values (CPU test, on float64's own values)
+RUNS16 = []                   # (tag, label, largest two-value share of a layer, far-neighbour elements, elements) per passing run
+MUTANTS16 = ("store_truncates", "bn2_rounded_before_add", "ds_identity_rounded", "input_fp32_pitch", "mask_bits_reversed",
+             "mask_shifted_quad", "stats_skip_rows_128", "dgrad_pack_via_fp16", "dgrad_weights_unrounded", "stem_rounds_operands")
+
+# 10 x the measured float32 spread under the pinning, in the order of D_NAMES (tests/test_trunk_bf16_cpu.py)
+D16 = {
+    "T1": (3.5e-05, 3.5e-05, 2.7e-05, 1.5e-05, 2.1e-05, 2.0e-05, 2.2e-05, 3.4e-05, 1.9e-05, 1.5e-05, 2.0e-05, 2.1e-05, 1.8e-05, 2.0e-05, 1.9e-05, 2.8e-05, 2.5e-05, 2.3e-05),
+    "T1e": (3.4e-05, 3.4e-05, 3.3e-05, 3.0e-05, 7.5e-05, 5.2e-05, 1.3e-04, 1.2e-04, 1.6e-04, 1.9e-04, 2.4e-04, 2.7e-04, 2.9e-04, 3.8e-04, 3.6e-04, 4.4e-04, 4.0e-04, 3.3e-04),
+    "T2": (2.9e-05, 2.9e-05, 2.8e-05, 2.1e-05, 2.1e-05, 2.1e-05, 2.2e-05, 2.5e-05, 2.7e-05, 1.6e-05, 2.0e-05, 2.2e-05, 1.8e-05, 1.9e-05, 2.3e-05, 2.5e-05, 1.8e-05, 1.9e-05),
+    "T3": (3.0e-05, 2.8e-05, 2.0e-05, 1.9e-05, 2.7e-05, 2.4e-05, 1.7e-05, 2.6e-05, 2.6e-05, 1.8e-05, 1.9e-05, 2.0e-05, 1.7e-05, 1.8e-05, 2.0e-05, 2.3e-05, 2.1e-05, 2.3e-05),
+    "T4": (2.6e-05, 2.5e-05, 2.5e-05, 1.6e-05, 2.2e-05, 1.8e-05, 3.4e-05, 2.9e-05, 1.7e-05, 1.9e-05, 2.1e-05, 2.2e-05, 1.6e-05, 1.6e-05, 1.2e-05, 1.9e-05, 1.7e-05, 1.3e-05),
+    "T5": (2.9e-05, 2.9e-05, 2.1e-05, 1.7e-05, 2.4e-05, 2.2e-05, 3.0e-05, 3.0e-05, 1.8e-05, 1.9e-05, 2.3e-05, 2.6e-05, 2.3e-05, 2.3e-05, 1.9e-05, 2.6e-05, 2.1e-05, 2.1e-05),
+    "T6": (3.2e-05, 2.6e-05, 2.2e-05, 2.3e-05, 2.9e-05, 3.1e-05, 2.6e-05, 2.7e-05, 2.5e-05, 2.4e-05, 2.7e-05, 3.7e-05, 2.6e-05, 2.5e-05, 2.7e-05, 3.1e-05, 2.4e-05, 2.3e-05),
+    "T7": (1.8e-05, 1.8e-05, 1.2e-05, 1.1e-05, 1.2e-05, 1.0e-05, 9.9e-06, 1.1e-05, 1.1e-05, 8.4e-06, 1.1e-05, 1.4e-05, 1.0e-05, 1.0e-05, 9.8e-06, 1.5e-05, 1.1e-05, 1.2e-05),
+    "T7e": (2.3e-05, 2.3e-05, 2.2e-05, 2.4e-05, 5.6e-05, 3.6e-05, 1.3e-04, 1.1e-04, 1.2e-04, 1.4e-04, 1.8e-04, 2.0e-04, 2.0e-04, 1.8e-04, 2.1e-04, 4.0e-04, 3.0e-04, 2.1e-04),
+    "T8": (3.4e-05, 3.1e-05, 2.3e-05, 2.2e-05, 2.1e-05, 2.5e-05, 1.8e-05, 2.8e-05, 1.8e-05, 1.9e-05, 2.0e-05, 2.8e-05, 2.6e-05, 2.2e-05, 2.3e-05, 2.9e-05, 2.6e-05, 1.9e-05),
+}
+E32 = 1.1e-2                 # measured 1.13e-2 (T5, d/d 4.0.bn1.weight); 0.9 .. 1.1e-2 in training mode, 3.5e-3 in eval mode
+B16 = max(1e-4, 10 * E32)
+
+
+def d16(case):
+    return dict(zip(D_NAMES, D16[case]))
+
+
+_DROP = 45                    # float64 keeps 52 mantissa bits, bf16 7
+
+
+def rne_bf16(t):
+    """round to nearest even to bf16 precision, in t's dtype (float64: ONE rounding, on the bits; values below bf16's normal
+    range, 1.2e-38, keep more bits than bf16 has)"""
+    if t.dtype != torch.float64:
+        return t.bfloat16().to(t.dtype)
+    b = t.contiguous().view(torch.int64)
+    return ((b + ((b >> _DROP) & 1) + ((1 << (_DROP - 1)) - 1)) & ~((1 << _DROP) - 1)).view(torch.float64)
+
+
+def trunc_bf16(t):
+    if t.dtype != torch.float64:
+        return (t.float().contiguous().view(torch.int32) & ~0xFFFF).view(torch.float32).to(t.dtype)
+    return (t.contiguous().view(torch.int64) & ~((1 << _DROP) - 1)).view(torch.float64)
+
+
+class _RoundGrad(torch.autograd.Function):
+    """identity forward; the cotangent is stored as bf16 (bn_bwd_apply<true>)"""
+
+    @staticmethod
+    def forward(ctx, c):
+        return c.view_as(c)
+
+    @staticmethod
+    def backward(ctx, g):
+        return rne_bf16(g)
+
+
+def _quads(m, f):
+    """f on the (quads, 4) view of an (N,C,H,W) mask in the kernels' NHWC order"""
+    n, c, h, w = m.shape
+    return f(m.permute(0, 2, 3, 1).reshape(-1, 4)).reshape(n, h, w, c).permute(0, 3, 1, 2)
+
+
+def trunk_restated_bf16(sd, x, training, cfg, argmax=None, mutant=None):
+    """the bf16 data path restated (see above).  cfg: namespace(acts: name -> the stored values (N,C,H,W) of the 17 layers to
+    continue with, or None: this evaluation's own, rne(relu(v)); stem: subset of {"fwd", "wgrad"}, the stem products that run
+    on the engine).  -> namespace(feat, stats, v (the 17 pre-ReLU pre-store values), z0, acts, masks, argmax)"""
+    assert mutant is None or mutant in MUTANTS16, mutant
+    dt = x.dtype
+    pin = cfg.acts
+    stats, v, acts, used = {}, {}, {}, {}
+    rnd = trunc_bf16 if mutant == "store_truncates" else rne_bf16
+
+    def bn(c, p, skip=False):
+        w, b, rm, rv = sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"]
+        if not training:
+            stats[p + ".running_mean"], stats[p + ".running_var"] = rm.detach().clone(), rv.detach().clone()
+            return (c - rm[None, :, None, None]) * (w / torch.sqrt(rv + EPS))[None, :, None, None] + b[None, :, None, None]
+        src = c[:128] if skip else c
+        n = src.numel() // src.shape[1]
+        mean = src.sum((0, 2, 3)) / n
+        var = ((src - mean[None, :, None, None]) ** 2).sum((0, 2, 3)) / n
+        stats[p + ".running_mean"] = ((1 - MOMENTUM) * rm + MOMENTUM * mean).detach()
+        stats[p + ".running_var"] = ((1 - MOMENTUM) * rv + MOMENTUM * var * (n / max(n - 1, 1))).detach()
+        return (c - mean[None, :, None, None]) * (w / torch.sqrt(var + EPS))[None, :, None, None] + b[None, :, None, None]
+
+    def wq(w, via_fp16=False):
+        w0 = w.detach()
+        if via_fp16:
+            w0 = w0.half().to(dt)
+        return _mix(rne_bf16(w0), w)
+
+    def conv(y, w, stride, pad):
+        if mutant in ("dgrad_weights_unrounded", "dgrad_pack_via_fp16"):      # the data gradient multiplies other weights
+            wd = w.detach() if mutant == "dgrad_weights_unrounded" else wq(w, True).detach()
+            dpath = F.conv2d(y, wd, None, stride, pad)
+            c = F.conv2d(y.detach(), wq(w), None, stride, pad) + (dpath - dpath.detach())
+        else:
+            c = F.conv2d(y, wq(w), None, stride, pad)
+        return _RoundGrad.apply(c)
+
+    def store(vk, name, bwd_mask=None):
+        v[name] = vk
+        s = pin[name].to(dt) if pin is not None else rnd(vk.detach().clamp(min=0))
+        m = s > 0
+        acts[name], used[name] = s, m
+        return _mix(s, vk * (m if bwd_mask is None else bwd_mask(m)).to(dt))
+
+    bwd = None
+    if mutant == "mask_bits_reversed":
+        bwd = lambda m: _quads(m, lambda q: q.flip(1))
+    if mutant == "mask_shifted_quad":
+        bwd = lambda m: _quads(m, lambda q: q.roll(1, 0))
+    # stem: value and gradient path apart, as the forward and the weight gradient may run on different forms
+    w0 = sd["0.weight"].sum(1, keepdim=True)
+    x1 = x[:, None]
+    if "fwd" in cfg.stem or mutant == "stem_rounds_operands":
+        c0 = F.conv2d(rne_bf16(x1), rne_bf16(w0.detach()), None, 2, 3)
+    else:
+        c0 = F.conv2d(x1, w0.detach(), None, 2, 3)
+    gp = _RoundGrad.apply(F.conv2d(rne_bf16(x1), w0, None, 2, 3)) if "wgrad" in cfg.stem else F.conv2d(x1, w0, None, 2, 3)
+    z0 = bn(_mix(c0, gp), "1")
+    zw = pool_windows(z0, 0.0)
+    yw = pool_windows(z0.detach().clamp(min=0), float("-inf"))
+    am = argmax.long() if argmax is not None else yw.argmax(0)
+    y = store(zw.gather(0, am[None])[0], "pool")
+    cin = 64
+    for li, (c, stride) in enumerate(resnet18.STAGES):
+        for bi in range(2):
+            p = "%d.%d" % (4 + li, bi)
+            s = stride if bi == 0 else 1
+            k = dict(skip=mutant == "stats_skip_rows_128") if c >= 128 else {}
+            o = store(bn(conv(y, sd[p + ".conv1.weight"], s, 1), p + ".bn1", **k), p + ".a1")
+            z2 = bn(conv(o, sd[p + ".conv2.weight"], 1, 1), p + ".bn2", **k)
+            if mutant == "bn2_rounded_before_add":
+                z2 = _mix(rne_bf16(z2.detach()), z2)
+            if s != 1 or cin != c:
+                idn = bn(conv(y, sd[p + ".downsample.0.weight"], s, 0), p + ".downsample.1", **k)
+                if mutant == "ds_identity_rounded":
+                    idn = _mix(rne_bf16(idn.detach()), idn)
+            else:
+                idn = y
+                if mutant == "input_fp32_pitch" and p == "5.1":      # the second half of every row comes from the next row
+                    n_, c_, h_, w_ = y.shape
+                    t = y.detach().permute(0, 2, 3, 1).reshape(-1, c_)
+                    t = torch.cat([t[:, :c_ // 2], t.roll(-1, 0)[:, :c_ // 2]], 1)
+                    idn = _mix(t.reshape(n_, h_, w_, c_).permute(0, 3, 1, 2), y)
+            y = store(z2 + idn, p, bwd)
+            cin = c
+    return types.SimpleNamespace(feat=y.mean((2, 3)), stats=stats, v=v, z0=z0, acts=acts, masks=used, argmax=am)
+
+
+def run16(case, dtype, acts=None, argmax=None, frozen=(), accumulate=False, mutant=None, stem=None):
+    """forward + backward of sum(feat * G) of the bf16 restatement in ``dtype`` (``acts``: pinned to these stored values)"""
+    inp = inputs(case)
+    sd = {k: v.to(dtype).clone() if v.is_floating_point() else v for k, v in inp.sd.items()}
+    params = {k: sd[k].requires_grad_(k not in frozen) for k in param_keys()}
+    if accumulate:
+        for k, v in params.items():
+            if k not in frozen:
+                v.grad = prefill(k, v.shape).to(dtype)
+    cfg = types.SimpleNamespace(acts=acts, stem=stem_rounding(case) if stem is None else stem)
+    r = trunk_restated(sd, inp.x.to(dtype), inp.training, argmax=argmax, mutant=mutant, bf16=cfg)
+    (r.feat * inp.G.to(dtype)).sum().backward()
+    return types.SimpleNamespace(
+        feat=r.feat.detach(), grads={k: v.grad for k, v in params.items()}, stats=r.stats, acts=r.acts,
+        argmax=r.argmax.to(torch.uint8), v={k: t.detach() for k, t in r.v.items()}, z0=r.z0.detach())
+
+
+def trunk_bf16_standin(inp, frozen=(), accumulate=False, mutant=None, stem=None):
+    """the float32 CPU stand-in of the bf16 data path: the restatement in float32 with .bfloat16().float() at the storage
+    points, under its own stored values and decisions"""
+    r = run16(inp.case, torch.float32, None, None, frozen, accumulate, mutant, stem)
+    return dict(feat=r.feat, grads=r.grads, stats=r.stats, acts=r.acts, argmax=r.argmax, v=r.v, z0=r.z0)
+
+
+def replay(case, got, stem=None):
+    """the float64 replay pinned to the stored values and pool positions of ``got``"""
+    return run16(case, torch.float64, {k: got["acts"][k].detach().cpu().double() for k in NAMES}, got["argmax"].cpu(), stem=stem)
+
+
+def admissible(vk, d):
+    """-> (lo, hi) of the forward rule"""
+    return rne_bf16((vk - d).clamp(min=0)), rne_bf16((vk + d).clamp(min=0))
+
+
+def two_value_shares(v, case):
+    """per layer: the share of elements whose admissible set holds more than one value"""
+    d = d16(case)
+    out = []
+    for k in NAMES:
+        lo, hi = admissible(v[k], d[k])
+        out.append(float((lo != hi).double().mean()))
+    return out
+
+
+def check_trunk_bf16(impl, case, frozen=(), options_label="", accumulate=False, tag="gpu", options=None):
+    """``impl(inp, frozen)`` -> dict(feat, grads, stats as for ``check_trunk``; acts {17 names: the stored activations as exact
+    float32 copies (N,C,H,W)}, argmax).  Every failing comparison is collected and raised as ONE AssertionError whose lines
+    start with the check that failed ("stored", "pool", "rule", "features", "running statistics", "gradient").
+    -> (elements with a two-value admissible set, elements on the far neighbour)"""
+    inp = inputs(case)
+    got = impl(inp, tuple(frozen))
+    t = "%s%s%s%s " % (case, " " + options_label if options_label else "", " [frozen: %d]" % len(frozen) if frozen else "",
+                       " [accumulate]" if accumulate else "")
+    d = d16(case)
+    for k in NAMES:                                  # what the accessor hands out: exact float32 copies of bf16 values
+        a = got["acts"][k]
+        assert a.dtype == torch.float32, "%sstored %s is %s" % (t, k, a.dtype)
+        a = a.cpu()
+        assert torch.equal(a.bfloat16().float(), a), "%sstored %s holds values that are no bf16 values" % (t, k)
+        assert bool((a >= 0).all()), "%sstored %s holds negative values" % (t, k)
+    ref = replay(case, got, stem_rounding(case, **(options or {})))
+    fails = []
+    am = got["argmax"].cpu().long()
+    yw = pool_windows(ref.z0.clamp(min=0), float("-inf"))
+    assert tuple(am.shape) == tuple(yw.shape[1:]), (tuple(am.shape), tuple(yw.shape[1:]))
+    assert int(am.max()) <= 8, "pool arg-max %d is no window position" % int(am.max())
+    diff = am != yw.argmax(0)
+    n_pool = int(diff.sum())
+    if n_pool:
+        gap = yw.max(0)[0] - yw.gather(0, am[None])[0]
+        out = diff & ~(gap <= d["z0"])
+        for idx in out.nonzero()[:4].tolist():
+            fails.append("pool: window %s takes position %d, %.3e below float64's maximum > tau = %.1e" % (
+                tuple(idx), int(am[tuple(idx)]), float(gap[tuple(idx)]), d["z0"]))
+    n_two = n_far = n_el = 0
+    worst_share = 0.0
+    for k in NAMES:
+        vk, s = ref.v[k], got["acts"][k].cpu().double()
+        assert tuple(s.shape) == tuple(vk.shape), (k, tuple(s.shape), tuple(vk.shape))
+        lo, hi = admissible(vk, d[k])
+        two, far = int((lo != hi).sum()), int((s != rne_bf16(vk.clamp(min=0))).sum())
+        n_two, n_far, n_el = n_two + two, n_far + far, n_el + s.numel()
+        worst_share = max(worst_share, two / s.numel())
+        bad = (s < lo) | (s > hi)
+        if tag is not None:
+            H.log_line("head %-5s %-8s %s%-7s two-value %.4f  far neighbour %d of %d  outside the rule %d" % (
+                tag, FAMILY16 + ".r", t, k, two / s.numel(), far, s.numel(), int(bad.sum())))
+        for idx in bad.nonzero()[:3].tolist():
+            i = tuple(idx)
+            fails.append("rule: %s%s stored %.9g outside [%.9g, %.9g]: v64 = %.9g, d = %.1e" % (
+                k, i, float(s[i]), float(lo[i]), float(hi[i]), float(vk[i]), d[k]))
+        if int(bad.sum()) > 3:
+            fails.append("rule: ... and %d more in %s" % (int(bad.sum()) - 3, k))
+
+    def rep(what, *a, **kw):
+        try:
+            H.report(*a, tag=tag, **kw)
+        except AssertionError as e:
+            fails.append("%s: %s" % (what, e))
+    rep("features", FAMILY16 + ".f", t + "features", got["feat"], ref.feat, FEAT_BOUND * max(1.0, float(ref.feat.abs().max())))
+    assert set(got["stats"]) == set(ref.stats), sorted(set(got["stats"]) ^ set(ref.stats))
+    for k in sorted(ref.stats):
+        rep("running statistics", FAMILY16 + ".s", t + k, got["stats"][k], ref.stats[k], 1e-5, rtol=1e-5)
+    grads = got["grads"]
+    assert set(grads) == set(ref.grads), sorted(set(grads) ^ set(ref.grads))
+    for k in param_keys():
+        if k in frozen:
+            assert grads[k] is None, t + k + " is frozen and has a gradient"
+            continue
+        assert grads[k] is not None, t + k + " has no gradient"
+        g, r = grads[k].detach().cpu().double(), ref.grads[k]
+        assert tuple(g.shape) == tuple(r.shape), (k, tuple(g.shape))
+        if accumulate:
+            g = g - prefill(k, r.shape).double()
+        rep("gradient", FAMILY16 + ".g", t + "d/d" + k, g, r, B16 * max(1.0, float(r.abs().max())))
+    if tag is not None:
+        H.log_line("head %-5s %-8s %stwo-value elements %d, far neighbour %d, of %d; largest two-value share of a layer %.4f; "
+                   "pool positions that differ %d" % (tag, FAMILY16, t, n_two, n_far, n_el, worst_share, n_pool))
+    kinds = []                                       # at most 4 lines per check, so that no check's verdict is cut off
+    for f in fails:
+        if f.split(":")[0] not in kinds:
+            kinds.append(f.split(":")[0])
+    shown = [f for kd in kinds for f in [x for x in fails if x.split(":")[0] == kd][:4]]
+    assert not fails, "%s%d comparisons fail\n%s" % (t, len(fails), "\n".join(shown))
+    if tag is not None:
+        RUNS16.append((tag, t.strip(), worst_share, n_far, n_el))
+    return n_two, n_far
+
+
+def log_worst16(tag):
+    for (tg, family), (ratio, name) in sorted(H.WORST.items()):
+        if tg == tag and family.startswith(FAMILY16):
+            H.log_line("head %-5s %-8s WORST ratio=%.4f  (%s)" % (tag, family, ratio, name))
+    runs = [r for r in RUNS16 if r[0] == tag]
+    H.log_line("head %-5s %-8s runs: %d; largest two-value share / far-neighbour elements: %s" % (
+        tag, FAMILY16, len(runs), "; ".join("%s: %.4f / %d of %d" % r[1:] for r in runs) or "none"))
+
+
+# ------------------------------------------------------------------------------------------ the bf16 form choices, restated
+# csrc/trunk.hip: bf16_conv_ok, cls16_common, conv_fwd16_cls_ok, conv_dgrad16_cls_ok, conv_wgrad16_tap_ok, conv64_ok(g, true)
+# and the b16 rows of fwd_form / dgrad_form / wgrad_form.  The stem keeps its fp32 row.
+def bf16_conv_ok(g):
+    return (g.C % 64 == 0 and g.Co % 64 == 0 and g.KS * g.KS <= 32 and fits_buf(g.N * g.H * g.W * g.C // 2) and
+            fits_buf(g.N * g.Ho * g.Wo * g.Co // 2) and fits_buf(g.KS * g.KS * g.C * g.Co // 2))
+
+
+def cls16_common(g, o):
+    return (not o["no_cls"] and g.KS == 3 and g.pad == 1 and g.N >= 128 and g.Ho >= 2 and g.Wo >= 2 and g.Ho * g.Wo <= 9 and
+            o["no_streamk"] == 0)
+
+
+def conv_fwd16_cls_ok(g, o):
+    return cls16_common(g, o) and g.Co >= 128 and g.Ho * g.Wo * cdiv(g.N, 128) * cdiv(g.Co, 128) <= cls_tile_cap(o)
+
+
+def conv_dgrad16_cls_ok(g, o):
+    form = cls16_common(g, o) if g.stride == 1 else (g.stride == 2 and g.KS == 3 and g.pad == 1 and not o["no_cls"] and
+                                                     not o["no_s2_cls"] and o["no_streamk"] == 0 and g.N >= 128)
+    return bool(form) and g.C >= 128 and g.H * g.W * cdiv(g.N, 128) * cdiv(g.C, 128) <= cls_tile_cap(o)
+
+
+def conv_wgrad16_tap_ok(g, o):
+    return cls16_common(g, o) and g.C % 128 == 0 and g.Co >= 128 and 9 * (g.C // 128) * cdiv(g.Co, 128) <= cls_tile_cap(o)
+
+
+def fwd_form16(g, o):
+    cols = 64 if g.Co <= 64 else 128
+    if conv64_ok(g, o):                              # (conv64_ok(g, true): whatever option bf16 says)
+        return "CONV64", min(max(cdiv(g.N * g.H * g.W, 32), 1), _cus(o))
+    if conv_fwd16_cls_ok(g, o):
+        return "CLS", g.Ho * g.Wo * cdiv(g.N, 128)
+    return _engine("ENGINE", 128, cols, True), cdiv(g.N * g.Ho * g.Wo, 128)
+
+
+def dgrad_form16(g, o):
+    if conv64_ok(g, o):
+        return "CONV64"
+    if conv_dgrad16_cls_ok(g, o):
+        return "CLS"
+    return _engine("PARITY" if g.stride == 2 else "ENGINE", 128, 64 if g.C <= 64 else 128, True)
+
+
+def wgrad_form16(g, o):
+    return "TAP" if conv_wgrad16_tap_ok(g, o) else _engine("ENGINE", 128, 64 if g.Co <= 64 else 128, True)
+
+
+def forms16(case, **options):
+    """``forms`` for the bf16 data path: the stem's row is the fp32 one (its launchers are the fp32 entry points)"""
+    c = CASES[case]
+    assert set(options) <= set(OPTIONS), options
+    o = dict(OPTIONS, **options)
+    ob = dict(o)
+    if o["bwd_max_cus"] > 0 and (o["max_cus"] <= 0 or o["bwd_max_cus"] < o["max_cus"]):
+        ob["max_cus"] = o["bwd_max_cus"]
+    rows = {}
+    for i, g in enumerate(geoms(c["N"], c["H"], c["W"])):
+        if i == 0:
+            rows[g.name] = forms(case, **options)[g.name]
+            continue
+        assert bf16_conv_ok(g), g.name
+        n = 0
+        if c["training"] and not o["no_fused_stats"]:
+            n = fwd_form16(g, o)[1]
+            n = n if n * g.Co <= STAT_CHUNKS * MAXC else 0
+        chunks = None if not c["training"] else (n if n else "col %d" % stat_ctx(g.N * g.Ho * g.Wo, g.Co)[0])
+        rows[g.name] = (fwd_form16(g, o)[0], dgrad_form16(g, ob), wgrad_form16(g, ob), chunks)
+    return rows
+
+
+def stem_rounding(case, **options):
+    """which of the stem's products round their operands to bf16 under the option: those on the engine"""
+    f = forms(case, **options)["0"]
+    return frozenset((["fwd"] if f[0] != "STEM" else []) + (["wgrad"] if f[2] != "STEM" else []))
+
+
+# option variants of the GPU test: (label, options, cases); the CPU test asserts that each changes a bf16 row of every case
+VARIANTS16 = [
+    ("no_cls", dict(no_cls=1), ("T1", "T8")),
+    ("no_s2_cls", dict(no_s2_cls=1), ("T1", "T8")),
+    ("no_conv64", dict(no_conv64=1), ("T1", "T7")),
+    ("no_streamk", dict(no_streamk=1), ("T1",)),
+    ("no_fused_stats", dict(no_fused_stats=1), ("T1", "T7")),
+    ("bwd_max_cus8", dict(bwd_max_cus=8), ("T1", "T8")),
 ]
