@@ -17,21 +17,21 @@
 //      image k-major, one row of BX bf16 (+64 B pad) per pixel; a fragment is two ds_read_b64_tr_b16 (4 pixels x 16
 //      channels per 16-lane group, delivered channel-on-lane): row stride = 64 B mod 256 B makes the four rows of a
 //      32-lane half cover all banks.
-// Work decomposition, slabs and the ordered fix-up are the fp32 engine's (igemm.h): data-parallel rounds of whole tiles +
-// one stream-K round, bit-reproducible.  One workgroup = 4 waves (2 x 2), each (BM/2) x (BN/2) as TM x TN 32x32 accumulators.
+// Work decomposition, share arithmetic, slabs, the ordered fix-up and the launch plan are streamk.h's, shared with the fp32
+// engine: data-parallel rounds of whole tiles + one stream-K round, bit-reproducible.  The walk and the tile epilogue below
+// are the fp32 kernel's text (igemm::kernel) on a 2 x 2 wave grid, without bias and K-major cells.
+// One workgroup = 4 waves (2 x 2), each (BM/2) x (BN/2) as TM x TN 32x32 accumulators.
 #pragma once
 #include "conv_ops.h"
 
 namespace bgemm {
 
 using igemm::ClassTile;
-using igemm::EpiCls;
-using igemm::EpiStore;
 using igemm::HasPrep2;
 using igemm::HasSched;
 using igemm::HasStat;
-using igemm::HasTile;
 using igemm::IsPlain;
+using igemm::HasTile;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -133,10 +133,9 @@ __global__ void __launch_bounds__(256, 2)
 
   const long G = gridDim.x;
   const long g = xcd_remap(blockIdx.x, gridDim.x);
-  long rem_iters = (long)rem_tiles * ktiles;
-  if constexpr (HasSched<Epi>::value) rem_iters = E.sched.total();      // position classes: every tile is in the pool
-  long it = g * rem_iters / G;
-  const long it_end = (g + 1) * rem_iters / G;
+  const igemm::Share<long> share = igemm::Share<long>::of(E, rem_tiles, ktiles, G);     // (streamk.h)
+  long it = share.lo(g);
+  const long it_end = share.hi(g);
   const long ntiles_all = (long)((M + BM - 1) / BM) * ntn;
   int round = 0;
 
@@ -152,9 +151,9 @@ __global__ void __launch_bounds__(256, 2)
       if constexpr (HasSched<Epi>::value) {
         E.sched.locate(it, tile, kt0, klen);
       } else {
-        const long tr = it / ktiles;
+        long tr;
+        igemm::Share<long>::locate(E, it, ktiles, tr, kt0, klen);
         tile = (int)((long)full_rounds * G + tr);
-        kt0 = (int)(it - tr * ktiles);
       }
       kt1 = (int)min((long)klen, kt0 + (it_end - it));
       it += kt1 - kt0;
@@ -386,71 +385,25 @@ static inline int launch(const AOp& a, const BOp& b, const Epi& e, int M, int N,
   if (M <= 0 || N <= 0 || K <= 0) return AVVAD_EINVAL;
   const int ktiles = cdiv(K, BKU);
   const long ntiles = (long)cdiv(M, BM) * cdiv(N, BN);
-  const AvvadTune& tn = avvad_tune();
-  const int cus = (tn.max_cus > 0 && tn.max_cus < igemm::NUM_CU) ? tn.max_cus : igemm::NUM_CU;
-  long G = (long)cus * 2;                                    // two 4-wave workgroups per CU (LDS: 2 x 72 KB at 128x128 KK)
-  if (G * BM * BN > (long)igemm::SLAB_FLOATS) G = (long)(igemm::SLAB_FLOATS / ((size_t)BM * BN));
-  const bool no_sk = !slab || tn.no_streamk == 1 || tn.no_streamk == 10 + e.mode || (double)ntiles * ktiles * (double)G >= 4.0e9;
-  long full_rounds = ntiles / G, rem = ntiles - full_rounds * G;
-  if (no_sk || rem * 10 >= G * 9) {
-    if (rem > 0) ++full_rounds;
-    rem = 0;
-  }
-  if (rem > 0 && full_rounds == 0) {
-    const long iters = ntiles * ktiles;
-    const long cap = iters / 4 > 0 ? iters / 4 : 1;
-    if (G > cap) G = cap;
-  }
-  bool stat = false;
-  if constexpr (std::is_same<Epi, EpiStore>::value) {
-    stat = e.stat != nullptr;
-    if (stat && (e.cs != 1 || (e.ldc & 3) || (N & 3) || (((uintptr_t)e.C) & 15) || e.bias != nullptr)) return AVVAD_EINVAL;
-  }
+  // two 4-wave workgroups per CU (LDS: 2 x 72 KB at 128x128 KK)
+  const igemm::Rounds plan = igemm::plan_rounds(ntiles, ktiles, igemm::workers(2, BM, BN), slab != nullptr, e.mode);
+  if (!igemm::stat_ok(e, N)) return AVVAD_EINVAL;
   if (e.bias != nullptr) return AVVAD_EINVAL;               // (no bias in this engine's epilogue: the convolutions have none)
-  const int fr = (int)full_rounds, rt = (int)rem;
-  hipLaunchKernelGGL((kernel<BM, BN, MM, AOp, BOp, Epi>), dim3((int)G), dim3(256), 0, s, a, b, e, M, N, ktiles, fr, rt, slab);
-  if (rt > 0 && stat) {
-    if constexpr (std::is_same<Epi, EpiStore>::value)
-      hipLaunchKernelGGL((igemm::fixup_tile<BM, BN>), dim3(rt), dim3(256), 0, s, e, slab, M, N, ktiles, G, fr, rt, cdiv(N, BN));
-  } else if (rt > 0) {
-    if ((G + rt - 1) / rt <= 6)
-      hipLaunchKernelGGL((igemm::fixup1<BM, BN, Epi>), dim3(rt * (BM * BN / 1024)), dim3(256), 0, s, e, slab, M, N, ktiles, G, fr, rt, cdiv(N, BN));
-    else
-      hipLaunchKernelGGL((igemm::fixup<BM, BN, Epi>), dim3(rt * (BM * BN / 256)), dim3(256), 0, s, e, slab, M, N, ktiles, G, fr, rt, cdiv(N, BN));
-  }
+  hipLaunchKernelGGL((kernel<BM, BN, MM, AOp, BOp, Epi>), dim3((int)plan.G), dim3(256), 0, s, a, b, e, M, N, ktiles,
+                     plan.full_rounds, plan.rem, slab);
+  if (plan.rem > 0) igemm::launch_fixup<BM, BN>(e, slab, M, N, ktiles, plan.G, plan.full_rounds, plan.rem, s);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
 
-// position-class product on the bf16 engine (igemm::launch_cls is the fp32 twin): 128x128 KK tiles
+// position-class product on the bf16 engine (igemm::launch_cls is the fp32 twin, the plan is shared): 128x128 KK tiles
 template <bool MM, class AOp, class BOp, class Epi>
 static inline int launch_cls(const AOp& a, const BOp& b, const Epi& e, int Mp, int N, hipStream_t s, float* slab) {
-  constexpr int BM = 128, BN = 128;
-  if (Mp <= 0 || N <= 0 || !slab) return AVVAD_EINVAL;
-  const AvvadTune& tn = avvad_tune();
-  const long ntiles = (long)cdiv(Mp, BM) * cdiv(N, BN);
-  const int cus = (tn.max_cus > 0 && tn.max_cus < igemm::NUM_CU) ? tn.max_cus : igemm::NUM_CU;
-  long G = (long)cus * 2;
-  if (G * BM * BN > (long)igemm::SLAB_FLOATS) G = (long)(igemm::SLAB_FLOATS / ((size_t)BM * BN));
-  const long R = e.sched.total();
-  if (R <= 0 || (double)R * (double)G >= 4.0e9) return AVVAD_EINVAL;
-  if (G > R / 4) G = R / 4 > 0 ? R / 4 : 1;
-  bool stat = false;
-  if constexpr (HasStat<Epi>::value) {
-    stat = e.stat != nullptr;
-    if (stat && (e.cs != 1 || (e.ldc & 3) || (N & 3) || (((uintptr_t)e.C) & 15) || (e.W & 3))) return AVVAD_EINVAL;
-  }
-  hipLaunchKernelGGL((kernel<BM, BN, MM, AOp, BOp, Epi>), dim3((int)G), dim3(256), 0, s, a, b, e, Mp, N, 1, 0, (int)ntiles, slab);
-  if (stat) {
-    if constexpr (HasStat<Epi>::value)
-      hipLaunchKernelGGL((igemm::fixup_tile<BM, BN, Epi>), dim3((int)ntiles), dim3(256), 0, s, e, slab, Mp, N, 1, G, 0, (int)ntiles, cdiv(N, BN));
-  } else if ((G + ntiles - 1) / ntiles <= 6) {
-    hipLaunchKernelGGL((igemm::fixup1<BM, BN, Epi>), dim3((int)ntiles * (BM * BN / 1024)), dim3(256), 0, s, e, slab, Mp, N, 1, G, 0,
-                       (int)ntiles, cdiv(N, BN));
-  } else {
-    hipLaunchKernelGGL((igemm::fixup<BM, BN, Epi>), dim3((int)ntiles * (BM * BN / 256)), dim3(256), 0, s, e, slab, Mp, N, 1, G, 0,
-                       (int)ntiles, cdiv(N, BN));
-  }
+  long G;
+  int ntiles;
+  if (const int rc = igemm::plan_cls(e, Mp, N, slab, G, ntiles)) return rc;
+  hipLaunchKernelGGL((kernel<128, 128, MM, AOp, BOp, Epi>), dim3((int)G), dim3(256), 0, s, a, b, e, Mp, N, 1, 0, ntiles, slab);
+  igemm::launch_fixup<128, 128>(e, slab, Mp, N, 1, G, 0, ntiles, s);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }

@@ -22,6 +22,7 @@
 //              global loads go straight to 16-byte LDS stores.
 #pragma once
 #include "common.h"
+#include "streamk.h"
 #include <type_traits>
 
 namespace igemm {
@@ -49,10 +50,6 @@ struct EpiStore {
   double* stat = nullptr;
   __device__ __forceinline__ float* ptr(int m, int n) const { return C + (long)m * ldc + (long)n * cs; }
 };
-template <class Epi, class = void>
-struct HasStat : std::false_type {};
-template <class Epi>
-struct HasStat<Epi, std::void_t<decltype(Epi::stat)>> : std::true_type {};
 
 // ---------------------------------------------------------------- position classes: skipping the zero padding
 // A 3x3 / pad 1 convolution multiplies structural zeros wherever a tap falls into the padding: 7 % of all products on a 17x17
@@ -261,19 +258,10 @@ struct TileOf<Op, std::void_t<decltype(&Op::tile)>> {
   typedef decltype(std::declval<const Op&>().tile(0)) type;
   __device__ static __forceinline__ type get(const Op& o, int m0) { return o.tile(m0); }
 };
-template <class Epi, class = void>
-struct HasSched : std::false_type {};
-template <class Epi>
-struct HasSched<Epi, std::void_t<decltype(Epi::sched)>> : std::true_type {};
 template <class Op, class = void>
 struct HasTile : std::false_type {};
 template <class Op>
 struct HasTile<Op, std::void_t<decltype(&Op::tile)>> : std::true_type {};
-template <class Epi>
-__device__ __forceinline__ bool epi_live(const Epi& E, int m, int M) {
-  if constexpr (HasSched<Epi>::value) return m < M && E.live(m);
-  else return m < M;
-}
 
 // ---------------------------------------------------------------- dense operands
 // element (x, k) = p[x*ld + k]
@@ -407,21 +395,6 @@ struct PerVec : std::false_type {};
 template <class Op>
 struct PerVec<Op, std::void_t<decltype(Op::PERVEC)>> : std::integral_constant<bool, Op::PERVEC> {};
 
-// An epilogue may FINISH elements: `finish4(m, n0, v, N)` receives the final sums of up to four consecutive columns of row m
-// from the fix-up kernel (the one place where a split tile's total exists) and does whatever follows the product -- the
-// LSTM backward runs the previous step's gate arithmetic there, one launch less per time step.  It is only honoured when
-// EVERY tile of the product passes through the stream-K pool (launch() tells the caller through `finished`); `active` is
-// set by launch().
-// epilogues whose output is a plain row-major matrix (C, ldc, cs, mode) take the kernel's fast store path
-template <class Epi, class = void>
-struct IsPlain : std::false_type {};
-template <class Epi>
-struct IsPlain<Epi, std::void_t<decltype(Epi::PLAIN)>> : std::integral_constant<bool, Epi::PLAIN> {};
-template <class Epi, class = void>
-struct HasFinish : std::false_type {};
-template <class Epi>
-struct HasFinish<Epi, std::void_t<decltype(&Epi::finish4)>> : std::true_type {};
-
 // ---------------------------------------------------------------- the kernel
 // bf16 operands (option "bf16", BASELINE config 5): the fp32 values are rounded to bf16 (RNE) on their way into LDS and
 // multiplied by v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- 16x the matrix rate of the fp32-input instruction.  That
@@ -507,21 +480,8 @@ struct Stage {
   }
 };
 
-// Work decomposition: data-parallel rounds + one "stream-K" round.  The launch creates G persistent workgroups
-// (= the number resident at once: 256 CUs x workgroups/CU).  Worker g first takes whole tiles g, g+G, ... for
-// `full_rounds` rounds (plain stores, all workers walk K in step -> weight panels are shared in L2); the
-// remaining rem_tiles < G tiles are then treated as ONE pool of rem_tiles x ktiles BK-deep iterations cut into G
-// equal contiguous shares: a tile may be split between workers, and split pieces are added with float atomics onto
-// a pre-zeroed (or accumulating) output.  That removes the tile-quantisation loss of e.g. 648 or 288 tiles on 512
-// resident slots (37 % / 44 % idle) while only the last round pays the ~1.3 TB/s float-atomic rate.
-// Measured balance of this static split (tools/lab/prof_conv.py, -DAVVAD_PROF): all G workers start within 0.5 us; the
-// two workgroups of a CU are raw block ids b and b+256 and the OLDER always finishes first (192 vs 237 us: the matrix
-// pipe is arbitrated oldest-first); XCDs finish up to 17 % apart on equal shares (the same two are slowest for every
-// shape on a given device).  Tried and dropped: age-skewed shares (+-1 %), a dynamically pulled tail pool of 8-K-tile
-// pieces (1-5 % slower: every piece pays a prologue and a 64 KB atomic flush), K-major cells for the weight gradients
-// (less HBM traffic, 2 % slower end to end), staggering the co-residents' phases (no effect), requesting the NEXT
-// segment's first K tile before the epilogue (the prefetched registers live across the epilogue: past the 128-VGPR
-// budget of 4 waves/SIMD the 8-wave kernels spill, 5 % slower end to end).
+// Work decomposition: data-parallel rounds + one stream-K round, slabs and the ordered fix-up -- described in streamk.h,
+// which owns the share arithmetic, the fix-up kernels and the launch plan for this engine and the bf16 one (bgemm.h).
 // NTH = 256: 4 waves as 2x2, each (BM/2)x(BN/2);  NTH = 512: 8 waves as 2x4, each (BM/2)x(BN/4) -- half the
 // accumulators and staging registers per wave, so twice the waves per SIMD fit next to the same LDS tile.
 template <int BM, int BN, bool DB, int NTH, class AOp, class BOp, class Epi, bool BF = false>
@@ -570,10 +530,9 @@ __global__ void __launch_bounds__(NTH, NTH == 512 ? 4 : ((DB || BM * BN < 128 * 
 #endif
   const long G = gridDim.x;
   const long g = xcd_remap(blockIdx.x, gridDim.x);
-  long rem_iters = (long)rem_tiles * ktiles;
-  if constexpr (HasSched<Epi>::value) rem_iters = E.sched.total();      // tiles of different lengths: every tile is in the pool
-  long it = g * rem_iters / G;
-  const long it_end = (g + 1) * rem_iters / G;
+  const Share<long> share = Share<long>::of(E, rem_tiles, ktiles, G);     // (streamk.h: the fix-ups invert this very split)
+  long it = share.lo(g);
+  const long it_end = share.hi(g);
   const long ntiles_all = (long)((M + BM - 1) / BM) * ntn;
   int round = 0;
   long cell = g;   // K-major mode (kchunks > 0): cell = chunk * ntiles + tile, workers take cells g, g+G, ...
@@ -602,9 +561,9 @@ __global__ void __launch_bounds__(NTH, NTH == 512 ? 4 : ((DB || BM * BN < 128 * 
       if constexpr (HasSched<Epi>::value) {
         E.sched.locate(it, tile, kt0, klen);
       } else {
-        const long tr = it / ktiles;
+        long tr;
+        Share<long>::locate(E, it, ktiles, tr, kt0, klen);
         tile = (int)((long)full_rounds * G + tr);
-        kt0 = (int)(it - tr * ktiles);
       }
       kt1 = (int)min((long)klen, kt0 + (it_end - it));
       it += kt1 - kt0;
@@ -918,247 +877,8 @@ __global__ void __launch_bounds__(NTH, NTH == 512 ? 4 : ((DB || BM * BN < 128 * 
 #endif
 }
 
-// Fix-up of the stream-K round: tile tr of the remainder pool was cut between workers ga .. gb (ascending K).  Worker ga
-// stored (or accumulated) its piece onto the output, workers ga+1 .. gb left theirs in their slabs; this kernel adds those
-// slabs in a FIXED order -- so the result is bit-reproducible run to run.  It replaces both the zero-fill launch in front
-// of the GEMM and the float atomics inside it.
-// One workgroup = 4 waves per 256-element strip of a tile (lane = one float4): wave w sums the tile's slabs ga+1+w,
-// ga+1+w+4, ... with four loads in flight, the four partial sums meet in LDS in wave order.  (First version: one thread
-// walked all of a tile's slabs in a serial loop -- latency-bound, 37 us for the 31-way split tiles of the LSTM's
-// recurrent products.)
-template <int BM, int BN, class Epi>
-__global__ void __launch_bounds__(256)
-    fixup(const Epi E, const float* __restrict__ slab, const int M, const int N, const int ktiles, const long G,
-          const int full_rounds, const int rem_tiles, const int ntn) {
-  constexpr int STRIPS = BM * BN / 256;                  // 256-element strips per tile
-  __shared__ float4 part[3][64];
-  const int tr = blockIdx.x / STRIPS, strip = blockIdx.x % STRIPS;
-  // worker of iteration it: shares are [g*R/G, (g+1)*R/G)  ->  g = ceil((it+1)*G/R) - 1.  All of this is block-uniform and
-  // in 32 bits (the host launches this kernel only when R * G < 2^32: a 64-bit software division per thread and slab was
-  // most of this kernel's time in its first version).
-  unsigned R = (unsigned)rem_tiles * (unsigned)ktiles, it0 = (unsigned)tr * (unsigned)ktiles, it1 = it0 + (unsigned)ktiles - 1u;
-  const unsigned Gu = (unsigned)G;
-  if constexpr (HasSched<Epi>::value) {            // tiles of different lengths, all of them in the pool
-    R = (unsigned)E.sched.total();
-    it0 = (unsigned)E.sched.base(tr);
-    it1 = it0 + (unsigned)E.sched.len(tr) - 1u;
-  }
-  const int ga = (int)(((it0 + 1u) * Gu + R - 1u) / R) - 1, gb = (int)(((it1 + 1u) * Gu + R - 1u) / R) - 1;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int e0 = strip * 256 + lane * 4;                 // tile-local element (row-major [BM][BN]) of this lane's float4
-  if (gb <= ga) {                                        // the tile was not split: its output is final already
-    if constexpr (HasFinish<Epi>::value) {
-      if (E.active && wave == 0) {
-        const unsigned tile_u = (unsigned)full_rounds * Gu + (unsigned)tr;
-        const int mu = (int)(tile_u / (unsigned)ntn) * BM + e0 / BN, nu = (int)(tile_u % (unsigned)ntn) * BN + e0 % BN;
-        if (epi_live(E, mu, M)) {
-          float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (nu + e < N) v[e] = *E.ptr(mu, nu + e);
-          E.finish4(mu, nu, v, N);
-        }
-      }
-    }
-    return;
-  }
-  const bool sparse = R < Gu;                            // fewer iterations than workers: some shares are empty
-  const float* S0 = slab + e0;
-  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-  // (a worker whose share is empty wrote no slab: its slot is skipped; shares are contiguous, so every non-empty worker
-  //  between ga and gb lies inside this tile)
-  for (int g = ga + 1 + wave; g <= gb; g += 16) {
-    float4 v[4];
-    bool ok[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int gu = g + 4 * u;
-      ok[u] = gu <= gb && (!sparse || ((unsigned)(gu + 1) * R) / Gu > ((unsigned)gu * R) / Gu);
-      v[u] = *reinterpret_cast<const float4*>(S0 + (long)(ok[u] ? gu : ga + 1) * (BM * BN));
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (ok[u]) { sum.x += v[u].x; sum.y += v[u].y; sum.z += v[u].z; sum.w += v[u].w; }
-  }
-  if (wave > 0) part[wave - 1][lane] = sum;
-  __syncthreads();
-  if (wave > 0) return;
-#pragma unroll
-  for (int w = 0; w < 3; ++w) { const float4 p = part[w][lane]; sum.x += p.x; sum.y += p.y; sum.z += p.z; sum.w += p.w; }
-  const unsigned tile = (unsigned)full_rounds * Gu + (unsigned)tr;
-  const int m = (int)(tile / (unsigned)ntn) * BM + e0 / BN, n0 = (int)(tile % (unsigned)ntn) * BN + e0 % BN;
-  if (!epi_live(E, m, M)) return;
-  const float sv[4] = {sum.x, sum.y, sum.z, sum.w};
-  if constexpr (HasFinish<Epi>::value) {
-    if (E.active) {
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (n0 + e < N) v[e] = *E.ptr(m, n0 + e) + sv[e];
-      E.finish4(m, n0, v, N);
-      return;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (n0 + e < N) *E.ptr(m, n0 + e) += sv[e];
-}
-
-// The same fix-up for SHALLOW splits (a tile cut between a handful of workers: the convolutions' stream-K rounds): one WAVE
-// per strip, four strips per workgroup, the wave walks its tile's slabs itself.  The kernel above spends four waves, an LDS
-// exchange and a barrier on every strip; with ~3 slabs per tile three of them load one slab each -- a 136-tile round was
-// 34816 waves for 43 MB, 15 us.  (Deep splits -- the LSTM's 31-way, the weight gradients' 100-way tiles -- keep the
-// four-wave form.)
-template <int BM, int BN, class Epi>
-__global__ void __launch_bounds__(256)
-    fixup1(const Epi E, const float* __restrict__ slab, const int M, const int N, const int ktiles, const long G,
-           const int full_rounds, const int rem_tiles, const int ntn) {
-  constexpr int STRIPS = BM * BN / 256;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sg = blockIdx.x * 4 + wave;
-  const int tr = sg / STRIPS, strip = sg % STRIPS;
-  if (tr >= rem_tiles) return;
-  unsigned R = (unsigned)rem_tiles * (unsigned)ktiles, it0 = (unsigned)tr * (unsigned)ktiles, it1 = it0 + (unsigned)ktiles - 1u;
-  const unsigned Gu = (unsigned)G;
-  if constexpr (HasSched<Epi>::value) {            // position classes: tiles of different lengths, all of them in the pool
-    R = (unsigned)E.sched.total();
-    it0 = (unsigned)E.sched.base(tr);
-    it1 = it0 + (unsigned)E.sched.len(tr) - 1u;
-  }
-  const int ga = (int)(((it0 + 1u) * Gu + R - 1u) / R) - 1, gb = (int)(((it1 + 1u) * Gu + R - 1u) / R) - 1;
-  const int e0 = strip * 256 + lane * 4;
-  const unsigned tile = (unsigned)full_rounds * Gu + (unsigned)tr;
-  const int m = (int)(tile / (unsigned)ntn) * BM + e0 / BN, n0 = (int)(tile % (unsigned)ntn) * BN + e0 % BN;
-  if (!epi_live(E, m, M)) return;
-  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (gb > ga) {
-    const bool sparse = R < Gu;
-    const float* S0 = slab + e0;
-    for (int g = ga + 1; g <= gb; g += 4) {
-      float4 v[4];
-      bool ok[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int gu = g + u;
-        ok[u] = gu <= gb && (!sparse || ((unsigned)(gu + 1) * R) / Gu > ((unsigned)gu * R) / Gu);
-        v[u] = *reinterpret_cast<const float4*>(S0 + (long)(ok[u] ? gu : ga + 1) * (BM * BN));
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (ok[u]) { sum.x += v[u].x; sum.y += v[u].y; sum.z += v[u].z; sum.w += v[u].w; }
-    }
-  } else if (!HasFinish<Epi>::value) {
-    return;                                              // unsplit tile, nothing to finish
-  }
-  const float sv[4] = {sum.x, sum.y, sum.z, sum.w};
-  if constexpr (HasFinish<Epi>::value) {
-    if (E.active) {
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (n0 + e < N) v[e] = *E.ptr(m, n0 + e) + sv[e];
-      E.finish4(m, n0, v, N);
-      return;
-    }
-    if (gb <= ga) return;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (n0 + e < N) *E.ptr(m, n0 + e) += sv[e];
-}
-
-// Fix-up of split tiles WITH the fused column statistics (EpiStore::stat): one workgroup per remainder tile.  Thread
-// (cq, rg) owns the float4 column cq of rows rg, rg + RG, ...: it adds the tile's slabs in ascending worker order onto the
-// piece the first worker stored, writes the total back and keeps sum / sum of squares of its columns (fp32 over its BM / RG
-// rows, then doubles); the RG row groups meet in LDS in a fixed order.  Tiles that one worker finished by itself are skipped
-// (the kernel wrote their statistics).
-template <int BM, int BN, class Epi = EpiStore>
-__global__ void __launch_bounds__(256)
-    fixup_tile(const Epi E, const float* __restrict__ slab, const int M, const int N, const int ktiles, const long G,
-               const int full_rounds, const int rem_tiles, const int ntn) {
-  constexpr int CQ = BN / 4, RG = 256 / CQ, RPT = BM / RG;
-  static_assert(RPT % 4 == 0, "four rows in flight per thread");
-  __shared__ double red[RG * BN * 2];
-  const int tr = blockIdx.x;
-  unsigned R = (unsigned)rem_tiles * (unsigned)ktiles, it0 = (unsigned)tr * (unsigned)ktiles, it1 = it0 + (unsigned)ktiles - 1u;
-  const unsigned Gu = (unsigned)G;
-  if constexpr (HasSched<Epi>::value) {
-    R = (unsigned)E.sched.total();
-    it0 = (unsigned)E.sched.base(tr);
-    it1 = it0 + (unsigned)E.sched.len(tr) - 1u;
-  }
-  const int ga = (int)(((it0 + 1u) * Gu + R - 1u) / R) - 1, gb = (int)(((it1 + 1u) * Gu + R - 1u) / R) - 1;
-  if (gb <= ga) return;                                  // block-uniform
-  const bool sparse = R < Gu;
-  const unsigned tile = (unsigned)full_rounds * Gu + (unsigned)tr;
-  const int tm = (int)(tile / (unsigned)ntn);
-  const int m0 = tm * BM, n0 = (int)(tile % (unsigned)ntn) * BN;
-  float* Cv = E.C;
-  int mrow0 = m0, Mv = M;
-  if constexpr (HasSched<Epi>::value) { const auto v = E.view(m0); Cv = v.C; mrow0 = v.row0; Mv = v.M; }
-  const int cq = threadIdx.x % CQ, rg = threadIdx.x / CQ;
-  const int n = n0 + cq * 4;
-  float s4[4] = {0.f, 0.f, 0.f, 0.f}, q4[4] = {0.f, 0.f, 0.f, 0.f};
-  if (n < N) {                                           // (N % 4 == 0: a float4 column is inside or outside as a whole)
-#pragma unroll 1
-    for (int rr = 0; rr < RPT; rr += 4) {
-      float4 tot[4];
-      bool live[4];
-      const float* sp[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int row = rg + RG * (rr + u);
-        live[u] = mrow0 + row < Mv;
-        sp[u] = slab + (long)(live[u] ? row : 0) * BN + cq * 4;
-        tot[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      for (int g = ga + 1; g <= gb; ++g) {
-        if (sparse && !(((unsigned)(g + 1) * R) / Gu > ((unsigned)g * R) / Gu)) continue;     // this worker's share was empty
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(sp[u] + (long)g * (BM * BN));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { tot[u].x += v[u].x; tot[u].y += v[u].y; tot[u].z += v[u].z; tot[u].w += v[u].w; }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (!live[u]) continue;
-        float4* const cp = reinterpret_cast<float4*>(Cv + (long)(mrow0 + rg + RG * (rr + u)) * E.ldc + n);
-        float4 o = *cp;
-        o.x += tot[u].x; o.y += tot[u].y; o.z += tot[u].z; o.w += tot[u].w;
-        *cp = o;
-        s4[0] += o.x; s4[1] += o.y; s4[2] += o.z; s4[3] += o.w;
-        q4[0] = fmaf(o.x, o.x, q4[0]); q4[1] = fmaf(o.y, o.y, q4[1]); q4[2] = fmaf(o.z, o.z, q4[2]); q4[3] = fmaf(o.w, o.w, q4[3]);
-      }
-    }
-  }
-  if (E.stat == nullptr) return;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    red[(rg * BN + cq * 4 + e) * 2 + 0] = (double)s4[e];
-    red[(rg * BN + cq * 4 + e) * 2 + 1] = (double)q4[e];
-  }
-  __syncthreads();
-  const int c = threadIdx.x;
-  if (c < BN && n0 + c < N) {
-    double a = 0, b = 0;
-#pragma unroll 4
-    for (int w = 0; w < RG; ++w) { a += red[(w * BN + c) * 2 + 0]; b += red[(w * BN + c) * 2 + 1]; }
-    E.stat[((long)tm * 2 + 0) * N + n0 + c] = a;
-    E.stat[((long)tm * 2 + 1) * N + n0 + c] = b;
-  }
-}
-
-constexpr int NUM_CU = 256;  // MI355X
-
-// Floats of slab workspace a launch may need: one BM x BN tile per persistent worker (512 x 128x128 = 1024 x 128x64 =
-// 1536 x 64x64 at most).  Callers carve this out of their own workspace (the C ABI's caller-allocates rule).
-// (... or one [576][64] weight-gradient partial per CU, conv64.h: 256 x 36864, the larger of the two)
-constexpr size_t SLAB_FLOATS = (size_t)256 * 576 * 64;
-static_assert(SLAB_FLOATS >= (size_t)512 * 128 * 128, "one 128x128 tile per persistent worker");
-
 // split_k_hint > 1 marks a "few tiles, very long K" product (the conv weight gradients); with the K-major tuning option
-// it is cut K-major (see the kernel); everything else is scheduled as data-parallel rounds + one stream-K round.
+// it is cut K-major (see the kernel); everything else is scheduled as data-parallel rounds + one stream-K round (streamk.h).
 // `slab`: SLAB_FLOATS floats of scratch for the split tiles of the stream-K round; nullptr selects whole-tile scheduling
 // (slower on tile counts that quantise badly, still deterministic).
 // `allow_bf16`: the process-wide option "bf16" applies to this product (false for the STFT, whose DFT stays exact fp32).
@@ -1169,7 +889,6 @@ static inline int launch(const AOp& a, const BOp& b, const Epi& e_in, int M, int
   if (M <= 0 || N <= 0 || K <= 0) return AVVAD_EINVAL;
   const int ktiles = (K + BK - 1) / BK;
   const long ntiles = (long)cdiv(M, BM) * cdiv(N, BN);
-  const long iters = ntiles * ktiles;
   const AvvadTune& tn = avvad_tune();
   const int var = tn.igemm_variant;  // tuning aid: 0/1 = 4-wave double/single LDS buffer, 2 = 8 waves
   constexpr bool BIG = (BM == 128 && BN == 128);
@@ -1181,47 +900,31 @@ static inline int launch(const AOp& a, const BOp& b, const Epi& e_in, int M, int
   else if (variant == 0) per_cu = BIG ? 2 : (BM * BN >= 128 * 64 ? 3 : 4);
   else if (variant == 1 || !BIG) per_cu = BIG ? 3 : (BM * BN >= 128 * 64 ? 4 : 6);
   else per_cu = 2;
-  const int cus = (tn.max_cus > 0 && tn.max_cus < NUM_CU) ? tn.max_cus : NUM_CU;   // room for RCCL's kernels at N > 1
-  long G = (long)cus * per_cu;
-  if (G * BM * BN > (long)SLAB_FLOATS) G = (long)(SLAB_FLOATS / ((size_t)BM * BN));
-  const bool no_sk = !slab || tn.no_streamk == 1 || tn.no_streamk == 10 + e.mode ||   // whole-tile schedule
-                     (double)ntiles * ktiles * (double)G >= 4.0e9;                     // (fix-up index math is 32-bit)
-  long full_rounds = ntiles / G, rem = ntiles - full_rounds * G;
+  Rounds plan{workers(per_cu, BM, BN), 0, 0};
   int kchunks = 0;
   // OFF by default (option "kmajor"): it removes most of the wgrad kernel's beyond-L2 fetches, but the
   // kernels are MFMA-bound -- isolated they time the same (+-2 %), and the whole training step measured 0.45 ms
   // (2 %) SLOWER in three A/B/A/B pairs on one device (23.7 vs 23.25 ms), so tile-major stream-K stays the default.
   // (Cells of one tile are added with float atomics onto an accumulating output: the one non-reproducible schedule left.)
-  if (split_k_hint > 1 && e.mode != 0 && ntiles <= G && tn.kmajor) {
+  if (split_k_hint > 1 && e.mode != 0 && ntiles <= plan.G && tn.kmajor) {
     // r cells per worker (r = 1 or 2): kchunks = floor(r*G / ntiles); cost in K-tile iterations incl. ~8 per atomic flush
     long best = -1;
     for (int r = 1; r <= 2; ++r) {
-      long nc = r * G / ntiles;
+      long nc = r * plan.G / ntiles;
       if (nc > ktiles) nc = ktiles;
       if (nc < 1) nc = 1;
-      const long rr = (nc * ntiles + G - 1) / G;
+      const long rr = (nc * ntiles + plan.G - 1) / plan.G;
       const long cost = rr * ((ktiles + nc - 1) / nc) + rr * 8;
       if (best < 0 || cost < best) { best = cost; kchunks = (int)nc; }
     }
-    full_rounds = 0; rem = 0;
-    if ((long)kchunks * ntiles < G) G = (long)kchunks * ntiles;
+    if ((long)kchunks * ntiles < plan.G) plan.G = (long)kchunks * ntiles;
   } else {
-    if (no_sk || rem * 10 >= G * 9) {   // (nearly) full last round: keep it data-parallel
-      if (rem > 0) ++full_rounds;
-      rem = 0;
-    }
-    if (rem > 0 && full_rounds == 0) {  // fewer tiles than workers: >= 4 iterations per worker amortise prologue/epilogue
-      const long cap = iters / 4 > 0 ? iters / 4 : 1;
-      if (G > cap) G = cap;
-    }
+    plan = plan_rounds(ntiles, ktiles, plan.G, slab != nullptr, e.mode);
   }
-  const int fr = (int)full_rounds, rt = (int)rem;
+  const long G = plan.G;
+  const int fr = plan.full_rounds, rt = plan.rem;
   const bool bf = allow_bf16 && tn.bf16;
-  bool stat = false;
-  if constexpr (std::is_same<Epi, EpiStore>::value) {
-    stat = e.stat != nullptr;
-    if (stat && (e.cs != 1 || (e.ldc & 3) || (N & 3) || (((uintptr_t)e.C) & 15) || kchunks > 0 || e.bias != nullptr)) return AVVAD_EINVAL;
-  }
+  if (!stat_ok(e, N, kchunks)) return AVVAD_EINVAL;
   if constexpr (HasFinish<Epi>::value) {
     // finish4() runs in the fix-up kernel: only when every tile of the product goes through the stream-K pool
     e.active = (rt > 0 && kchunks == 0 && fr == 0 && (long)rt == ntiles) ? 1 : 0;
@@ -1247,16 +950,8 @@ static inline int launch(const AOp& a, const BOp& b, const Epi& e_in, int M, int
     else AVVAD_IGEMM_LAUNCH(true, (BIG ? 512 : 256));
   }
 #undef AVVAD_IGEMM_LAUNCH
-  if (rt > 0 && kchunks == 0 && stat) {
-    if constexpr (std::is_same<Epi, EpiStore>::value)
-      hipLaunchKernelGGL((fixup_tile<BM, BN>), dim3(rt), dim3(256), 0, s, e, slab, M, N, ktiles, G, fr, rt, cdiv(N, BN));
-  } else if (rt > 0 && kchunks == 0) {
-    const int deep = tn.no_fixup1 > 1 ? tn.no_fixup1 : 6;     // (option values > 1: the depth threshold, tuning aid)
-    if ((G + rt - 1) / rt <= deep && tn.no_fixup1 != 1)      // a handful of slabs per tile: one wave per strip
-      hipLaunchKernelGGL((fixup1<BM, BN, Epi>), dim3(rt * (BM * BN / 1024)), dim3(256), 0, s, e, slab, M, N, ktiles, G, fr, rt, cdiv(N, BN));
-    else
-      hipLaunchKernelGGL((fixup<BM, BN, Epi>), dim3(rt * (BM * BN / 256)), dim3(256), 0, s, e, slab, M, N, ktiles, G, fr, rt, cdiv(N, BN));
-  }
+  // (option "no_fixup1": 1 = always the four-wave fix-up kernel, values > 1 = the depth threshold, tuning aids)
+  if (rt > 0) launch_fixup<BM, BN>(e, slab, M, N, ktiles, G, fr, rt, s, tn.no_fixup1 == 1 ? 0 : (tn.no_fixup1 > 1 ? tn.no_fixup1 : FIXUP1_DEPTH));
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
@@ -1266,33 +961,12 @@ static inline int launch(const AOp& a, const BOp& b, const Epi& e_in, int M, int
 // AVVAD_EINVAL without launching anything).  128x128 tiles, 8 waves, fp32.
 template <class AOp, class BOp, class Epi>
 static inline int launch_cls(const AOp& a, const BOp& b, const Epi& e, int Mp, int N, hipStream_t s, float* slab) {
-  constexpr int BM = 128, BN = 128;
-  if (Mp <= 0 || N <= 0 || !slab) return AVVAD_EINVAL;
-  const AvvadTune& tn = avvad_tune();
-  const long ntiles = (long)cdiv(Mp, BM) * cdiv(N, BN);
-  const int cus = (tn.max_cus > 0 && tn.max_cus < NUM_CU) ? tn.max_cus : NUM_CU;
-  long G = (long)cus * 2;
-  if (G * BM * BN > (long)SLAB_FLOATS) G = (long)(SLAB_FLOATS / ((size_t)BM * BN));
-  const long R = e.sched.total();
-  if (R <= 0 || (double)R * (double)G >= 4.0e9) return AVVAD_EINVAL;
-  if (G > R / 4) G = R / 4 > 0 ? R / 4 : 1;
-  bool stat = false;
-  if constexpr (HasStat<Epi>::value) {
-    stat = e.stat != nullptr;
-    if (stat && (e.cs != 1 || (e.ldc & 3) || (N & 3) || (((uintptr_t)e.C) & 15) || (e.W & 3))) return AVVAD_EINVAL;
-  }
-  hipLaunchKernelGGL((kernel<BM, BN, true, 512, AOp, BOp, Epi, false>), dim3((int)G), dim3(512), 0, s, a, b, e, Mp, N,
-                     tn.stagger ? 1 : 0, 1, 0, (int)ntiles, 0, slab);
-  if (stat) {
-    if constexpr (HasStat<Epi>::value)
-      hipLaunchKernelGGL((fixup_tile<BM, BN, Epi>), dim3((int)ntiles), dim3(256), 0, s, e, slab, Mp, N, 1, G, 0, (int)ntiles, cdiv(N, BN));
-  } else if ((G + ntiles - 1) / ntiles <= 6) {
-    hipLaunchKernelGGL((fixup1<BM, BN, Epi>), dim3((int)ntiles * (BM * BN / 1024)), dim3(256), 0, s, e, slab, Mp, N, 1, G, 0,
-                       (int)ntiles, cdiv(N, BN));
-  } else {
-    hipLaunchKernelGGL((fixup<BM, BN, Epi>), dim3((int)ntiles * (BM * BN / 256)), dim3(256), 0, s, e, slab, Mp, N, 1, G, 0, (int)ntiles,
-                       cdiv(N, BN));
-  }
+  long G;
+  int ntiles;
+  if (const int rc = plan_cls(e, Mp, N, slab, G, ntiles)) return rc;
+  hipLaunchKernelGGL((kernel<128, 128, true, 512, AOp, BOp, Epi, false>), dim3((int)G), dim3(512), 0, s, a, b, e, Mp, N,
+                     avvad_tune().stagger ? 1 : 0, 1, 0, ntiles, 0, slab);
+  launch_fixup<128, 128>(e, slab, Mp, N, 1, G, 0, ntiles, s);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }

@@ -1006,7 +1006,8 @@ def test_bf16_convolutions_vs_rounded_operands(N, H, W, C, Co, KS, stride, pad, 
                                                       (2, 17, 17, 64, 128, 1, 2, 0), (4, 3, 3, 512, 512, 3, 1, 1), (700, 9, 9, 128, 128, 3, 1, 1),
                                                       (300, 5, 5, 256, 256, 3, 1, 1), (96, 9, 9, 128, 256, 3, 2, 1), (40, 17, 17, 64, 64, 3, 1, 1),
                                                       (130, 3, 3, 512, 512, 3, 1, 1), (256, 9, 9, 128, 256, 3, 2, 1), (200, 5, 5, 256, 512, 3, 2, 1),
-                                                      (333, 9, 9, 128, 256, 3, 1, 1), (1024, 17, 17, 64, 64, 3, 1, 1)])
+                                                      (333, 9, 9, 128, 256, 3, 1, 1), (1024, 17, 17, 64, 64, 3, 1, 1),
+                                                      (814, 17, 17, 64, 128, 1, 2, 0)])
 def test_bf16_data_path_convolutions(N, H, W, C, Co, KS, stride, pad):
     """The bf16 DATA PATH's convolutions (csrc/bgemm.h; what the trunk runs under option bf16 = 1): operands are bf16 in
     memory -- NHWC bf16 activations / output gradients, K-contiguous bf16 weight packs -- staged with 16-byte loads, the
@@ -1016,7 +1017,8 @@ def test_bf16_data_path_convolutions(N, H, W, C, Co, KS, stride, pad):
     stream-K rounds with the ordered fix-up (N = 700, 300), the four stride-2 parity classes, the 1x1 downsample, and -- from
     128 images up, where the tile count fits the stream-K pool -- the position-class schedule that skips the zero padding.
     The 64 -> 64 channel shapes run the bf16 form of the weights-stationary kernel (conv64::kernel16), at 1024 frames with four
-    to five tiles per wave (the cross-tile prefetch)."""
+    to five tiles per wave (the cross-tile prefetch).  The 1x1 downsample at 814 frames is 516 tiles of ONE K tile: a full round
+    plus a four-iteration pool on 512 workers, so most workers' stream-K shares are empty (csrc/streamk.h, Share)."""
     import ctypes as Ct
     import torch.nn.functional as F
     from avvad import _lib as L, ops
