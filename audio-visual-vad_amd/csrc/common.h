@@ -70,6 +70,11 @@ struct BwdCuCap {
   }
   ~BwdCuCap() { avvad_tune().max_cus = saved; }
 };
+// CUs a persistent grid may occupy: the MI355X's 256, fewer when option max_cus leaves room for RCCL's kernels at N > 1
+static inline int grid_cus() {
+  const int m = avvad_tune().max_cus;
+  return (m > 0 && m < 256) ? m : 256;
+}
 
 // A launch with more than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize raised first, per kernel
 // AND per device.  Every kernel (the template argument) has its own flags, one per device, atomic: a second thread at

@@ -61,7 +61,7 @@ static inline TapDiv tap_div(int T, int KS) { return TapDiv{div_magic((unsigned)
 // ---- forward A: rows = output pixels, K = (kh,kw,c), c contiguous (16-byte loads)
 // Context per staged vector: the BYTE offset of (window origin, channel kin) and one validity bit per tap.  A K tile is
 // one tap of one 32-channel chunk (wave-uniform), so load() adds a scalar tap offset and tests one bit.
-// (host, trunk.hip conv_fwd_t / conv_dgrad_t: the activation tensor is < 4 GiB -- 32-bit byte offsets -- and KS*KS <= 32,
+// (host, trunk.hip conv_fwd_engine / conv_dgrad_engine: the activation tensor is < 4 GiB -- 32-bit byte offsets -- and KS*KS <= 32,
 //  one tap-validity bit each; larger kernels are refused with AVVAD_EINVAL)
 template <bool BUF>
 struct Im2colFwd {

@@ -330,8 +330,8 @@ extern "C" int avvad_lip_decode(const float* coef, const int* starts, const int*
   float *tab = (float*)(ws + c.tab), *flo = (float*)(ws + c.flo), *fhi = (float*)(ws + c.fhi), *gmin = (float*)(ws + c.gmin),
         *inv = (float*)(ws + c.inv);
   double* part = acc ? (double*)(ws + c.part) : nullptr;
-  const int cus = avvad_tune().max_cus > 0 ? avvad_tune().max_cus : 256;
-  const int gx = max(1, min(cdiv(d->n_max, 4), cus / d->B));      // one resident workgroup per CU; a wave walks its frames      // one resident workgroup per CU; a wave walks its frames
+  const int cus = avvad_tune().max_cus > 0 ? avvad_tune().max_cus : 256;      // (not grid_cus(): no upper clamp here, kept as behaviour)
+  const int gx = max(1, min(cdiv(d->n_max, 4), cus / d->B));      // one resident workgroup per CU; a wave walks its frames
   hipLaunchKernelGGL(dct_table, dim3(cdiv(BUF, 256)), dim3(256), 0, s, tab);
   float* A = (float*)(ws + c.A);
   hipLaunchKernelGGL(lip_frames, dim3(gx, d->B), dim3(256), 0, s, coef, d->rows, starts, n_in, tab, flo, fhi, A);

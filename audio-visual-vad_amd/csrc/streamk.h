@@ -312,8 +312,6 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------- the host plan
-constexpr int NUM_CU = 256;  // MI355X
-
 // Floats of slab workspace a launch may need: one BM x BN tile per persistent worker (512 x 128x128 = 1024 x 128x64 =
 // 1536 x 64x64 at most).  Callers carve this out of their own workspace (the C ABI's caller-allocates rule).
 // (... or one [576][64] weight-gradient partial per CU, conv64.h: 256 x 36864, the larger of the two)
@@ -322,9 +320,7 @@ static_assert(SLAB_FLOATS >= (size_t)512 * 128 * 128, "one 128x128 tile per pers
 
 // persistent workers of a kernel with per_cu resident workgroups per CU: what is resident at once, within the slab space
 static inline long workers(int per_cu, int BM, int BN) {
-  const AvvadTune& tn = avvad_tune();
-  const int cus = (tn.max_cus > 0 && tn.max_cus < NUM_CU) ? tn.max_cus : NUM_CU;   // room for RCCL's kernels at N > 1
-  long G = (long)cus * per_cu;
+  long G = (long)grid_cus() * per_cu;
   if (G * BM * BN > (long)SLAB_FLOATS) G = (long)(SLAB_FLOATS / ((size_t)BM * BN));
   return G;
 }

@@ -554,7 +554,7 @@ static inline bool stem_wgrad_ok(const Geom& g, bool slab) {
 // fix-up's traffic grows with the tile count; option "cls_cap" overrides)
 static inline long cls_tile_cap() {
   if (avvad_tune().cls_cap > 0) return avvad_tune().cls_cap;
-  return 4L * ((avvad_tune().max_cus > 0 && avvad_tune().max_cus < 256) ? avvad_tune().max_cus : 256);     // (measured: 2/CU -> 4/CU: step -0.07 ms)
+  return 4L * grid_cus();     // (measured: 2/CU -> 4/CU: step -0.07 ms)
 }
 // ---- position classes (igemm.h): 3x3 / pad 1 convolutions whose tile count fits the stream-K pool skip the zero padding
 static inline bool cls_common(const Geom& g, bool slab) {
@@ -583,8 +583,7 @@ static inline bool conv_wgrad_tap_ok(const Geom& g, bool slab) {
          fits_buf((long)g.N * g.H * g.W * g.C) && fits_buf((long)g.N * g.Ho * g.Wo * g.Co);
 }
 // ---- the 64 -> 64 channel 3x3 / 1 / 1 convolutions (ResNet layer1): weights-stationary kernel, conv64.h.  The fp32 form
-// also wants option bf16 at 0; the bf16 form (conv64::kernel16) serves the bf16 data path whatever the option
-static inline int conv64_cus() { return (avvad_tune().max_cus > 0 && avvad_tune().max_cus < 256) ? avvad_tune().max_cus : 256; }
+// also wants option bf16 at 0; the bf16 form (conv64::kernel<conv64::B16, .>) serves the bf16 data path whatever the option
 static inline bool conv64_ok(const Geom& g, bool b16) {
   const long M = (long)g.N * g.H * g.W;
   return (b16 || avvad_tune().bf16 == 0) && !avvad_tune().no_conv64 && g.C == 64 && g.Co == 64 && g.KS == 3 && g.stride == 1 &&
@@ -593,7 +592,7 @@ static inline bool conv64_ok(const Geom& g, bool b16) {
 }
 // (the weight gradient: output-stationary kernel + ordered reduction of the per-CU partials)
 static inline bool conv64_wgrad_ok(const Geom& g, bool slab) {
-  return conv64_ok(g, false) && slab && g.W <= conv64::WG_MAXW && (size_t)conv64_cus() * conv64::WG_PART <= igemm::SLAB_FLOATS &&
+  return conv64_ok(g, false) && slab && g.W <= conv64::WG_MAXW && (size_t)grid_cus() * conv64::WG_PART <= igemm::SLAB_FLOATS &&
          (long)g.N * g.H * g.W * 256 < (1L << 31);
 }
 
@@ -631,7 +630,7 @@ static inline bool conv_wgrad16_tap_ok(const Geom& g, bool slab) {
 }
 
 // ---- which kernel form runs a convolution: one choice per direction and data path, made at every call (the backward runs
-// under BwdCuCap, whose lower max_cus changes cls_tile_cap() and conv64_cus()).  The launchers switch on it, and the forward's
+// under BwdCuCap, whose lower max_cus changes cls_tile_cap() and grid_cus()).  The launchers switch on it, and the forward's
 // BatchNorm statistics read from it how many partial-sum chunks the epilogue leaves.
 // STEM: the stem's LDS-resident-frame kernels.  CONV64: conv64.h.  CLS: position classes (igemm.h; the stride-2 data gradient
 // as one product over its parity classes).  TAP: the weight gradient by taps (igemm.h TapSched).  PARITY: the stride-2 data
@@ -646,7 +645,7 @@ struct ConvForm {
 static ConvForm fwd_form(const Geom& g, bool b16, bool slab) {
   const long M = (long)g.N * g.Ho * g.Wo;
   const int cols = g.Co <= 64 ? 64 : 128;
-  if (conv64_ok(g, b16)) return {CONV64, 0, 0, false, conv64::grid_for((long)g.N * g.H * g.W, conv64_cus())};   // one per workgroup
+  if (conv64_ok(g, b16)) return {CONV64, 0, 0, false, conv64::grid_for((long)g.N * g.H * g.W, grid_cus())};   // one per workgroup
   if (b16 ? conv_fwd16_cls_ok(g, slab) : conv_fwd_cls_ok(g, slab)) return {CLS, 0, 0, false, g.Ho * g.Wo * cdiv(g.N, 128)};
   if (b16) return {ENGINE, 128, cols, true, cdiv(M, 128)};
   if (g.C == 1) return stem_kernel_ok(g) ? ConvForm{STEM, 0, 0, false, g.N} : ConvForm{ENGINE, 128, 64, false, 0};   // (per frame)
@@ -682,6 +681,132 @@ static igemm::ClassSched dgrad_sched(const Geom& g, int kc) {
   if (g.stride == 2) { sc.s2 = 1; sc.Hq = g.Ho; sc.Wq = g.Wo; }
   return sc;
 }
+static inline igemm::TapSched tap_sched(const Geom& g, int tiles_per_tap) {
+  const int NP = cdiv(g.N, 128) * 128;
+  const int lsh = ((g.Ho - 1) * g.stride - g.pad + 2 > g.H - 1) ? 1 : 0, lsw = ((g.Wo - 1) * g.stride - g.pad + 2 > g.W - 1) ? 1 : 0;
+  return igemm::TapSched{g.Ho, g.Wo, tiles_per_tap, NP / 32, 3, 1, lsh, 1, lsw};
+}
+
+// ---- what the data paths do differently, in one place.  The launchers below are one text per direction and kernel form; B16
+// selects the bf16 data path (bgemm.h): its operands are bf16 PAIRS behind float pointers, so the gathers see a geometry with
+// half the channels; its weights are the K-contiguous packs (RowPairs*); its K chunk is 64 channels; its gathers always take
+// the buffer form; its engine has 128-row tiles only, takes no split-K hint, and wants to be told when K runs over pixels (MM).
+template <bool B16> constexpr int KCH = B16 ? 64 : 32;     // channels per K chunk of the class schedules
+template <bool B16> constexpr int UNIT = B16 ? 2 : 1;      // elements per operand unit
+template <bool B16>
+static Geom unit_geom(Geom g, bool c, bool co) {           // the geometry a gather sees: g with C and / or Co in operand units
+  if (c) g.C /= UNIT<B16>;
+  if (co) g.Co /= UNIT<B16>;
+  return g;
+}
+// B operand of a forward (n = Co, cin = C) or data-gradient (n = C, cin = Co) product: the rows of the weight pack
+template <bool B16, bool BUF>
+static auto weight_rows(const float* w, int n, int cin, int T) {
+  if constexpr (B16) return bgemm::RowPairs{w, T * cin / 2, n, T * cin / 2};
+  else return convop::ColTapRows<BUF>{w, n, n, T * cin, cin, T, convop::div_magic(T)};
+}
+// ... for the live taps of a tile's position class (3x3; flip: the data gradient)
+template <bool B16>
+static auto weight_rows_cls(const float* w, int n, int cin, int flip, const igemm::ClassRow& cr, const igemm::ClassSched& sc) {
+  if constexpr (B16) return bgemm::RowPairsCls{w, 9 * cin / 2, n, 9, 3, flip, cr, sc};
+  else return convop::ColTapRowsCls{w, n, n, cin, 3, flip, cr, sc};
+}
+template <bool B16, bool MM = false, class A, class B, class E>
+static int cls_launch(const A& a, const B& b, const E& e, int Mp, int N, hipStream_t s, float* slab) {
+  if constexpr (B16) return bgemm::launch_cls<MM>(a, b, e, Mp, N, s, slab);
+  else return igemm::launch_cls(a, b, e, Mp, N, s, slab);
+}
+// the ENGINE / PARITY forms' tile dispatch (TALL: this product has the fp32 engine's 256-row instantiation; K in operand units)
+template <bool B16, bool TALL, bool MM = false, class A, class B, class E>
+static int tile_launch(const ConvForm& f, const A& a, const B& b, const E& e, int M, int N, int K, int split, hipStream_t s, float* slab) {
+  if constexpr (B16) {
+    if (f.cols == 64) return bgemm::launch<128, 64, MM>(a, b, e, M, N, K, s, slab);
+    return bgemm::launch<128, 128, MM>(a, b, e, M, N, K, s, slab);
+  } else {
+    if constexpr (TALL)
+      if (f.rows == 256) return igemm::launch<256, 64>(a, b, e, M, N, K, split, s, slab);
+    if (f.cols == 64) return igemm::launch<128, 64>(a, b, e, M, N, K, split, s, slab);
+    return igemm::launch<128, 128>(a, b, e, M, N, K, split, s, slab);
+  }
+}
+
+// y = conv(x) (flip = false, wpk = forward pack) or dx (+)= dgrad(dy) (flip = true, wpk = dgrad pack); b16: bf16 activations /
+// packs in (conv64::B16), fp32 out
+static int conv64_launch(bool b16, bool flip, const float* x, const float* wpk, float* y, const Geom& g, int accumulate, hipStream_t s,
+                         double* stat) {
+  const int M = g.N * g.H * g.W;
+  const int grid = conv64::grid_for(M, grid_cus());
+  const unsigned mg_hw = convop::div_magic((unsigned)(g.H * g.W)), mg_w = convop::div_magic((unsigned)g.W);
+  auto k = b16 ? (flip ? conv64::kernel<conv64::B16, true> : conv64::kernel<conv64::B16, false>)
+               : (flip ? conv64::kernel<conv64::F32, true> : conv64::kernel<conv64::F32, false>);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(conv64::NW * 64), 0, s, x, wpk, y, M, g.H, g.W, mg_hw, mg_w, accumulate, stat);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+// ---- forward: y = conv(x).  b16: x and the pack wf are bf16.  stat: the column sums / sums of squares of y for the fused
+// BatchNorm statistics, one chunk per ConvForm::chunks (igemm::EpiStore::stat), or null
+template <bool B16>
+static int conv_fwd_cls(const float* x, const float* wf, float* y, const Geom& g, hipStream_t s, float* slab, double* stat) {
+  const int MB = cdiv(g.N, 128), P = g.Ho * g.Wo;
+  const igemm::ClassSched sc = fwd_sched(g, KCH<B16>);
+  const igemm::ClassRow cr{P, convop::div_magic(P)};
+  convop::Im2colFwdCls a{x, unit_geom<B16>(g, true, false), g.N, cr, sc};
+  const auto b = weight_rows_cls<B16>(wf, g.Co, g.C, 0, cr, sc);
+  igemm::EpiCls e{y, (long)P * g.Co, nullptr, 0};
+  e.stat = stat; e.W = g.Co; e.rows = g.N; e.cr = cr; e.sched = sc;
+  return cls_launch<B16>(a, b, e, MB * P * 128, g.Co, s, slab);
+}
+template <bool B16, bool BUF>
+static int conv_fwd_engine(const float* x, const float* wf, float* y, const Geom& g, const ConvForm& f, hipStream_t s, float* slab,
+                           double* stat) {
+  const int M = g.N * g.Ho * g.Wo, T = g.KS * g.KS, K = T * g.C;
+  igemm::EpiStore e{y, g.Co, nullptr, 0};
+  if constexpr (!B16) {
+    if (g.C == 1) {                                            // the stem's own operands
+      igemm::ColPlain<4> b{wf, g.Co, g.Co, K, 0};
+      convop::StemFwd a{x, g, M, K};
+      return igemm::launch<128, 64>(a, b, e, M, g.Co, K, 1, s, slab);
+    }
+    if (g.C % 32 || g.Co % 4 || !taps_fit(g)) return AVVAD_EINVAL;
+    if (!fits_u30((long)g.N * g.H * g.W * g.C) || !fits_u30((long)K * g.Co)) return AVVAD_EINVAL;   // 32-bit BYTE offsets in the gathers
+  }
+  e.stat = stat;
+  convop::Im2colFwd<BUF> a{x, unit_geom<B16>(g, true, false), M, convop::tap_div(T, g.KS)};
+  const auto b = weight_rows<B16, BUF>(wf, g.Co, g.C, T);
+  return tile_launch<B16, true>(f, a, b, e, M, g.Co, K / UNIT<B16>, 1, s, slab);
+}
+static int conv_fwd(bool b16, const float* x, const float* wf, float* y, const Geom& g, hipStream_t s, float* slab, double* stat = nullptr) {
+  if (b16 && !bf16_conv_ok(g)) return AVVAD_EINVAL;
+  const ConvForm f = fwd_form(g, b16, slab);
+  switch (f.form) {
+    case STEM: {
+      const int LDW = (g.W + 6) | 1;
+      hipLaunchKernelGGL(stem_fwd_mfma, dim3(g.N), dim3(256), (size_t)(g.H + 6) * LDW * sizeof(float), s, x, wf, y, g.H, g.W, g.Ho, g.Wo,
+                         LDW, stat);
+      AVVAD_LAUNCH_CHECK();
+      return AVVAD_OK;
+    }
+    case CONV64: return conv64_launch(b16, false, x, wf, y, g, 0, s, stat);
+    case CLS: return b16 ? conv_fwd_cls<true>(x, wf, y, g, s, slab, stat) : conv_fwd_cls<false>(x, wf, y, g, s, slab, stat);
+    default:
+      if (b16) return conv_fwd_engine<true, true>(x, wf, y, g, f, s, slab, stat);
+      return f.buf ? conv_fwd_engine<false, true>(x, wf, y, g, f, s, slab, stat) : conv_fwd_engine<false, false>(x, wf, y, g, f, s, slab, stat);
+  }
+}
+
+// ---- data gradient: dx (+)= dgrad(dy).  b16: dy and the pack wd are bf16
+template <bool B16>
+static int conv_dgrad_cls(const float* dy, const float* wd, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
+  const int MB = cdiv(g.N, 128), P = g.H * g.W;
+  const igemm::ClassSched sc = dgrad_sched(g, KCH<B16>);
+  const igemm::ClassRow cr{P, convop::div_magic(P)};
+  convop::Im2colDgradCls a{dy, unit_geom<B16>(g, false, true), g.N, cr, sc};
+  const auto b = weight_rows_cls<B16>(wd, g.C, g.Co, 1, cr, sc);
+  igemm::EpiCls e{dx, (long)P * g.C, nullptr, accumulate ? 1 : 0};
+  e.W = g.C; e.rows = g.N; e.cr = cr; e.sched = sc;
+  return cls_launch<B16>(a, b, e, MB * P * 128, g.C, s, slab);
+}
 // stride-2 data gradient by parity classes (conv_ops.h): per class (ph, pw) of input positions, one small GEMM over the taps
 // that reach it, accumulating into dx.  gemm(c, Mc, ntap, e) launches class c's.
 template <class Gemm>
@@ -707,154 +832,93 @@ static int dgrad_parity(float* dx, const Geom& g, int accumulate, hipStream_t s,
     }
   return AVVAD_OK;
 }
-
-// y = conv(x) (flip = false, wpk = forward pack) or dx (+)= dgrad(dy) (flip = true, wpk = dgrad pack); b16: bf16 activations /
-// packs in (conv64::kernel16), fp32 out
-static int conv64_launch(bool b16, bool flip, const float* x, const float* wpk, float* y, const Geom& g, int accumulate, hipStream_t s,
-                         double* stat) {
-  const int M = g.N * g.H * g.W;
-  const int grid = conv64::grid_for(M, conv64_cus());
-  const unsigned mg_hw = convop::div_magic((unsigned)(g.H * g.W)), mg_w = convop::div_magic((unsigned)g.W);
-  auto k = b16 ? (flip ? conv64::kernel16<true> : conv64::kernel16<false>) : (flip ? conv64::kernel<true> : conv64::kernel<false>);
-  hipLaunchKernelGGL(k, dim3(grid), dim3(conv64::NW * 64), 0, s, x, wpk, y, M, g.H, g.W, mg_hw, mg_w, accumulate, stat);
-  AVVAD_LAUNCH_CHECK();
-  return AVVAD_OK;
-}
-static int conv_fwd_cls(const float* x, const float* wf, float* y, const Geom& g, hipStream_t s, float* slab, double* stat) {
-  const int MB = cdiv(g.N, 128), P = g.Ho * g.Wo;
-  const igemm::ClassSched sc = fwd_sched(g, 32);
-  const igemm::ClassRow cr{P, convop::div_magic(P)};
-  convop::Im2colFwdCls a{x, g, g.N, cr, sc};
-  convop::ColTapRowsCls b{wf, g.Co, g.Co, g.C, 3, 0, cr, sc};
-  igemm::EpiCls e{y, (long)P * g.Co, nullptr, 0};
-  e.stat = stat; e.W = g.Co; e.rows = g.N; e.cr = cr; e.sched = sc;
-  return igemm::launch_cls(a, b, e, MB * P * 128, g.Co, s, slab);
-}
-static int conv_dgrad_cls(const float* dy, const float* wd, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
-  const int MB = cdiv(g.N, 128), P = g.H * g.W;
-  const igemm::ClassSched sc = dgrad_sched(g, 32);
-  const igemm::ClassRow cr{P, convop::div_magic(P)};
-  convop::Im2colDgradCls a{dy, g, g.N, cr, sc};
-  convop::ColTapRowsCls b{wd, g.C, g.C, g.Co, 3, 1, cr, sc};
-  igemm::EpiCls e{dx, (long)P * g.C, nullptr, accumulate ? 1 : 0};
-  e.W = g.C; e.rows = g.N; e.cr = cr; e.sched = sc;
-  return igemm::launch_cls(a, b, e, MB * P * 128, g.C, s, slab);
-}
-
-// stat: per-M-tile column sums / sums of squares of y (igemm::EpiStore::stat), or null
-template <bool BUF>
-static int conv_fwd_t(const float* x, const float* wf, float* y, const Geom& g, const ConvForm& f, hipStream_t s, float* slab, double* stat) {
-  const int M = g.N * g.Ho * g.Wo, K = g.KS * g.KS * g.C;
-  igemm::EpiStore e{y, g.Co, nullptr, 0};
-  if (g.C == 1) {
-    igemm::ColPlain<4> b{wf, g.Co, g.Co, K, 0};
-    convop::StemFwd a{x, g, M, K};
-    return igemm::launch<128, 64>(a, b, e, M, g.Co, K, 1, s, slab);
+// (the ENGINE and PARITY forms)
+template <bool B16, bool BUF>
+static int conv_dgrad_engine(const float* dy, const float* wd, float* dx, const Geom& g, const ConvForm& f, int accumulate, hipStream_t s,
+                             float* slab) {
+  const int M = g.N * g.H * g.W, T = g.KS * g.KS, K = T * g.Co;
+  if constexpr (!B16) {
+    if (g.Co % 32 || g.C % 4 || !taps_fit(g)) return AVVAD_EINVAL;
+    if (!fits_u30((long)g.N * g.Ho * g.Wo * g.Co) || !fits_u30((long)K * g.C)) return AVVAD_EINVAL;   // 32-bit BYTE offsets in the gathers
   }
-  e.stat = stat;
-  if (g.C % 32 || g.Co % 4 || !taps_fit(g)) return AVVAD_EINVAL;
-  if (!fits_u30((long)g.N * g.H * g.W * g.C) || !fits_u30((long)K * g.Co)) return AVVAD_EINVAL;   // 32-bit BYTE offsets in the gathers
-  const int T = g.KS * g.KS;
-  convop::ColTapRows<BUF> b{wf, g.Co, g.Co, K, g.C, T, convop::div_magic(T)};
-  convop::Im2colFwd<BUF> a{x, g, M, convop::tap_div(T, g.KS)};
-  if (f.rows == 256) return igemm::launch<256, 64>(a, b, e, M, g.Co, K, 1, s, slab);
-  if (f.cols == 64) return igemm::launch<128, 64>(a, b, e, M, g.Co, K, 1, s, slab);
-  return igemm::launch<128, 128>(a, b, e, M, g.Co, K, 1, s, slab);
-}
-static int conv_fwd(const float* x, const float* wf, float* y, const Geom& g, hipStream_t s, float* slab, double* stat = nullptr) {
-  const ConvForm f = fwd_form(g, false, slab);
-  switch (f.form) {
-    case STEM: {
-      const int LDW = (g.W + 6) | 1;
-      hipLaunchKernelGGL(stem_fwd_mfma, dim3(g.N), dim3(256), (size_t)(g.H + 6) * LDW * sizeof(float), s, x, wf, y, g.H, g.W, g.Ho, g.Wo,
-                         LDW, stat);
-      AVVAD_LAUNCH_CHECK();
-      return AVVAD_OK;
-    }
-    case CONV64: return conv64_launch(false, false, x, wf, y, g, 0, s, stat);
-    case CLS: return conv_fwd_cls(x, wf, y, g, s, slab, stat);
-    default: return f.buf ? conv_fwd_t<true>(x, wf, y, g, f, s, slab, stat) : conv_fwd_t<false>(x, wf, y, g, f, s, slab, stat);
-  }
-}
-// dx (+)= dgrad
-template <bool BUF>
-static int conv_dgrad_t(const float* dy, const float* wd, float* dx, const Geom& g, const ConvForm& f, int accumulate, hipStream_t s,
-                        float* slab) {
-  const int M = g.N * g.H * g.W, K = g.KS * g.KS * g.Co;
-  if (g.Co % 32 || g.C % 4 || !taps_fit(g)) return AVVAD_EINVAL;
-  if (!fits_u30((long)g.N * g.Ho * g.Wo * g.Co) || !fits_u30((long)K * g.C)) return AVVAD_EINVAL;   // 32-bit BYTE offsets in the gathers
+  const Geom gu = unit_geom<B16>(g, false, true);
   if (f.form == PARITY)
     return dgrad_parity(dx, g, accumulate, s, [&](const convop::S2Class& c, int Mc, int ntap, const convop::EpiS2& e) {
-      convop::Im2colDgradS2<BUF> a{dy, g, c, Mc};
-      convop::ColSegRows<BUF> b{wd, g.C, g.C, ntap * g.Co, ntap, {0, 0, 0, 0}, convop::div_magic(ntap)};
+      const int Kc = ntap * g.Co / UNIT<B16>;
+      convop::Im2colDgradS2<BUF> a{dy, gu, c, Mc};
+      auto b = [&] {      // the class's taps: their K positions in the bf16 pack, their first rows in the fp32 one
+        if constexpr (B16) return bgemm::RowPairsSeg{wd, K / 2, g.C, Kc, T, ntap, {0, 0, 0, 0}, convop::div_magic(ntap)};
+        else return convop::ColSegRows<BUF>{wd, g.C, g.C, Kc, ntap, {0, 0, 0, 0}, convop::div_magic(ntap)};
+      }();
       for (int ia = 0; ia < c.nkh; ++ia)
-        for (int ib = 0; ib < c.nkw; ++ib) b.rowbase[ia * c.nkw + ib] = ((c.kh0 + 2 * ia) * g.KS + (c.kw0 + 2 * ib)) * g.Co;
-      return f.cols == 64 ? igemm::launch<128, 64>(a, b, e, Mc, g.C, ntap * g.Co, 1, s, slab)
-                          : igemm::launch<128, 128>(a, b, e, Mc, g.C, ntap * g.Co, 1, s, slab);
+        for (int ib = 0; ib < c.nkw; ++ib) {
+          const int tap = (c.kh0 + 2 * ia) * g.KS + (c.kw0 + 2 * ib);
+          if constexpr (B16) b.tap[ia * c.nkw + ib] = tap;
+          else b.rowbase[ia * c.nkw + ib] = tap * g.Co;
+        }
+      return tile_launch<B16, false>(f, a, b, e, Mc, g.C, Kc, 1, s, slab);
     });
   igemm::EpiStore e{dx, g.C, nullptr, accumulate ? 1 : 0};
-  const int T = g.KS * g.KS;
-  convop::ColTapRows<BUF> b{wd, g.C, g.C, K, g.Co, T, convop::div_magic(T)};
-  convop::Im2colDgrad<BUF> a{dy, g, M, convop::tap_div(T, g.KS)};
-  if (f.rows == 256) return igemm::launch<256, 64>(a, b, e, M, g.C, K, 1, s, slab);
-  if (f.cols == 64) return igemm::launch<128, 64>(a, b, e, M, g.C, K, 1, s, slab);
-  return igemm::launch<128, 128>(a, b, e, M, g.C, K, 1, s, slab);
+  convop::Im2colDgrad<BUF> a{dy, gu, M, convop::tap_div(T, g.KS)};
+  const auto b = weight_rows<B16, BUF>(wd, g.C, g.Co, T);
+  return tile_launch<B16, true>(f, a, b, e, M, g.C, K / UNIT<B16>, 1, s, slab);
 }
-static int conv_dgrad(const float* dy, const float* wd, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
-  const ConvForm f = dgrad_form(g, false, slab);
+static int conv_dgrad(bool b16, const float* dy, const float* wd, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
+  if (b16 && !bf16_conv_ok(g)) return AVVAD_EINVAL;
+  const ConvForm f = dgrad_form(g, b16, slab);
   switch (f.form) {
-    case CONV64: return conv64_launch(false, true, dy, wd, dx, g, accumulate, s, nullptr);
-    case CLS: return conv_dgrad_cls(dy, wd, dx, g, accumulate, s, slab);
-    default: return f.buf ? conv_dgrad_t<true>(dy, wd, dx, g, f, accumulate, s, slab) : conv_dgrad_t<false>(dy, wd, dx, g, f, accumulate, s, slab);
+    case CONV64: return conv64_launch(b16, true, dy, wd, dx, g, accumulate, s, nullptr);
+    case CLS: return b16 ? conv_dgrad_cls<true>(dy, wd, dx, g, accumulate, s, slab) : conv_dgrad_cls<false>(dy, wd, dx, g, accumulate, s, slab);
+    default:      // PARITY, ENGINE
+      if (b16) return conv_dgrad_engine<true, true>(dy, wd, dx, g, f, accumulate, s, slab);
+      return f.buf ? conv_dgrad_engine<false, true>(dy, wd, dx, g, f, accumulate, s, slab)
+                   : conv_dgrad_engine<false, false>(dy, wd, dx, g, f, accumulate, s, slab);
   }
 }
-// pk[(kh,kw,c)][co] = wgrad (overwritten; tiles split along K are combined by the engine's fix-up kernel, in a fixed order)
-template <bool BUF>
-static int conv_wgrad_t(const float* x, const float* dy, float* pk, const Geom& g, const ConvForm& f, hipStream_t s, float* slab) {
-  const int M = g.KS * g.KS * g.C, K = g.N * g.Ho * g.Wo;
-  igemm::ColPlain<4, BUF> b{dy, g.Co, g.Co, K, 0};
-  const int ktiles = cdiv(K, igemm::BK);
-  if (g.C == 1) {
-    igemm::EpiStore e{pk, g.Co, nullptr, 0};
-    convop::StemWgradX a{x, g, M, K};
-    int split = 1024; if (split > ktiles) split = ktiles;
-    return igemm::launch<64, 64>(a, b, e, M, g.Co, K, split, s, slab);
-  }
-  if (g.C % 32) return AVVAD_EINVAL;
-  convop::EpiWgrad e{pk, g.Co, nullptr, 0, 1, g.C, g.KS * g.KS, convop::div_magic(g.KS * g.KS)};
-  if ((unsigned long)(K + igemm::BK) * (unsigned long)(g.Ho * g.Wo) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
-  if (!fits_u30((long)g.N * g.H * g.W * g.C) || !fits_u30((long)K * g.Co)) return AVVAD_EINVAL;                // 32-bit BYTE offsets in the gathers
-  convop::WgradX<BUF> a{x, g, M, K, convop::div_magic(g.Ho * g.Wo), convop::div_magic(g.Wo)};
-  const int nb = cdiv(M, 128) * cdiv(g.Co, f.cols);
-  int split = cdiv(1024, nb); if (split > ktiles) split = ktiles;
-  if (f.cols == 64) return igemm::launch<128, 64>(a, b, e, M, g.Co, K, split, s, slab);
-  return igemm::launch<128, 128>(a, b, e, M, g.Co, K, split, s, slab);
-}
-static inline igemm::TapSched tap_sched(const Geom& g, int tiles_per_tap) {
-  const int NP = cdiv(g.N, 128) * 128;
-  const int lsh = ((g.Ho - 1) * g.stride - g.pad + 2 > g.H - 1) ? 1 : 0, lsw = ((g.Wo - 1) * g.stride - g.pad + 2 > g.W - 1) ? 1 : 0;
-  return igemm::TapSched{g.Ho, g.Wo, tiles_per_tap, NP / 32, 3, 1, lsh, 1, lsw};
-}
+
+// ---- weight gradient: pk[(kh,kw,c)][co] = wgrad (overwritten; tiles split along K are combined by the engine's fix-up kernel,
+// in a fixed order).  b16: x and dy are bf16
+template <bool B16>
 static int conv_wgrad_tap(const float* x, const float* dy, float* pk, const Geom& g, hipStream_t s, float* slab) {
   const int M = 9 * g.C;
   const igemm::TapSched sc = tap_sched(g, (g.C / 128) * cdiv(g.Co, 128));
-  convop::WgradXTap a{x, g, M, g.C, g.N, convop::div_magic(g.C), sc};
-  convop::ColDyTap b{dy, g, g.Co, g.C, g.N, sc};
+  const Geom gu = unit_geom<B16>(g, true, true);
+  convop::WgradXTap a{x, gu, M / UNIT<B16>, g.C, g.N, convop::div_magic(gu.C), sc};
+  convop::ColDyTap b{dy, gu, gu.Co, g.C, g.N, sc};
   igemm::EpiTap e{pk, g.Co, nullptr, 0};
   e.Mrows = M; e.sched = sc;
-  return igemm::launch_cls(a, b, e, M, g.Co, s, slab);
+  return cls_launch<B16, true>(a, b, e, M, g.Co, s, slab);
 }
-static int conv64_wgrad(const float* x, const float* dy, float* pk, const Geom& g, hipStream_t s, float* slab) {
-  const int NR = g.N * g.H;
-  const int grid = NR < conv64_cus() ? NR : conv64_cus();
-  hipLaunchKernelGGL(conv64::wgrad_kernel, dim3(grid), dim3(conv64::WG_WAVES * 64), 0, s, x, dy, slab, NR, g.H, g.W,
-                     convop::div_magic((unsigned)g.H));
-  hipLaunchKernelGGL(conv64::wgrad_reduce, dim3(conv64::WG_PART / 256), dim3(256), 0, s, (const float*)slab, grid, pk);
-  AVVAD_LAUNCH_CHECK();
-  return AVVAD_OK;
+template <bool B16, bool BUF>
+static int conv_wgrad_engine(const float* x, const float* dy, float* pk, const Geom& g, const ConvForm& f, hipStream_t s, float* slab) {
+  const int T = g.KS * g.KS, M = T * g.C, K = g.N * g.Ho * g.Wo;
+  igemm::ColPlain<4, BUF> b{dy, g.Co / UNIT<B16>, g.Co / UNIT<B16>, K, 0};
+  int split = 1;                                               // (the fp32 engine's split-K hint)
+  if constexpr (!B16) {
+    const int ktiles = cdiv(K, igemm::BK);
+    if (g.C == 1) {                                            // the stem's own operands
+      igemm::EpiStore e{pk, g.Co, nullptr, 0};
+      convop::StemWgradX a{x, g, M, K};
+      split = 1024; if (split > ktiles) split = ktiles;
+      return igemm::launch<64, 64>(a, b, e, M, g.Co, K, split, s, slab);
+    }
+    if (g.C % 32) return AVVAD_EINVAL;
+    if ((unsigned long)(K + igemm::BK) * (unsigned long)(g.Ho * g.Wo) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
+    if (!fits_u30((long)g.N * g.H * g.W * g.C) || !fits_u30((long)K * g.Co)) return AVVAD_EINVAL;                // 32-bit BYTE offsets in the gathers
+    const int nb = cdiv(M, 128) * cdiv(g.Co, f.cols);
+    split = cdiv(1024, nb); if (split > ktiles) split = ktiles;
+  }
+  convop::EpiWgrad e{pk, g.Co, nullptr, 0, 1, g.C, T, convop::div_magic(T), B16 ? 6 : 5};     // (log2 of the K chunk's channels)
+  convop::WgradX<BUF> a{x, unit_geom<B16>(g, true, false), M / UNIT<B16>, K, convop::div_magic(g.Ho * g.Wo), convop::div_magic(g.Wo)};
+  return tile_launch<B16, false, true>(f, a, b, e, M, g.Co, K, split, s, slab);
 }
-static int conv_wgrad(const float* x, const float* dy, float* pk, const Geom& g, hipStream_t s, float* slab) {
-  const ConvForm f = wgrad_form(g, false, slab);
+static int conv_wgrad(bool b16, const float* x, const float* dy, float* pk, const Geom& g, hipStream_t s, float* slab) {
+  if (b16) {
+    const int K = g.N * g.Ho * g.Wo;
+    if (!bf16_conv_ok(g)) return AVVAD_EINVAL;
+    if ((unsigned long)(K + bgemm::BKU) * (unsigned long)(g.Ho * g.Wo) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
+  }
+  const ConvForm f = wgrad_form(g, b16, slab);
   switch (f.form) {
     case STEM: {
       const int LDW = (g.W + 6) | 1;
@@ -865,91 +929,20 @@ static int conv_wgrad(const float* x, const float* dy, float* pk, const Geom& g,
       AVVAD_LAUNCH_CHECK();
       return AVVAD_OK;
     }
-    case CONV64: return conv64_wgrad(x, dy, pk, g, s, slab);
-    case TAP: return conv_wgrad_tap(x, dy, pk, g, s, slab);
-    default: return f.buf ? conv_wgrad_t<true>(x, dy, pk, g, f, s, slab) : conv_wgrad_t<false>(x, dy, pk, g, f, s, slab);
+    case CONV64: {      // (fp32 only: output-stationary kernel + ordered reduction of the per-CU partials)
+      const int NR = g.N * g.H;
+      const int grid = NR < grid_cus() ? NR : grid_cus();
+      hipLaunchKernelGGL(conv64::wgrad_kernel, dim3(grid), dim3(conv64::WG_WAVES * 64), 0, s, x, dy, slab, NR, g.H, g.W,
+                         convop::div_magic((unsigned)g.H));
+      hipLaunchKernelGGL(conv64::wgrad_reduce, dim3(conv64::WG_PART / 256), dim3(256), 0, s, (const float*)slab, grid, pk);
+      AVVAD_LAUNCH_CHECK();
+      return AVVAD_OK;
+    }
+    case TAP: return b16 ? conv_wgrad_tap<true>(x, dy, pk, g, s, slab) : conv_wgrad_tap<false>(x, dy, pk, g, s, slab);
+    default:
+      if (b16) return conv_wgrad_engine<true, true>(x, dy, pk, g, f, s, slab);
+      return f.buf ? conv_wgrad_engine<false, true>(x, dy, pk, g, f, s, slab) : conv_wgrad_engine<false, false>(x, dy, pk, g, f, s, slab);
   }
-}
-
-// ---- the bf16 data path's launchers
-static int conv_fwd16(const float* x16, const float* wf16, float* y, const Geom& g, hipStream_t s, float* slab, double* stat) {
-  if (!bf16_conv_ok(g)) return AVVAD_EINVAL;
-  const ConvForm f = fwd_form(g, true, slab);
-  if (f.form == CONV64) return conv64_launch(true, false, x16, wf16, y, g, 0, s, stat);
-  Geom gp = g;
-  gp.C = g.C / 2;                                            // the gathers address bf16 PAIRS
-  if (f.form == CLS) {
-    const int MB = cdiv(g.N, 128), P = g.Ho * g.Wo;
-    const igemm::ClassSched sc = fwd_sched(g, 64);
-    const igemm::ClassRow cr{P, convop::div_magic(P)};
-    convop::Im2colFwdCls a{x16, gp, g.N, cr, sc};
-    bgemm::RowPairsCls b{wf16, 9 * g.C / 2, g.Co, 9, 3, 0, cr, sc};
-    igemm::EpiCls e{y, (long)P * g.Co, nullptr, 0};
-    e.stat = stat; e.W = g.Co; e.rows = g.N; e.cr = cr; e.sched = sc;
-    return bgemm::launch_cls<false>(a, b, e, MB * P * 128, g.Co, s, slab);
-  }
-  const int M = g.N * g.Ho * g.Wo, T = g.KS * g.KS, Kp = T * g.C / 2;
-  convop::Im2colFwd<true> a{x16, gp, M, convop::tap_div(T, g.KS)};
-  bgemm::RowPairs b{wf16, Kp, g.Co, Kp};
-  igemm::EpiStore e{y, g.Co, nullptr, 0};
-  e.stat = stat;
-  if (f.cols == 64) return bgemm::launch<128, 64, false>(a, b, e, M, g.Co, Kp, s, slab);
-  return bgemm::launch<128, 128, false>(a, b, e, M, g.Co, Kp, s, slab);
-}
-static int conv_dgrad16(const float* dy16, const float* wd16, float* dx, const Geom& g, int accumulate, hipStream_t s, float* slab) {
-  if (!bf16_conv_ok(g)) return AVVAD_EINVAL;
-  const ConvForm f = dgrad_form(g, true, slab);
-  if (f.form == CONV64) return conv64_launch(true, true, dy16, wd16, dx, g, accumulate, s, nullptr);
-  const int M = g.N * g.H * g.W, T = g.KS * g.KS, Kp = T * g.Co / 2;
-  Geom gp = g;
-  gp.Co = g.Co / 2;
-  if (f.form == CLS) {
-    const int MB = cdiv(g.N, 128), P = g.H * g.W;
-    const igemm::ClassSched sc = dgrad_sched(g, 64);
-    const igemm::ClassRow cr{P, convop::div_magic(P)};
-    convop::Im2colDgradCls a{dy16, gp, g.N, cr, sc};
-    bgemm::RowPairsCls b{wd16, Kp, g.C, 9, 3, 1, cr, sc};
-    igemm::EpiCls e{dx, (long)P * g.C, nullptr, accumulate ? 1 : 0};
-    e.W = g.C; e.rows = g.N; e.cr = cr; e.sched = sc;
-    return bgemm::launch_cls<false>(a, b, e, MB * P * 128, g.C, s, slab);
-  }
-  if (f.form == PARITY)
-    return dgrad_parity(dx, g, accumulate, s, [&](const convop::S2Class& c, int Mc, int ntap, const convop::EpiS2& e) {
-      convop::Im2colDgradS2<true> a{dy16, gp, c, Mc};
-      bgemm::RowPairsSeg b{wd16, Kp, g.C, ntap * g.Co / 2, T, ntap, {0, 0, 0, 0}, convop::div_magic(ntap)};
-      for (int ia = 0; ia < c.nkh; ++ia)
-        for (int ib = 0; ib < c.nkw; ++ib) b.tap[ia * c.nkw + ib] = (c.kh0 + 2 * ia) * g.KS + (c.kw0 + 2 * ib);
-      return f.cols == 64 ? bgemm::launch<128, 64, false>(a, b, e, Mc, g.C, ntap * g.Co / 2, s, slab)
-                          : bgemm::launch<128, 128, false>(a, b, e, Mc, g.C, ntap * g.Co / 2, s, slab);
-    });
-  convop::Im2colDgrad<true> a{dy16, gp, M, convop::tap_div(T, g.KS)};
-  bgemm::RowPairs b{wd16, Kp, g.C, Kp};
-  igemm::EpiStore e{dx, g.C, nullptr, accumulate ? 1 : 0};
-  if (f.cols == 64) return bgemm::launch<128, 64, false>(a, b, e, M, g.C, Kp, s, slab);
-  return bgemm::launch<128, 128, false>(a, b, e, M, g.C, Kp, s, slab);
-}
-static int conv_wgrad16(const float* x16, const float* dy16, float* pk, const Geom& g, hipStream_t s, float* slab) {
-  if (!bf16_conv_ok(g)) return AVVAD_EINVAL;
-  const int T = g.KS * g.KS, M = T * g.C, K = g.N * g.Ho * g.Wo;
-  if ((unsigned long)(K + bgemm::BKU) * (unsigned long)(g.Ho * g.Wo) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
-  const ConvForm f = wgrad_form(g, true, slab);
-  if (f.form == TAP) {
-    const igemm::TapSched sc = tap_sched(g, (g.C / 128) * cdiv(g.Co, 128));
-    Geom gq = g;
-    gq.C = g.C / 2; gq.Co = g.Co / 2;                        // operand elements are bf16 pairs
-    convop::WgradXTap a{x16, gq, M / 2, g.C, g.N, convop::div_magic(g.C / 2), sc};
-    convop::ColDyTap b{dy16, gq, g.Co / 2, g.C, g.N, sc};
-    igemm::EpiTap e{pk, g.Co, nullptr, 0};
-    e.Mrows = M; e.sched = sc;
-    return bgemm::launch_cls<true>(a, b, e, M, g.Co, s, slab);
-  }
-  Geom gp = g;
-  gp.C = g.C / 2;
-  convop::WgradX<true> a{x16, gp, M / 2, K, convop::div_magic(g.Ho * g.Wo), convop::div_magic(g.Wo)};
-  igemm::ColPlain<4, true> b{dy16, g.Co / 2, g.Co / 2, K, 0};
-  convop::EpiWgrad e{pk, g.Co, nullptr, 0, 1, g.C, T, convop::div_magic(T), 6};
-  if (f.cols == 64) return bgemm::launch<128, 64, true>(a, b, e, M, g.Co, K, s, slab);
-  return bgemm::launch<128, 128, true>(a, b, e, M, g.Co, K, s, slab);
 }
 
 struct StatCtx { double* part; int nchunk; long rows_per_chunk; };
@@ -1055,12 +1048,30 @@ extern "C" int avvad_conv2d_pack_weights(const float* w_oihw, float* wf, float* 
 }
 static float* slab_of(void* ws, size_t ws_bytes) { return (ws && ws_bytes >= igemm::SLAB_FLOATS * sizeof(float)) ? (float*)ws : nullptr; }
 extern "C" size_t avvad_engine_workspace(void) { return igemm::SLAB_FLOATS * sizeof(float); }
-extern "C" int avvad_conv2d_fwd(const float* x, const float* wf, float* y, const avvad_conv_desc* d, void* ws, size_t ws_bytes,
-                                avvad_stream_t s) {
+// (one body per direction; the _bf16 entry points below pass b16 = true)
+static int conv2d_fwd(bool b16, const void* x, const void* wf, float* y, const avvad_conv_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s) {
   AVVAD_ENTER();
   Geom g;
   if (!x || !wf || !y || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
-  return conv_fwd(x, wf, y, g, (hipStream_t)s, slab_of(ws, ws_bytes));
+  return conv_fwd(b16, (const float*)x, (const float*)wf, y, g, (hipStream_t)s, slab_of(ws, ws_bytes));
+}
+static int conv2d_dgrad(bool b16, const void* dy, const void* wd, float* dx, const avvad_conv_desc* d, int accumulate, void* ws,
+                        size_t ws_bytes, avvad_stream_t s) {
+  AVVAD_ENTER();
+  Geom g;
+  if (!dy || !wd || !dx || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
+  return conv_dgrad(b16, (const float*)dy, (const float*)wd, dx, g, accumulate, (hipStream_t)s, slab_of(ws, ws_bytes));
+}
+static int conv2d_wgrad(bool b16, const void* x, const void* dy, float* dw_packed, const avvad_conv_desc* d, void* ws, size_t ws_bytes,
+                        avvad_stream_t s) {
+  AVVAD_ENTER();
+  Geom g;
+  if (!x || !dy || !dw_packed || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
+  return conv_wgrad(b16, (const float*)x, (const float*)dy, dw_packed, g, (hipStream_t)s, slab_of(ws, ws_bytes));
+}
+extern "C" int avvad_conv2d_fwd(const float* x, const float* wf, float* y, const avvad_conv_desc* d, void* ws, size_t ws_bytes,
+                                avvad_stream_t s) {
+  return conv2d_fwd(false, x, wf, y, d, ws, ws_bytes, s);
 }
 #ifdef AVVAD_PROF
 extern "C" int avvad_debug_prof(unsigned long long* out, int reset) {
@@ -1083,17 +1094,11 @@ extern "C" int avvad_debug_prof_hw(unsigned long long* out, int n) {
 #endif
 extern "C" int avvad_conv2d_dgrad(const float* dy, const float* wd, float* dx, const avvad_conv_desc* d, int accumulate,
                                   void* ws, size_t ws_bytes, avvad_stream_t s) {
-  AVVAD_ENTER();
-  Geom g;
-  if (!dy || !wd || !dx || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
-  return conv_dgrad(dy, wd, dx, g, accumulate, (hipStream_t)s, slab_of(ws, ws_bytes));
+  return conv2d_dgrad(false, dy, wd, dx, d, accumulate, ws, ws_bytes, s);
 }
 extern "C" int avvad_conv2d_wgrad(const float* x, const float* dy, float* dw_packed, const avvad_conv_desc* d, void* ws,
                                   size_t ws_bytes, avvad_stream_t s) {
-  AVVAD_ENTER();
-  Geom g;
-  if (!x || !dy || !dw_packed || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
-  return conv_wgrad(x, dy, dw_packed, g, (hipStream_t)s, slab_of(ws, ws_bytes));
+  return conv2d_wgrad(false, x, dy, dw_packed, d, ws, ws_bytes, s);
 }
 
 // ---- the bf16 data path's convolutions on their own (bgemm.h): operands bf16 in HBM, fp32 results.  Exported for the
@@ -1122,24 +1127,15 @@ extern "C" int avvad_conv2d_pack_weights_bf16(const float* w_oihw, void* wf16, v
 }
 extern "C" int avvad_conv2d_fwd_bf16(const void* x16, const void* wf16, float* y, const avvad_conv_desc* d, void* ws, size_t ws_bytes,
                                      avvad_stream_t s) {
-  AVVAD_ENTER();
-  Geom g;
-  if (!x16 || !wf16 || !y || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
-  return conv_fwd16((const float*)x16, (const float*)wf16, y, g, (hipStream_t)s, slab_of(ws, ws_bytes), nullptr);
+  return conv2d_fwd(true, x16, wf16, y, d, ws, ws_bytes, s);
 }
 extern "C" int avvad_conv2d_dgrad_bf16(const void* dy16, const void* wd16, float* dx, const avvad_conv_desc* d, int accumulate,
                                        void* ws, size_t ws_bytes, avvad_stream_t s) {
-  AVVAD_ENTER();
-  Geom g;
-  if (!dy16 || !wd16 || !dx || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
-  return conv_dgrad16((const float*)dy16, (const float*)wd16, dx, g, accumulate, (hipStream_t)s, slab_of(ws, ws_bytes));
+  return conv2d_dgrad(true, dy16, wd16, dx, d, accumulate, ws, ws_bytes, s);
 }
 extern "C" int avvad_conv2d_wgrad_bf16(const void* x16, const void* dy16, float* dw_packed, const avvad_conv_desc* d, void* ws,
                                        size_t ws_bytes, avvad_stream_t s) {
-  AVVAD_ENTER();
-  Geom g;
-  if (!x16 || !dy16 || !dw_packed || !conv_geom(d, &g) || ws_misaligned(ws)) return AVVAD_EINVAL;
-  return conv_wgrad16((const float*)x16, (const float*)dy16, dw_packed, g, (hipStream_t)s, slab_of(ws, ws_bytes));
+  return conv2d_wgrad(true, x16, dy16, dw_packed, d, ws, ws_bytes, s);
 }
 
 extern "C" size_t avvad_trunk_workspace(const avvad_trunk_desc* d) {
@@ -1198,7 +1194,7 @@ extern "C" int avvad_trunk_fwd(const float* frames, const avvad_trunk_params* pr
   }
   // stem
   const long N = d->N;
-  if ((rc = conv_fwd(frames, ws + p.wf[0], ws + p.c0, p.geom[0], s, ws + p.slab, fused_stat(&p, ws, 0, d)))) return rc;
+  if ((rc = conv_fwd(false, frames, ws + p.wf[0], ws + p.c0, p.geom[0], s, ws + p.slab, fused_stat(&p, ws, 0, d)))) return rc;
   const long M0 = N * p.h[1] * p.w[1];
   if ((rc = bn_prepare(&p, ws, 0, ws + p.c0, M0, prm, d, s))) return rc;
   {
@@ -1207,10 +1203,7 @@ extern "C" int avvad_trunk_fwd(const float* frames, const avvad_trunk_params* pr
     hipLaunchKernelGGL(pool, dim3(ew_grid(N * p.h[2] * p.w[2] * 16)), dim3(256), 0, s, ws + p.c0, ws + p.bn_scale, ws + p.bn_shift,
                        ws + p.p0, am, d->N, p.h[1], p.w[1], p.h[2], p.w[2]);
   }
-  auto cfwd = [&](const float* xin, int i, float* yout) -> int {
-    if (b16) return conv_fwd16(xin, ws + p.wf16[i], yout, p.geom[i], s, ws + p.slab, fused_stat(&p, ws, i, d));
-    return conv_fwd(xin, ws + p.wf[i], yout, p.geom[i], s, ws + p.slab, fused_stat(&p, ws, i, d));
-  };
+  const size_t* wf = b16 ? p.wf16 : p.wf;      // the data path's forward packs
   // residual stages (bn_act writes bf16 on the bf16 data path; the residual it adds is bf16 there only when it is the block's input)
   auto act = b16 ? bn_act<true, false> : bn_act<false, false>;
   auto act_id = b16 ? bn_act<true, true> : bn_act<false, false>;
@@ -1226,14 +1219,14 @@ extern "C" int avvad_trunk_fwd(const float* frames, const avvad_trunk_params* pr
       const long nq = M * C / 4;
       const int i1 = ci, i2 = ci + 1, id = ci + 2;
       unsigned char* qmo = d->save_for_backward ? reinterpret_cast<unsigned char*>(ws + p.qm[st * 2 + b]) : (unsigned char*)nullptr;
-      if ((rc = cfwd(x, i1, ws + o[0]))) return rc;
+      if ((rc = conv_fwd(b16, x, ws + wf[i1], ws + o[0], p.geom[i1], s, ws + p.slab, fused_stat(&p, ws, i1, d)))) return rc;
       if ((rc = bn_prepare(&p, ws, i1, ws + o[0], M, prm, d, s))) return rc;
       hipLaunchKernelGGL(act, dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[0], ws + p.bn_scale + i1 * MAXC, ws + p.bn_shift + i1 * MAXC,
                          (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ws + o[1], nq, C, 1, (unsigned char*)nullptr);
-      if ((rc = cfwd(ws + o[1], i2, ws + o[2]))) return rc;
+      if ((rc = conv_fwd(b16, ws + o[1], ws + wf[i2], ws + o[2], p.geom[i2], s, ws + p.slab, fused_stat(&p, ws, i2, d)))) return rc;
       if ((rc = bn_prepare(&p, ws, i2, ws + o[2], M, prm, d, s))) return rc;
       if (ds) {
-        if ((rc = cfwd(x, id, ws + o[3]))) return rc;
+        if ((rc = conv_fwd(b16, x, ws + wf[id], ws + o[3], p.geom[id], s, ws + p.slab, fused_stat(&p, ws, id, d)))) return rc;
         if ((rc = bn_prepare(&p, ws, id, ws + o[3], M, prm, d, s))) return rc;
         // (the identity input is the downsample convolution's RAW fp32 output in either data path)
         hipLaunchKernelGGL(act, dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC, ws + p.bn_shift + i2 * MAXC,
@@ -1273,15 +1266,8 @@ extern "C" int avvad_trunk_bwd(const float* frames, const avvad_trunk_params* pr
                      p.h[5] * p.w[5], 512);
   const bool b16 = native_bf16();        // the forward ran the bf16 data path (same process-wide option): activations,
                                          // and the BatchNorm-backward outputs that feed convolutions, are bf16
-  auto wgrad = [&](int i, const float* xin, const float* dyraw) -> int {
-    if (!g->conv_w[i]) return AVVAD_OK;
-    if (b16 && i > 0) return conv_wgrad16(xin, dyraw, ws + p.wg[i], p.geom[i], s, ws + p.slab);
-    return conv_wgrad(xin, dyraw, ws + p.wg[i], p.geom[i], s, ws + p.slab);   // unpacked at the end (unpack_all)
-  };
-  auto dgrad = [&](const float* dyv, int i, float* dxv, int accumulate) -> int {
-    if (b16) return conv_dgrad16(dyv, ws + p.wd16[i], dxv, p.geom[i], accumulate, s, ws + p.slab);
-    return conv_dgrad(dyv, ws + p.wd[i], dxv, p.geom[i], accumulate, s, ws + p.slab);
-  };
+  const size_t* wd = b16 ? p.wd16 : p.wd;      // the data path's data-gradient packs
+  // (weight gradients: wanted ones only, into ws + p.wg[i], unpacked at the end by unpack_all)
   int ci = NCONV;
   for (int st = 3; st >= 0; --st)
     for (int b = 1; b >= 0; --b) {
@@ -1297,17 +1283,17 @@ extern "C" int avvad_trunk_bwd(const float* frames, const avvad_trunk_params* pr
         if ((rc = bn_backward(&p, ws, i2, ws + o[2], G0, ws + o[4], G1, nullptr, M, prm, g, d, s, false, qmb, b16))) return rc;
         // identity branch through downsample BN + 1x1 conv: d cd in G2, d x in G3
         if ((rc = bn_backward(&p, ws, id, ws + o[3], G0, ws + o[4], G2, nullptr, M, prm, g, d, s, false, qmb, b16))) return rc;
-        if ((rc = wgrad(id, x, G2))) return rc;
-        if ((rc = dgrad(G2, id, G3, 0))) return rc;
+        if (g->conv_w[id] && (rc = conv_wgrad(b16, x, G2, ws + p.wg[id], p.geom[id], s, ws + p.slab))) return rc;
+        if ((rc = conv_dgrad(b16, G2, ws + wd[id], G3, p.geom[id], 0, s, ws + p.slab))) return rc;
       } else {
         // identity branch: d x = masked d out (written to G3 by the apply kernel)
         if ((rc = bn_backward(&p, ws, i2, ws + o[2], G0, ws + o[4], G1, G3, M, prm, g, d, s, false, qmb, b16))) return rc;
       }
-      if ((rc = wgrad(i2, ws + o[1], G1))) return rc;
-      if ((rc = dgrad(G1, i2, G2, 0))) return rc;  // d a1 in G2
+      if (g->conv_w[i2] && (rc = conv_wgrad(b16, ws + o[1], G1, ws + p.wg[i2], p.geom[i2], s, ws + p.slab))) return rc;
+      if ((rc = conv_dgrad(b16, G1, ws + wd[i2], G2, p.geom[i2], 0, s, ws + p.slab))) return rc;  // d a1 in G2
       if ((rc = bn_backward(&p, ws, i1, ws + o[0], G2, ws + o[1], G1, nullptr, M, prm, g, d, s, true, nullptr, b16))) return rc;  // d c1 in G1
-      if ((rc = wgrad(i1, x, G1))) return rc;
-      if ((rc = dgrad(G1, i1, G3, 1))) return rc;  // d x += ...
+      if (g->conv_w[i1] && (rc = conv_wgrad(b16, x, G1, ws + p.wg[i1], p.geom[i1], s, ws + p.slab))) return rc;
+      if ((rc = conv_dgrad(b16, G1, ws + wd[i1], G3, p.geom[i1], 1, s, ws + p.slab))) return rc;  // d x += ...
       float* t = G0; G0 = G3; G3 = t;
     }
   // stem: G0 = d p0
@@ -1324,7 +1310,7 @@ extern "C" int avvad_trunk_bwd(const float* frames, const avvad_trunk_params* pr
     const long M0 = N * p.h[1] * p.w[1];
     // in place: d c0 overwrites g0
     if ((rc = bn_backward(&p, ws, 0, ws + p.c0, g0, nullptr, g0, nullptr, M0, prm, g, d, s, false, nullptr, false, fuse0 ? grid0 : 0))) return rc;
-    if ((rc = wgrad(0, frames, g0))) return rc;
+    if (g->conv_w[0] && (rc = conv_wgrad(false, frames, g0, ws + p.wg[0], p.geom[0], s, ws + p.slab))) return rc;   // (the stem: fp32 in either data path)
   }
   {
     UnpackTab tab;

@@ -954,7 +954,7 @@ def test_training_is_reproducible_under_allocator_churn_and_stream_timing():
 # last block rising to 3.0e-1 at the stem, whose gradient has passed 20 bf16 convolutions).  The figures move by +-2e-2 with
 # the fp32 summation order INSIDE the convolutions: an activation that lands on the other side of a bf16 rounding boundary
 # changes by 2^-8 relative, and a 12-frame train-mode BatchNorm passes that on (the head's weight_ih_l1: 4.2e-2 with the engine's
-# layer-1 kernels, 7.1e-2 with conv64::kernel16 -- the same exact products, another order).  The bounds are sanity bounds for a
+# layer-1 kernels, 7.1e-2 with conv64::kernel<B16, .> -- the same exact products, another order).  The bounds are sanity bounds for a
 # toy; the benched model's logits (3e-2 of max|ref|) and the exact-product tests carry the real claim.
 BF16_GRAD_REL = {"head": 1e-1, "encoder": 1e-1, "trunk": 3.5e-1}
 
@@ -1007,7 +1007,7 @@ def test_bf16_convolutions_vs_rounded_operands(N, H, W, C, Co, KS, stride, pad, 
                                                       (300, 5, 5, 256, 256, 3, 1, 1), (96, 9, 9, 128, 256, 3, 2, 1), (40, 17, 17, 64, 64, 3, 1, 1),
                                                       (130, 3, 3, 512, 512, 3, 1, 1), (256, 9, 9, 128, 256, 3, 2, 1), (200, 5, 5, 256, 512, 3, 2, 1),
                                                       (333, 9, 9, 128, 256, 3, 1, 1), (1024, 17, 17, 64, 64, 3, 1, 1),
-                                                      (814, 17, 17, 64, 128, 1, 2, 0)])
+                                                      (814, 17, 17, 64, 128, 1, 2, 0), (70, 9, 13, 64, 64, 3, 1, 1)])
 def test_bf16_data_path_convolutions(N, H, W, C, Co, KS, stride, pad):
     """The bf16 DATA PATH's convolutions (csrc/bgemm.h; what the trunk runs under option bf16 = 1): operands are bf16 in
     memory -- NHWC bf16 activations / output gradients, K-contiguous bf16 weight packs -- staged with 16-byte loads, the
@@ -1016,8 +1016,8 @@ def test_bf16_data_path_convolutions(N, H, W, C, Co, KS, stride, pad):
     k-slot / chunk in the LDS images, the transposed reads or the weight packs is an O(1) error.  Covers whole-tile rounds,
     stream-K rounds with the ordered fix-up (N = 700, 300), the four stride-2 parity classes, the 1x1 downsample, and -- from
     128 images up, where the tile count fits the stream-K pool -- the position-class schedule that skips the zero padding.
-    The 64 -> 64 channel shapes run the bf16 form of the weights-stationary kernel (conv64::kernel16), at 1024 frames with four
-    to five tiles per wave (the cross-tile prefetch).  The 1x1 downsample at 814 frames is 516 tiles of ONE K tile: a full round
+    The 64 -> 64 channel shapes run the bf16 form of the weights-stationary kernel (conv64::kernel<B16, .>), at 1024 frames with four
+    to five tiles per wave (the cross-tile prefetch), and on a 9x13 grid (H != W, 8190 pixels: a last tile of 30).  The 1x1 downsample at 814 frames is 516 tiles of ONE K tile: a full round
     plus a four-iteration pool on 512 workers, so most workers' stream-K shares are empty (csrc/streamk.h, Share)."""
     import ctypes as Ct
     import torch.nn.functional as F

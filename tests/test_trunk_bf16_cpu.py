@@ -78,7 +78,7 @@ def test_standin_passes_stem_frozen_and_accumulate():
 def test_bf16_forms_of_the_cases():
     f = {case: R.forms16(case) for case in R.CASES}
     eng, par = "ENGINE 128x128 buf", "PARITY 128x128 buf"
-    for case in R.CASES:                             # kernel16 in layer 1 everywhere; its weight gradient on the engine
+    for case in R.CASES:                             # conv64::kernel<B16, .> in layer 1 everywhere; its weight gradient on the engine
         assert all(f[case]["4.%d.conv%d" % (b, j)][:3] == ("CONV64", "CONV64", "ENGINE 128x64 buf") for b in (0, 1) for j in (1, 2))
         assert f[case]["0"] == R.forms(case)["0"]
     # T1, T8: CLS16 forward on 3x3 and 2x2 grids, two row tiles, the second ragged, feeding the fused statistics

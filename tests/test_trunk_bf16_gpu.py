@@ -1,4 +1,4 @@
-"""The ResNet-18 trunk's bf16 data path (option "bf16" = 1: bgemm.h, conv64::kernel16, the <true> forms of the BatchNorm
+"""The ResNet-18 trunk's bf16 data path (option "bf16" = 1: bgemm.h, conv64::kernel<B16, .>, the <true> forms of the BatchNorm
 and pooling kernels, pack_all's bf16 packs) on the GPU against the value-pinned float64 replay of tests/trunk_ref.py: every
 case under the default options, the schedule options on the cases where the restated table says a bf16 form changes, one
 gradient subset and one accumulating run.  The implementation's 17 stored activations (``ops.trunk_saved_activations``:
