@@ -27,17 +27,27 @@ namespace {
 constexpr int NCONV = AVVAD_TRUNK_NCONV;
 
 // ------------------------------------------------------------------ static network description
-struct ConvSpec {
-  int cin, cout, ks, stride, pad;
-  int stage;    // -1 stem
-  int role;     // 0 stem, 1 block conv1, 2 block conv2, 3 downsample
+constexpr int NBLOCK = 8;                             // 4 stages x 2 residual blocks
+constexpr int WIDTHS[4] = {64, 128, 256, 512};        // channels of a stage
+
+// One residual block: out = relu(bn2(conv2(a1)) + identity), a1 = relu(bn1(conv1(in))); identity = in, or with `ds` (the
+// first block of stages 1..3) bnd(convd(in)).  Tensor offsets are in floats of the workspace; NHWC, M x width each.
+struct Block {
+  int stage, width;
+  int h, w;          // output grid (of all its convolutions)
+  long M;            // N * h * w: rows of its tensors
+  bool ds;           // stride-2 entry, downsample convolution on the identity branch
+  int i1, i2, id;    // its convolutions in the order of include/avvad.h (id: -1 without ds)
+  size_t in;         // the block's input: the pooled stem output or the previous block's `out`
+  size_t c1, a1;     // conv1's raw output; relu(bn1(c1))
+  size_t c2, cd;     // conv2's raw output; the downsample convolution's (ds only)
+  size_t out, qm;    // the block's output; its ReLU mask, one BYTE per quad of `out` (save_for_backward)
 };
 
 struct Plan {
-  int N, H, W;
   int h[6], w[6];  // 0: input, 1: stem out, 2: pooled / stage0, 3..5: stage1..3
-  ConvSpec conv[NCONV];
-  Geom geom[NCONV];
+  Geom geom[NCONV];                  // the convolutions in the order of include/avvad.h
+  Block block[NBLOCK];
   // workspace offsets in floats
   size_t wf[NCONV], wd[NCONV];
   size_t wf16[NCONV], wd16[NCONV];   // bf16 packs of the bf16 data path: [co][(cc,tap,r)] and [c][(cc,tap,r)] (64-channel chunks cc)
@@ -45,76 +55,74 @@ struct Plan {
   size_t coef;                                    // [3][MAXC] backward coefficients
   size_t part;                                    // doubles: [STAT_CHUNKS][2][MAXC]
   size_t c0, p0, am;   // am: arg-max position (0..8, one byte per channel) of every pooled stem element
-  size_t blk[8][5];  // c1, a1, c2, cd, out
-  size_t qm[8];      // bytes (as floats): one ReLU-mask byte per quad of a block's output (save_for_backward)
   size_t G[4], g0, wg[NCONV];   // wg[i]: conv i's packed weight gradient (all 20 kept: ONE unpack launch at the end)
   size_t slab;     // igemm::SLAB_FLOATS: partial tiles of the engine's stream-K round
   size_t total;
 };
 
-static void make_plan(const avvad_trunk_desc* d, Plan* p) {
-  p->N = d->N; p->H = d->H; p->W = d->W;
-  p->h[0] = d->H; p->w[0] = d->W;
-  p->h[1] = (d->H + 6 - 7) / 2 + 1; p->w[1] = (d->W + 6 - 7) / 2 + 1;
-  p->h[2] = (p->h[1] + 2 - 3) / 2 + 1; p->w[2] = (p->w[1] + 2 - 3) / 2 + 1;
-  for (int s = 3; s < 6; ++s) { p->h[s] = (p->h[s - 1] + 2 - 3) / 2 + 1; p->w[s] = (p->w[s - 1] + 2 - 3) / 2 + 1; }
+static bool trunk_desc_ok(const avvad_trunk_desc* d) { return d && d->N > 0 && d->H >= 32 && d->W >= 32; }
+static Plan make_plan(const avvad_trunk_desc* d) {
+  Plan p;
+  p.h[0] = d->H; p.w[0] = d->W;
+  // every halving -- 7x7 / 2 pad 3, the 3x3 / 2 pad 1 pool and stage entries -- is (n + 2 pad - ks) / 2 + 1 = (n - 1) / 2 + 1
+  for (int s = 1; s < 6; ++s) { p.h[s] = (p.h[s - 1] - 1) / 2 + 1; p.w[s] = (p.w[s - 1] - 1) / 2 + 1; }
+  // the network, once: the stem, then 4 stages x 2 blocks, a stride-2 entry with a downsample in the first block of stages 1..3
   int i = 0;
-  p->conv[i++] = {1, 64, 7, 2, 3, -1, 0};
+  auto add_conv = [&](int cin, int cout, int ks, int stride, int pad, int hin, int win, int ho, int wo) {
+    p.geom[i] = {d->N, hin, win, cin, ho, wo, cout, ks, stride, pad};
+    return i++;
+  };
+  add_conv(1, 64, 7, 2, 3, p.h[0], p.w[0], p.h[1], p.w[1]);
   int cin = 64;
-  const int widths[4] = {64, 128, 256, 512};
   for (int s = 0; s < 4; ++s)
     for (int b = 0; b < 2; ++b) {
-      const int c = widths[s], st = (b == 0 && s > 0) ? 2 : 1;
-      p->conv[i++] = {cin, c, 3, st, 1, s, 1};
-      p->conv[i++] = {c, c, 3, 1, 1, s, 2};
-      if (b == 0 && s > 0) p->conv[i++] = {cin, c, 1, 2, 0, s, 3};
-      cin = c;
+      Block& k = p.block[s * 2 + b];
+      k.stage = s; k.width = WIDTHS[s]; k.ds = b == 0 && s > 0;
+      k.h = p.h[s + 2]; k.w = p.w[s + 2]; k.M = (long)d->N * k.h * k.w;
+      const int hin = k.ds ? p.h[s + 1] : k.h, win = k.ds ? p.w[s + 1] : k.w;
+      k.i1 = add_conv(cin, k.width, 3, k.ds ? 2 : 1, 1, hin, win, k.h, k.w);
+      k.i2 = add_conv(k.width, k.width, 3, 1, 1, k.h, k.w, k.h, k.w);
+      k.id = k.ds ? add_conv(cin, k.width, 1, 2, 0, hin, win, k.h, k.w) : -1;
+      cin = k.width;
     }
-  // geometry
-  i = 0;
-  p->geom[i++] = {d->N, p->h[0], p->w[0], 1, p->h[1], p->w[1], 64, 7, 2, 3};
-  for (int s = 0; s < 4; ++s)
-    for (int b = 0; b < 2; ++b) {
-      const int hin = (b == 0 && s > 0) ? p->h[s + 1] : p->h[s + 2], win = (b == 0 && s > 0) ? p->w[s + 1] : p->w[s + 2];
-      const int ho = p->h[s + 2], wo = p->w[s + 2];
-      const ConvSpec c1 = p->conv[i];
-      p->geom[i++] = {d->N, hin, win, c1.cin, ho, wo, c1.cout, 3, c1.stride, 1};
-      const ConvSpec c2 = p->conv[i];
-      p->geom[i++] = {d->N, ho, wo, c2.cin, ho, wo, c2.cout, 3, 1, 1};
-      if (b == 0 && s > 0) { const ConvSpec cd = p->conv[i]; p->geom[i++] = {d->N, hin, win, cd.cin, ho, wo, cd.cout, 1, 2, 0}; }
-    }
+  // the workspace (the order and sizes of the parts are the layout avvad_trunk_workspace / avvad_trunk_activation publish)
   size_t off = 0;
   auto take = [&](size_t n) { size_t o = off; off += align_up(n, 64); return o; };
+  auto weights = [&](int j) { const Geom& g = p.geom[j]; return (size_t)g.KS * g.KS * g.C * g.Co; };
   for (i = 0; i < NCONV; ++i) {
-    const ConvSpec& c = p->conv[i];
-    const size_t n = (size_t)c.ks * c.ks * c.cin * c.cout;
-    p->wf[i] = take(n);
-    p->wd[i] = (i == 0) ? 0 : take(n);
-    p->wf16[i] = (i == 0) ? 0 : take(n / 2);
-    p->wd16[i] = (i == 0) ? 0 : take(n / 2);
+    const size_t n = weights(i);
+    p.wf[i] = take(n);
+    p.wd[i] = (i == 0) ? 0 : take(n);
+    p.wf16[i] = (i == 0) ? 0 : take(n / 2);
+    p.wd16[i] = (i == 0) ? 0 : take(n / 2);
   }
-  p->bn_scale = take(NCONV * MAXC); p->bn_shift = take(NCONV * MAXC);
-  p->bn_mean = take(NCONV * MAXC); p->bn_invstd = take(NCONV * MAXC);
-  p->coef = take(3 * MAXC);
-  p->part = take((size_t)STAT_CHUNKS * 2 * MAXC * 2);  // doubles
-  p->slab = take(igemm::SLAB_FLOATS);
+  p.bn_scale = take(NCONV * MAXC); p.bn_shift = take(NCONV * MAXC);
+  p.bn_mean = take(NCONV * MAXC); p.bn_invstd = take(NCONV * MAXC);
+  p.coef = take(3 * MAXC);
+  p.part = take((size_t)STAT_CHUNKS * 2 * MAXC * 2);  // doubles
+  p.slab = take(igemm::SLAB_FLOATS);
   const size_t N = d->N;
-  p->c0 = take(N * p->h[1] * p->w[1] * 64);
-  p->p0 = take(N * p->h[2] * p->w[2] * 64);
-  p->am = take(N * p->h[2] * p->w[2] * 16);     // 4 bytes (one channel quad) per word
-  for (int s = 0; s < 4; ++s)
-    for (int b = 0; b < 2; ++b) {
-      const size_t n = N * p->h[s + 2] * p->w[s + 2] * widths[s];
-      for (int j = 0; j < 5; ++j) p->blk[s * 2 + b][j] = (j == 3 && !(b == 0 && s > 0)) ? 0 : take(n);
-      p->qm[s * 2 + b] = d->save_for_backward ? take((n / 4 + 3) / 4) : 0;
-    }
-  if (d->save_for_backward) {
-    const size_t gmax = N * p->h[2] * p->w[2] * 64;  // stage0 is the largest block tensor
-    for (int j = 0; j < 4; ++j) p->G[j] = take(gmax);
-    p->g0 = take(N * p->h[1] * p->w[1] * 64);
-    for (int j = 0; j < NCONV; ++j) p->wg[j] = take((size_t)p->conv[j].ks * p->conv[j].ks * p->conv[j].cin * p->conv[j].cout);
+  p.c0 = take(N * p.h[1] * p.w[1] * 64);
+  p.p0 = take(N * p.h[2] * p.w[2] * 64);
+  p.am = take(N * p.h[2] * p.w[2] * 16);     // 4 bytes (one channel quad) per word
+  size_t in = p.p0;
+  for (Block& k : p.block) {
+    const size_t n = (size_t)k.M * k.width;
+    k.in = in;
+    k.c1 = take(n); k.a1 = take(n); k.c2 = take(n);
+    k.cd = k.ds ? take(n) : 0;
+    k.out = take(n);
+    k.qm = d->save_for_backward ? take((n / 4 + 3) / 4) : 0;
+    in = k.out;
   }
-  p->total = off;
+  if (d->save_for_backward) {
+    const size_t gmax = N * p.h[2] * p.w[2] * 64;  // stage0 is the largest block tensor
+    for (int j = 0; j < 4; ++j) p.G[j] = take(gmax);
+    p.g0 = take(N * p.h[1] * p.w[1] * 64);
+    for (int j = 0; j < NCONV; ++j) p.wg[j] = take(weights(j));
+  }
+  p.total = off;
+  return p;
 }
 
 // ------------------------------------------------------------------ weight (un)packing
@@ -143,7 +151,7 @@ struct PackTab {
   __bf16* wf16[NCONV];   // bf16 data path (may be null): wf16[co][(cc * T + tap) * 64 + r] = w[co][cc * 64 + r][tap]
   __bf16* wd16[NCONV];   //                               wd16[c][(cc * T + tap) * 64 + r] = w[cc * 64 + r][c][tap]
   int cout[NCONV], cin[NCONV], ks[NCONV];
-  int blk0[NCONV + 1];   // first block of conv i (conv 0 = stem: its 3 input channels are folded, see pack_stem)
+  int blk0[NCONV + 1];   // first block of conv i (conv 0 = stem: one element per thread, see below)
 };
 constexpr int PACK_LD = 32 * 9 + 1;
 __global__ void __launch_bounds__(256) pack_all(const PackTab tab) {
@@ -154,7 +162,7 @@ __global__ void __launch_bounds__(256) pack_all(const PackTab tab) {
   const int lb = (int)blockIdx.x - tab.blk0[i];
   const float* w = tab.w[i];
   float* wf = tab.wf[i];
-  if (i == 0) {
+  if (i == 0) {     // the stem: its 3 identical input channels (Video_Net.py:64) are folded, Wf[kh*7+kw][co] = sum_c w[co][c][kh][kw]
     const int e = lb * 256 + threadIdx.x;
     if (e >= 64 * 49) return;
     const int co = e / 49, k = e % 49;
@@ -186,13 +194,6 @@ __global__ void __launch_bounds__(256) pack_all(const PackTab tab) {
     wf[((long)(tap * C + c0 + a)) * Co + co0 + b] = tl[b * PACK_LD + a * T + tap];           // row (tap, c = a), column co = b
     if (wd) wd[((long)(tap * Co + co0 + a)) * C + c0 + b] = tl[a * PACK_LD + b * T + tap];    // row (tap, co = a), column c = b
   }
-}
-// stem: fold the 3 identical input channels (Video_Net.py:64): Wf[kh*7+kw][co] = sum_c w[co][c][kh][kw]
-__global__ void pack_stem(const float* __restrict__ w, float* __restrict__ wf) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 64 * 49) return;
-  const int co = i / 49, k = i % 49;
-  wf[k * 64 + co] = w[(co * 3 + 0) * 49 + k] + w[(co * 3 + 1) * 49 + k] + w[(co * 3 + 2) * 49 + k];
 }
 // every convolution's packed gradient -> += the OIHW gradient, ONE launch behind the last weight-gradient GEMM (19 launches
 // of ~8 us each were 0.15 ms of the step; the whole trunk is one autograd node, nobody consumes a gradient earlier)
@@ -945,82 +946,115 @@ static int conv_wgrad(bool b16, const float* x, const float* dy, float* pk, cons
   }
 }
 
-struct StatCtx { double* part; int nchunk; long rows_per_chunk; };
-static StatCtx stat_ctx(Plan* p, float* ws, long M, int C) {
-  StatCtx c;
-  c.part = reinterpret_cast<double*>(ws + p->part);
+// ------------------------------------------------------------------ one run of the trunk: what every step of a forward or backward needs
+constexpr const float* NOF = nullptr;      // an optional float operand that is absent, as a typed kernel argument
+struct BnSlots { float *scale, *shift, *mean, *invstd; };      // one convolution's BatchNorm: the forward's affine map, its batch statistics
+struct Run {
+  const Plan& p;
+  float* ws;
+  const avvad_trunk_params* prm;
+  const avvad_trunk_grads* g;      // (the backward's; null in a forward)
+  const avvad_trunk_desc* d;
+  hipStream_t s;
+  float* at(size_t off) const { return ws + off; }
+  double* part() const { return reinterpret_cast<double*>(ws + p.part); }      // the column statistics' partial sums
+  BnSlots bn(int i) const {      // conv i's slots
+    const size_t o = (size_t)i * MAXC;
+    return {at(p.bn_scale + o), at(p.bn_shift + o), at(p.bn_mean + o), at(p.bn_invstd + o)};
+  }
+  long rows(int i) const { const Geom& g = p.geom[i]; return (long)g.N * g.Ho * g.Wo; }      // pixels of conv i's output
+};
+
+struct StatCtx { int nchunk; long rows_per_chunk; };
+static StatCtx stat_ctx(long M, int C) {
   const int RL = 256 / (C / 4);
   long per = (M + STAT_CHUNKS - 1) / STAT_CHUNKS;
   if (per < 16L * RL) per = 16L * RL;   // >= 16 rows per thread: fewer, fuller chunks for the small deep layers (the finalize
                                          // kernels read every chunk's partial sums)
   per = (per + RL - 1) / RL * RL;
-  c.rows_per_chunk = per;
-  c.nchunk = cdiv(M, per);
-  return c;
+  return {cdiv(M, per), per};
 }
 
 // partial-sum chunks of conv i's batch statistics that its forward leaves in the partial-sum buffer (the form's: one per M tile of
 // its GEMM, per conv64 workgroup, per stem frame), 0: the separate column-reduction pass forms them
-static int fused_chunks(Plan* p, int i, const avvad_trunk_desc* d) {
-  if (!d->training || avvad_tune().no_fused_stats) return 0;
-  const int n = fwd_form(p->geom[i], i > 0 && native_bf16(), true).chunks;
-  return (long)n * p->conv[i].cout <= (long)STAT_CHUNKS * MAXC ? n : 0;      // the partial-sum buffer's size
+static int fused_chunks(const Run& r, int i, bool b16) {
+  if (!r.d->training || avvad_tune().no_fused_stats) return 0;
+  const int n = fwd_form(r.p.geom[i], b16, true).chunks;
+  return (long)n * r.p.geom[i].Co <= (long)STAT_CHUNKS * MAXC ? n : 0;      // the partial-sum buffer's size
 }
-// where conv i's forward can leave its fused statistics (null: take the separate column-reduction pass)
-static double* fused_stat(Plan* p, float* ws, int i, const avvad_trunk_desc* d) {
-  return fused_chunks(p, i, d) ? reinterpret_cast<double*>(ws + p->part) : nullptr;
-}
-// batch statistics of conv output i -> scale/shift/mean/invstd slots i (+ running stats)
-static int bn_prepare(Plan* p, float* ws, int i, const float* craw, long M, const avvad_trunk_params* prm,
-                      const avvad_trunk_desc* d, hipStream_t s) {
-  const int C = p->conv[i].cout;
-  StatCtx sc = stat_ctx(p, ws, M, C);
-  if (const int n = fused_chunks(p, i, d)) {
-    sc.nchunk = n;
-  } else if (d->training) {
-    hipLaunchKernelGGL(col_reduce<0>, dim3(sc.nchunk), dim3(256), 0, s, craw, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, M, C, sc.rows_per_chunk, sc.part);
+// batch statistics of conv output i -> scale/shift/mean/invstd slots i (+ running stats).  fused: the chunks its forward left
+static int bn_prepare(const Run& r, int i, const float* craw, int fused) {
+  const int C = r.p.geom[i].Co;
+  const long M = r.rows(i);
+  StatCtx sc = stat_ctx(M, C);
+  if (fused) {
+    sc.nchunk = fused;
+  } else if (r.d->training) {
+    hipLaunchKernelGGL(col_reduce<0>, dim3(sc.nchunk), dim3(256), 0, r.s, craw, NOF, NOF, NOF, NOF, M, C, sc.rows_per_chunk, r.part());
   }
-  hipLaunchKernelGGL(bn_finalize, dim3(cdiv(C, FIN_CH)), dim3(256), 0, s, sc.part, sc.nchunk, M, C, prm->bn_w[i], prm->bn_b[i],
-                     prm->bn_rm[i], prm->bn_rv[i], d->training, d->momentum, d->eps, ws + p->bn_scale + i * MAXC,
-                     ws + p->bn_shift + i * MAXC, ws + p->bn_mean + i * MAXC, ws + p->bn_invstd + i * MAXC);
+  const BnSlots bn = r.bn(i);
+  hipLaunchKernelGGL(bn_finalize, dim3(cdiv(C, FIN_CH)), dim3(256), 0, r.s, r.part(), sc.nchunk, M, C, r.prm->bn_w[i], r.prm->bn_b[i],
+                     r.prm->bn_rm[i], r.prm->bn_rv[i], r.d->training, r.d->momentum, r.d->eps, bn.scale, bn.shift, bn.mean, bn.invstd);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+// forward of conv i and its BatchNorm's statistics: y = conv(x), then slots i.  Whether the convolution's epilogue leaves the
+// statistics' partial sums is decided here, once, for both launches.  (The stem is fp32 on either data path.)
+static int conv_bn(const Run& r, int i, const float* x, float* y) {
+  const bool b16 = i > 0 && native_bf16();
+  const int fused = fused_chunks(r, i, b16);
+  const float* wf = r.at(b16 ? r.p.wf16[i] : r.p.wf[i]);
+  if (const int rc = conv_fwd(b16, x, wf, y, r.p.geom[i], r.s, r.at(r.p.slab), fused ? r.part() : nullptr)) return rc;
+  return bn_prepare(r, i, y, fused);
+}
+
+// BatchNorm backward of conv i:  dx = BN'(xraw; dy masked by the ReLU behind this BatchNorm).  Which mask, and what else is
+// read or written, is said by name:
+struct BnBwd {
+  bool own_relu = false;         // the output went straight through a ReLU (a block's first BN): the mask is rebuilt from xraw with
+                                 // the forward's saved scale / shift (ymask and qmask are not read)
+  const float* ymask = nullptr;  // else: the post-ReLU activation whose sign is the mask (null: none, the stem's pool backward applied it)
+  const unsigned char* qmask = nullptr;   // ymask as one byte per quad, written by bn_act.  The apply kernel reads it instead of ymask
+                                 // (32.5 -> 28.2 us); the column reduction keeps the float activation -- with byte loads it got 9 % SLOWER
+  bool out16 = false;            // the bf16 data path: dx is stored as bf16, and qmask serves BOTH passes (the activation is bf16 there)
+  float* gout = nullptr;         // also write the masked dy here (a block's identity branch)
+  int reduced_chunks = 0;        // > 0: the producer of dy left the column sums in the partial-sum buffer, in that many chunks
+};
+static int bn_backward(const Run& r, int i, const float* xraw, const float* dy, float* dx, const BnBwd& o) {
+  const int C = r.p.geom[i].Co;
+  const long M = r.rows(i);
+  StatCtx sc = stat_ctx(M, C);
+  const BnSlots bn = r.bn(i);
+  const float* msc = o.own_relu ? bn.scale : NOF;
+  const float* msh = o.own_relu ? bn.shift : NOF;
+  const float* ymask = o.own_relu ? NOF : o.ymask;
+  const bool qred = o.out16 && o.qmask != nullptr;
+  if (o.reduced_chunks > 0)
+    sc.nchunk = o.reduced_chunks;
+  else
+    hipLaunchKernelGGL(col_reduce<1>, dim3(sc.nchunk), dim3(256), 0, r.s, xraw, dy, qred ? NOF : ymask,
+                       bn.mean, bn.invstd, M, C, sc.rows_per_chunk, r.part(), msc, msh, qred ? o.qmask : (const unsigned char*)nullptr);
+  hipLaunchKernelGGL(bn_bwd_finalize, dim3(cdiv(C, FIN_CH)), dim3(256), 0, r.s, r.part(), sc.nchunk, M, C, r.prm->bn_w[i],
+                     bn.invstd, r.d->training, r.g->bn_w[i], r.g->bn_b[i], r.at(r.p.coef));
+  const long nq = M * C / 4;
+  auto apply = o.out16 ? bn_bwd_apply<true> : bn_bwd_apply<false>;
+  hipLaunchKernelGGL(apply, dim3(ew_grid(nq)), dim3(256), 0, r.s, xraw, dy, o.qmask ? NOF : ymask,
+                     bn.mean, bn.invstd, r.at(r.p.coef), dx, o.gout, nq, C, msc, msh, o.qmask);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
 
-// BatchNorm backward of conv i:  dx = BN'(x_raw; dy masked by ymask>0); optional gout = masked dy
-// own_relu: this BatchNorm's output went straight through a ReLU (the first BN of a block): the mask is rebuilt from xraw
-// with the forward's saved scale / shift instead of reading the activation (ymask is then ignored)
-static int bn_backward(Plan* p, float* ws, int i, const float* xraw, const float* dy, const float* ymask, float* dx,
-                       float* gout, long M, const avvad_trunk_params* prm, const avvad_trunk_grads* g,
-                       const avvad_trunk_desc* d, hipStream_t s, bool own_relu = false, const unsigned char* qmask = nullptr,
-                       bool out16 = false, int reduced_chunks = 0) {
-  // reduced_chunks > 0: the column sums are already in the partial-sum buffer (that many chunks), written by the producer of dy
-  // out16 (the bf16 data path): dx is stored as bf16, and the block output's ReLU mask comes from the byte mask in BOTH
-  // passes (the activation itself is bf16 there)
-  const int C = p->conv[i].cout;
-  StatCtx sc = stat_ctx(p, ws, M, C);
-  const float* mean = ws + p->bn_mean + i * MAXC;
-  const float* invstd = ws + p->bn_invstd + i * MAXC;
-  const float* msc = own_relu ? ws + p->bn_scale + i * MAXC : (const float*)nullptr;
-  const float* msh = own_relu ? ws + p->bn_shift + i * MAXC : (const float*)nullptr;
-  // qmask: the block output's ReLU mask as one byte per quad, written by bn_act.  The apply kernel reads it instead of the
-  // activation (32.5 -> 28.2 us); the column reduction keeps the float activation -- with byte loads it got 9 % SLOWER.
-  if (own_relu) ymask = nullptr;
-  const bool qred = out16 && qmask != nullptr;
-  if (reduced_chunks > 0)
-    sc.nchunk = reduced_chunks;
-  else
-    hipLaunchKernelGGL(col_reduce<1>, dim3(sc.nchunk), dim3(256), 0, s, xraw, dy, qred ? (const float*)nullptr : ymask, mean, invstd, M, C,
-                       sc.rows_per_chunk, sc.part, msc, msh, qred ? qmask : (const unsigned char*)nullptr);
-  hipLaunchKernelGGL(bn_bwd_finalize, dim3(cdiv(C, FIN_CH)), dim3(256), 0, s, sc.part, sc.nchunk, M, C, prm->bn_w[i], invstd,
-                     d->training, g->bn_w[i], g->bn_b[i], ws + p->coef);
-  const long nq = M * C / 4;
-  auto apply = out16 ? bn_bwd_apply<true> : bn_bwd_apply<false>;
-  hipLaunchKernelGGL(apply, dim3(ew_grid(nq)), dim3(256), 0, s, xraw, dy, qmask ? (const float*)nullptr : ymask, mean, invstd,
-                     ws + p->coef, dx, gout, nq, C, msc, msh, qmask);
-  AVVAD_LAUNCH_CHECK();
-  return AVVAD_OK;
+// the part PackTab and UnpackTab share: every convolution's shape and its first workgroup (one per 32 x 32 channel tile; the
+// stem's elements go 256 to a workgroup: stem_blocks).  -> the grid
+template <class Tab>
+static int tab_shapes(Tab& tab, const Plan& p, int stem_blocks) {
+  int nb = 0;
+  for (int i = 0; i < NCONV; ++i) {
+    const Geom& g = p.geom[i];
+    tab.cout[i] = g.Co; tab.cin[i] = g.C; tab.ks[i] = g.KS; tab.blk0[i] = nb;
+    nb += i == 0 ? stem_blocks : (g.Co / 32) * (g.C / 32);
+  }
+  tab.blk0[NCONV] = nb; return nb;
 }
 
 }  // namespace
@@ -1139,107 +1173,84 @@ extern "C" int avvad_conv2d_wgrad_bf16(const void* x16, const void* dy16, float*
 }
 
 extern "C" size_t avvad_trunk_workspace(const avvad_trunk_desc* d) {
-  if (!d || d->N <= 0 || d->H < 32 || d->W < 32) return 0;
-  Plan p;
-  make_plan(d, &p);
+  if (!trunk_desc_ok(d)) return 0;
+  const Plan p = make_plan(d);
   return p.total * sizeof(float);
 }
 
 // Where the post-ReLU activations a forward run with save_for_backward keeps in its workspace live (test support: the
 // parity tests compare their sign patterns with the oracle's to tell a flipped ReLU unit from an indexing error).
 // index 0: pooled stem output; 1 + 2k: block k's first activation (after bn1 + ReLU); 2 + 2k: block k's output. NHWC.
-// index 17: the pool's arg-max plane (N * H * W * 16 32-bit words, byte k of word q: window position dh*3+dw of channel 4q+k).
+// the last index, 17: the pool's arg-max plane (N * H * W * 16 32-bit words, byte k of word q: window position dh*3+dw of channel 4q+k).
 extern "C" int avvad_trunk_activation(const avvad_trunk_desc* d, int index, size_t* offset_floats, int* C, int* H, int* W) {
-  if (!d || d->N <= 0 || d->H < 32 || d->W < 32 || index < 0 || index > 17 || !offset_floats || !C || !H || !W) return AVVAD_EINVAL;
-  if (index == 17 && !d->save_for_backward) return AVVAD_EINVAL;     // (the plane is written only for a backward)
-  Plan p;
-  make_plan(d, &p);
-  const int widths[4] = {64, 128, 256, 512};
-  if (index == 0) { *offset_floats = p.p0; *C = 64; *H = p.h[2]; *W = p.w[2]; return AVVAD_OK; }
-  if (index == 17) { *offset_floats = p.am; *C = 64; *H = p.h[2]; *W = p.w[2]; return AVVAD_OK; }
-  const int k = (index - 1) / 2, st = k / 2;
-  *offset_floats = p.blk[k][(index - 1) % 2 == 0 ? 1 : 4];
-  *C = widths[st]; *H = p.h[st + 2]; *W = p.w[st + 2];
+  constexpr int ARGMAX = 1 + 2 * NBLOCK;
+  if (!trunk_desc_ok(d) || index < 0 || index > ARGMAX || !offset_floats || !C || !H || !W) return AVVAD_EINVAL;
+  if (index == ARGMAX && !d->save_for_backward) return AVVAD_EINVAL;     // (the plane is written only for a backward)
+  const Plan p = make_plan(d);
+  if (index == 0 || index == ARGMAX) {
+    *offset_floats = index == 0 ? p.p0 : p.am; *C = 64; *H = p.h[2]; *W = p.w[2];
+    return AVVAD_OK;
+  }
+  const Block& k = p.block[(index - 1) / 2];
+  *offset_floats = (index - 1) % 2 == 0 ? k.a1 : k.out;
+  *C = k.width; *H = k.h; *W = k.w;
   return AVVAD_OK;
 }
 
 extern "C" int avvad_trunk_fwd(const float* frames, const avvad_trunk_params* prm, float* feat, const avvad_trunk_desc* d,
                                void* wsv, size_t ws_bytes, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!frames || !prm || !feat || !d || !wsv || ws_misaligned(wsv) || d->N <= 0 || d->H < 32 || d->W < 32) return AVVAD_EINVAL;
-  hipStream_t s = (hipStream_t)sv;
-  Plan p;
-  make_plan(d, &p);
+  if (!frames || !prm || !feat || !wsv || ws_misaligned(wsv) || !trunk_desc_ok(d)) return AVVAD_EINVAL;
+  const Plan p = make_plan(d);
   if (ws_bytes < p.total * sizeof(float)) return AVVAD_EWORKSPACE;
-  float* ws = (float*)wsv;
-  int rc;
+  const Run r{p, (float*)wsv, prm, nullptr, d, (hipStream_t)sv};
+  hipStream_t s = r.s; int rc;
   const bool b16 = native_bf16();        // the bf16 data path: activations between convolutions are stored as bf16
+  const bool save = d->save_for_backward;
   // weights: OIHW -> packed
-  {
-    PackTab tab;
-    int nb = 0;
-    for (int i = 0; i < NCONV; ++i) {
-      const ConvSpec& c = p.conv[i];
-      tab.w[i] = prm->conv_w[i];
-      tab.wf[i] = ws + p.wf[i];
-      tab.wd[i] = (i > 0 && d->save_for_backward) ? ws + p.wd[i] : (float*)nullptr;
-      tab.wf16[i] = (b16 && i > 0) ? reinterpret_cast<__bf16*>(ws + p.wf16[i]) : (__bf16*)nullptr;
-      tab.wd16[i] = (b16 && i > 0 && d->save_for_backward) ? reinterpret_cast<__bf16*>(ws + p.wd16[i]) : (__bf16*)nullptr;
-      tab.cout[i] = c.cout; tab.cin[i] = c.cin; tab.ks[i] = c.ks;
-      tab.blk0[i] = nb;
-      nb += i == 0 ? cdiv(64 * 49, 256) : (c.cout / 32) * (c.cin / 32);
-    }
-    tab.blk0[NCONV] = nb;
-    hipLaunchKernelGGL(pack_all, dim3(nb), dim3(256), 0, s, tab);
+  PackTab tab;
+  const int nb = tab_shapes(tab, p, cdiv(64 * 49, 256));
+  for (int i = 0; i < NCONV; ++i) {
+    tab.w[i] = prm->conv_w[i];
+    tab.wf[i] = r.at(p.wf[i]);
+    tab.wd[i] = (i > 0 && save) ? r.at(p.wd[i]) : nullptr;
+    tab.wf16[i] = (b16 && i > 0) ? reinterpret_cast<__bf16*>(r.at(p.wf16[i])) : nullptr;
+    tab.wd16[i] = (b16 && i > 0 && save) ? reinterpret_cast<__bf16*>(r.at(p.wd16[i])) : nullptr;
   }
+  hipLaunchKernelGGL(pack_all, dim3(nb), dim3(256), 0, s, tab);
   // stem
-  const long N = d->N;
-  if ((rc = conv_fwd(false, frames, ws + p.wf[0], ws + p.c0, p.geom[0], s, ws + p.slab, fused_stat(&p, ws, 0, d)))) return rc;
-  const long M0 = N * p.h[1] * p.w[1];
-  if ((rc = bn_prepare(&p, ws, 0, ws + p.c0, M0, prm, d, s))) return rc;
-  {
-    unsigned* am = d->save_for_backward ? reinterpret_cast<unsigned*>(ws + p.am) : (unsigned*)nullptr;
-    auto pool = b16 ? stem_bn_relu_pool<true> : stem_bn_relu_pool<false>;
-    hipLaunchKernelGGL(pool, dim3(ew_grid(N * p.h[2] * p.w[2] * 16)), dim3(256), 0, s, ws + p.c0, ws + p.bn_scale, ws + p.bn_shift,
-                       ws + p.p0, am, d->N, p.h[1], p.w[1], p.h[2], p.w[2]);
-  }
-  const size_t* wf = b16 ? p.wf16 : p.wf;      // the data path's forward packs
+  if ((rc = conv_bn(r, 0, frames, r.at(p.c0)))) return rc;
+  const BnSlots bn0 = r.bn(0);
+  unsigned* am = save ? reinterpret_cast<unsigned*>(r.at(p.am)) : nullptr;
+  auto pool = b16 ? stem_bn_relu_pool<true> : stem_bn_relu_pool<false>;
+  hipLaunchKernelGGL(pool, dim3(ew_grid((long)d->N * p.h[2] * p.w[2] * 16)), dim3(256), 0, s, r.at(p.c0), bn0.scale, bn0.shift, r.at(p.p0), am,
+                     d->N, p.h[1], p.w[1], p.h[2], p.w[2]);
   // residual stages (bn_act writes bf16 on the bf16 data path; the residual it adds is bf16 there only when it is the block's input)
   auto act = b16 ? bn_act<true, false> : bn_act<false, false>;
   auto act_id = b16 ? bn_act<true, true> : bn_act<false, false>;
-  const float* x = ws + p.p0;
-  int ci = 1;
-  const int widths[4] = {64, 128, 256, 512};
-  for (int st = 0; st < 4; ++st)
-    for (int b = 0; b < 2; ++b) {
-      const int C = widths[st];
-      const size_t* o = p.blk[st * 2 + b];
-      const bool ds = (b == 0 && st > 0);
-      const long M = N * p.h[st + 2] * p.w[st + 2];
-      const long nq = M * C / 4;
-      const int i1 = ci, i2 = ci + 1, id = ci + 2;
-      unsigned char* qmo = d->save_for_backward ? reinterpret_cast<unsigned char*>(ws + p.qm[st * 2 + b]) : (unsigned char*)nullptr;
-      if ((rc = conv_fwd(b16, x, ws + wf[i1], ws + o[0], p.geom[i1], s, ws + p.slab, fused_stat(&p, ws, i1, d)))) return rc;
-      if ((rc = bn_prepare(&p, ws, i1, ws + o[0], M, prm, d, s))) return rc;
-      hipLaunchKernelGGL(act, dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[0], ws + p.bn_scale + i1 * MAXC, ws + p.bn_shift + i1 * MAXC,
-                         (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ws + o[1], nq, C, 1, (unsigned char*)nullptr);
-      if ((rc = conv_fwd(b16, ws + o[1], ws + wf[i2], ws + o[2], p.geom[i2], s, ws + p.slab, fused_stat(&p, ws, i2, d)))) return rc;
-      if ((rc = bn_prepare(&p, ws, i2, ws + o[2], M, prm, d, s))) return rc;
-      if (ds) {
-        if ((rc = conv_fwd(b16, x, ws + wf[id], ws + o[3], p.geom[id], s, ws + p.slab, fused_stat(&p, ws, id, d)))) return rc;
-        if ((rc = bn_prepare(&p, ws, id, ws + o[3], M, prm, d, s))) return rc;
-        // (the identity input is the downsample convolution's RAW fp32 output in either data path)
-        hipLaunchKernelGGL(act, dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC, ws + p.bn_shift + i2 * MAXC,
-                           ws + o[3], ws + p.bn_scale + id * MAXC, ws + p.bn_shift + id * MAXC, ws + o[4], nq, C, 1, qmo);
-      } else {
-        hipLaunchKernelGGL(act_id, dim3(ew_grid(nq)), dim3(256), 0, s, ws + o[2], ws + p.bn_scale + i2 * MAXC, ws + p.bn_shift + i2 * MAXC,
-                           x, (const float*)nullptr, (const float*)nullptr, ws + o[4], nq, C, 1, qmo);
-      }
-      x = ws + o[4];
-      ci += ds ? 3 : 2;
+  for (const Block& k : p.block) {
+    const int C = k.width;
+    const long nq = k.M * C / 4;
+    const float* x = r.at(k.in);
+    unsigned char* qmo = save ? reinterpret_cast<unsigned char*>(r.at(k.qm)) : nullptr;
+    const BnSlots bn1 = r.bn(k.i1), bn2 = r.bn(k.i2);
+    if ((rc = conv_bn(r, k.i1, x, r.at(k.c1)))) return rc;
+    hipLaunchKernelGGL(act, dim3(ew_grid(nq)), dim3(256), 0, s, r.at(k.c1), bn1.scale, bn1.shift, NOF, NOF, NOF, r.at(k.a1), nq, C, 1,
+                       (unsigned char*)nullptr);
+    if ((rc = conv_bn(r, k.i2, r.at(k.a1), r.at(k.c2)))) return rc;
+    if (k.ds) {
+      if ((rc = conv_bn(r, k.id, x, r.at(k.cd)))) return rc;
+      const BnSlots bnd = r.bn(k.id);
+      // (the identity input is the downsample convolution's RAW fp32 output in either data path)
+      hipLaunchKernelGGL(act, dim3(ew_grid(nq)), dim3(256), 0, s, r.at(k.c2), bn2.scale, bn2.shift, r.at(k.cd), bnd.scale, bnd.shift,
+                         r.at(k.out), nq, C, 1, qmo);
+    } else {
+      hipLaunchKernelGGL(act_id, dim3(ew_grid(nq)), dim3(256), 0, s, r.at(k.c2), bn2.scale, bn2.shift, x, NOF, NOF, r.at(k.out), nq, C, 1, qmo);
     }
+  }
+  const Block& last = p.block[NBLOCK - 1];
   auto avg = b16 ? avgpool_fwd<true> : avgpool_fwd<false>;
-  hipLaunchKernelGGL(avg, dim3(ew_grid(N * 512)), dim3(256), 0, s, x, feat, d->N, p.h[5] * p.w[5], 512);
+  hipLaunchKernelGGL(avg, dim3(ew_grid((long)d->N * last.width)), dim3(256), 0, s, r.at(last.out), feat, d->N, last.h * last.w, last.width);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
@@ -1249,86 +1260,73 @@ extern "C" int avvad_trunk_bwd(const float* frames, const avvad_trunk_params* pr
                                avvad_stream_t sv) {
   AVVAD_ENTER();
   BwdCuCap cu_cap;
-  if (!frames || !prm || !dfeat || !g || !d || !wsv || ws_misaligned(wsv) || !d->save_for_backward) return AVVAD_EINVAL;
-  hipStream_t s = (hipStream_t)sv;
-  Plan p;
-  make_plan(d, &p);
+  if (!frames || !prm || !dfeat || !g || !wsv || ws_misaligned(wsv) || !trunk_desc_ok(d) || !d->save_for_backward) return AVVAD_EINVAL;
+  const Plan p = make_plan(d);
   if (ws_bytes < p.total * sizeof(float)) return AVVAD_EWORKSPACE;
-  float* ws = (float*)wsv;
-  int rc;
-  const long N = d->N;
-  float* G0 = ws + p.G[0];
-  float* G1 = ws + p.G[1];
-  float* G2 = ws + p.G[2];
-  float* G3 = ws + p.G[3];
+  const Run r{p, (float*)wsv, prm, g, d, (hipStream_t)sv};
+  hipStream_t s = r.s; int rc;
+  float *G0 = r.at(p.G[0]), *G1 = r.at(p.G[1]), *G2 = r.at(p.G[2]), *G3 = r.at(p.G[3]);
   // d(out of last block) from the average pool
-  hipLaunchKernelGGL(avgpool_bwd, dim3(ew_grid(N * p.h[5] * p.w[5] * 512)), dim3(256), 0, s, dfeat, G0, d->N,
-                     p.h[5] * p.w[5], 512);
+  const Block& last = p.block[NBLOCK - 1];
+  hipLaunchKernelGGL(avgpool_bwd, dim3(ew_grid(last.M * last.width)), dim3(256), 0, s, dfeat, G0, d->N, last.h * last.w, last.width);
   const bool b16 = native_bf16();        // the forward ran the bf16 data path (same process-wide option): activations,
                                          // and the BatchNorm-backward outputs that feed convolutions, are bf16
   const size_t* wd = b16 ? p.wd16 : p.wd;      // the data path's data-gradient packs
-  // (weight gradients: wanted ones only, into ws + p.wg[i], unpacked at the end by unpack_all)
-  int ci = NCONV;
-  for (int st = 3; st >= 0; --st)
-    for (int b = 1; b >= 0; --b) {
-      const bool ds = (b == 0 && st > 0);
-      ci -= ds ? 3 : 2;
-      const int i1 = ci, i2 = ci + 1, id = ci + 2;
-      const size_t* o = p.blk[st * 2 + b];
-      const float* x = (st == 0 && b == 0) ? ws + p.p0 : (b == 1 ? ws + p.blk[st * 2][4] : ws + p.blk[st * 2 - 1][4]);
-      const long M = N * p.h[st + 2] * p.w[st + 2];
-      const unsigned char* qmb = reinterpret_cast<const unsigned char*>(ws + p.qm[st * 2 + b]);
-      // G0 = d(block output, post-ReLU).  main branch: BN2 backward (mask out>0) -> d c2 in G1
-      if (ds) {
-        if ((rc = bn_backward(&p, ws, i2, ws + o[2], G0, ws + o[4], G1, nullptr, M, prm, g, d, s, false, qmb, b16))) return rc;
-        // identity branch through downsample BN + 1x1 conv: d cd in G2, d x in G3
-        if ((rc = bn_backward(&p, ws, id, ws + o[3], G0, ws + o[4], G2, nullptr, M, prm, g, d, s, false, qmb, b16))) return rc;
-        if (g->conv_w[id] && (rc = conv_wgrad(b16, x, G2, ws + p.wg[id], p.geom[id], s, ws + p.slab))) return rc;
-        if ((rc = conv_dgrad(b16, G2, ws + wd[id], G3, p.geom[id], 0, s, ws + p.slab))) return rc;
-      } else {
-        // identity branch: d x = masked d out (written to G3 by the apply kernel)
-        if ((rc = bn_backward(&p, ws, i2, ws + o[2], G0, ws + o[4], G1, G3, M, prm, g, d, s, false, qmb, b16))) return rc;
-      }
-      if (g->conv_w[i2] && (rc = conv_wgrad(b16, ws + o[1], G1, ws + p.wg[i2], p.geom[i2], s, ws + p.slab))) return rc;
-      if ((rc = conv_dgrad(b16, G1, ws + wd[i2], G2, p.geom[i2], 0, s, ws + p.slab))) return rc;  // d a1 in G2
-      if ((rc = bn_backward(&p, ws, i1, ws + o[0], G2, ws + o[1], G1, nullptr, M, prm, g, d, s, true, nullptr, b16))) return rc;  // d c1 in G1
-      if (g->conv_w[i1] && (rc = conv_wgrad(b16, x, G1, ws + p.wg[i1], p.geom[i1], s, ws + p.slab))) return rc;
-      if ((rc = conv_dgrad(b16, G1, ws + wd[i1], G3, p.geom[i1], 1, s, ws + p.slab))) return rc;  // d x += ...
-      float* t = G0; G0 = G3; G3 = t;
+  // (weight gradients: wanted ones only, into p.wg[i], unpacked at the end by unpack_all)
+  // (the stem's is fp32 on either data path)
+  auto wgrad = [&](int i, const float* x, const float* dy) {
+    return g->conv_w[i] ? conv_wgrad(i > 0 && b16, x, dy, r.at(p.wg[i]), p.geom[i], s, r.at(p.slab)) : AVVAD_OK;
+  };
+  auto dgrad = [&](int i, const float* dy, float* dx, int acc) { return conv_dgrad(b16, dy, r.at(wd[i]), dx, p.geom[i], acc, s, r.at(p.slab)); };
+  for (int kb = NBLOCK - 1; kb >= 0; --kb) {
+    const Block& k = p.block[kb];
+    const float* x = r.at(k.in);
+    // G0 = d(block output, post-ReLU).  BN2 and the downsample's BN sit under the block output's ReLU; BN1 under its own
+    BnBwd under_out, under_own;
+    under_out.ymask = r.at(k.out);
+    under_out.qmask = reinterpret_cast<const unsigned char*>(r.at(k.qm));
+    under_out.out16 = under_own.out16 = b16; under_own.own_relu = true;
+    if (k.ds) {
+      if ((rc = bn_backward(r, k.i2, r.at(k.c2), G0, G1, under_out))) return rc;           // main branch: d c2 in G1
+      if ((rc = bn_backward(r, k.id, r.at(k.cd), G0, G2, under_out))) return rc;           // identity branch, downsample BN: d cd in G2
+      if ((rc = wgrad(k.id, x, G2))) return rc;
+      if ((rc = dgrad(k.id, G2, G3, 0))) return rc;                                        // ... and its 1x1 conv: d x in G3
+    } else {
+      under_out.gout = G3;                                                                 // identity branch: d x = masked d out
+      if ((rc = bn_backward(r, k.i2, r.at(k.c2), G0, G1, under_out))) return rc;           // main branch: d c2 in G1
     }
+    if ((rc = wgrad(k.i2, r.at(k.a1), G1))) return rc;
+    if ((rc = dgrad(k.i2, G1, G2, 0))) return rc;                                        // d a1 in G2
+    if ((rc = bn_backward(r, k.i1, r.at(k.c1), G2, G1, under_own))) return rc;           // d c1 in G1
+    if ((rc = wgrad(k.i1, x, G1))) return rc;
+    if ((rc = dgrad(k.i1, G1, G3, 1))) return rc;                                        // d x += ...
+    float* t = G0; G0 = G3; G3 = t;
+  }
   // stem: G0 = d p0
   if (g->conv_w[0] || g->bn_w[0] || g->bn_b[0]) {
-    float* g0 = ws + p.g0;
+    float* g0 = r.at(p.g0);
+    const BnSlots bn0 = r.bn(0);
     // the BatchNorm backward's column sums (sum g0, sum g0 xhat) are formed here, where g0 is produced: 2048 workgroups = chunks
     const bool fuse0 = !avvad_tune().no_fused_stats;
-    int grid0 = ew_grid(N * p.h[1] * p.w[1] * 16);
+    int grid0 = ew_grid((long)d->N * p.h[1] * p.w[1] * 16);
     if (fuse0 && grid0 > 2048) grid0 = 2048;
-    hipLaunchKernelGGL(stem_pool_relu_bwd, dim3(grid0), dim3(256), 0, s, ws + p.c0,
-                       ws + p.bn_scale, ws + p.bn_shift, reinterpret_cast<const unsigned*>(ws + p.am), G0, g0, d->N, p.h[1], p.w[1],
-                       p.h[2], p.w[2], fuse0 ? ws + p.bn_mean : (const float*)nullptr, fuse0 ? ws + p.bn_invstd : (const float*)nullptr,
-                       fuse0 ? reinterpret_cast<double*>(ws + p.part) : (double*)nullptr);
-    const long M0 = N * p.h[1] * p.w[1];
-    // in place: d c0 overwrites g0
-    if ((rc = bn_backward(&p, ws, 0, ws + p.c0, g0, nullptr, g0, nullptr, M0, prm, g, d, s, false, nullptr, false, fuse0 ? grid0 : 0))) return rc;
-    if (g->conv_w[0] && (rc = conv_wgrad(false, frames, g0, ws + p.wg[0], p.geom[0], s, ws + p.slab))) return rc;   // (the stem: fp32 in either data path)
+    hipLaunchKernelGGL(stem_pool_relu_bwd, dim3(grid0), dim3(256), 0, s, r.at(p.c0), bn0.scale, bn0.shift,
+                       reinterpret_cast<const unsigned*>(r.at(p.am)), G0, g0, d->N, p.h[1], p.w[1], p.h[2], p.w[2],
+                       fuse0 ? bn0.mean : NOF, fuse0 ? bn0.invstd : NOF, fuse0 ? r.part() : (double*)nullptr);
+    // in place: d c0 overwrites g0.  No mask: the pool's backward applied the stem's ReLU
+    BnBwd stem; stem.reduced_chunks = fuse0 ? grid0 : 0;
+    if ((rc = bn_backward(r, 0, r.at(p.c0), g0, g0, stem))) return rc;
+    if ((rc = wgrad(0, frames, g0))) return rc;
   }
-  {
-    UnpackTab tab;
-    int nb = 0;
-    bool any = false;
-    for (int i = 0; i < NCONV; ++i) {
-      const ConvSpec& c = p.conv[i];
-      const bool done = g->conv_w[i] && (i > 0 || g->conv_w[0]);
-      tab.pk[i] = ws + p.wg[i];
-      tab.dw[i] = done ? g->conv_w[i] : (float*)nullptr;
-      tab.cout[i] = c.cout; tab.cin[i] = c.cin; tab.ks[i] = c.ks;
-      tab.blk0[i] = nb;
-      nb += i == 0 ? cdiv(64 * 3 * 49, 256) : (c.cout / 32) * (c.cin / 32);
-      any = any || done;
-    }
-    tab.blk0[NCONV] = nb;
-    if (any) hipLaunchKernelGGL(unpack_all, dim3(nb), dim3(256), 0, s, tab);
+  UnpackTab tab;
+  const int nb = tab_shapes(tab, p, cdiv(64 * 3 * 49, 256));
+  bool any = false;
+  for (int i = 0; i < NCONV; ++i) {
+    tab.pk[i] = r.at(p.wg[i]);
+    tab.dw[i] = g->conv_w[i];      // null: not wanted
+    any = any || g->conv_w[i];
   }
+  if (any) hipLaunchKernelGGL(unpack_all, dim3(nb), dim3(256), 0, s, tab);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }

@@ -275,6 +275,8 @@ int avvad_conv2d_dgrad_bf16(const void* dy16, const void* wd16, float* dx, const
 int avvad_conv2d_wgrad_bf16(const void* x16, const void* dy16, float* dw_packed, const avvad_conv_desc* d, void* ws,
                             size_t ws_bytes, avvad_stream_t s);
 
+/* A trunk descriptor needs N > 0 and H, W >= 32.  For any other the size query answers 0 and the three calls below
+ * AVVAD_EINVAL, before anything is computed or launched. */
 size_t avvad_trunk_workspace(const avvad_trunk_desc* d);
 /* Test support: offset (floats), channels and spatial size of the post-ReLU activation `index` that a forward run with
  * save_for_backward keeps in its workspace, NHWC.  index 0: pooled stem output; 1 + 2k: block k's first activation

@@ -100,6 +100,102 @@ def test_spectrum_workspace_queries_agree(desc):
         assert q[4] == 0 if bad[4] in (0, t_past) else q[4] < engine, bad
 
 
+# (N, H, W, save_for_backward) -> bytes of the trunk's workspace and, for activation indices 0 .. 17, what
+# avvad_trunk_activation answers: (rc, offset in floats, C, H, W), as recorded values.  Callers size their buffers by the
+# first and the parity tests read activations through the second, so a change of the layout behind them (make_plan in
+# csrc/trunk.hip) must not pass unseen.  Index 17, the pool's arg-max plane, is refused without save_for_backward (a refused
+# query leaves its outputs alone: the zeros are the test's own).
+TRUNK_WS = {
+    (1, 32, 32, 0): (180726016, [
+        (0, 45111360, 64, 8, 8), (0, 45120576, 64, 8, 8), (0, 45128768, 64, 8, 8),
+        (0, 45136960, 64, 8, 8), (0, 45145152, 64, 8, 8), (0, 45151296, 128, 4, 4),
+        (0, 45157440, 128, 4, 4), (0, 45161536, 128, 4, 4), (0, 45165632, 128, 4, 4),
+        (0, 45168704, 256, 2, 2), (0, 45171776, 256, 2, 2), (0, 45173824, 256, 2, 2),
+        (0, 45175872, 256, 2, 2), (0, 45177408, 512, 1, 1), (0, 45178944, 512, 1, 1),
+        (0, 45179968, 512, 1, 1), (0, 45180992, 512, 1, 1), (-1, 0, 0, 0, 0),
+    ]),
+    (1, 32, 32, 1): (225503744, [
+        (0, 45111360, 64, 8, 8), (0, 45120576, 64, 8, 8), (0, 45128768, 64, 8, 8),
+        (0, 45137216, 64, 8, 8), (0, 45145408, 64, 8, 8), (0, 45151808, 128, 4, 4),
+        (0, 45157952, 128, 4, 4), (0, 45162176, 128, 4, 4), (0, 45166272, 128, 4, 4),
+        (0, 45169472, 256, 2, 2), (0, 45172544, 256, 2, 2), (0, 45174656, 256, 2, 2),
+        (0, 45176704, 256, 2, 2), (0, 45178304, 512, 1, 1), (0, 45179840, 512, 1, 1),
+        (0, 45180928, 512, 1, 1), (0, 45181952, 512, 1, 1), (0, 45115456, 64, 8, 8),
+    ]),
+    (4, 67, 67, 1): (234469632, [
+        (0, 45390912, 64, 17, 17), (0, 45557376, 64, 17, 17), (0, 45705344, 64, 17, 17),
+        (0, 45857984, 64, 17, 17), (0, 46005952, 64, 17, 17), (0, 46126080, 128, 9, 9),
+        (0, 46250496, 128, 9, 9), (0, 46336064, 128, 9, 9), (0, 46419008, 128, 9, 9),
+        (0, 46488704, 256, 5, 5), (0, 46565504, 256, 5, 5), (0, 46618304, 256, 5, 5),
+        (0, 46669504, 256, 5, 5), (0, 46715136, 512, 3, 3), (0, 46770432, 512, 3, 3),
+        (0, 46808448, 512, 3, 3), (0, 46845312, 512, 3, 3), (0, 45464896, 64, 17, 17),
+    ]),
+    (6, 33, 40, 1): (229570304, [
+        (0, 45225536, 64, 9, 10), (0, 45303296, 64, 9, 10), (0, 45372416, 64, 9, 10),
+        (0, 45443712, 64, 9, 10), (0, 45512832, 64, 9, 10), (0, 45568768, 128, 5, 5),
+        (0, 45626368, 128, 5, 5), (0, 45665984, 128, 5, 5), (0, 45704384, 128, 5, 5),
+        (0, 45738624, 256, 3, 3), (0, 45780096, 256, 3, 3), (0, 45808640, 256, 3, 3),
+        (0, 45836288, 256, 3, 3), (0, 45863296, 512, 2, 2), (0, 45900160, 512, 2, 2),
+        (0, 45925504, 512, 2, 2), (0, 45950080, 512, 2, 2), (0, 45260096, 64, 9, 10),
+    ]),
+    (3, 70, 45, 0): (184025600, [
+        (0, 45249536, 64, 18, 12), (0, 45342848, 64, 18, 12), (0, 45425792, 64, 18, 12),
+        (0, 45508736, 64, 18, 12), (0, 45591680, 64, 18, 12), (0, 45653888, 128, 9, 6),
+        (0, 45716096, 128, 9, 6), (0, 45757568, 128, 9, 6), (0, 45799040, 128, 9, 6),
+        (0, 45831296, 256, 5, 3), (0, 45865856, 256, 5, 3), (0, 45888896, 256, 5, 3),
+        (0, 45911936, 256, 5, 3), (0, 45932672, 512, 3, 2), (0, 45960320, 512, 3, 2),
+        (0, 45978752, 512, 3, 2), (0, 45997184, 512, 3, 2), (-1, 0, 0, 0, 0),
+    ]),
+    (130, 35, 43, 1): (334319104, [
+        (0, 48389696, 64, 9, 11), (0, 50243008, 64, 9, 11), (0, 51890368, 64, 9, 11),
+        (0, 53589248, 64, 9, 11), (0, 55236608, 64, 9, 11), (0, 56611008, 128, 5, 6),
+        (0, 58108608, 128, 5, 6), (0, 59138240, 128, 5, 6), (0, 60136640, 128, 5, 6),
+        (0, 60966592, 256, 3, 3), (0, 61865152, 256, 3, 3), (0, 62482944, 256, 3, 3),
+        (0, 63081984, 256, 3, 3), (0, 63666496, 512, 2, 2), (0, 64465216, 512, 2, 2),
+        (0, 65014336, 512, 2, 2), (0, 65546816, 512, 2, 2), (0, 49213376, 64, 9, 11),
+    ]),
+}
+
+
+def _trunk_activation(h, d, index):
+    import ctypes as C
+    off, c, hh, ww = C.c_size_t(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = h.avvad_trunk_activation(C.byref(d), index, C.byref(off), C.byref(c), C.byref(hh), C.byref(ww))
+    return rc, off.value, c.value, hh.value, ww.value
+
+
+@pytest.mark.parametrize("desc", sorted(TRUNK_WS))
+def test_trunk_workspace_and_activation_slots_are_the_recorded_layout(desc):
+    import ctypes as C
+    from avvad import _lib as L
+    h = L.lib()
+    N, H, W, save = desc
+    d = L.TrunkDesc(N, H, W, 1, 0.1, 1e-5, save)
+    ws, slots = TRUNK_WS[desc]
+    assert h.avvad_trunk_workspace(C.byref(d)) == ws
+    assert [_trunk_activation(h, d, i) for i in range(18)] == slots
+    for i in (-1, 18):                                                    # the index bounds
+        assert _trunk_activation(h, d, i) == (-1, 0, 0, 0, 0)
+
+
+def test_trunk_entry_points_refuse_a_bad_descriptor_before_any_launch():
+    """N = 0, H = 31 and W = 31 are refused by the size queries and by forward and backward alike, with AVVAD_EINVAL and
+    before anything is computed or launched: the pointers are non-null host dummies, no GPU is needed.  (The workspace is
+    given as 0 bytes: an entry point that let the descriptor pass would answer AVVAD_EWORKSPACE, still without a launch.)"""
+    import ctypes as C
+    from avvad import _lib as L
+    h = L.lib()
+    buf = (C.c_float * 64)()
+    dummy = (C.addressof(buf) + 15) & ~15                                 # 16-byte aligned, like a workspace
+    prm, grads = L.TrunkParams(), L.TrunkGrads()
+    for (N, H, W) in ((0, 67, 67), (4, 31, 67), (4, 67, 31)):
+        d = L.TrunkDesc(N, H, W, 1, 0.1, 1e-5, 1)
+        assert h.avvad_trunk_workspace(C.byref(d)) == 0
+        assert _trunk_activation(h, d, 0) == (-1, 0, 0, 0, 0)
+        assert h.avvad_trunk_fwd(dummy, C.byref(prm), dummy, C.byref(d), dummy, 0, None) == -1
+        assert h.avvad_trunk_bwd(dummy, C.byref(prm), dummy, C.byref(grads), C.byref(d), dummy, 0, None) == -1
+
+
 def test_dropin_state_dict_keys_and_sizes():
     from packages.models.AV_Net import DeepVAD_AV
     from packages.models.Audio_Net import DeepVAD_audio
