@@ -22,8 +22,10 @@
 // cross-tile prefetch (beside another stream's kernels), flat addressing (round 1).
 // Any other (R, D, filter_width) runs generic direct kernels.
 // Weight gradients contract over (sequence, time) on the igemm engine.
+// The tail (bottleneck 1x1, ReLU, adaptive average pool) has its device code in wn_tail.h; its form choice and launchers are here.
 #include "gemm_api.h"
 #include "wn_block.h"
+#include "wn_tail.h"
 
 namespace {
 
@@ -137,58 +139,6 @@ __global__ void narrow_conv1d_grads_sum(const float* __restrict__ part, int ny, 
   else if (db) db[co] += s;
 }
 
-__device__ __forceinline__ void pool_bin(int p, int Lv, int P, int& a, int& e) {
-  a = (int)(((long)p * Lv) / P);
-  e = (int)((((long)(p + 1)) * Lv + P - 1) / P);
-}
-
-// out[b][bn][p] = mean_{t in bin p} relu(bb[bn] + sum_c Wb[bn][c] s[b][c][t])
-__global__ void __launch_bounds__(256)
-    tail_fwd_generic(const float* __restrict__ s, const float* __restrict__ wb, const float* __restrict__ bb,
-                     float* __restrict__ out, int R, int Bn, int Lv, int P) {
-  const int b = blockIdx.y, p = blockIdx.x;
-  int a, e;
-  pool_bin(p, Lv, P, a, e);
-  const float* sb = s + (long)b * R * Lv;
-  for (int bn = threadIdx.x; bn < Bn; bn += 256) {
-    const float* wr = wb + (long)bn * R;
-    const float bias = bb ? bb[bn] : 0.f;
-    float sum = 0.f;
-    for (int t = a; t < e; ++t) {
-      float z = bias;
-      for (int c = 0; c < R; ++c) z = fmaf(wr[c], sb[(long)c * Lv + t], z);
-      sum += fmaxf(z, 0.f);
-    }
-    out[((long)b * Bn + bn) * P + p] = sum / (float)(e - a);
-  }
-}
-
-// dz[b][bn][t] = (z>0) * sum_{p: t in bin p} dout[b][bn][p] / len_p
-__global__ void tail_bwd_dz_generic(const float* __restrict__ s, const float* __restrict__ wb, const float* __restrict__ bb,
-                                    const float* __restrict__ dout, float* __restrict__ dz, int B, int R, int Bn, int Lv, int P) {
-  const long n = (long)B * Bn * Lv;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int t = (int)(i % Lv);
-    const int bn = (int)((i / Lv) % Bn);
-    const int b = (int)(i / ((long)Lv * Bn));
-    float z = bb ? bb[bn] : 0.f;
-    const float* sb = s + (long)b * R * Lv + t;
-    for (int c = 0; c < R; ++c) z = fmaf(wb[(long)bn * R + c], sb[(long)c * Lv], z);
-    float g = 0.f;
-    if (z > 0.f) {
-      // the bins that contain t are exactly floor(t P / Lv) .. ceil((t + 1) P / Lv) - 1: two at the most while P <= Lv,
-      // any number beyond (Lv = 3, P = 5: sample 1 is in bins 1, 2, 3)
-      const int p0 = (int)(((long)t * P) / Lv), p1 = (int)((((long)t + 1) * P + Lv - 1) / Lv);
-      for (int p = p0; p < p1; ++p) {
-        int a, e;
-        pool_bin(p, Lv, P, a, e);
-        g += dout[((long)b * Bn + bn) * P + p] / (float)(e - a);
-      }
-    }
-    dz[i] = g;
-  }
-}
-
 // ------------------------------------------------------------------ fused MFMA residual block (R = D = 32, fw = 2)
 // The device toolkit every block kernel below stands on -- the LDS weight image and its stagers, the tile decode, the
 // ping-pong loop -- is wn_block.h; the tile walk is xcd_walk in common.h.
@@ -273,7 +223,6 @@ __global__ void __launch_bounds__(256)
     }
   }
 }
-
 
 // BUFFER-ADDRESSED forms of the same block (option "wn_flat" selects the kernel above).  On this chip the fp32
 // MFMA runs on the vector lanes: every VALU instruction costs ~4 matrix-pipe cycles whatever the occupancy (tools/lab/
@@ -751,482 +700,6 @@ __global__ void __launch_bounds__(256, 4)
   wn_block_bwd_dx_body<false>(wl, DZ, s_in, dS_out, w_dil, dS_in, B, Lin, dil);
 }
 
-// ------------------------------------------------------------------ MFMA bottleneck + ReLU + adaptive average pool (R = 32, Bn % 32 == 0)
-// One wave per (sequence, pool bin, group of NT bn-tiles).  Transposed product z^T[t][bn] = s^T . Wb^T: the
-// activation tile is the A operand (lane = time, loaded as it lies in memory), the weights the B operand, so the
-// accumulator has TIME IN ITS REGISTERS and bn on the lane: the pool is 16 register adds + one lane-half swap.
-template <int NT>
-__global__ void __launch_bounds__(256)
-    tail_fwd_mfma(const float* __restrict__ s, const float* __restrict__ wb, const float* __restrict__ bb,
-                  float* __restrict__ out, int B, int Bn, int Lv, int P) {
-  const int lane = threadIdx.x & 63;
-  const int li = lane & 31, lh = lane >> 5;
-  const int ngrp = Bn / (32 * NT);
-  const long nitems = (long)B * P * ngrp;
-  const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-  for (long item = wave0; item < nitems; item += nwaves) {
-    const int grp = (int)(item % ngrp);
-    const int p = (int)((item / ngrp) % P);
-    const int b = (int)(item / ((long)ngrp * P));
-    const int bn0 = grp * 32 * NT;
-    int a, e;
-    pool_bin(p, Lv, P, a, e);
-    float w[NT][16], bias[NT], sum[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-#pragma unroll
-      for (int k = 0; k < 16; ++k) w[n][k] = wb[(long)(bn0 + n * 32 + li) * 32 + 2 * k + lh];
-      bias[n] = bb ? bb[bn0 + n * 32 + li] : 0.f;
-      sum[n] = 0.f;
-    }
-    const float* sp = s + (long)b * 32 * Lv;
-    for (int t0 = a; t0 < e; t0 += 32) {
-      const int t = t0 + li;
-      const bool ok = t < e;
-      const int tcl = ok ? t : a;
-      float x[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) x[k] = sp[(long)(2 * k + lh) * Lv + tcl];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) x[k] = ok ? x[k] : 0.f;
-#pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) acc = mfma32(x[k], w[n][k], acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (t0 + mfma32_row(r, lh) < e) sum[n] += relu1(acc[r] + bias[n]);
-      }
-    }
-    const float inv = 1.f / (float)(e - a);
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-      const float v = sum[n] + __shfl_xor(sum[n], 32, 64);
-      if (lh == 0) out[((long)b * Bn + bn0 + n * 32 + li) * P + p] = v * inv;
-    }
-  }
-}
-
-// backward of the tail for one 32-sample tile per wave: for every bn-tile recompute z (16 MFMAs), form
-// dz = (z>0) * pooled upstream gradient (written out for the weight gradients) and accumulate
-// dS[c][t] += sum_bn Wb[bn][c] dz[bn][t] (16 MFMAs, the z accumulator tile reused in place as the B operand).
-__global__ void __launch_bounds__(256)
-    tail_bwd_mfma(const float* __restrict__ s, const float* __restrict__ wb, const float* __restrict__ bb,
-                  const float* __restrict__ dout, float* __restrict__ dzt, float* __restrict__ dS, int B, int Bn, int Lv,
-                  int P) {
-  const int lane = threadIdx.x & 63;
-  const int li = lane & 31, lh = lane >> 5;
-  const int tiles_per_seq = (Lv + 31) >> 5;
-  const long ntiles = (long)B * tiles_per_seq;
-  const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-  // the bottleneck weights (Bn x 32) are copied coalesced into padded LDS once per workgroup: the per-lane fragment
-  // pattern is a 128-byte-strided gather (32 cache lines per load instruction) that made this kernel TA-bound
-  extern __shared__ float wl[];
-  for (int i = threadIdx.x; i < Bn * 32; i += 256) wl[(i >> 5) * 33 + (i & 31)] = wb[i];
-  __syncthreads();
-  for (long tile = wave0; tile < ntiles; tile += nwaves) {
-    const int b = (int)(tile / tiles_per_seq);
-    const int t = (int)(tile - (long)b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lv;
-    const float* sp = s + (long)b * 32 * Lv + (ok ? t : 0);
-    float x[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = sp[(long)(2 * k + lh) * Lv];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = ok ? x[k] : 0.f;
-    // pool bins that contain t: P <= Lv here (tail_bwd_form), so they are bin c0 = floor(t P / Lv) and at most its successor
-    int pb[3];
-    float pc[3];
-    {
-      const int c0 = ok ? (int)(((long)t * P) / Lv) : 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int p = c0 - 1 + j;
-        int a = 0, e = 0;
-        const bool in = ok && p >= 0 && p < P;
-        if (in) pool_bin(p, Lv, P, a, e);
-        const bool hit = in && t >= a && t < e;
-        pb[j] = hit ? p : 0;
-        pc[j] = hit ? 1.f / (float)(e - a) : 0.f;
-      }
-    }
-    f32x16 accS;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accS[r] = 0.f;
-    for (int nb = 0; nb < Bn; nb += 32) {
-      float wz[16], wt[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        wz[k] = wl[(nb + li) * 33 + 2 * k + lh];                  // A[i = bn][k = c] for z
-        wt[k] = wl[(nb + mfma32_row(k, lh)) * 33 + li];            // A[i = c][k = bn] for dS
-      }
-      f32x16 accZ;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accZ[r] = bb ? bb[nb + mfma32_row(r, lh)] : 0.f;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) accZ = mfma32(wz[k], x[k], accZ);
-      float dz[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const long o = ((long)b * Bn + nb + mfma32_row(r, lh)) * P;
-        float g = 0.f;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) g = fmaf(dout[o + pb[j]], pc[j], g);   // pb is clamped to a valid bin, pc = 0 when not a member
-        dz[r] = accZ[r] > 0.f ? g : 0.f;
-        if (ok) dzt[((long)b * Bn + nb + mfma32_row(r, lh)) * Lv + t] = dz[r];
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accS = mfma32(wt[r], dz[r], accS);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if (ok) dS[((long)b * 32 + mfma32_row(r, lh)) * Lv + t] = accS[r];
-  }
-}
-
-
-// ------------------------------------------------------------------ tail backward + bottleneck weight/bias gradients in ONE pass
-// tail_bwd_mfma wrote dz_t (B x Bn x Lv: 268 MB at the bench shape) only so that a GEMM and a column sum could read it
-// back for dW_b = dz_t . s^T and db = sum_t dz_t: 800 MB of traffic for 8 K numbers.  Here each dz tile goes from the
-// accumulator through a per-wave 32x33 LDS transpose straight into NBT resident 32x32 weight-gradient accumulators
-// (dW_b[bn][c], one per 32-row bn tile), with the s tile transposed once per time tile; dz_t is never written.
-// Partial sums leave through per-workgroup slabs + a fixed-order reduce, like the residual blocks' gradients.
-template <int NBT>   // Bn / 32
-__global__ void __launch_bounds__(256)
-    tail_bwd_wgrad_mfma(const float* __restrict__ s, const float* __restrict__ wb, const float* __restrict__ bb,
-                        const float* __restrict__ dout, float* __restrict__ dS, float* __restrict__ slab, int B, int Lv, int P) {
-  constexpr int Bn = NBT * 32;
-  constexpr int SLAB = Bn * 32 + Bn;
-  extern __shared__ float dyn[];
-  float* wl = dyn;                       // Bn x 33 padded weights
-  float* red = dyn + Bn * 33;            // SLAB partial sums of this workgroup
-  float* tiles = red + SLAB;             // 4 waves x 2 transpose tiles of 32 x 33
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int tiles_per_seq = (Lv + 31) >> 5;
-  const long ntiles = (long)B * tiles_per_seq;
-  const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-  float* T0 = tiles + wave * 2 * 1056;   // s tile
-  float* T1 = T0 + 1056;                 // dz tile
-  for (int i = threadIdx.x; i < Bn * 32; i += 256) wl[(i >> 5) * 33 + (i & 31)] = wb[i];
-  for (int i = threadIdx.x; i < SLAB; i += 256) red[i] = 0.f;
-  __syncthreads();
-  f32x16 accW[NBT];
-  float bsum[NBT];
-#pragma unroll
-  for (int n = 0; n < NBT; ++n) {
-    bsum[n] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accW[n][r] = 0.f;
-  }
-  // buffer addressing (common.h): one wave per SIMD is resident, so every VALU instruction adds to the MFMA time; the flat
-  // form spent ~1150 of them per tile on the 64-bit addresses of the 384 pooled-gradient gathers alone
-  const int rowV = Lv * 4;
-  const bool single = (Lv % P) == 0;
-  for (long tile = wave0; tile < ntiles; tile += nwaves) {
-    const int b = __builtin_amdgcn_readfirstlane((int)(tile / tiles_per_seq));
-    const int t = (int)(tile - (long)b * tiles_per_seq) * 32 + li;
-    const bool ok = t < Lv;
-    const __amdgpu_buffer_rsrc_t rs = brsrc(s + (long)b * 32 * Lv, 32 * rowV);
-    const __amdgpu_buffer_rsrc_t rd = brsrc(dS + (long)b * 32 * Lv, 32 * rowV);
-    const __amdgpu_buffer_rsrc_t rg = brsrc(dout + (long)b * Bn * P, Bn * P * 4);
-    const int offs = ok ? t * 4 + lh * rowV : BUF_OOB;            // s row 2k + lh
-    const int offd = ok ? t * 4 + 4 * lh * rowV : BUF_OOB;        // dS row mfma32_row(r, lh)
-    float x[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = bload(rs, offs, 2 * k * rowV);   // 0 past the sequence
-    __builtin_amdgcn_sched_barrier(0);     // keep the 16 loads together (see wn_block_bwd_dz_wgrad_mfma)
-    int pb[3];
-    float pc[3];
-    {
-      const int c0 = ok ? (int)(((long)t * P) / Lv) : 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int p = c0 - 1 + j;
-        int a = 0, e = 0;
-        const bool in = ok && p >= 0 && p < P;
-        if (in) pool_bin(p, Lv, P, a, e);
-        const bool hit = in && t >= a && t < e;
-        pb[j] = hit ? p : 0;
-        pc[j] = hit ? 1.f / (float)(e - a) : 0.f;
-      }
-    }
-    int pbo[3];       // byte offset of (row 4 lh, bin pb[j]) inside this sequence's dout slab; the row of register r is scalar
-#pragma unroll
-    for (int j = 0; j < 3; ++j) pbo[j] = (pb[j] + 4 * lh * P) * 4;
-    // s tile -> fragment fs[q] = s[c = li][t = 2q + lh]  (B operand of the weight-gradient products)
-    float fs[16];
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) T0[(2 * k + lh) * 33 + li] = x[k];
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) fs[q] = T0[li * 33 + 2 * q + lh];
-    f32x16 accS;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accS[r] = 0.f;
-#pragma unroll
-    for (int n = 0; n < NBT; ++n) {
-      const int nb = n * 32;
-      float wz[16], wt[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        wz[k] = wl[(nb + li) * 33 + 2 * k + lh];                  // A[i = bn][k = c] for z
-        wt[k] = wl[(nb + mfma32_row(k, lh)) * 33 + li];            // A[i = c][k = bn] for dS
-      }
-      f32x16 accZ;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accZ[r] = bb ? bb[nb + mfma32_row(r, lh)] : 0.f;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) accZ = mfma32(wz[k], x[k], accZ);
-      float dz[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float g = 0.f;
-        if (single) {          // Lv % P == 0: the bins do not overlap, candidate 1 (bin t*P/Lv) is the only member
-          g = bload(rg, pbo[1], (nb + mfma32_row(r, 0)) * P * 4) * pc[1];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 3; ++j) g = fmaf(bload(rg, pbo[j], (nb + mfma32_row(r, 0)) * P * 4), pc[j], g);   // pb clamped to a valid bin, pc = 0 when not a member
-        }
-        dz[r] = accZ[r] > 0.f ? g : 0.f;                                   // (0 outside the sequence: pc = 0)
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accS = mfma32(wt[r], dz[r], accS);
-      // dz tile (rows bn, column time) -> fragment fz[q] = dz[bn = li][t = 2q + lh]
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) T1[mfma32_row(r, lh) * 33 + li] = dz[r];
-      __builtin_amdgcn_wave_barrier();
-      float fz[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) { fz[q] = T1[li * 33 + 2 * q + lh]; bsum[n] += fz[q]; }
-#pragma unroll
-      for (int q = 0; q < 16; ++q) accW[n] = mfma32(fz[q], fs[q], accW[n]);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bstore(accS[r], rd, offd, mfma32_row(r, 0) * rowV);
-  }
-  // the four waves' sums meet in LDS in WAVE ORDER (plain adds between barriers, not LDS atomics in arrival order)
-  for (int w = 0; w < 4; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int n = 0; n < NBT; ++n) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[(n * 32 + mfma32_row(r, lh)) * 32 + li] += accW[n][r];
-      }
-      if (lh == 0) {
-#pragma unroll
-        for (int n = 0; n < NBT; ++n) red[Bn * 32 + n * 32 + li] += bsum[n];
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (lh == 1) {
-#pragma unroll
-        for (int n = 0; n < NBT; ++n) red[Bn * 32 + n * 32 + li] += bsum[n];
-      }
-    }
-  }
-  __syncthreads();
-  float* out = slab + (long)blockIdx.x * SLAB;
-  for (int i = threadIdx.x; i < SLAB; i += 256) out[i] = red[i];
-}
-
-// The same pass with TWO waves per time tile (8 waves per workgroup, two per SIMD).  The kernel above keeps all Bn / 32 = 8
-// weight-gradient accumulators in one wave: 416 registers, one wave per SIMD, and its chain -- load, MFMA, LDS transpose, MFMA --
-// runs at a quarter of the matrix rate (310 us for 12.9 GFLOP at the bench shape).  Here waves 2p and 2p + 1 share tile after
-// tile: each takes HALF of the bottleneck rows (four 32-row tiles: z, dz, its four weight-gradient accumulators) and a partial
-// sum of d s over them; wave 2p + 1 hands its partial through LDS to wave 2p, which adds (fixed order) and stores.  Half the
-// registers per wave, twice the waves: the chains of two waves interleave on every SIMD.
-template <int NBT>   // Bn / 32 (even)
-__global__ void __launch_bounds__(512, 2)
-    tail_bwd_wgrad_pair(const float* __restrict__ s, const float* __restrict__ wb, const float* __restrict__ bb,
-                        const float* __restrict__ dout, float* __restrict__ dS, float* __restrict__ slab, int B, int Lv, int P) {
-  constexpr int Bn = NBT * 32, NH = NBT / 2;
-  constexpr int SLAB = Bn * 32 + Bn;
-  extern __shared__ float dyn[];
-  float* wl = dyn;                       // Bn x 33 padded weights
-  float* red = dyn + Bn * 33;            // SLAB partial sums of this workgroup
-  float* tiles = red + SLAB;             // 8 waves x 2 transpose tiles of 32 x 33
-  float* psum = tiles + 8 * 2 * 1056;    // 4 pairs x one 32 x 33 tile: the odd wave's partial d s
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int pair = wave >> 1, half = wave & 1;
-  const int tiles_per_seq = (Lv + 31) >> 5;
-  const long ntiles = (long)B * tiles_per_seq;
-  const long npairs = (long)gridDim.x * 4;
-  float* T0 = tiles + wave * 2 * 1056;   // s tile
-  float* T1 = T0 + 1056;                 // dz tile
-  float* PS = psum + pair * 1056;
-  for (int i = threadIdx.x; i < Bn * 32; i += 512) wl[(i >> 5) * 33 + (i & 31)] = wb[i];
-  for (int i = threadIdx.x; i < SLAB; i += 512) red[i] = 0.f;
-  __syncthreads();
-  f32x16 accW[NH];
-  float bsum[NH];
-#pragma unroll
-  for (int n = 0; n < NH; ++n) {
-    bsum[n] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accW[n][r] = 0.f;
-  }
-  const int rowV = Lv * 4;
-  const bool single = (Lv % P) == 0;
-  // every pair of the workgroup runs the same number of rounds (the barriers below are workgroup barriers)
-  const long rounds = (ntiles + npairs - 1) / npairs;
-  for (long rd_ = 0; rd_ < rounds; ++rd_) {
-    const long tile = rd_ * npairs + (long)blockIdx.x * 4 + pair;
-    const bool live = tile < ntiles;
-    const int b = __builtin_amdgcn_readfirstlane((int)((live ? tile : 0) / tiles_per_seq));
-    const int t = (int)((live ? tile : 0) - (long)b * tiles_per_seq) * 32 + li;
-    const bool ok = live && t < Lv;
-    const __amdgpu_buffer_rsrc_t rs = brsrc(s + (long)b * 32 * Lv, 32 * rowV);
-    const __amdgpu_buffer_rsrc_t rd = brsrc(dS + (long)b * 32 * Lv, 32 * rowV);
-    const __amdgpu_buffer_rsrc_t rg = brsrc(dout + (long)b * Bn * P, Bn * P * 4);
-    const int offs = ok ? t * 4 + lh * rowV : BUF_OOB;            // s row 2k + lh
-    const int offd = ok ? t * 4 + 4 * lh * rowV : BUF_OOB;        // dS row mfma32_row(r, lh)
-    float x[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = bload(rs, offs, 2 * k * rowV);   // 0 past the sequence
-    __builtin_amdgcn_sched_barrier(0);
-    int pb[3];
-    float pc[3];
-    {
-      const int c0 = ok ? (int)(((long)t * P) / Lv) : 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int p = c0 - 1 + j;
-        int a = 0, e = 0;
-        const bool in = ok && p >= 0 && p < P;
-        if (in) pool_bin(p, Lv, P, a, e);
-        const bool hit = in && t >= a && t < e;
-        pb[j] = hit ? p : 0;
-        pc[j] = hit ? 1.f / (float)(e - a) : 0.f;
-      }
-    }
-    int pbo[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) pbo[j] = (pb[j] + 4 * lh * P) * 4;
-    float fs[16];
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) T0[(2 * k + lh) * 33 + li] = x[k];
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) fs[q] = T0[li * 33 + 2 * q + lh];
-    f32x16 accS;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accS[r] = 0.f;
-#pragma unroll
-    for (int n = 0; n < NH; ++n) {
-      const int nb = (half * NH + n) * 32;
-      f32x16 accZ;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accZ[r] = bb ? bb[nb + mfma32_row(r, lh)] : 0.f;
-      {
-        float wz[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) wz[k] = wl[(nb + li) * 33 + 2 * k + lh];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) accZ = mfma32(wz[k], x[k], accZ);
-      }
-      __builtin_amdgcn_sched_barrier(0);      // (phase by phase: hoisted, the next phases' operands spill)
-      float dz[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float g = 0.f;
-        if (single) {
-          g = bload(rg, pbo[1], (nb + mfma32_row(r, 0)) * P * 4) * pc[1];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 3; ++j) g = fmaf(bload(rg, pbo[j], (nb + mfma32_row(r, 0)) * P * 4), pc[j], g);
-        }
-        dz[r] = accZ[r] > 0.f ? g : 0.f;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      {
-        float wt[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) wt[k] = wl[(nb + mfma32_row(k, lh)) * 33 + li];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accS = mfma32(wt[r], dz[r], accS);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) T1[mfma32_row(r, lh) * 33 + li] = dz[r];
-      __builtin_amdgcn_wave_barrier();
-      float fz[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) { fz[q] = T1[li * 33 + 2 * q + lh]; bsum[n] += fz[q]; }
-#pragma unroll
-      for (int q = 0; q < 16; ++q) accW[n] = mfma32(fz[q], fs[q], accW[n]);
-    }
-    // d s = (rows of the first half) + (rows of the second half): the odd wave's partial crosses LDS, the even wave adds and stores
-    if (half == 1) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) PS[mfma32_row(r, lh) * 33 + li] = accS[r];
-    }
-    __syncthreads();
-    if (half == 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bstore(accS[r] + PS[mfma32_row(r, lh) * 33 + li], rd, offd, mfma32_row(r, 0) * rowV);
-    }
-    __syncthreads();                     // (PS is free for the next round)
-  }
-  // the eight waves' sums meet in LDS in WAVE ORDER (plain adds between barriers)
-  for (int w = 0; w < 8; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int n = 0; n < NH; ++n) {
-        const int nt = half * NH + n;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[(nt * 32 + mfma32_row(r, lh)) * 32 + li] += accW[n][r];
-      }
-      if (lh == 0) {
-#pragma unroll
-        for (int n = 0; n < NH; ++n) red[Bn * 32 + (half * NH + n) * 32 + li] += bsum[n];
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (lh == 1) {
-#pragma unroll
-        for (int n = 0; n < NH; ++n) red[Bn * 32 + (half * NH + n) * 32 + li] += bsum[n];
-      }
-    }
-  }
-  __syncthreads();
-  float* out = slab + (long)blockIdx.x * SLAB;
-  for (int i = threadIdx.x; i < SLAB; i += 512) out[i] = red[i];
-}
-
-// dW_b[bn][c] += sum_blocks slab[bn*32 + c]; db[bn] += slab[Bn*32 + bn]   -- fixed order: 32 elements x 8 slab groups per
-// workgroup, ascending slabs inside a group, the groups combined in LDS in order (no atomics, see wn_wgrad_reduce_all)
-__global__ void __launch_bounds__(256)
-    tail_wgrad_reduce(const float* __restrict__ slab, int nslab, int Bn, float* __restrict__ dW, float* __restrict__ db) {
-  __shared__ float sm[8][32];
-  const int n = Bn * 32 + Bn;
-  const int el = threadIdx.x & 31, grp = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + el;
-  float sum = 0.f;
-  if (i < n) {
-#pragma unroll 4
-    for (int b = grp; b < nslab; b += 8) sum += slab[(long)b * n + i];
-  }
-  sm[grp][el] = sum;
-  __syncthreads();
-  if (grp != 0 || i >= n) return;
-#pragma unroll
-  for (int k = 1; k < 8; ++k) sum += sm[k][el];
-  if (i < Bn * 32) { if (dW) dW[i] += sum; }
-  else if (db) db[i - Bn * 32] += sum;
-}
-
 constexpr int WG_SLAB = 3 * 1024 + 64;   // per-workgroup partial sums of wn_block_wgrad_mfma
 constexpr int WG_MAXBLK = 512;
 
@@ -1661,10 +1134,9 @@ __global__ void __launch_bounds__(256, 2)
 }
 
 // dW_dil[d][c][k] += sum_blocks slab[k*1024 + d*32 + c]; dW_dense[r][d] += slab[2048 + r*32 + d]; biases likewise.
-// ALL residual blocks in one launch behind the last of them (blockIdx.y = layer; 20 launches of ~5 us before), and in a
-// FIXED order: 32 elements x 8 slab groups per workgroup, each thread adds its group's slabs in ascending order, the eight
-// partial sums meet in LDS in group order, one thread adds the total onto the gradient.  (The per-layer version spread
-// the slabs over gridDim.y and added with float atomics: the last place where the encoder's weight gradients could
+// ALL residual blocks in one launch behind the last of them (blockIdx.y = layer; 20 launches of ~5 us before), and in the
+// FIXED order of slab_sum_fixed_order (wn_tail.h); one thread adds the total onto the gradient.  (The per-layer version
+// spread the slabs over gridDim.y and added with float atomics: the last place where the encoder's weight gradients could
 // differ in the last bit from run to run.)
 constexpr int WN_MAXL = 64;       // residual blocks one reduce launch covers
 struct WgradTab {
@@ -1676,22 +1148,11 @@ struct WgradTab {
   float* db_dense[WN_MAXL];
 };
 __global__ void __launch_bounds__(256) wn_wgrad_reduce_all(const WgradTab tab) {
-  __shared__ float sm[8][32];
   const int l = blockIdx.y;
-  const int el = threadIdx.x & 31, grp = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + el;                     // WG_SLAB = 98 * 32
+  const int i = blockIdx.x * 32 + (threadIdx.x & 31);     // WG_SLAB = 98 * 32
   const int nslab = tab.nslab[l];
-  float s = 0.f;
-  if (nslab > 0) {
-    const float* sl = tab.slab[l] + i;
-#pragma unroll 4
-    for (int b = grp; b < nslab; b += 8) s += sl[(long)b * WG_SLAB];
-  }
-  sm[grp][el] = s;
-  __syncthreads();
-  if (grp != 0 || nslab <= 0) return;
-#pragma unroll
-  for (int k = 1; k < 8; ++k) s += sm[k][el];
+  const float s = slab_sum_fixed_order(tab.slab[l] + i, nslab, WG_SLAB);
+  if (threadIdx.x >= 32 || nslab <= 0) return;
   if (i < 2048) { if (tab.dW_dil[l]) tab.dW_dil[l][(i & 1023) * 2 + (i >> 10)] += s; }   // every pointer may be NULL (frozen)
   else if (i < 3072) { if (tab.dW_dense[l]) tab.dW_dense[l][i - 2048] += s; }
   else if (i < 3104) { if (tab.db_dil[l]) tab.db_dil[l][i - 3072] += s; }
@@ -1729,9 +1190,9 @@ static int make_plan(const avvad_wavenet_desc* d, Plan* p) {
       const size_t zb = (d->R == 32 && d->D == 32 && d->fw == 2 && p->n > 0) ? take(B * d->D * p->L[1]) : 0;
       for (int i = 0; i < p->n; ++i) p->zs[i] = zb;
     }
-    {   // weight-gradient slabs: residual blocks (WG_MAXBLK x WG_SLAB) or the tail (256 workgroups x (Bn*32 + Bn))
+    {   // weight-gradient slabs: residual blocks (WG_MAXBLK x WG_SLAB) or the tail (TAIL_MAXBLK x tail_slab_floats)
       const bool perlayer = d->R == 32 && d->D == 32 && d->fw == 2;      // one slab set per residual block: ONE reduce launch
-      const size_t a = (size_t)WG_MAXBLK * WG_SLAB * (perlayer ? (size_t)p->n : 1), b2 = (size_t)256 * ((size_t)d->Bn * 33);
+      const size_t a = (size_t)WG_MAXBLK * WG_SLAB * (perlayer ? (size_t)p->n : 1), b2 = (size_t)TAIL_MAXBLK * tail_slab_floats(d->Bn);
       p->slab = take(a > b2 ? a : b2);
     }
     p->gslab = take(igemm::SLAB_FLOATS);
@@ -1760,11 +1221,13 @@ static inline bool buf_ok(int B, int Lin) {
 enum class FwdForm { FLAT, BUF, OCC, WIDE, DMA };
 enum class DxForm { FLAT, BUF, OCC };
 enum class BwdForm { RESIDENT, OCC, TRANSPOSED, UNFUSED };
+enum class TailFwdForm { GENERIC, MFMA1, MFMA4 };     // MFMAn: tail_fwd_mfma<n>, n bn-tiles per wave
 enum class TailBwdForm { PAIR, FUSED, MFMA, GENERIC };
 struct FwdChoice { FwdForm form; int grid; };
 struct DxChoice { DxForm form; int grid; };
 struct BwdChoice { BwdForm form; int grid; int grid_z, grid_dz; };   // grid: weight-gradient workgroups = slabs; UNFUSED also runs z and dz
-struct TailBwdChoice { TailBwdForm form; int grid; };
+struct TailFwdChoice { TailFwdForm form; int grid; };
+struct TailBwdChoice { TailBwdForm form; int grid; };                // PAIR, FUSED: grid = slabs
 
 // Workgroups of a persistent grid: `per_wg` tiles' worth of waves per workgroup, at most `cap` (and at most wn_grid when
 // that tuning option is set), then whole XCD groups of 8 for the XCD-aware walk.  Rounding UP leaves surplus waves that
@@ -1832,6 +1295,13 @@ static BwdChoice bwd_form(int B, int Lo, bool shared_device, bool any_grad) {
   }
 }
 
+// forward of the tail: one wave per (sequence, pool bin, group of 1 or 4 bn-tiles); GENERIC: one workgroup per (bin, sequence)
+static TailFwdChoice tail_fwd_form(int B, int R, int Bn, int P) {
+  if (!(R == 32 && Bn % 32 == 0)) return {TailFwdForm::GENERIC, 0};
+  const int nt = Bn % 128 == 0 ? 4 : 1;
+  return {nt == 4 ? TailFwdForm::MFMA4 : TailFwdForm::MFMA1, wn_grid_size((long)B * P * (Bn / (32 * nt)), 4, 2048, 0, XcdRound::NONE)};
+}
+
 // backward of the tail (bottleneck + ReLU + pool) over Lv samples per sequence.  The three MFMA forms look for the bins of
 // sample t in the three-register window c0 - 1 .. c0 + 1, c0 = floor(t P / Lv); the bins that contain t are
 // c0 .. ceil((t + 1) P / Lv) - 1, which is inside the window exactly when P <= Lv ((t + 1) P / Lv <= t P / Lv + 1).  A pool
@@ -1841,8 +1311,8 @@ static TailBwdChoice tail_bwd_form(int B, int Lv, int R, int Bn, int P, bool any
   const AvvadTune& t = avvad_tune();
   const long ntiles = (long)B * cdiv(Lv, 32);
   if (!(R == 32 && Bn % 32 == 0 && Bn <= 1024) || P > Lv) return {TailBwdForm::GENERIC, 0};
-  if (Bn == 256 && any_grad && !t.wn_no_fused_tail)        // 1 workgroup / CU is resident: one round
-    return {t.wn_no_tail_pair ? TailBwdForm::FUSED : TailBwdForm::PAIR, wn_grid_size(ntiles, 4, 256, 0, XcdRound::NONE)};
+  if (Bn == 256 && any_grad && !t.wn_no_fused_tail)        // one slab per workgroup: the plan holds TAIL_MAXBLK of them
+    return {t.wn_no_tail_pair ? TailBwdForm::FUSED : TailBwdForm::PAIR, wn_grid_size(ntiles, 4, TAIL_MAXBLK, 0, XcdRound::NONE)};
   return {TailBwdForm::MFMA, wn_grid_size(ntiles, 4, 2048, 0, XcdRound::NONE)};
 }
 
@@ -1885,6 +1355,44 @@ static void bias_grad(const float* dy, float* db, int B, int C, int L, hipStream
   hipLaunchKernelGGL(chan_sum_acc, dim3(C, 1), dim3(256), 0, s, dy, db, B, C, L);
 }
 
+// forward of the tail: out = pool(relu(bb + Wb s_N))
+static void launch_tail_fwd(const float* sN, const float* wb, const float* bb, float* out, int B, int R, int Bn, int Lv, int P,
+                            hipStream_t s) {
+  const TailFwdChoice c = tail_fwd_form(B, R, Bn, P);
+  switch (c.form) {
+    case TailFwdForm::MFMA4: hipLaunchKernelGGL(tail_fwd_mfma<4>, dim3(c.grid), dim3(256), 0, s, sN, wb, bb, out, B, Bn, Lv, P); break;
+    case TailFwdForm::MFMA1: hipLaunchKernelGGL(tail_fwd_mfma<1>, dim3(c.grid), dim3(256), 0, s, sN, wb, bb, out, B, Bn, Lv, P); break;
+    case TailFwdForm::GENERIC: hipLaunchKernelGGL(tail_fwd_generic, dim3(P, B), dim3(256), 0, s, sN, wb, bb, out, R, Bn, Lv, P); break;
+  }
+}
+
+// backward of the tail: dS = d s_N, dW / db += the bottleneck's gradients (either may be NULL); dzt, slab, gslab: workspace
+static int launch_tail_bwd(const float* sN, const float* wb, const float* bb, const float* dout, float* dW, float* db, float* dS,
+                           float* dzt, float* slab, float* gslab, int B, int R, int Bn, int Lv, int P, hipStream_t s) {
+  const TailBwdChoice c = tail_bwd_form(B, Lv, R, Bn, P, dW || db);
+  int rc;
+  if (c.form == TailBwdForm::PAIR || c.form == TailBwdForm::FUSED) {      // one pass + the slab reduce; dz_t is never materialised
+    const bool pair = c.form == TailBwdForm::PAIR;
+    const size_t lds = (size_t)tail_fused_lds_floats(Bn, pair ? 2 : 1) * sizeof(float);
+    if ((rc = pair ? allow_large_lds<tail_bwd_wgrad_pair<8>>(lds, lds) : allow_large_lds<tail_bwd_wgrad_mfma<8>>(lds, lds))) return rc;
+    hipLaunchKernelGGL(pair ? tail_bwd_wgrad_pair<8> : tail_bwd_wgrad_mfma<8>, dim3(c.grid), dim3(pair ? 512 : 256), lds, s, sN, wb,
+                       bb, dout, dS, slab, B, Lv, P);
+    hipLaunchKernelGGL(tail_wgrad_reduce, dim3(cdiv(tail_slab_floats(Bn), 32)), dim3(256), 0, s, slab, c.grid, Bn, dW, db);
+    return AVVAD_OK;
+  }
+  if (c.form == TailBwdForm::MFMA)
+    hipLaunchKernelGGL(tail_bwd_mfma, dim3(c.grid), dim3(256), (size_t)tail_wimg_floats(Bn) * sizeof(float), s, sN, wb, bb, dout,
+                       dzt, dS, B, Bn, Lv, P);
+  else
+    hipLaunchKernelGGL(tail_bwd_dz_generic, dim3(grid1((long)B * Bn * Lv)), dim3(256), 0, s, sN, wb, bb, dout, dzt, B, R, Bn, Lv, P);
+  if (dW && (rc = wgrad_conv1d(dzt, sN, dW, B, Bn, R, Lv, Lv, 1, 1, 0, s, gslab))) return rc;
+  bias_grad(dzt, db, B, Bn, Lv, s);
+  if (c.form == TailBwdForm::GENERIC)
+    hipLaunchKernelGGL(conv1d_bwd_data_generic, dim3(grid1((long)B * R * Lv)), dim3(256), 0, s, dzt, wb, (const float*)nullptr,
+                       (const float*)nullptr, dS, B, R, Bn, Lv, Lv, 1, 1, 0, 0);
+  return AVVAD_OK;
+}
+
 }  // namespace
 
 extern "C" size_t avvad_wavenet_workspace(const avvad_wavenet_desc* d) {
@@ -1921,21 +1429,8 @@ extern "C" int avvad_wavenet_fwd(const float* wave, const avvad_wavenet_params* 
                          ws + p.s[i], ws + p.s[i + 1], B, D, R, p.L[i + 1], p.L[i + 1], 1, 1, 1, p.L[i] - p.L[i + 1], p.L[i]);
     }
   }
-  const float* bbp = d->use_bias ? prm->bott_b : (const float*)nullptr;
-  if (R == 32 && d->Bn % 32 == 0) {
-    const int nt = (d->Bn % 128 == 0) ? 4 : 1;
-    long blocks = ((long)B * d->P * (d->Bn / (32 * nt)) + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    if (nt == 4)
-      hipLaunchKernelGGL(tail_fwd_mfma<4>, dim3((int)blocks), dim3(256), 0, s, ws + p.s[p.n], prm->bott_w, bbp, out, B, d->Bn,
-                         p.L[p.n], d->P);
-    else
-      hipLaunchKernelGGL(tail_fwd_mfma<1>, dim3((int)blocks), dim3(256), 0, s, ws + p.s[p.n], prm->bott_w, bbp, out, B, d->Bn,
-                         p.L[p.n], d->P);
-  } else {
-    hipLaunchKernelGGL(tail_fwd_generic, dim3(d->P, B), dim3(256), 0, s, ws + p.s[p.n], prm->bott_w, bbp, out, R, d->Bn,
-                       p.L[p.n], d->P);
-  }
+  launch_tail_fwd(ws + p.s[p.n], prm->bott_w, d->use_bias ? prm->bott_b : (const float*)nullptr, out, B, R, d->Bn, p.L[p.n],
+                  d->P, s);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }
@@ -1962,51 +1457,15 @@ extern "C" int avvad_wavenet_bwd(const float* wave, const avvad_wavenet_params* 
   float* ws = (float*)wsv;
   const int B = d->B, R = d->R, D = d->D, fw = d->fw, Bn = d->Bn;
   int rc;
-  const int Lv = p.L[p.n];
   float* Z = ws + p.z;
   float* DZ = ws + p.dz;
   float* GA = ws + p.ga;  // d s_{i+1}
   float* GB = ws + p.gb;  // d s_i
-  // ---- tail: dz_t = relu'(z) * pooled-grad ; d s_N = Wb^T dz_t
-  float* DZT = ws + p.dzt;
-  const float* bbp = d->use_bias ? prm->bott_b : (const float*)nullptr;
-  const TailBwdChoice tc = tail_bwd_form(B, Lv, R, Bn, d->P, g->bott_w || (d->use_bias && g->bott_b));
-  const bool tail_fused = tc.form == TailBwdForm::PAIR || tc.form == TailBwdForm::FUSED;
-  switch (tc.form) {
-    case TailBwdForm::PAIR: {
-      // d s_N and the bottleneck's weight + bias gradients in one pass, two waves per time tile; dz_t is never materialised
-      const size_t lds = ((size_t)Bn * 33 + (size_t)Bn * 33 + 16 * 1056 + 4 * 1056) * sizeof(float);
-      if ((rc = allow_large_lds<tail_bwd_wgrad_pair<8>>(lds, lds))) return rc;
-      hipLaunchKernelGGL(tail_bwd_wgrad_pair<8>, dim3(tc.grid), dim3(512), lds, s, ws + p.s[p.n], prm->bott_w, bbp, dout, GA,
-                         ws + p.slab, B, Lv, d->P);
-      break;
-    }
-    case TailBwdForm::FUSED: {
-      const size_t lds = ((size_t)Bn * 33 + (size_t)Bn * 33 + 8 * 1056) * sizeof(float);
-      if ((rc = allow_large_lds<tail_bwd_wgrad_mfma<8>>(lds, lds))) return rc;
-      hipLaunchKernelGGL(tail_bwd_wgrad_mfma<8>, dim3(tc.grid), dim3(256), lds, s, ws + p.s[p.n], prm->bott_w, bbp, dout, GA,
-                         ws + p.slab, B, Lv, d->P);
-      break;
-    }
-    case TailBwdForm::MFMA:
-      hipLaunchKernelGGL(tail_bwd_mfma, dim3(tc.grid), dim3(256), (size_t)Bn * 33 * sizeof(float), s, ws + p.s[p.n], prm->bott_w,
-                         bbp, dout, DZT, GA, B, Bn, Lv, d->P);
-      break;
-    case TailBwdForm::GENERIC:
-      hipLaunchKernelGGL(tail_bwd_dz_generic, dim3(grid1((long)B * Bn * Lv)), dim3(256), 0, s, ws + p.s[p.n], prm->bott_w, bbp,
-                         dout, DZT, B, R, Bn, Lv, d->P);
-      break;
-  }
-  if (tail_fused) {
-    hipLaunchKernelGGL(tail_wgrad_reduce, dim3(cdiv(Bn * 33, 32)), dim3(256), 0, s, ws + p.slab, tc.grid, Bn, g->bott_w,
-                       d->use_bias ? g->bott_b : (float*)nullptr);
-  } else {
-    if (g->bott_w && (rc = wgrad_conv1d(DZT, ws + p.s[p.n], g->bott_w, B, Bn, R, Lv, Lv, 1, 1, 0, s, ws + p.gslab))) return rc;
-    if (d->use_bias) bias_grad(DZT, g->bott_b, B, Bn, Lv, s);
-  }
-  if (tc.form == TailBwdForm::GENERIC)
-    hipLaunchKernelGGL(conv1d_bwd_data_generic, dim3(grid1((long)B * R * Lv)), dim3(256), 0, s, DZT, prm->bott_w,
-                       (const float*)nullptr, (const float*)nullptr, GA, B, R, Bn, Lv, Lv, 1, 1, 0, 0);
+  // ---- tail: d s_N into GA, the bottleneck's gradients
+  if ((rc = launch_tail_bwd(ws + p.s[p.n], prm->bott_w, d->use_bias ? prm->bott_b : (const float*)nullptr, dout, g->bott_w,
+                            d->use_bias ? g->bott_b : (float*)nullptr, GA, ws + p.dzt, ws + p.slab, ws + p.gslab, B, R, Bn,
+                            p.L[p.n], d->P, s)))
+    return rc;
   // ---- residual blocks, last to first
   WgradTab wtab;
   bool any_slab = false;

@@ -165,6 +165,16 @@ def test_case_table_reaches_what_it_claims():
     assert C["T2"]["P"] == ow.W0["en_pool_kernel_size"]
     assert L("T4")[-1] == C["T4"]["P"] == 32 and C["T5"]["P"] == 1
     assert R.tail_bwd_form(32, 32, 32, 32) == "MFMA" and R.tail_bwd_form(32, 32, 32, 1) == "MFMA"
+    # T6: more time tiles than one round of the fused tail backward takes (4 per workgroup, TAIL_MAXBLK workgroups), in
+    # each of its three forms; the bins overlap, so the Lv % P shortcut is off
+    assert L("T6")[-1] == 33 and 513 * R.cdiv(33, 32) == 1026 > 4 * R.TAIL_MAXBLK and 33 % 4 != 0
+    assert R.pool_bins(33, 4) == [(0, 9), (8, 17), (16, 25), (24, 33)]
+    assert R.tail_bwd_form(33, 32, 256, 4) == "PAIR"
+    assert R.tail_bwd_form(33, 32, 256, 4, wn_no_tail_pair=1) == "FUSED"
+    assert R.tail_bwd_form(33, 32, 256, 4, wn_no_fused_tail=1) == "MFMA"
+    # the tail forward: E1 one bn-tile per wave, E8 four, E6 generic
+    assert R.tail_fwd_form(1, 32, C["E1"]["Bn"], 4) == ("<1>", 1) and R.tail_fwd_form(2, 32, C["E8"]["Bn"], 3) == ("<4>", 2)
+    assert R.tail_fwd_form(3, C["E6"]["R"], C["E6"]["Bn"], 5)[0] == "GENERIC"
     # E1r, E2 (the form cases): every layer of every case is short enough for a single int of tiles, long enough for a tile
     for name in ("E1r", "E2", "E3"):
         assert R.mfma_shape(name) and min(L(name)) >= 32

@@ -1,4 +1,4 @@
-"""The WaveNet encoder on the GPU (csrc/wavenet.hip, wn_block.h) -- forward + backward of
+"""The WaveNet encoder on the GPU (csrc/wavenet.hip, wn_block.h, wn_tail.h) -- forward + backward of
 ``packages.models.wavenet_autoencoder`` -- against the flip-aware float64 reference of tests/encoder_ref.py: every case under
 the default options, every form of the block forward, of the input gradient, of the dz + weight-gradient pass and of the tail
 backward on the cases that tell them apart, subsets of the gradients, and accumulation.  The cases, bounds and the assertion
@@ -89,11 +89,12 @@ def test_encoder_input_gradient_forms(name, dx, lib_options):
 
 @pytest.mark.parametrize("option", [None, ("wn_no_tail_pair", 1), ("wn_no_fused_tail", 1)],
                          ids=lambda o: "default" if o is None else "%s=%d" % o)
-@pytest.mark.parametrize("name", ["E2", "T1-256", "T2"])
+@pytest.mark.parametrize("name", ["E2", "T1-256", "T2", "T6"])
 def test_encoder_tail_backward_forms(name, option, lib_options):
     """Bn = 256: two waves per tile, one wave per tile, and dz_t written out for the engine.  E2 has overlapping bins with
     P <= Lv; T1-256 and T2 have P > Lv, where a sample lies in more bins than the three-register window of those forms
-    holds: whatever the options say, they must take a path that walks the full range"""
+    holds: whatever the options say, they must take a path that walks the full range.  T6 has more time tiles than one
+    round of the fused forms takes: a second round with dead pairs, a second stride step, 256 slabs to reduce"""
     if option is not None:
         lib_options(*option)
     R.check_encoder(encoder_gpu, name, tag=TAG, label="tail " + ("default" if option is None else "%s=%d" % option))
