@@ -1424,8 +1424,119 @@ def f1_from_counts(counts, eps=1e-8):
     return torch.stack([accuracy, precision, recall, f1], dim=-1)
 
 
+# --------------------------------------------------------------------------- mixing at a target SNR (csrc/mix.hip, no gradient)
+MIX_CHUNK = L.MIX_CHUNK          # samples of one energy partial of the mix (include/avvad.h AVVAD_MIX_CHUNK)
+
+
+class NoiseBank:
+    """Noise clips as ``avvad_mix`` reads them: ``data`` one flat float32 tensor on ``device`` that holds the clips back to
+    back, ``clip_off`` (int64) / ``clip_len`` (int32) device arrays, and the same numbers on the host -- ``offsets`` /
+    ``lengths``, Python lists -- for validation and for drawing starts.  ``clips``: a list of 1-D float tensors or arrays,
+    each of at least one sample."""
+
+    def __init__(self, clips, device):
+        clips = [torch.as_tensor(c).detach().to("cpu", torch.float32) for c in clips]
+        if not clips or any(c.dim() != 1 or c.numel() < 1 for c in clips):
+            raise L.AvvadError("a noise bank holds at least one clip, each a 1-D signal of at least one sample")
+        self.lengths = [int(c.numel()) for c in clips]
+        if max(self.lengths) >= 2 ** 31:
+            raise L.AvvadError("a noise clip holds fewer than 2^31 samples")
+        self.offsets = [0]
+        for n in self.lengths[:-1]:
+            self.offsets.append(self.offsets[-1] + n)
+        self.K = len(clips)
+        self.device = torch.device(device)
+        self.data = torch.cat(clips).to(self.device)
+        self.clip_off = torch.tensor(self.offsets, dtype=torch.int64).to(self.device)
+        self.clip_len = torch.tensor(self.lengths, dtype=torch.int32).to(self.device)
+
+    def __len__(self):
+        return self.K
+
+
+def mix_ratio(snr_db):
+    """The linear power ratio ``10 ** (snr_db / 10)`` ``avvad_mix`` takes, as a float64 computed on the host."""
+    import numpy as np
+    with np.errstate(over="ignore"):         # (an SNR beyond a double's range gives inf, which ``mix`` refuses)
+        return np_power10(float(snr_db) / 10.0)
+
+
+def mix(clean, lengths, bank, clip, start, snr_db, return_noise=False, return_info=False, out=None, noise_out=None):
+    """Clean speech and noise mixed at a target SNR on the GPU (avvad_mix): ``clean`` (B, L) (or (L,)) float32 rows with
+    ``lengths`` real samples each (None: L), ``bank`` a ``NoiseBank``; row b takes clip ``clip[b]`` read circularly from
+    ``start[b]`` and is scaled by ``g_b`` so that ``sum clean^2 / sum (g_b noise)^2 = 10 ** (snr_db[b] / 10)`` over the
+    row's samples.  ``clip``, ``start``, ``snr_db``: host lists or tensors of B entries (``snr_db`` may be one number),
+    validated here: ``0 <= clip < len(bank)``, ``0 <= start < `` the clip's length, a finite ``snr_db``.  Returns
+    ``noisy`` (B, L) -- ``clean + g noise``, exact zeros behind each length -- then ``noise`` (B, L), the scaled noise
+    ``g_b n``, with ``return_noise``, then ``{"gain" (B,) float32, "energies" (B, 2) float64 (speech, unscaled noise),
+    "peak" (B,) float32 = ops.peak(noisy)}`` with ``return_info``.  A row whose speech or noise segment is silent, or whose
+    length is 0, has gain 0 and ``noisy == clean``.  Nothing is peak-normalised here.  ``clean`` is read through its
+    strides; ``out`` / ``noise_out``: float32 GPU tensors of B rows of at least L unit-stride samples to write into
+    (columns from L on are left alone), e.g. column slices of wider tensors."""
+    if not isinstance(clean, torch.Tensor) or clean.dim() not in (1, 2):
+        raise L.AvvadError("clean must be a (B, L) or (L,) GPU tensor: the AV-VAD hot path has no CPU fallback")
+    if not isinstance(bank, NoiseBank):
+        raise L.AvvadError("bank must be an ops.NoiseBank")
+    B, Ls = (1, clean.shape[0]) if clean.dim() == 1 else clean.shape
+    s, ld_s = _score_rows(clean, "clean", B, Ls)
+    if bank.data.device != s.device:
+        raise L.AvvadError("the noise bank must live on the GPU of the clean batch (%s), it is on %s" % (s.device, bank.data.device))
+    lens = [Ls] * B if lengths is None else _ints(lengths, B, Ls, "lengths must hold %d values within 0..%d" % (B, Ls))
+    clips = _ints(clip, B, bank.K - 1, "clip must hold %d clip indices within 0..%d" % (B, bank.K - 1))
+    starts = _ints(start, B, None, "start must hold %d values that are not negative" % B)
+    for b, (k, st) in enumerate(zip(clips, starts)):
+        if st >= bank.lengths[k]:
+            raise L.AvvadError("start[%d] = %d lies outside clip %d of %d samples" % (b, st, k, bank.lengths[k]))
+    snr = snr_db.tolist() if isinstance(snr_db, torch.Tensor) else snr_db
+    snr = [float(snr)] * B if isinstance(snr, (int, float)) else [float(v) for v in snr]
+    if len(snr) != B or not all(math.isfinite(v) for v in snr):
+        raise L.AvvadError("snr_db must hold %d finite values" % B)
+    ratio = [mix_ratio(v) for v in snr]
+    if not all(math.isfinite(r) and r > 0.0 for r in ratio):
+        raise L.AvvadError("snr_db must stay within what a float64 power ratio can hold")
+
+    def dest(t, name, want):
+        if t is None:
+            return (torch.empty(B, Ls, dtype=torch.float32, device=s.device), Ls) if want else (None, 0)
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.device != s.device:
+            raise L.AvvadError("%s must be a float32 GPU tensor on the clean batch's device" % name)
+        t2 = t.view(1, -1) if t.dim() == 1 else t
+        if t2.dim() != 2 or t2.shape[0] != B or t2.shape[1] < Ls or t2.stride(1) != 1 or (B > 1 and t2.stride(0) < Ls):
+            raise L.AvvadError("%s must hold %d rows of at least %d unit-stride samples" % (name, B, Ls))
+        return t2[:, :Ls], (t2.stride(0) if B > 1 else Ls)
+    noisy, ld_y = dest(out, "out", True)
+    noise, ld_z = dest(noise_out, "noise_out", return_noise)
+    gain = peak_ = energies = None
+    if return_info:
+        gain = torch.empty(B, dtype=torch.float32, device=s.device)
+        peak_ = torch.empty(B, dtype=torch.float32, device=s.device)
+        energies = torch.empty(B, 2, dtype=torch.float64, device=s.device)
+    # the per-row arguments in ONE host-to-device copy: B doubles (8-byte aligned at the block's base), then 3 x B int32
+    import numpy as np
+    host = np.empty(20 * B, dtype=np.uint8)
+    host[:8 * B].view(np.float64)[:] = ratio
+    host[8 * B:].view(np.int32)[:] = lens + clips + starts
+    args = torch.from_numpy(host).to(s.device)
+    rat, idx = args[:8 * B].view(torch.float64), args[8 * B:].view(torch.int32).view(3, B)
+    ws = _ws(L.lib().avvad_mix_workspace(B, Ls), s.device)
+    L.check(L.lib().avvad_mix(L.ptr(s), ld_s, L.ptr(idx[0]), L.ptr(bank.data), bank.data.numel(), L.ptr(bank.clip_off),
+                              L.ptr(bank.clip_len), bank.K, L.ptr(idx[1]), L.ptr(idx[2]), L.ptr(rat), L.ptr(noisy), ld_y,
+                              L.ptr(noise), ld_z, L.ptr(gain), L.ptr(energies), L.ptr(peak_), B, Ls, L.ptr(ws), ws.numel() * 4,
+                              _stream()), "avvad_mix")
+    if clean.dim() == 1 and out is None:
+        noisy = noisy.view(-1)
+    if clean.dim() == 1 and noise is not None and noise_out is None:
+        noise = noise.view(-1)
+    res = (noisy,)
+    if noise is not None:
+        res += (noise,)
+    if return_info:
+        res += ({"gain": gain, "energies": energies, "peak": peak_},)
+    return res[0] if len(res) == 1 else res
+
+
 # --------------------------------------------------------------------------- training labels from clean speech (no gradient)
-_CENTER = {"reflect": 1, "constant": 2}
+_CENTER ={"reflect": 1, "constant": 2}
 
 
 def target_frames(L, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, center=False, pad_at_end=True):

@@ -8,10 +8,12 @@ reference's Python loops over the batch replaced by single fused calls, ``nn.Dat
 GPU + bucketed RCCL all-reduce, and a synthetic data source for training (the reference's HDF5 readers are out of scope,
 SURVEY.md 2.1; h5py and torchaudio are not installed in this image), (noisy, clean) wav pairs whose labels are computed
 on the GPU from the clean files (``WavPairs``, ``wav_pair_step``), or such pairs with the utterance's lip-region DCT
-coefficients, decoded to video frames on the GPU (``AVFiles``, ``av_file_step``).  On wav pairs a 513-bin mask model can
+coefficients, decoded to video frames on the GPU (``AVFiles``, ``av_file_step``).  Clean utterances can also be mixed
+with clips of a noise bank at a drawn SNR in the step itself (``CleanWavs``, ``mix_step``, ``ops.mix``).  On wav pairs a 513-bin mask model can
 be trained on the SI-SDR of its resynthesised waveform instead of the BCE (``objective="si_sdr"``, ``SiSdrObjective``).  The per-utterance evaluator of the audio network
 (``process_utt``, ``evaluate_audio_net.py:107-180``) runs the reference's whole chain on real waveforms: peak
 normalisation -> STFT -> power -> log -> crop to the label length -> standardise -> classifier -> sigmoid -> threshold."""
+import math
 import os
 import time
 
@@ -178,6 +180,12 @@ def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, ho
     lens, noisy, clean = batch
     noisy = ops.peak_normalize(noisy.to(device, non_blocking=True))
     clean = ops.peak_normalize(clean.to(device, non_blocking=True))
+    return _pair_tail(lens, noisy, clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves)
+
+
+def _pair_tail(lens, noisy, clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves, more=()):
+    """What ``wav_pair_step`` and ``mix_step`` share, from the peak-normalised noisy and clean waves on: the labels of the
+    clean wave, the features of the noisy one, the frame-count check.  ``more``: further members of the ``waves`` tuple."""
     frames, target = ops.speech_targets(clean, lens, labels, fs=fs, wlen_sec=wlen_sec, hop_percent=hop_percent, center=False,
                                         pad_at_end=True, eps=eps)
     nfft = int(wlen_sec * fs)
@@ -190,20 +198,132 @@ def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, ho
     if x.shape[1] != T:                 # the longest row's frame count on both sides (same lengths, same rule)
         raise RuntimeError("feature frames %d != label frames %d" % (x.shape[1], T))
     if waves:
-        return frames.to(device), x, target, (noisy, clean, [int(n) for n in lens])
+        return frames.to(device), x, target, (noisy, clean, [int(n) for n in lens]) + tuple(more)
     return frames.to(device), x, target
+
+
+class CleanWavs(torch.utils.data.Dataset):
+    """Clean 16 kHz utterances to be mixed with noise in the training step (``mix_step``).  ``paths``: a list of paths or
+    a text file with one path per line (blank lines and # comments skipped).  Items: (clean (L,), L)."""
+
+    def __init__(self, paths):
+        self.paths = read_path_list(paths) if isinstance(paths, str) else [str(p) for p in paths]
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        clean, fs = load_waveform(self.paths[i])
+        if fs != 16000:
+            raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (self.paths[i], fs))
+        return clean, clean.numel()
+
+    @staticmethod
+    def collate(batch):
+        """-> (sample lengths LongTensor (B,), clean (B, Lmax)), rows zero-padded."""
+        lens = [item[1] for item in batch]
+        clean = torch.zeros(len(batch), max(lens))
+        for i, (cl, n) in enumerate(batch):
+            clean[i, :n] = cl
+        return torch.LongTensor(lens), clean
+
+
+def read_path_list(path):
+    """A text file with one path per line (blank lines and # comments skipped)."""
+    with open(path) as f:
+        return [line for line in (raw.split("#", 1)[0].strip() for raw in f) if line]
+
+
+def read_noise_bank(paths, device):
+    """The noise clips of ``paths`` (a list, or a text file with one path per line) as an ``ops.NoiseBank`` on ``device``:
+    every file read with ``load_waveform``, 16 kHz enforced, not normalised (the mix sets each row's gain)."""
+    clips = []
+    for p in (read_path_list(paths) if isinstance(paths, str) else list(paths)):
+        x, fs = load_waveform(str(p))
+        if fs != 16000:
+            raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (p, fs))
+        clips.append(x)
+    return ops.NoiseBank(clips, device)
+
+
+def mix_generator(mix_seed, epoch, rank):
+    """The host generator of one pass of mixtures, seeded by (mix_seed, epoch, rank); ``epoch`` is a number or a name
+    ("valid", "stats").  The seed is the first 63 bits of a SHA-256 of the triple: the same on every machine, and no two
+    triples share a stream by arithmetic accident."""
+    import hashlib
+    key = repr((int(mix_seed), epoch if isinstance(epoch, str) else int(epoch), int(rank))).encode()
+    return torch.Generator().manual_seed(int.from_bytes(hashlib.sha256(key).digest()[:8], "little") >> 1)
+
+
+def snr_range(snr_db):
+    """(lo, hi) in dB as floats from a pair or a single number; anything but a finite range with lo <= hi is a ValueError."""
+    try:
+        lo, hi = (snr_db, snr_db) if isinstance(snr_db, (int, float)) else snr_db
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError("snr_db %r: a number or a (lo, hi) pair in dB" % (snr_db,))
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+        raise ValueError("snr_db %r: a finite (lo, hi) range in dB with lo <= hi" % (snr_db,))
+    return lo, hi
+
+
+def draw_mix(gen, lengths, bank, snr_db):
+    """One draw per row of a batch from the host generator ``gen``: a clip of ``bank`` (uniform over the clips), a start
+    within it (uniform over its samples) and an SNR uniform in ``snr_db = (lo, hi)`` dB (a single number: that SNR).
+    ``lengths``: the batch's sample lengths (their count is the batch size).  -> (clip, start, snr_db), lists of B."""
+    B = len(lengths)
+    lo, hi = snr_range(snr_db)
+    clip = torch.randint(0, bank.K, (B,), generator=gen).tolist()
+    u = torch.rand(2, B, dtype=torch.float64, generator=gen)
+    start = [min(int(float(u[0, b]) * bank.lengths[k]), bank.lengths[k] - 1) for b, k in enumerate(clip)]
+    snr = [lo + (hi - lo) * float(u[1, b]) for b in range(B)]
+    return clip, start, snr
+
+
+class MixDraw:
+    """The ``draw`` of ``mix_step`` in ``train_main``: ``seed(epoch)`` starts the pass (mix_seed, epoch, rank), every call
+    then draws one batch's (clip, start, snr_db) from it in the order the batches arrive."""
+
+    def __init__(self, bank, snr_db, mix_seed=0, rank=0):
+        self.bank, self.snr_db, self.mix_seed, self.rank = bank, snr_db, mix_seed, rank
+        self.gen = None
+
+    def seed(self, epoch):
+        self.gen = mix_generator(self.mix_seed, epoch, self.rank)
+        return self
+
+    def __call__(self, lengths):
+        if self.gen is None:
+            raise RuntimeError("MixDraw.seed(epoch) starts a pass of mixtures")
+        return draw_mix(self.gen, lengths, self.bank, self.snr_db)
+
+
+def mix_step(batch, device, labels, bank, draw, stats=None, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS, waves=False):
+    """A ``CleanWavs.collate`` batch -> what ``wav_pair_step`` returns, with a mixture made in the step in place of the noisy
+    file: the clean waves are peak-normalised, ``draw(lengths)`` gives every row a clip of ``bank``, a start and an SNR
+    in dB (``draw_mix``), ``ops.mix`` adds the noise at that SNR on the GPU, and the mixture is peak-normalised like a
+    noisy file that was read.  ``waves``: the fourth value is (peak-normalised mixture (B, L), clean (B, L), sample
+    lengths, noise (B, L)) -- the noise as it was added, ``g_b n``, on the scale of the mixture BEFORE its
+    normalisation (SI-SIR and SI-SAR do not depend on that scale)."""
+    lens, clean = batch
+    clean = ops.peak_normalize(clean.to(device, non_blocking=True))
+    n = [int(v) for v in lens]
+    clip, start, snr = draw(n)
+    mixed = ops.mix(clean, n, bank, clip, start, snr, return_noise=waves)
+    noisy, more = (mixed[0], (mixed[1],)) if waves else (mixed, ())
+    return _pair_tail(lens, ops.peak_normalize(noisy), clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves, more)
 
 
 OBJECTIVES = ("bce", "si_sdr")
 
 
-def check_objective(objective, kind, waveform, wav_pairs, y_dim=None):
-    """``objective`` "si_sdr" trains a 513-bin mask model of the audio network on wav pairs; anything else is a
-    ValueError (``y_dim`` None: not known yet)."""
+def check_objective(objective, kind, waveform, wav_pairs, y_dim=None, clean_wavs=None):
+    """``objective`` "si_sdr" trains a 513-bin mask model of the audio network on wav pairs, or on clean utterances mixed
+    with noise in the step (``clean_wavs``); anything else is a ValueError (``y_dim`` None: not known yet)."""
     if objective not in OBJECTIVES:
         raise ValueError("objective %r: one of %s" % (objective, ", ".join(OBJECTIVES)))
     if objective == "si_sdr":
-        if kind != "audio" or waveform or wav_pairs is None:
+        if kind != "audio" or waveform or (wav_pairs is None and clean_wavs is None):
             raise ValueError("objective 'si_sdr' trains the audio network on spectrograms of wav_pairs: it resynthesises "
                              "the noisy file through the model's mask")
         if y_dim is not None and y_dim != 513:
@@ -217,20 +337,24 @@ class SiSdrObjective:
     The first and last ``n_fft - hop`` samples of every utterance stay out of the loss: with ``center=False`` they divide by
     a window sum of squares that falls to 1e-10, and a masked estimate there would own it."""
 
-    def __init__(self, device, labels, stats, fs=16e3, wlen_sec=64e-3, hop_percent=0.25):
+    def __init__(self, device, labels, stats, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, step=None):
         self.device, self.labels, self.stats = device, labels, stats      # stats: a callable, read at every step
         self.fs, self.wlen_sec, self.hop_percent = fs, wlen_sec, hop_percent
         self.n_fft = int(wlen_sec * fs)
         self.hop = int(hop_percent * self.n_fft)
         self.waves = None
+        self.step = step                  # (batch, stats) -> wav_pair_step's four values (mix_step); None: wav pairs
 
     def prepare(self, batch):
-        frames, x, target, self.waves = wav_pair_step(batch, self.device, self.labels, self.stats(), self.fs, self.wlen_sec,
-                                                      self.hop_percent, waves=True)
+        if self.step is not None:
+            frames, x, target, self.waves = self.step(batch, self.stats())
+        else:
+            frames, x, target, self.waves = wav_pair_step(batch, self.device, self.labels, self.stats(), self.fs, self.wlen_sec,
+                                                          self.hop_percent, waves=True)
         return frames, x, target
 
     def loss(self, logits, y, lengths):
-        noisy, clean, lens = self.waves
+        noisy, clean, lens = self.waves[:3]
         est = ops.resynth(noisy, logits, mask_mode=2, n_fft=self.n_fft, hop=self.hop, sample_lengths=lens, pad_at_end=True, fs=self.fs)
         skip = self.n_fft - self.hop
         loss, ratios = ops.si_sdr_loss(est, clean, lens, skip, skip, return_ratios=True)
@@ -273,6 +397,30 @@ def wav_pair_stats(pairs, device, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_pe
         ops.stft_stats(acc, noisy, lens, nfft, int(hop_percent * nfft), eps=eps, pad_at_end=True, fs=fs)
     if multi:
         dist.all_reduce(acc)                 # the merge across ranks: merge_stats of the ranks' accumulators
+    mean, std = ops.finalize_stats(acc)
+    return Stats(audio_mean=mean.cpu().numpy().reshape(-1, 1), audio_std=std.cpu().numpy().reshape(-1, 1), eps=eps)
+
+
+def mix_stats(clean, bank, device, draw, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS):
+    """``wav_pair_stats`` over mixtures made on the fly: one pass over the clean utterances (``clean``: a ``CleanWavs``, a
+    list of paths or a text file of them), every batch mixed as ``mix_step`` mixes it with ``draw(lengths)`` -- a seeded
+    ``MixDraw`` makes the pass reproducible -- peak-normalised and accumulated with ``ops.stft_stats``."""
+    import torch.distributed as dist
+    if not isinstance(clean, CleanWavs):
+        clean = CleanWavs(clean)
+    multi = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
+    nfft = int(wlen_sec * fs)
+    acc = ops.stats_new(nfft // 2 + 1, device)
+    loader = torch.utils.data.DataLoader(torch.utils.data.Subset(clean, rank_shard(len(clean), rank, world)),
+                                         batch_size=batch_size, shuffle=False, collate_fn=CleanWavs.collate)
+    for lens, wave in loader:
+        n = [int(v) for v in lens]
+        clip, start, snr = draw(n)
+        noisy = ops.mix(ops.peak_normalize(wave.to(device, non_blocking=True)), n, bank, clip, start, snr)
+        ops.stft_stats(acc, ops.peak_normalize(noisy), lens, nfft, int(hop_percent * nfft), eps=eps, pad_at_end=True, fs=fs)
+    if multi:
+        dist.all_reduce(acc)
     mean, std = ops.finalize_stats(acc)
     return Stats(audio_mean=mean.cpu().numpy().reshape(-1, 1), audio_std=std.cpu().numpy().reshape(-1, 1), eps=eps)
 
@@ -435,7 +583,7 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
 
 def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_size=16, n_items=64, lr=1e-4,
                freeze_features=False, out_dir=None, stats=None, wav_pairs=None, compute_stats=False, av_files=None,
-               objective="bce"):
+               objective="bce", clean_wavs=None, noise_wavs=None, snr_db=(-5.0, 20.0), mix_seed=0):
     """The body of ``scripts/train_{audio,video,AV}_net.py``; settings come from the caller's module-level constants
     (the reference's "config system") and may be overridden by AVVAD_* environment variables.
 
@@ -453,9 +601,26 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
 
     ``objective``: "bce" (the summed masked BCE against the labels) or, with ``wav_pairs`` and a y_dim 513 head, "si_sdr":
     minus the SI-SDR of the noisy file resynthesised through sigmoid(logits) against the clean file (``SiSdrObjective``);
-    the F1 figures against the IBM label stay in the log.  AVVAD_OBJECTIVE overrides it."""
+    the F1 figures against the IBM label stay in the log.  AVVAD_OBJECTIVE overrides it.
+
+    ``clean_wavs`` + ``noise_wavs`` (audio network, spectrogram input, both objectives; instead of ``wav_pairs``): lists
+    or text files of clean utterances (``CleanWavs``) and of noise clips (``read_noise_bank``).  Every batch is mixed on
+    the GPU in the step (``mix_step``, ``ops.mix``): per row a clip, a uniform start and an SNR uniform in ``snr_db`` =
+    (lo, hi) dB, drawn on the host from a generator seeded by (``mix_seed``, epoch, rank) -- a fresh draw per epoch, the
+    same one in every run.  Validation draws from (``mix_seed``, "valid", rank) in every epoch, so its losses are
+    comparable.  ``compute_stats`` accumulates the statistics over one pass of mixtures seeded (``mix_seed``, "stats",
+    rank) (``mix_stats``)."""
     objective = os.environ.get("AVVAD_OBJECTIVE", objective)
-    check_objective(objective, kind, waveform, wav_pairs)
+    check_objective(objective, kind, waveform, wav_pairs, clean_wavs=clean_wavs)
+    if (clean_wavs is None) != (noise_wavs is None):
+        raise ValueError("clean_wavs and noise_wavs go together: the clean utterances and the noise clips they are mixed with")
+    if clean_wavs is not None:
+        if wav_pairs is not None or av_files is not None:
+            raise ValueError("give one data source: wav_pairs, av_files, or clean_wavs with noise_wavs")
+        if kind != "audio" or waveform:
+            raise ValueError("clean_wavs / noise_wavs train the audio network on spectrograms; video / AV mixing and WaveNet "
+                             "waveform training on mixtures are not supported")
+        snr_range(snr_db)                 # refuses a bad range before anything is set up
     if av_files is not None and (kind.lower() not in ("video", "av") or waveform or wav_pairs is not None):
         raise ValueError("av_files trains the video or the AV network on spectrograms and lip coefficients; give either "
                          "wav_pairs (audio) or av_files, and no WaveNet waveform input")
@@ -470,7 +635,7 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     torch.cuda.set_device(device)
     torch.manual_seed(0)
     model = make_model().to(device)
-    check_objective(objective, kind, waveform, wav_pairs, getattr(model, "y_dim", None))
+    check_objective(objective, kind, waveform, wav_pairs, getattr(model, "y_dim", None), clean_wavs=clean_wavs)
     if freeze_features:                      # train_AV_net.py:241-245
         for name, child in model.named_children():
             if name == "features":
@@ -479,8 +644,20 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     opt = FlatAdam(model.parameters(), lr=lr, betas=(0.9, 0.999))
     reducer = avd.BucketReducer(opt.params, opt.flat_grad, opt.offsets,
                                 names=[n for n, q in model.named_parameters() if q.requires_grad]) if world > 1 else None
-    prepare = loss_fn = None
-    if av_files is not None:
+    prepare = loss_fn = mixer = None
+    if clean_wavs is not None:
+        pairs = CleanWavs(clean_wavs)
+        bank = read_noise_bank(noise_wavs, device)
+        mixer = MixDraw(bank, snr_db, mix_seed, rank)
+        labels = labels_for_ydim(model.y_dim)
+        collate = CleanWavs.collate
+        ds_train = ds_valid = torch.utils.data.Subset(pairs, range(rank, len(pairs), world))
+        prepare = lambda batch: mix_step(batch, device, labels, bank, mixer, stats)   # noqa: E731
+        if objective == "si_sdr":
+            step = SiSdrObjective(device, labels, lambda: stats,
+                                  step=lambda batch, st: mix_step(batch, device, labels, bank, mixer, st, waves=True))
+            prepare, loss_fn = step.prepare, step.loss
+    elif av_files is not None:
         pairs = AVFiles(av_files)
         labels = labels_for_ydim(model.y_dim)
         collate = AVFiles.collate
@@ -526,6 +703,16 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         if rank == 0:
             stats.save(out_dir)
         log("- Train-set statistics over {} pairs in {:.1f} s, saved in {}".format(len(pairs), time.perf_counter() - t0, out_dir))
+    if compute_stats and clean_wavs is not None and (stats is None or stats.get("audio_mean", device) is None):
+        t0 = time.perf_counter()
+        made = mix_stats(pairs, bank, device, mixer.seed("stats"), batch_size=batch_size)
+        if stats is None:
+            stats = made
+        else:
+            stats._raw.update(audio_mean=made._raw["audio_mean"], audio_std=made._raw["audio_std"])
+        if rank == 0:
+            stats.save(out_dir)
+        log("- Train-set statistics over {} mixed utterances in {:.1f} s, saved in {}".format(len(pairs), time.perf_counter() - t0, out_dir))
     if compute_stats and av_files is not None and (stats is None or stats.get("video_mean", device) is None):
         t0 = time.perf_counter()
         made = av_file_stats(pairs, device, batch_size=batch_size)
@@ -538,8 +725,12 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         log("- Train-set statistics over {} utterances in {:.1f} s, saved in {}".format(len(pairs), time.perf_counter() - t0, out_dir))
     for epoch in range(1, epochs + 1):
         t0 = time.perf_counter()
+        if mixer is not None:
+            mixer.seed(epoch)
         tr = run_epoch(model, kind, mk(ds_train, True), device, waveform, opt, reducer, log, stats=stats, prepare=prepare,
                        loss_fn=loss_fn)
+        if mixer is not None:
+            mixer.seed("valid")
         with torch.no_grad():
             va = run_epoch(model, kind, mk(ds_valid, False), device, waveform, stats=stats, prepare=prepare, loss_fn=loss_fn)
         log("====> Epoch: {:2d}  train loss {:.3f} f1 {:.3f} | valid loss {:.3f} f1 {:.3f} | {:.1f} s".format(

@@ -35,6 +35,7 @@
  *         where a wrong one would be an error (AVVAD_EINVAL):
  *           workspace                      16 bytes, every entry point (avvad_score_accumulate: 256)
  *           float64 statistics and score accumulators, score ratios, int64 confusion counts  8 bytes
+ *           ratio / energies / clip_off of avvad_mix                                        8 bytes
  *           int64 / int32 index arrays      their natural alignment
  *           bf16 operands, avvad_lip_decode's coef, the avvad_stft_stream basis,
  *           (checked by avvad_stft_stream_fwd / _fwd_spec), the avvad_istft_stream
@@ -45,7 +46,8 @@
  *           any 4-byte aligned float pointer (a contiguous slice such as
  *           wave + 3): A / B of avvad_gemm_f32, the four vectors of
  *           avvad_adam_step, wave / vad / ibm / out of avvad_target_*, wave of
- *           avvad_stft*, w_hh / h0 / hT of the LSTM entry points, and every
+ *           avvad_stft*, clean / bank / noisy / noise_out of avvad_mix,
+ *           w_hh / h0 / hT of the LSTM entry points, and every
  *           argument of the element-wise helpers (loss, copy, transpose,
  *           standardise, peak).  These pick a vector form when the pointer
  *           (and the shape) allows it and a scalar form otherwise: same
@@ -82,7 +84,7 @@ typedef void* avvad_stream_t; /* hipStream_t */
                                  existing signature, so they keep the version: a version-3 binding still describes the
                                  library exactly for every symbol it binds.  The avvad_stats_* section is such an addition, and so
                                  are the avvad_score_* / avvad_confusion_* scores, and avvad_istft_bwd / avvad_resynth_bwd /
-                                 avvad_si_sdr_loss. */
+                                 avvad_si_sdr_loss, and avvad_mix_workspace / avvad_mix. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -676,6 +678,49 @@ int avvad_si_sdr_loss(const float* est, long ld_est, const float* ref, long ld_r
  * not read. */
 int avvad_confusion_accumulate(const float* pred, int pred_mode, const float* target, const int* lengths,
                                long long* counts /* [B][4], added to */, int B, int T, int Y, avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Mixing clean speech and noise at a target SNR, for training
+ * Replaces: nothing the reference has -- its corpus module leaves the noise-aware dataset as a TODO
+ *   (packages/dataset/ntcd_timit.py:13, 246) and training reads mixtures that were made offline at fixed SNRs.
+ * A ragged batch clean [B][ld_clean], row b holding len_b = n_samples[b] (clamped to [0, L]; NULL: L each) samples s, and
+ * a noise BANK: one flat buffer of n_bank floats that holds K clips, clip k at bank[clip_off[k] .. + clip_len[k]),
+ * clip_off int64 [K], clip_len int32 [K] (>= 1).  Per row a clip index clip[b], a start start[b] (int32 [B] each) and a
+ * linear power ratio ratio[b] = 10^(snr_db / 10), a DOUBLE computed on the host like avvad_target_desc.vad_coef: no pow
+ * runs on the device.  The row's noise is its clip read circularly,
+ *   n[i] = bank[clip_off[k] + (start[b] + i) mod clip_len[k]],   0 <= i < len_b
+ *   Es = sum_i s[i]^2,  En = sum_i n[i]^2  over i < len_b (En over the segment actually read, not the whole clip),
+ *        every value widened to double before it is squared
+ *   g_b = (float) sqrt(Es / (En ratio[b]))      formed in double and rounded once;
+ *         g_b = 0 (noisy = clean, bit for bit) when len_b <= 0, Es == 0, En == 0 or ratio[b] is not finite and positive
+ *   noise_out[b][i] = g_b n[i]                  one float product
+ *   noisy[b][i]     = s[i] + noise_out[b][i]    one float addition (never contracted into an fma)
+ * Columns len_b .. L - 1 of noisy and noise_out hold exact zeros; columns from L to the pitch are not touched.  Optional
+ * outputs (each NULL or): gain [B] float g_b; energies [B][2] double (Es, En); peak [B] float max |noisy[b][:]|, equal to
+ * avvad_abs_max of the written mixture bit for bit.  Nothing is rescaled here.
+ * Rows are cut into chunks of AVVAD_MIX_CHUNK samples (a function of the row length alone); per-chunk double partials are
+ * summed in a fixed lane and wave order and then in ascending chunk order; the peak is an integer maximum on |x|'s bits.
+ * Guarantees:
+ *   - no floating-point atomics; the same bits from run to run and under any "max_cus";
+ *   - a row's outputs depend on that row alone: the same bits at B = 1;
+ *   - nothing of clean at or behind len_b is read;
+ *   - nothing outside [0, n_bank) is read, whatever the device arrays hold: clip[b] is clamped to [0, K), start[b] is
+ *     taken mod the clip's length, a clip that would run past n_bank is cut there, and a clip whose offset lies outside
+ *     the bank or whose length is below 1 is silent (nothing is read, g_b = 0);
+ *   - clean, noisy, noise_out and bank are any 4-byte aligned float pointers, the first three each with its own row pitch
+ *     >= L; no load assumes a 16-byte aligned row base;
+ *   - noisy may not alias clean, nor noise_out either of them (equal pointers: AVVAD_EINVAL);
+ *   - ws 16-byte aligned; ratio, energies and clip_off 8-byte aligned: AVVAD_EINVAL otherwise, before anything is launched;
+ *   - a workspace below avvad_mix_workspace(B, L) bytes: AVVAD_EWORKSPACE before anything is launched.
+ * ---------------------------------------------------------------------- */
+#define AVVAD_MIX_CHUNK 4096
+size_t avvad_mix_workspace(int B, long L);     /* 0 on a bad shape: B outside 1..65535, L < 1 */
+int avvad_mix(const float* clean, long ld_clean, const int* n_samples /* NULL: L each */,
+              const float* bank, long n_bank, const long long* clip_off, const int* clip_len, int K,
+              const int* clip, const int* start, const double* ratio,
+              float* noisy, long ld_noisy, float* noise_out /* or NULL */, long ld_noise,
+              float* gain, double* energies, float* peak,      /* each NULL or as above */
+              int B, long L, void* ws, size_t ws_bytes, avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Training labels from clean speech: framed-energy VAD and ideal binary mask (IBM)
