@@ -184,7 +184,13 @@ SIGNATURES = {
     "avvad_target_vad": (C.c_int, [FP, FP, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
     "avvad_target_ibm": (C.c_int, [FP, FP, FP, C.c_int, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
     "avvad_target_ibm_from_spectrum": (C.c_int, [FP, C.c_long, C.c_long, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
-    "avvad_lip_decode_workspace": (C.c_size_t, [C.POINTER(LipDesc)]),
+    "avvad_target_noise_aware_workspace": (C.c_size_t, [C.POINTER(TargetDesc)]),
+    "avvad_target_noise_aware_from_spectrum": (C.c_int, [FP, C.c_long, C.c_long, C.c_long, FP, C.c_long, C.c_long, C.c_long, FP, FP,
+                                                         FP, FP, C.c_int, C.c_int, C.c_double, C.c_double, FP, FP, FP, C.c_int,
+                                                         C.c_int, C.c_int, FP]),
+    "avvad_target_noise_aware": (C.c_int, [FP, FP, FP, FP, FP, FP, FP, C.c_int, C.c_int, C.c_double, FP, FP, FP,
+                                           C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
+    "avvad_lip_decode_workspace":(C.c_size_t, [C.POINTER(LipDesc)]),
     "avvad_lip_decode": (C.c_int, [FP] * 9 + [C.POINTER(LipDesc), FP, C.c_size_t, FP]),
     "avvad_peak_normalize": (C.c_int, [FP, FP, C.c_int, C.c_long, FP]),
     "avvad_standardize": (C.c_int, [FP, FP, FP, FP, C.c_size_t, C.c_int, C.c_int, C.c_float, FP]),

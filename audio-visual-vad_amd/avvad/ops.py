@@ -1635,6 +1635,152 @@ def ibm_from_spectrum(spec, eps=1e-8, ibm_threshold=50, vad=None):
     return out
 
 
+# --------------------------------------------------------------------------- noise-aware masks from speech and noise (no gradient)
+NOISE_AWARE_OUTPUTS = ("speech", "noise", "irm")
+
+
+def voiced_unvoiced_characteristic(F):
+    """``_voiced_unvoiced_split_characteristic`` of the reference (packages/processing/target.py:110-149) -> (voiced,
+    unvoiced), float64 (F,): two weights per bin that cross over around bin 200 on a 99-bin raised cosine (bins 149 ..
+    247), voiced rising from 0 over bins 3 .. 7, unvoiced falling to 0 over bins 499 .. 503.  Every value is formed by the
+    reference's operations in its order, so the tables equal its bits.  The fixed bins need F >= 505."""
+    import numpy as np
+    if F < 505:
+        raise ValueError("the voiced / unvoiced characteristic has fixed bins up to 503 and needs F >= 505, got %d" % F)
+    split, width, fast_width, low, high = 200, 99, 5, 4, 500
+    slow = 0.5 * (1 + np.cos(np.pi / (width - 1) * np.arange(0, width)))
+    fast = (np.cos(np.pi / (fast_width - 1) * np.arange(0, fast_width)) + 1) / 2
+    first = int(split - width / 2) - 1                  # 149: where the cross-over starts
+    voiced, unvoiced = np.ones(F), np.ones(F)
+    voiced[first:first + width] = slow
+    voiced[first + width:] = 0
+    voiced[:low] = 0
+    voiced[low - 1:low - 1 + fast_width] = 1 - fast
+    unvoiced[first:first + width] = 1 - slow
+    unvoiced[:first + 1] = 0
+    unvoiced[high - 1:] = 0
+    unvoiced[high - 1:high - 1 + fast_width] = fast
+    return voiced, unvoiced
+
+
+def noise_aware_tables(F, threshold_unvoiced_speech=5, threshold_voiced_speech=0, threshold_unvoiced_noise=-10,
+                       threshold_voiced_noise=-10):
+    """(c_speech, c_noise), float64 (F,): the per-bin power ratios ``10 ** (threshold_f / 10)`` that ``noise_aware_IBM``
+    divides the speech power by (target.py:175-186), on the host.  As there, the noise row weights ``voiced`` with
+    ``threshold_unvoiced_noise`` and ``unvoiced`` with ``threshold_voiced_noise``."""
+    import numpy as np
+    voiced, unvoiced = voiced_unvoiced_characteristic(F)
+    thr_speech = threshold_voiced_speech * voiced + threshold_unvoiced_speech * unvoiced
+    thr_noise = threshold_unvoiced_noise * voiced + threshold_voiced_noise * unvoiced
+    return np.power(10, (thr_speech / 10)), np.power(10, (thr_noise / 10))
+
+
+def _na_args(F, B, device, outputs, peak, thresholds, low_cut, high_cut):
+    """What the two noise-aware calls share: the tables on the device (one copy), the checked cuts, peak and outputs."""
+    import numpy as np
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in NOISE_AWARE_OUTPUTS for o in outputs) or len(set(outputs)) != len(outputs):
+        raise L.AvvadError("outputs: one or more of %s, got %r" % (", ".join(NOISE_AWARE_OUTPUTS), outputs))
+    low_cut, high_cut = int(low_cut), int(high_cut)
+    if low_cut < 1 or high_cut > F:
+        raise L.AvvadError("low_cut %d / high_cut %d: 1 <= low_cut and high_cut <= %d bins" % (low_cut, high_cut, F))
+    tables = torch.from_numpy(np.stack(noise_aware_tables(F, *thresholds))).to(device)
+    if peak is not None:
+        peak = _dev(peak, "peak").reshape(-1)
+        if peak.numel() != B:
+            raise L.AvvadError("peak holds %d values, the batch %d rows" % (peak.numel(), B))
+    return outputs, tables, peak, low_cut, high_cut
+
+
+def noise_aware_targets(speech, noise, sample_lengths, peak=None, outputs=("speech",), threshold_unvoiced_speech=5,
+                        threshold_voiced_speech=0, threshold_unvoiced_noise=-10, threshold_voiced_noise=-10, low_cut=5,
+                        high_cut=500, floor=0.005, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, pad_at_end=True):
+    """Noise-aware labels of a ragged batch of mixtures from their two components (avvad_target_noise_aware): ``speech``
+    and ``noise`` (B, L) zero-padded rows (or (L,)) -- for ``ops.mix``, the clean wave and the scaled noise ``g n`` --
+    ``sample_lengths`` the B real lengths, ``peak`` (B,) what both are divided by (the mixture's peak puts them on the
+    scale of the normalised mixture; it matters for the ``floor`` only) or None.  ``outputs``: any of "speech" (the
+    speech mask of ``noise_aware_IBM``, target.py:151-202), "noise" (its noise mask) and "irm" (the ideal ratio mask
+    ``|S|^2 / (|S|^2 + |N|^2)``); the six thresholds and cuts default as in the reference.  Framing as ``speech_targets``
+    with ``center=False``.  Returns (frame_lengths LongTensor (B,) on the host, {name: (B, T, n_fft/2+1) float32}); frames
+    t >= T_b are zero."""
+    w, w2 = _wave2d(speech)
+    _, n2 = _wave2d(noise)
+    if n2.shape != w2.shape or n2.device != w2.device:
+        raise L.AvvadError("speech %s and noise %s must have one shape and one device" % (tuple(w2.shape), tuple(n2.shape)))
+    B, Lp = w2.shape
+    lens = _ints(sample_lengths, B, Lp, "sample_lengths must hold %d lengths within 0..%d" % (B, Lp))
+    if wlen_sec * fs != int(wlen_sec * fs):
+        raise ValueError("wlen_sample of STFT is not an integer.")
+    nfft = int(wlen_sec * fs)
+    hop = int(hop_percent * nfft)
+    if nfft % 32:
+        raise L.AvvadError("noise-aware labels need an FFT length that is a multiple of 32")
+    F = nfft // 2 + 1
+    thresholds = (threshold_unvoiced_speech, threshold_voiced_speech, threshold_unvoiced_noise, threshold_voiced_noise)
+    outputs, tables, peak, low_cut, high_cut = _na_args(F, B, w2.device, outputs, peak, thresholds, low_cut, high_cut)
+    pads, frames = zip(*[target_frames(n, fs, wlen_sec, hop_percent, False, pad_at_end) for n in lens])
+    T = max(frames)
+    d = L.TargetDesc(B, Lp, nfft, hop, T, 0, 0.0, 1.0, 1.0)
+    ws = _ws(L.lib().avvad_target_noise_aware_workspace(C.byref(d)), w2.device)
+    cnt = torch.tensor([list(pads), list(frames)], dtype=torch.int32).to(w2.device)
+    res = {o: torch.empty(B, T, F, dtype=torch.float32, device=w2.device) for o in outputs}
+    L.check(L.lib().avvad_target_noise_aware(L.ptr(w2), L.ptr(n2), L.ptr(cnt[0]), L.ptr(cnt[1]), L.ptr(peak), L.ptr(tables[0]),
+                                             L.ptr(tables[1]), low_cut, high_cut, float(floor), L.ptr(res.get("speech")),
+                                             L.ptr(res.get("noise")), L.ptr(res.get("irm")), C.byref(d), L.ptr(ws), ws.numel() * 4,
+                                             _stream()), "avvad_target_noise_aware")
+    return torch.LongTensor(frames), res
+
+
+def _spectrum_view(spec, name):
+    """A complex64 (T, F) / (B, T, F) GPU tensor or its float32 (..., 2) view -> (the (B, T, F, 2) view read through its
+    strides, batched?)"""
+    if isinstance(spec, torch.Tensor) and spec.is_complex():
+        if spec.dtype != torch.complex64:
+            raise L.AvvadError("%s must be complex64, got %s" % (name, spec.dtype))
+        spec = torch.view_as_real(spec)
+    if not isinstance(spec, torch.Tensor) or not spec.is_cuda or spec.dtype != torch.float32:
+        raise L.AvvadError("%s must be a complex64 or float32 (..., 2) GPU tensor" % name)
+    if spec.dim() not in (3, 4) or spec.shape[-1] != 2 or 0 in spec.shape:
+        raise L.AvvadError("%s must be (T, F) or (B, T, F) complex, or the (..., 2) real view, got shape %s" % (name, tuple(spec.shape)))
+    batched = spec.dim() == 4
+    s4 = spec if batched else spec.unsqueeze(0)
+    st = s4.stride()
+    if st[3] != 1 or any(v % 2 or v <= 0 for v in st[1:3]) or (s4.shape[0] > 1 and (st[0] % 2 or st[0] <= 0)) or s4.data_ptr() % 8:
+        s4 = s4.contiguous()
+    return s4, batched
+
+
+def noise_aware_from_spectrum(X, N=None, n_frames=None, peak=None, outputs=("speech", "noise"), threshold_unvoiced_speech=5,
+                              threshold_voiced_speech=0, threshold_unvoiced_noise=-10, threshold_voiced_noise=-10, low_cut=5,
+                              high_cut=500, floor=0.005, noise_psd=10.0):
+    """The masks of ``noise_aware_targets`` from given spectra (avvad_target_noise_aware_from_spectrum): ``X`` (speech)
+    and ``N`` (noise) complex64 (T, F) or (B, T, F) GPU tensors, or their float32 (..., 2) views, each read in place
+    through its strides -- a transposed legacy (F, T, 2) view or a column slice of a wider tensor is not copied.
+    ``N`` None: the noise power is the constant ``noise_psd`` in every cell (``threshold_IBM``, target.py:205-251).
+    ``n_frames``: B frame counts (frames behind them are zero) or None; ``peak`` as in ``noise_aware_targets``.
+    Returns {name: (T, F) or (B, T, F) float32}."""
+    x4, batched = _spectrum_view(X, "X")
+    B, T, F = x4.shape[:3]
+    n4 = None
+    if N is not None:
+        n4, _ = _spectrum_view(N, "N")
+        if n4.shape != x4.shape or n4.device != x4.device:
+            raise L.AvvadError("X %s and N %s must have one shape and one device" % (tuple(x4.shape), tuple(n4.shape)))
+    thresholds = (threshold_unvoiced_speech, threshold_voiced_speech, threshold_unvoiced_noise, threshold_voiced_noise)
+    outputs, tables, peak, low_cut, high_cut = _na_args(F, B, x4.device, outputs, peak, thresholds, low_cut, high_cut)
+    cnt = None
+    if n_frames is not None:
+        cnt = torch.tensor(_ints(n_frames, B, T, "n_frames must hold %d counts within 0..%d" % (B, T)), dtype=torch.int32).to(x4.device)
+    res = {o: torch.empty(B, T, F, dtype=torch.float32, device=x4.device) for o in outputs}
+    sx = (x4.stride(0) if B > 1 else 0,) + tuple(x4.stride()[1:3])          # (one row: its batch stride is not read)
+    sn = ((n4.stride(0) if B > 1 else 0,) + tuple(n4.stride()[1:3])) if n4 is not None else (0, 0, 0)
+    L.check(L.lib().avvad_target_noise_aware_from_spectrum(
+        L.ptr(x4), sx[0], sx[1], sx[2], L.ptr(n4), sn[0], sn[1], sn[2], L.ptr(cnt), L.ptr(peak), L.ptr(tables[0]), L.ptr(tables[1]),
+        low_cut, high_cut, float(floor), float(noise_psd), L.ptr(res.get("speech")), L.ptr(res.get("noise")), L.ptr(res.get("irm")),
+        B, T, F, _stream()), "avvad_target_noise_aware_from_spectrum")
+    return res if batched else {o: v[0] for o, v in res.items()}
+
+
 # --------------------------------------------------------------------------- video front-end: lip DCT frames (no gradient)
 LIP_W = LIP_H = 67
 

@@ -183,11 +183,12 @@ def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, ho
     return _pair_tail(lens, noisy, clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves)
 
 
-def _pair_tail(lens, noisy, clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves, more=()):
+def _pair_tail(lens, noisy, clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves, more=(), made=None):
     """What ``wav_pair_step`` and ``mix_step`` share, from the peak-normalised noisy and clean waves on: the labels of the
-    clean wave, the features of the noisy one, the frame-count check.  ``more``: further members of the ``waves`` tuple."""
-    frames, target = ops.speech_targets(clean, lens, labels, fs=fs, wlen_sec=wlen_sec, hop_percent=hop_percent, center=False,
-                                        pad_at_end=True, eps=eps)
+    clean wave, the features of the noisy one, the frame-count check.  ``more``: further members of the ``waves`` tuple.
+    ``made``: (frame lengths, target) made by the caller; no clean-speech label is computed then."""
+    frames, target = made if made is not None else ops.speech_targets(
+        clean, lens, labels, fs=fs, wlen_sec=wlen_sec, hop_percent=hop_percent, center=False, pad_at_end=True, eps=eps)
     nfft = int(wlen_sec * fs)
     mean = std = None
     if stats is not None:
@@ -298,20 +299,52 @@ class MixDraw:
         return draw_mix(self.gen, lengths, self.bank, self.snr_db)
 
 
-def mix_step(batch, device, labels, bank, draw, stats=None, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS, waves=False):
+MIX_LABELS = {"clean": None, "noise_aware": "speech", "irm": "irm"}      # -> the output of ops.noise_aware_targets
+
+
+def check_mix_labels(mix_labels, mixing, y_dim=None):
+    """``mix_labels`` "noise_aware" and "irm" label a mixture made in the step (``mixing``: clean_wavs / noise_wavs are
+    given) for a 513-bin mask head; anything else is a ValueError (``y_dim`` None: not known yet)."""
+    if mix_labels not in MIX_LABELS:
+        raise ValueError("mix_labels %r: one of %s" % (mix_labels, ", ".join(MIX_LABELS)))
+    if mix_labels != "clean":
+        if not mixing:
+            raise ValueError("mix_labels %r needs the noise of the mixture: it goes with clean_wavs / noise_wavs" % mix_labels)
+        if y_dim is not None and y_dim != 513:
+            raise ValueError("mix_labels %r are 513-bin masks (y_dim 513), got y_dim %d" % (mix_labels, y_dim))
+
+
+def mix_step(batch, device, labels, bank, draw, stats=None, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS, waves=False,
+             mix_labels="clean"):
     """A ``CleanWavs.collate`` batch -> what ``wav_pair_step`` returns, with a mixture made in the step in place of the noisy
     file: the clean waves are peak-normalised, ``draw(lengths)`` gives every row a clip of ``bank``, a start and an SNR
     in dB (``draw_mix``), ``ops.mix`` adds the noise at that SNR on the GPU, and the mixture is peak-normalised like a
     noisy file that was read.  ``waves``: the fourth value is (peak-normalised mixture (B, L), clean (B, L), sample
     lengths, noise (B, L)) -- the noise as it was added, ``g_b n``, on the scale of the mixture BEFORE its
-    normalisation (SI-SIR and SI-SAR do not depend on that scale)."""
+    normalisation (SI-SIR and SI-SAR do not depend on that scale).
+    ``mix_labels``: "clean" labels the clean wave alone (``labels``); "noise_aware" / "irm" (``labels`` "ibm_labels" only)
+    take the target from the mixture's two components instead -- the speech mask of ``noise_aware_IBM`` or the ideal ratio
+    mask of (clean, ``g_b n``), both over the mixture's peak, i.e. on the scale of the normalised mixture the model sees
+    (``ops.noise_aware_targets``) -- and compute no clean-speech label."""
+    check_mix_labels(mix_labels, True)
+    if mix_labels != "clean" and labels != "ibm_labels":
+        raise ValueError("mix_labels %r are 513-bin masks: they go with labels 'ibm_labels', got %r" % (mix_labels, labels))
     lens, clean = batch
     clean = ops.peak_normalize(clean.to(device, non_blocking=True))
     n = [int(v) for v in lens]
     clip, start, snr = draw(n)
-    mixed = ops.mix(clean, n, bank, clip, start, snr, return_noise=waves)
-    noisy, more = (mixed[0], (mixed[1],)) if waves else (mixed, ())
-    return _pair_tail(lens, ops.peak_normalize(noisy), clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves, more)
+    made = None
+    if mix_labels == "clean":
+        mixed = ops.mix(clean, n, bank, clip, start, snr, return_noise=waves)
+        noisy, more = (mixed[0], (mixed[1],)) if waves else (mixed, ())
+    else:
+        noisy, noise, info = ops.mix(clean, n, bank, clip, start, snr, return_noise=True, return_info=True)
+        which = MIX_LABELS[mix_labels]
+        frames, out = ops.noise_aware_targets(clean, noise, n, peak=info["peak"], outputs=(which,), fs=fs, wlen_sec=wlen_sec,
+                                              hop_percent=hop_percent, pad_at_end=True)
+        made, more = (frames, out[which]), ((noise,) if waves else ())
+    return _pair_tail(lens, ops.peak_normalize(noisy), clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves, more,
+                      made)
 
 
 OBJECTIVES = ("bce", "si_sdr")
@@ -583,7 +616,7 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
 
 def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_size=16, n_items=64, lr=1e-4,
                freeze_features=False, out_dir=None, stats=None, wav_pairs=None, compute_stats=False, av_files=None,
-               objective="bce", clean_wavs=None, noise_wavs=None, snr_db=(-5.0, 20.0), mix_seed=0):
+               objective="bce", clean_wavs=None, noise_wavs=None, snr_db=(-5.0, 20.0), mix_seed=0, mix_labels="clean"):
     """The body of ``scripts/train_{audio,video,AV}_net.py``; settings come from the caller's module-level constants
     (the reference's "config system") and may be overridden by AVVAD_* environment variables.
 
@@ -609,9 +642,15 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     (lo, hi) dB, drawn on the host from a generator seeded by (``mix_seed``, epoch, rank) -- a fresh draw per epoch, the
     same one in every run.  Validation draws from (``mix_seed``, "valid", rank) in every epoch, so its losses are
     comparable.  ``compute_stats`` accumulates the statistics over one pass of mixtures seeded (``mix_seed``, "stats",
-    rank) (``mix_stats``)."""
+    rank) (``mix_stats``).
+
+    ``mix_labels`` (with ``clean_wavs`` + ``noise_wavs`` and a y_dim 513 head): "clean" (the default) labels the clean
+    utterance alone, as wav pairs are labelled; "noise_aware" trains against the speech mask of the reference's
+    ``noise_aware_IBM`` and "irm" against the ideal ratio mask, both computed in the step from the clean wave and the
+    noise that was just added (``mix_step``).  With ``objective="si_sdr"`` the label feeds the F1 log line only."""
     objective = os.environ.get("AVVAD_OBJECTIVE", objective)
     check_objective(objective, kind, waveform, wav_pairs, clean_wavs=clean_wavs)
+    check_mix_labels(mix_labels, clean_wavs is not None and noise_wavs is not None)
     if (clean_wavs is None) != (noise_wavs is None):
         raise ValueError("clean_wavs and noise_wavs go together: the clean utterances and the noise clips they are mixed with")
     if clean_wavs is not None:
@@ -636,6 +675,7 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     torch.manual_seed(0)
     model = make_model().to(device)
     check_objective(objective, kind, waveform, wav_pairs, getattr(model, "y_dim", None), clean_wavs=clean_wavs)
+    check_mix_labels(mix_labels, clean_wavs is not None, getattr(model, "y_dim", None))
     if freeze_features:                      # train_AV_net.py:241-245
         for name, child in model.named_children():
             if name == "features":
@@ -652,10 +692,11 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         labels = labels_for_ydim(model.y_dim)
         collate = CleanWavs.collate
         ds_train = ds_valid = torch.utils.data.Subset(pairs, range(rank, len(pairs), world))
-        prepare = lambda batch: mix_step(batch, device, labels, bank, mixer, stats)   # noqa: E731
+        prepare = lambda batch: mix_step(batch, device, labels, bank, mixer, stats, mix_labels=mix_labels)   # noqa: E731
         if objective == "si_sdr":
             step = SiSdrObjective(device, labels, lambda: stats,
-                                  step=lambda batch, st: mix_step(batch, device, labels, bank, mixer, st, waves=True))
+                                  step=lambda batch, st: mix_step(batch, device, labels, bank, mixer, st, waves=True,
+                                                                   mix_labels=mix_labels))
             prepare, loss_fn = step.prepare, step.loss
     elif av_files is not None:
         pairs = AVFiles(av_files)

@@ -6,6 +6,8 @@
 //   clean_speech_IBM (:58-70)              20 log10(|S| + eps) > max(20 log10(|S| + eps)) - ibm_threshold
 //                                          <=>  |S| > (max|S| + eps) * 10**(-ibm_threshold/20) - eps (per utterance)
 //   noise_robust_clean_speech_IBM (:72-107)  IBM * VAD, broadcast over frequency
+//   noise_aware_IBM (:151-202), threshold_IBM (:205-251)   speech and noise masks from a speech and a noise spectrum (or a
+//                                          constant noise power), and the ideal ratio mask of the same pair
 // The reference computes them offline, one utterance at a time, into HDF5 files (scripts/create_audio_train_files.py);
 // here a ragged batch wave [B][L] (zero-padded rows, per-utterance sample and frame counts in device arrays) gets its
 // labels in the training step.  Every reduction stays inside one utterance and frames t >= T_b are written as zeros.
@@ -20,6 +22,9 @@
 //        pass over S (float4 loads, block reduction, one integer atomicMax per workgroup on the bit pattern of a
 //        non-negative double: order-independent, so bit-reproducible); ibm_mask thresholds every bin in a second pass
 //        (float4 stores), times the utterance's VAD when `robust`.
+//   Noise-aware masks: one DFT GEMM per wave with the batch's own (B, T) (the bits of avvad_stft_complex), then
+//        noise_aware_mask, one pass over the two spectra in ibm_mask's form: every step in double, per-bin thresholds from
+//        two host tables, up to three outputs; a pure function of its inputs.
 #include <math.h>
 
 #include "frames.h"
@@ -216,6 +221,73 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// ---- noise-aware masks (noise_aware_IBM / threshold_IBM, target.py:108-251) and the ideal ratio mask, one pass
+// A batch of spectra given as interleaved (re, im) pairs, bin (b, t, f) at p[b*sb + t*st + f*sf] (float strides, even).
+struct Spec { const float* p; long sb, st, sf; };
+struct NaOut { float *speech, *noise, *irm; };
+
+// peak[b]^2 as the divisor of both powers; 1 (no scaling) without a peak or when the square is not finite and positive
+__device__ __forceinline__ double peak_sq(const float* __restrict__ peak, int b) {
+  if (!peak) return 1.0;
+  const double p2 = (double)peak[b] * (double)peak[b];
+  return (p2 > 0.0 && p2 < __builtin_huge_val()) ? p2 : 1.0;
+}
+__device__ __forceinline__ double cell_power(const Spec& s, int b, int t, int f, double p2) {
+  const float2 c = *reinterpret_cast<const float2*>(s.p + b * s.sb + t * s.st + f * s.sf);
+  return ((double)c.x * c.x + (double)c.y * c.y) / p2;
+}
+
+// speech / noise / irm [B][Tp][F] (each may be null): four consecutive outputs per thread, threads along f, so a wave
+// reads 2 KB of a spectrum row in a piece and stores one float4 per output; every step in double, thresholds from the
+// host's tables c_speech / c_noise (read through the cache: 16 F bytes that every workgroup shares).
+__global__ void __launch_bounds__(256)
+    noise_aware_mask(Spec X, Spec N, const int* __restrict__ n_frames, const float* __restrict__ peak,
+                     const double* __restrict__ c_speech, const double* __restrict__ c_noise, int f_lo, int f_hi, double floor,
+                     double noise_psd, int F, int Tp, int B, int vec, NaOut out) {
+  const long n = (long)B * Tp * F, n4 = (n + 3) >> 2;
+  for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < n4; g += (long)gridDim.x * 256) {
+    const long i = g * 4;
+    const long m = i / F;
+    int f = (int)(i - m * F);
+    int b = (int)(m / Tp), t = (int)(m - (long)b * Tp);
+    int Tb = n_frames ? clamp_count(n_frames[b], Tp) : Tp;
+    double p2 = peak_sq(peak, b);
+    float vs[4], vn[4], vr[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float s = 0.f, z = 0.f, r = 0.f;
+      if (i + q < n && t < Tb) {
+        const double xP = cell_power(X, b, t, f, p2);
+        const double nP = N.p ? cell_power(N, b, t, f, p2) : noise_psd;
+        const bool cut = f < f_lo || f >= f_hi;
+        const double xs = xP / c_speech[f], xn = xP / c_noise[f];
+        s = (!cut && xs > nP && xs > floor) ? 1.f : 0.f;
+        z = (cut || xn < nP || xn < floor) ? 1.f : 0.f;
+        const double sum = xP + nP;
+        r = sum == 0.0 ? 0.f : (float)(xP / sum);
+      }
+      vs[q] = s, vn[q] = z, vr[q] = r;
+      if (++f == F) {                                      // next spectrum row (and maybe the next utterance)
+        f = 0;
+        if (++t == Tp && i + q + 1 < n) {
+          t = 0, ++b;
+          Tb = n_frames ? clamp_count(n_frames[b], Tp) : Tp;
+          p2 = peak_sq(peak, b);
+        }
+      }
+    }
+    float* const dst[3] = {out.speech, out.noise, out.irm};
+    const float* const src[3] = {vs, vn, vr};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (!dst[k]) continue;
+      if ((vec >> k & 1) && i + 3 < n) *reinterpret_cast<float4*>(dst[k] + i) = make_float4(src[k][0], src[k][1], src[k][2], src[k][3]);
+      else
+        for (int q = 0; q < 4 && i + q < n; ++q) dst[k][i + q] = src[k][q];
+    }
+  }
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline int div_up(long a, long b) { return (int)((a + b - 1) / b); }
 inline int grid_cap(long n4, int cap) { const long g = (n4 + 255) / 256; return (int)(g < 1 ? 1 : (g > cap ? cap : g)); }
@@ -331,4 +403,95 @@ extern "C" int avvad_target_ibm_from_spectrum(const float* spec, long stride_t, 
                      d->ibm_coef, (double)d->eps, vad, (int)aligned16(out), out);
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
+}
+
+// ---- noise-aware masks
+namespace {
+
+struct NaParams {
+  const int* n_frames;
+  const float* peak;
+  const double *c_speech, *c_noise;
+  int low_cut, high_cut;
+  double floor, noise_psd;
+};
+bool ok_na(const NaParams& p, const NaOut& o, int F) {
+  return p.c_speech && p.c_noise && !((uintptr_t)p.c_speech & 7) && !((uintptr_t)p.c_noise & 7) && p.low_cut >= 1 &&
+         p.high_cut <= F && (o.speech || o.noise || o.irm);
+}
+bool ok_spec(const Spec& s, int B) {
+  return !((uintptr_t)s.p & 7) && s.st > 0 && s.sf > 0 && s.sb >= 0 && (B == 1 || s.sb > 0) && !((s.sb | s.st | s.sf) & 1);
+}
+int na_launch(const Spec& X, const Spec& N, const NaParams& p, const NaOut& o, int B, int T, int F, hipStream_t s) {
+  const long n4 = ((long)B * T * F + 3) / 4;
+  const int vec = (int)aligned16(o.speech) | (int)aligned16(o.noise) << 1 | (int)aligned16(o.irm) << 2;
+  hipLaunchKernelGGL(noise_aware_mask, dim3(grid_cap(n4, 8192)), dim3(256), 0, s, X, N, p.n_frames, p.peak, p.c_speech, p.c_noise,
+                     p.low_cut - 1, p.high_cut, p.floor, p.noise_psd, F, T, B, vec, o);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+// workspace of the waveform entry: [W][S speech][S noise][engine slab] -- one basis and one slab for the two products, which
+// run one after the other on the stream; .x / .n are what frames::framed_dft takes for each
+struct NaWs { frames::SpecWs x, n; };
+NaWs na_ws(const avvad_target_desc* d) {
+  NaWs w;
+  w.x = frames::spec_ws(d->n_fft, (size_t)d->B * d->T);
+  w.n = w.x;
+  w.n.S = w.x.S_end;
+  w.n.S_end = w.n.S + (w.x.S_end - w.x.S);
+  w.n.slab = w.n.S_end;
+  w.n.total = w.n.slab + igemm::SLAB_FLOATS;
+  w.x.slab = w.n.slab, w.x.total = w.n.total;
+  return w;
+}
+bool ok_na_desc(const avvad_target_desc* d) { return ok_desc(d) && d->center == 0 && frames::ok_n_fft(d->n_fft); }
+
+}  // namespace
+
+extern "C" size_t avvad_target_noise_aware_workspace(const avvad_target_desc* d) {
+  if (!ok_na_desc(d)) return 0;
+  return na_ws(d).n.total * sizeof(float);
+}
+
+extern "C" int avvad_target_noise_aware_from_spectrum(const float* spec, long stride_b, long stride_t, long stride_f,
+                                                      const float* noise_spec, long nstride_b, long nstride_t, long nstride_f,
+                                                      const int* n_frames, const float* peak, const double* c_speech,
+                                                      const double* c_noise, int low_cut, int high_cut, double floor,
+                                                      double noise_psd, float* speech, float* noise, float* irm, int B, int T,
+                                                      int F, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  const Spec X = {spec, stride_b, stride_t, stride_f}, N = {noise_spec, nstride_b, nstride_t, nstride_f};
+  const NaParams p = {n_frames, peak, c_speech, c_noise, low_cut, high_cut, floor, noise_psd};
+  const NaOut o = {speech, noise, irm};
+  if (!spec || B <= 0 || T <= 0 || F <= 0 || (long)B * T >= (1L << 31) / F || !ok_na(p, o, F) || !ok_spec(X, B) ||
+      (noise_spec && !ok_spec(N, B)))
+    return AVVAD_EINVAL;
+  return na_launch(X, N, p, o, B, T, F, (hipStream_t)sv);
+}
+
+extern "C" int avvad_target_noise_aware(const float* speech_wave, const float* noise_wave, const int* n_samples,
+                                        const int* n_frames, const float* peak, const double* c_speech, const double* c_noise,
+                                        int low_cut, int high_cut, double floor, float* speech, float* noise, float* irm,
+                                        const avvad_target_desc* d, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  (void)n_samples;                    // rows are zero-padded past each utterance: the DFT reads them as avvad_stft does
+  if (!speech_wave || !noise_wave || !n_frames || !wsv || ws_misaligned(wsv) || !ok_na_desc(d)) return AVVAD_EINVAL;
+  const int F = d->n_fft / 2 + 1;
+  const NaParams p = {n_frames, peak, c_speech, c_noise, low_cut, high_cut, floor, 0.0};
+  const NaOut o = {speech, noise, irm};
+  const NaWs w = na_ws(d);
+  const int ld = w.x.ld;
+  if (!ok_na(p, o, F) || (long)d->B * d->T * ld >= (1L << 31)) return AVVAD_EINVAL;
+  if (ws_bytes < w.n.total * sizeof(float)) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  float* ws = (float*)wsv;
+  // one product per wave with the batch's own (B, T): the stream-K split depends on the row count, and with it the
+  // summation order of a bin, so only this gives the bits of avvad_stft_complex for the same batch
+  int rc = frames::framed_dft(speech_wave, d->L, d->B, d->T, d->n_fft, d->hop, ws, w.x, s);
+  if (rc) return rc;
+  rc = frames::framed_dft(noise_wave, d->L, d->B, d->T, d->n_fft, d->hop, ws, w.n, s);
+  if (rc) return rc;
+  const Spec X = {ws + w.x.S, (long)d->T * ld, ld, 2}, N = {ws + w.n.S, (long)d->T * ld, ld, 2};
+  return na_launch(X, N, p, o, d->B, d->T, F, s);
 }

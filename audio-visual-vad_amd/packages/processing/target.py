@@ -7,7 +7,9 @@ to the current GPU, labelled there and returned as a float32 numpy array in the 
 VAD, ``(F, T)`` for the masks.  This is not a CPU fallback: without a GPU every function raises ``AvvadError``, like
 ``stft_pytorch``.  ``pad_mode`` may be ``'reflect'`` or ``'constant'``.
 
-Not ported: ``noise_aware_IBM`` and ``threshold_IBM`` (``:108-250``); no script of the reference calls them."""
+``noise_aware_IBM`` and ``threshold_IBM`` (``:151-251``) take spectra of shape (frames, bins), complex, as the reference
+does, and return boolean masks of that shape: GPU tensors for GPU tensors, numpy arrays for host input.  Spectra are read
+as complex64."""
 import numpy as np
 import torch
 
@@ -72,3 +74,40 @@ def noise_robust_clean_speech_IBM(speech_t, speech_tf, fs=16e3, wlen_sec=50e-3, 
         vad = vad.expand(1, T).contiguous()
     out = ops.ibm_from_spectrum(x, eps=eps, ibm_threshold=ibm_threshold, vad=vad)
     return out.cpu().numpy() if (host_tf or host_t) else out
+
+
+def _frames_by_bins(S, what):
+    """(frames, bins) complex spectrum -> (complex64 tensor on the GPU, came from the host?)"""
+    x, host = _on_gpu(S, what)
+    if not x.is_complex() or x.dim() != 2:
+        raise ValueError("%s: a complex spectrum of shape (frames, frequency-bins), got %s %s" % (what, x.dtype, tuple(x.shape)))
+    return x.to(torch.complex64), host
+
+
+def noise_aware_IBM(X, N, threshold_unvoiced_speech=5, threshold_voiced_speech=0, threshold_unvoiced_noise=-10,
+                    threshold_voiced_noise=-10, low_cut=5, high_cut=500):
+    """(speech mask, noise mask) of a speech spectrum ``X`` and a noise spectrum ``N``, both (frames, bins): the speech
+    power over a per-bin threshold against the noise power and against 0.005, bins below ``low_cut - 1`` and from
+    ``high_cut`` on forced to 0 in the speech mask and to 1 in the noise mask."""
+    from avvad import ops
+    x, host_x = _frames_by_bins(X, "noise_aware_IBM")
+    n, host_n = _frames_by_bins(N, "noise_aware_IBM")
+    out = ops.noise_aware_from_spectrum(x, n, outputs=("speech", "noise"), threshold_unvoiced_speech=threshold_unvoiced_speech,
+                                        threshold_voiced_speech=threshold_voiced_speech,
+                                        threshold_unvoiced_noise=threshold_unvoiced_noise,
+                                        threshold_voiced_noise=threshold_voiced_noise, low_cut=low_cut, high_cut=high_cut)
+    speech, noise = out["speech"] != 0, out["noise"] != 0
+    return (speech.cpu().numpy(), noise.cpu().numpy()) if (host_x or host_n) else (speech, noise)
+
+
+def threshold_IBM(X, threshold_unvoiced_speech=5, threshold_voiced_speech=0, threshold_unvoiced_noise=-10,
+                  threshold_voiced_noise=-10, low_cut=5, high_cut=500):
+    """The speech mask of ``noise_aware_IBM`` against a constant noise power of 10 in every cell."""
+    from avvad import ops
+    x, host = _frames_by_bins(X, "threshold_IBM")
+    out = ops.noise_aware_from_spectrum(x, None, outputs=("speech",), threshold_unvoiced_speech=threshold_unvoiced_speech,
+                                        threshold_voiced_speech=threshold_voiced_speech,
+                                        threshold_unvoiced_noise=threshold_unvoiced_noise,
+                                        threshold_voiced_noise=threshold_voiced_noise, low_cut=low_cut, high_cut=high_cut)
+    speech = out["speech"] != 0
+    return speech.cpu().numpy() if host else speech

@@ -36,6 +36,7 @@
  *           workspace                      16 bytes, every entry point (avvad_score_accumulate: 256)
  *           float64 statistics and score accumulators, score ratios, int64 confusion counts  8 bytes
  *           ratio / energies / clip_off of avvad_mix                                        8 bytes
+ *           c_speech / c_noise and the spectra of avvad_target_noise_aware*                 8 bytes
  *           int64 / int32 index arrays      their natural alignment
  *           bf16 operands, avvad_lip_decode's coef, the avvad_stft_stream basis,
  *           (checked by avvad_stft_stream_fwd / _fwd_spec), the avvad_istft_stream
@@ -84,7 +85,8 @@ typedef void* avvad_stream_t; /* hipStream_t */
                                  existing signature, so they keep the version: a version-3 binding still describes the
                                  library exactly for every symbol it binds.  The avvad_stats_* section is such an addition, and so
                                  are the avvad_score_* / avvad_confusion_* scores, and avvad_istft_bwd / avvad_resynth_bwd /
-                                 avvad_si_sdr_loss, and avvad_mix_workspace / avvad_mix. */
+                                 avvad_si_sdr_loss, and avvad_mix_workspace / avvad_mix, and the
+                                 avvad_target_noise_aware* masks. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -762,6 +764,39 @@ int avvad_target_ibm(const float* wave, const int* n_samples, const int* n_frame
  * aligned like every workspace. */
 int avvad_target_ibm_from_spectrum(const float* spec, long stride_t, long stride_f, const float* vad, float* out,
                                    const avvad_target_desc* d, void* ws, size_t ws_bytes, avvad_stream_t s);
+/* Noise-aware masks from the two components of a mixture, the speech X and the noise N (target.py noise_aware_IBM :151-202,
+ * threshold_IBM :205-251), and the ideal ratio mask of the same pair.  Per cell (b, t, f), every step in double:
+ *   p2 = (double)peak[b] * peak[b]   (1 when peak is NULL or p2 is not finite and positive: no scaling)
+ *   xP = ((double)re re + (double)im im) / p2 of X, nP likewise of N; nP = noise_psd when the noise spectrum is NULL
+ *        (threshold_IBM: 10)
+ *   speech = (xP / c_speech[f] > nP) && (xP / c_speech[f] > floor),  forced to 0 for f < low_cut - 1 and f >= high_cut
+ *   noise  = (xP / c_noise[f]  < nP) || (xP / c_noise[f]  < floor),  forced to 1 on the same bins
+ *   irm    = (float)(xP / (xP + nP)), 0 where xP + nP == 0; no cuts
+ * strict comparisons and cut indices as the reference writes them (floor: its 0.005).  c_speech / c_noise: DOUBLE [F]
+ * tables 10^(threshold_f / 10) computed on the host (no pow runs on the device), 8-byte aligned.  speech / noise / irm
+ * [B][T][F] float32, each may be NULL but not all three; frames t >= n_frames[b] (int32 [B], clamped to 0..T; NULL: T
+ * each) are written as zeros in all three.  peak: float [B] or NULL.  1 <= low_cut, high_cut <= F.  A pure function of
+ * its inputs: no atomics, no reduction.
+ * From spectra: interleaved (re, im) pairs, bin (b, t, f) at spec[b * stride_b + t * stride_t + f * stride_f] (float
+ * strides: even, stride_t and stride_f positive, stride_b positive unless B == 1; the pointer 8-byte aligned), the
+ * noise spectrum with strides of its own -- a [B][T][F][2] tensor, the legacy [F][T][2] view of one utterance and a
+ * column slice of a wider tensor go in as they are.  No workspace.
+ * From waveforms: speech_wave / noise_wave [B][d->L] (one pitch, rows zero-padded past each utterance; n_samples is not
+ * read and may be NULL), d as for the waveform IBM (center == 0, n_fft % 32 == 0; eps and the two coefficients are not
+ * read), F = n_fft/2 + 1.  The DFT runs once per wave with the batch's own (B, T), so both spectra are bit for bit those
+ * of the complex-spectrum entry point of the STFT front-end for the same batch.  ws: 16-byte aligned, at least the
+ * bytes of the query below (0 on a bad descriptor).
+ * Bad arguments are AVVAD_EINVAL and a short workspace AVVAD_EWORKSPACE, before anything is launched. */
+size_t avvad_target_noise_aware_workspace(const avvad_target_desc* d);
+int avvad_target_noise_aware_from_spectrum(const float* spec, long stride_b, long stride_t, long stride_f,
+                                           const float* noise_spec /* or NULL */, long nstride_b, long nstride_t,
+                                           long nstride_f, const int* n_frames, const float* peak, const double* c_speech,
+                                           const double* c_noise, int low_cut, int high_cut, double floor, double noise_psd,
+                                           float* speech, float* noise, float* irm, int B, int T, int F, avvad_stream_t s);
+int avvad_target_noise_aware(const float* speech_wave, const float* noise_wave, const int* n_samples, const int* n_frames,
+                             const float* peak, const double* c_speech, const double* c_noise, int low_cut, int high_cut,
+                             double floor, float* speech, float* noise, float* irm, const avvad_target_desc* d, void* ws,
+                             size_t ws_bytes, avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Video front-end: lip-region DCT coefficients -> the 67 x 67 crops of the trunk, at the STFT's frame rate

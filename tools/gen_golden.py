@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by RUNNING THE REFERENCE in the build container.
 
     python tools/gen_golden.py [group ...]   # needs /root/reference (absent on the GPU box); groups: wavenet audio
-                                             # video av misc metrics eval targets scores (default: all)
+                                             # video av misc metrics eval targets scores noise_aware (default: all)
 
 The reference's own classes/functions are imported from /root/reference and run
 on seeded inputs; only inputs, (small) weights and outputs are written -- data,
@@ -392,7 +392,31 @@ def gen_scores():
     save("scores", **arrs)
 
 
+# ------------------------------------------------------------------ noise-aware masks (packages/processing/target.py
+# :110-251): the reference's own noise_aware_IBM, threshold_IBM and split characteristic on the sa1 pair, both waves over
+# the noisy file's peak: X = STFT(clean / peak), N = STFT((noisy - clean) / peak) (stft_pytorch's transform with
+# return_complex, 64 ms, hop 0.25, center=False), transposed to (frames, bins).  Results only; writes noise_aware.npz.
+def gen_noise_aware():
+    from oracle import frontend
+    _librosa_stub()
+    from packages.processing import target as ref_target
+    clean = np.load(os.path.join(OUT, "utt_sa1_clean.npz"))["samples"].astype(np.float32) / 32768.0
+    noisy = np.load(os.path.join(OUT, "utt_sa1.npz"))["samples"].astype(np.float32) / 32768.0
+    peak = np.max(np.abs(noisy))
+
+    def spectrum(x):
+        S = torch.view_as_complex(frontend.stft(torch.from_numpy(x), wlen_sec=64e-3, center=False)).numpy()
+        return np.ascontiguousarray(S.T)
+    X, N = spectrum(clean / peak), spectrum((noisy - clean) / peak)
+    speech, noise = ref_target.noise_aware_IBM(X, N)
+    thr = ref_target.threshold_IBM(X)
+    voiced, unvoiced = ref_target._voiced_unvoiced_split_characteristic(513)
+    assert speech.shape == noise.shape == thr.shape == X.shape and X.shape[1] == 513
+    save("noise_aware", shape=np.array(X.shape, dtype=np.int64), speech=np.packbits(speech.astype(bool)),
+         noise=np.packbits(noise.astype(bool)), threshold=np.packbits(thr.astype(bool)), voiced=voiced, unvoiced=unvoiced)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["wavenet", "audio", "video", "av", "misc", "metrics", "eval", "targets", "scores"]
+    which = sys.argv[1:] or ["wavenet", "audio", "video", "av", "misc", "metrics", "eval", "targets", "scores", "noise_aware"]
     for w in which:
         globals()["gen_" + w]()
