@@ -119,10 +119,11 @@ def _cdiv(a, b):
     return -(-a // b)
 
 
-def gemm_plan(d, a_aligned=True, b_aligned=True, ws=True, **opt):
+def gemm_plan(d, a_aligned=True, b_aligned=True, ws=True, tile=None, **opt):
     """What ``avvad_gemm_f32`` launches for descriptor ``d`` (a dict of DESC_FIELDS), restated from the source; ``a_aligned`` /
     ``b_aligned``: the base pointer is 16-byte aligned; ``ws``: a workspace of avvad_engine_workspace() bytes is given; ``opt``:
-    the options of OPTIONS that are not at their defaults."""
+    the options of OPTIONS that are not at their defaults.  ``tile``: the plan of a caller that instantiates
+    ``igemm::launch<tile, tile>`` itself, whatever M and N are (the STFT, tests/stft_ref.py); None: the entry point's own rule."""
     assert set(opt) <= set(OPTIONS), opt
     M, N, K = d["M"], d["N"], d["K"]
     p = {}
@@ -138,7 +139,7 @@ def gemm_plan(d, a_aligned=True, b_aligned=True, ws=True, **opt):
     else:
         p["b_form"] = "ColPlain4" if d["ldb"] % 4 == 0 and N % 4 == 0 and b_aligned else "ColPlain1"
     # gemm.hip run1 (line 16): the tile
-    BM = BN = 64 if (M <= SMALL_TILE_AT or N <= SMALL_TILE_AT) else 128
+    BM = BN = tile if tile is not None else (64 if (M <= SMALL_TILE_AT or N <= SMALL_TILE_AT) else 128)
     big = BM == 128
     p["tile"] = BM
     # gemm.hip avvad_gemm_impl (line 40): the epilogue mode
