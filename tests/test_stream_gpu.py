@@ -1,7 +1,9 @@
 """Streaming inference on the GPU: the LSTM layer with state, the streaming encoder and the session, against torch on
 the CPU, the oracle and the golden vectors the reference produced.  Bounds are the project's own: outputs |d| <= 1e-4
 (BASELINE north star); intermediate / unbounded quantities (c_n) atol 1e-4 + rtol 1e-5 |ref|, as on the trunk
-features.  Observed maxima are appended to the parity log, the way test_gpu_parity._report does."""
+features.  Observed maxima are appended to the parity log, the way test_gpu_parity._report does.  The kernels themselves,
+fed directly with per-row schedules and held element-wise to float64 references, are in tests/test_stream_kernels_gpu.py
+(oracle: tests/stream_ref.py)."""
 import os
 import random
 
