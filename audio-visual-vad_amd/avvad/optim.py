@@ -49,7 +49,23 @@ class FlatAdam:
             if st != cur:
                 cur.wait_stream(st)
 
+    def _check_grads(self):
+        """Every ``.grad`` must still be its view into ``flat_grad``: a gradient that autograd built elsewhere (after
+        ``p.grad = None`` -- the default of ``Module.zero_grad()`` and of torch's optimisers -- or after ``.grad`` was
+        replaced) never reaches the flat buffer, and the step would apply zeros in its place.  Host-side pointer
+        comparison only, as in ``zero_grad()``: no launch, no synchronisation."""
+        base = self.flat_grad.data_ptr()
+        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
+            g = p.grad
+            if g is None or g.data_ptr() != base + 4 * o:
+                raise L.AvvadError(
+                    "FlatAdam.step(): the gradient of parameter %d (shape %s) is %s, so this step would ignore it; "
+                    "clear gradients with FlatAdam.zero_grad() only (it re-attaches the views), never with "
+                    "set_to_none or by assigning .grad" % (i, tuple(p.shape), "None" if g is None else
+                                                            "no longer its view into the flat gradient buffer"))
+
     def step(self):
+        self._check_grads()
         self._join()
         self.t += 1
         L.check(L.lib().avvad_adam_step(L.ptr(self.flat), L.ptr(self.flat_grad), L.ptr(self.exp_avg),
