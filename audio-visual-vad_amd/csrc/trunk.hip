@@ -764,6 +764,7 @@ static int conv_fwd_engine(const float* x, const float* wf, float* y, const Geom
   const int M = g.N * g.Ho * g.Wo, T = g.KS * g.KS, K = T * g.C;
   igemm::EpiStore e{y, g.Co, nullptr, 0};
   if constexpr (!B16) {
+    if (g.Co % 4) return AVVAD_EINVAL;                         // ColPlain<4> / ColTapRows fetch 16 bytes of a weight row
     if (g.C == 1) {                                            // the stem's own operands
       igemm::ColPlain<4> b{wf, g.Co, g.Co, K, 0};
       convop::StemFwd a{x, g, M, K};
@@ -813,22 +814,33 @@ static int conv_dgrad_cls(const float* dy, const float* wd, float* dx, const Geo
 template <class Gemm>
 static int dgrad_parity(float* dx, const Geom& g, int accumulate, hipStream_t s, Gemm gemm) {
   const long n = (long)g.N * g.H * g.W * g.C;
+  const auto cls = [&](int ph, int pw) {
+    convop::S2Class c;
+    c.ph = ph; c.pw = pw;
+    c.Hc = (g.H - ph + 1) / 2; c.Wc = (g.W - pw + 1) / 2;
+    c.kh0 = (ph + g.pad) & 1; c.kw0 = (pw + g.pad) & 1;
+    c.nkh = c.kh0 < g.KS ? (g.KS - c.kh0 + 1) / 2 : 0;
+    c.nkw = c.kw0 < g.KS ? (g.KS - c.kw0 + 1) / 2 : 0;
+    c.oh = (ph + g.pad - c.kh0) / 2; c.ow = (pw + g.pad - c.kw0) / 2;
+    c.mg_ntap = c.mg_nkw = 0u;
+    return c;
+  };
+  // every refusal comes before the first launch: a refused call leaves dx as it was
+  for (int q = 0; q < 4; ++q) {
+    const convop::S2Class c = cls(q >> 1, q & 1);
+    const int Mc = g.N * c.Hc * c.Wc, ntap = c.nkh * c.nkw;
+    if (Mc <= 0 || ntap <= 0) continue;
+    if (ntap > 4) return AVVAD_EINVAL;
+    if ((unsigned long)(Mc + 128) * (unsigned long)(c.Hc * c.Wc) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
+  }
   if (!accumulate) hipLaunchKernelGGL(zero_f32, dim3(ew_grid(n)), dim3(256), 0, s, dx, n);
   for (int ph = 0; ph < 2; ++ph)
     for (int pw = 0; pw < 2; ++pw) {
-      convop::S2Class c;
-      c.ph = ph; c.pw = pw;
-      c.Hc = (g.H - ph + 1) / 2; c.Wc = (g.W - pw + 1) / 2;
-      c.kh0 = (ph + g.pad) & 1; c.kw0 = (pw + g.pad) & 1;
-      c.nkh = c.kh0 < g.KS ? (g.KS - c.kh0 + 1) / 2 : 0;
-      c.nkw = c.kw0 < g.KS ? (g.KS - c.kw0 + 1) / 2 : 0;
-      c.oh = (ph + g.pad - c.kh0) / 2; c.ow = (pw + g.pad - c.kw0) / 2;
+      convop::S2Class c = cls(ph, pw);
       const int Mc = g.N * c.Hc * c.Wc, ntap = c.nkh * c.nkw;
       if (Mc <= 0 || ntap <= 0) continue;
-      if (ntap > 4) return AVVAD_EINVAL;
       c.mg_ntap = convop::div_magic(ntap); c.mg_nkw = convop::div_magic(c.nkw);
       const convop::EpiS2 e{dx, g.C, nullptr, 1, 1, g.H, g.W, c.Hc, c.Wc, ph, pw, convop::div_magic(c.Hc * c.Wc), convop::div_magic(c.Wc)};
-      if ((unsigned long)(Mc + 128) * (unsigned long)(c.Hc * c.Wc) >= 0x100000000ull) return AVVAD_EINVAL;   // fast_div range
       if (const int rc = gemm(c, Mc, ntap, e)) return rc;
     }
   return AVVAD_OK;
@@ -893,6 +905,9 @@ static int conv_wgrad_tap(const float* x, const float* dy, float* pk, const Geom
 template <bool B16, bool BUF>
 static int conv_wgrad_engine(const float* x, const float* dy, float* pk, const Geom& g, const ConvForm& f, hipStream_t s, float* slab) {
   const int T = g.KS * g.KS, M = T * g.C, K = g.N * g.Ho * g.Wo;
+  // ColPlain<4> fetches 16 bytes of a dy row: with Co % 4 != 0 the last fetch of a row runs into the next one and, in the last
+  // row, past the operand's end (the bf16 path's Co % 64 == 0 is checked by bf16_conv_ok)
+  if (!B16 && g.Co % 4) return AVVAD_EINVAL;
   igemm::ColPlain<4, BUF> b{dy, g.Co / UNIT<B16>, g.Co / UNIT<B16>, K, 0};
   int split = 1;                                               // (the fp32 engine's split-K hint)
   if constexpr (!B16) {
@@ -1065,6 +1080,7 @@ static int tab_shapes(Tab& tab, const Plan& p, int stem_blocks) {
 static bool conv_geom(const avvad_conv_desc* d, Geom* g) {
   if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0 || d->Co <= 0 || d->KS <= 0 || d->stride <= 0 || d->pad < 0)
     return false;
+  if (d->H + 2 * d->pad < d->KS || d->W + 2 * d->pad < d->KS) return false;      // (C division rounds -1 / 2 to 0: no window fits)
   const int Ho = (d->H + 2 * d->pad - d->KS) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->KS) / d->stride + 1;
   if (Ho <= 0 || Wo <= 0 || (d->stride != 1 && d->stride != 2)) return false;
   *g = Geom{d->N, d->H, d->W, d->C, Ho, Wo, d->Co, d->KS, d->stride, d->pad};

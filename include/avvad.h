@@ -251,6 +251,9 @@ typedef struct {
  * per launch for the roofline).  x [N][H][W][C] NHWC, y [N][Ho][Wo][Co]; square kernel KS, stride 1|2.
  * Weights are packed once from OIHW: wf [(kh,kw,c)][co] (forward) and wd [(kh,kw,co)][c] (dgrad; may be
  * NULL).  C must be 1 (stem, forward/wgrad only) or a multiple of 32; Co a multiple of 4.
+ * dgrad also needs Co % 32 == 0; forward and dgrad a kernel of at most 32 taps (C > 1); dgrad with stride 2 needs KS <= 4.
+ * A shape outside these limits, or one in which no window fits (H + 2 pad < KS), is refused with AVVAD_EINVAL before
+ * anything is launched: the output buffer keeps every bit.
  * wgrad writes the packed layout [(kh,kw,c)][co] (overwritten).  ws: avvad_engine_workspace() bytes.  Replaces nn.Conv2d inside
  * torchvision's resnet18 (packages/models/Video_Net.py:35-37). */
 typedef struct {
