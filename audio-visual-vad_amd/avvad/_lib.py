@@ -19,6 +19,7 @@ TRUNK_NCONV = 20
 ABI_VERSION = 3          # include/avvad.h AVVAD_ABI_VERSION: the signatures below describe exactly this version
 SCORE_CHUNK = 4096       # include/avvad.h AVVAD_SCORE_CHUNK: samples of one partial of avvad_score_accumulate
 MIX_CHUNK = 4096         # include/avvad.h AVVAD_MIX_CHUNK: samples of one energy partial of avvad_mix
+SPECTRAL_CHUNK = 2048    # include/avvad.h AVVAD_SPECTRAL_CHUNK: cells of one partial of avvad_spectral_loss
 _ERR = {-1: "AVVAD_EINVAL (bad descriptor / unsupported shape)", -2: "AVVAD_EWORKSPACE (workspace too small)",
         -3: "AVVAD_ELAUNCH (kernel launch failed)"}
 
@@ -177,6 +178,9 @@ SIGNATURES = {
     "avvad_si_sdr_loss_workspace": (C.c_size_t, [C.c_int, C.c_long]),
     "avvad_si_sdr_loss": (C.c_int, [FP, C.c_long, FP, C.c_long, FP, FP, FP, FP, C.c_long, C.c_int, C.c_long, FP, C.c_size_t, FP]),
     "avvad_confusion_accumulate": (C.c_int, [FP, C.c_int, FP, FP, FP, C.c_int, C.c_int, C.c_int, FP]),
+    "avvad_spectral_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "avvad_spectral_loss": (C.c_int, [FP, C.c_int, C.c_int, FP, FP, C.c_long, C.c_long, C.c_long, FP, C.c_long, C.c_long, C.c_long,
+                                      FP, FP, FP, FP, C.c_int, C.c_int, C.c_int, FP, C.c_size_t, FP]),
     "avvad_mix_workspace": (C.c_size_t, [C.c_int, C.c_long]),
     "avvad_mix": (C.c_int, [FP, C.c_long, FP, FP, C.c_long, FP, FP, C.c_int, FP, FP, FP, FP, C.c_long, FP, C.c_long, FP, FP, FP,
                             C.c_int, C.c_long, FP, C.c_size_t, FP]),

@@ -1781,6 +1781,96 @@ def noise_aware_from_spectrum(X, N=None, n_frames=None, peak=None, outputs=("spe
     return res if batched else {o: v[0] for o, v in res.items()}
 
 
+# --------------------------------------------------------------------------- mask-regression losses (csrc/spectral_loss.hip)
+SPECTRAL_CHUNK = L.SPECTRAL_CHUNK    # cells of one partial of the loss pass (include/avvad.h AVVAD_SPECTRAL_CHUNK)
+SPECTRAL_KINDS = {"mask": 0, "signal": 1, "spectrum": 2}
+
+
+class SpectralLossFn(torch.autograd.Function):
+    """The summed mask-regression loss of a ragged batch and its gradient in ``pred`` from the same call
+    (avvad_spectral_loss); without a gradient to compute (``pred`` needs none) the kernel writes none."""
+
+    @staticmethod
+    def forward(ctx, pred, kind, pred_mode, target, mix4, speech4, lens32):
+        B, T, F = pred.shape
+        p = pred.detach()
+        loss = torch.empty(1, dtype=torch.float32, device=p.device)
+        rows = torch.empty(B, dtype=torch.float64, device=p.device)
+        dpred = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        ws = _ws(L.lib().avvad_spectral_loss_workspace(B, T, F), p.device)
+
+        def strides(s4):                    # (one row: its batch stride is not read)
+            return (0, 0, 0) if s4 is None else ((s4.stride(0) if B > 1 else 0,) + tuple(s4.stride()[1:3]))
+        L.check(L.lib().avvad_spectral_loss(L.ptr(p), pred_mode, kind, L.ptr(target), L.ptr(mix4), *strides(mix4), L.ptr(speech4),
+                                            *strides(speech4), L.ptr(lens32), L.ptr(loss), L.ptr(rows), L.ptr(dpred), B, T, F,
+                                            L.ptr(ws), ws.numel() * 4, _stream()), "avvad_spectral_loss")
+        if dpred is not None:
+            ctx.save_for_backward(dpred)
+        ctx.mark_non_differentiable(rows)
+        return loss.view(()), rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss, _drows):
+        (dpred,) = ctx.saved_tensors
+        g = dpred.clone()
+        L.check(L.lib().avvad_scale_by_device_scalar(L.ptr(g), L.ptr(_dev(dloss, "dloss").view(1)), g.numel(), _stream()),
+                "avvad_scale_by_device_scalar")
+        return g, None, None, None, None, None, None
+
+
+def spectral_loss(pred, kind, target=None, mix=None, speech=None, lengths=None, pred_mode=2, return_rows=False):
+    """The mask-regression losses of ``packages/models/utils.py:151-162`` for a ragged batch, as a float32 scalar that is
+    differentiable in ``pred`` (B, T, F) (or one utterance (T, F)).  ``pred_mode`` 2: ``pred`` holds logits and the mask is
+    ``m = sigmoid(pred)``; 1: ``pred`` is the mask itself (``ops.istft``'s numbers).  ``kind``:
+      "mask"      ``(y - m)^2``                 ``target`` y, float32, shaped like ``pred``
+      "signal"    ``((y - m) |X|)^2``           ``target`` and ``mix`` X
+      "spectrum"  ``|S - m X|^2`` (complex)     ``mix`` X and ``speech`` S
+    summed over the bins, averaged over each row's first ``lengths[b]`` frames (None: T) and summed over the batch, like
+    ``masked_bce`` and ``si_sdr_loss``; a row of length 0 adds nothing.  ``mix`` / ``speech``: complex64 (T, F) or
+    (B, T, F) GPU tensors or their float32 (..., 2) views -- ``ops.stft_complex``'s (B, T, F, 2), a transposed legacy
+    (F, T, 2) view -- read in place through their strides.  ``target``, ``mix`` and ``speech`` are data: no gradient.
+    Double sums in a fixed order: bit-identical run to run, and a row's value and gradient do not depend on its batch.
+    ``return_rows``: also the (B,) float64 per-row losses."""
+    if kind not in SPECTRAL_KINDS:
+        raise L.AvvadError("kind %r: one of %s" % (kind, ", ".join(SPECTRAL_KINDS)))
+    if pred_mode not in (1, 2):
+        raise L.AvvadError("pred_mode must be 1 (pred is the mask) or 2 (pred holds logits), got %r" % (pred_mode,))
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda or pred.dim() not in (2, 3) or 0 in pred.shape:
+        raise L.AvvadError("pred must be a (B, T, F) or (T, F) GPU tensor: the AV-VAD hot path has no CPU fallback")
+    if pred.dtype != torch.float32:
+        raise L.AvvadError("pred must be float32, got %s" % pred.dtype)
+    k = SPECTRAL_KINDS[kind]
+    p = (pred.unsqueeze(0) if pred.dim() == 2 else pred).contiguous()
+    B, T, F = p.shape
+    y = x4 = s4 = None
+    if k < 2:
+        if target is None:
+            raise L.AvvadError("kind %r needs target" % kind)
+        y = _dev(target.detach() if isinstance(target, torch.Tensor) else target, "target")
+        if y.numel() != p.numel() or tuple(y.shape[-2:]) != (T, F) or y.device != p.device:
+            raise L.AvvadError("target %s must have the shape and device of pred %s" % (tuple(y.shape), tuple(pred.shape)))
+    for name, spec, need in (("mix", mix, k >= 1), ("speech", speech, k == 2)):
+        if not need:
+            continue
+        if spec is None:
+            raise L.AvvadError("kind %r needs %s" % (kind, name))
+        v4, _ = _spectrum_view(spec.detach() if isinstance(spec, torch.Tensor) else spec, name)
+        if tuple(v4.shape[:3]) != (B, T, F) or v4.device != p.device:
+            raise L.AvvadError("%s %s must hold the (B, T, F) = %s complex bins of pred, on its device" % (name, tuple(v4.shape), (B, T, F)))
+        if name == "mix":
+            x4 = v4
+        else:
+            s4 = v4
+    lens32 = None
+    if lengths is not None:
+        lens32 = lengths_i32(lengths, p.device)
+        if lens32.numel() != B:
+            raise L.AvvadError("lengths must hold %d values, got %d" % (B, lens32.numel()))
+    loss, rows = SpectralLossFn.apply(p, k, int(pred_mode), y, x4, s4, lens32)
+    return (loss, rows) if return_rows else loss
+
+
 # --------------------------------------------------------------------------- video front-end: lip DCT frames (no gradient)
 LIP_W = LIP_H = 67
 

@@ -315,7 +315,7 @@ def check_mix_labels(mix_labels, mixing, y_dim=None):
 
 
 def mix_step(batch, device, labels, bank, draw, stats=None, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS, waves=False,
-             mix_labels="clean"):
+             mix_labels="clean", peak=False):
     """A ``CleanWavs.collate`` batch -> what ``wav_pair_step`` returns, with a mixture made in the step in place of the noisy
     file: the clean waves are peak-normalised, ``draw(lengths)`` gives every row a clip of ``bank``, a start and an SNR
     in dB (``draw_mix``), ``ops.mix`` adds the noise at that SNR on the GPU, and the mixture is peak-normalised like a
@@ -325,7 +325,9 @@ def mix_step(batch, device, labels, bank, draw, stats=None, fs=16e3, wlen_sec=64
     ``mix_labels``: "clean" labels the clean wave alone (``labels``); "noise_aware" / "irm" (``labels`` "ibm_labels" only)
     take the target from the mixture's two components instead -- the speech mask of ``noise_aware_IBM`` or the ideal ratio
     mask of (clean, ``g_b n``), both over the mixture's peak, i.e. on the scale of the normalised mixture the model sees
-    (``ops.noise_aware_targets``) -- and compute no clean-speech label."""
+    (``ops.noise_aware_targets``) -- and compute no clean-speech label.
+    ``peak`` (with ``waves``): a fifth member of that tuple, the (B,) peak of the mixture before its normalisation
+    (``ops.mix``'s ``info["peak"]``), the scale a spectrum-approximation loss puts the clean spectrum on."""
     check_mix_labels(mix_labels, True)
     if mix_labels != "clean" and labels != "ibm_labels":
         raise ValueError("mix_labels %r are 513-bin masks: they go with labels 'ibm_labels', got %r" % (mix_labels, labels))
@@ -334,27 +336,37 @@ def mix_step(batch, device, labels, bank, draw, stats=None, fs=16e3, wlen_sec=64
     n = [int(v) for v in lens]
     clip, start, snr = draw(n)
     made = None
-    if mix_labels == "clean":
+    if mix_labels == "clean" and not peak:
         mixed = ops.mix(clean, n, bank, clip, start, snr, return_noise=waves)
         noisy, more = (mixed[0], (mixed[1],)) if waves else (mixed, ())
     else:
         noisy, noise, info = ops.mix(clean, n, bank, clip, start, snr, return_noise=True, return_info=True)
-        which = MIX_LABELS[mix_labels]
-        frames, out = ops.noise_aware_targets(clean, noise, n, peak=info["peak"], outputs=(which,), fs=fs, wlen_sec=wlen_sec,
-                                              hop_percent=hop_percent, pad_at_end=True)
-        made, more = (frames, out[which]), ((noise,) if waves else ())
+        if mix_labels != "clean":
+            which = MIX_LABELS[mix_labels]
+            frames, out = ops.noise_aware_targets(clean, noise, n, peak=info["peak"], outputs=(which,), fs=fs, wlen_sec=wlen_sec,
+                                                  hop_percent=hop_percent, pad_at_end=True)
+            made = (frames, out[which])
+        more = ((noise,) if waves else ()) + ((info["peak"],) if waves and peak else ())
     return _pair_tail(lens, ops.peak_normalize(noisy), clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves, more,
                       made)
 
 
-OBJECTIVES = ("bce", "si_sdr")
+SPECTRAL_OBJECTIVES = {"mse_mask": "mask", "mse_signal": "signal", "msa": "spectrum"}      # -> the kind of ops.spectral_loss
+OBJECTIVES = ("bce", "si_sdr") + tuple(SPECTRAL_OBJECTIVES)
 
 
 def check_objective(objective, kind, waveform, wav_pairs, y_dim=None, clean_wavs=None):
     """``objective`` "si_sdr" trains a 513-bin mask model of the audio network on wav pairs, or on clean utterances mixed
-    with noise in the step (``clean_wavs``); anything else is a ValueError (``y_dim`` None: not known yet)."""
+    with noise in the step (``clean_wavs``), and so do the mask-regression objectives "mse_mask", "mse_signal" and "msa";
+    anything else is a ValueError (``y_dim`` None: not known yet)."""
     if objective not in OBJECTIVES:
         raise ValueError("objective %r: one of %s" % (objective, ", ".join(OBJECTIVES)))
+    if objective in SPECTRAL_OBJECTIVES:
+        if kind != "audio" or waveform or (wav_pairs is None and clean_wavs is None):
+            raise ValueError("objective %r trains the audio network on spectrograms of wav_pairs, or of clean_wavs mixed with "
+                             "noise_wavs: it regresses the model's mask onto the step's label or spectra" % objective)
+        if y_dim is not None and y_dim != 513:
+            raise ValueError("objective %r needs a 513-bin mask head (y_dim 513), got y_dim %d" % (objective, y_dim))
     if objective == "si_sdr":
         if kind != "audio" or waveform or (wav_pairs is None and clean_wavs is None):
             raise ValueError("objective 'si_sdr' trains the audio network on spectrograms of wav_pairs: it resynthesises "
@@ -392,6 +404,60 @@ class SiSdrObjective:
         skip = self.n_fft - self.hop
         loss, ratios = ops.si_sdr_loss(est, clean, lens, skip, skip, return_ratios=True)
         return loss, "  si-sdr %.2f dB" % float(torch.nanmean(ratios))
+
+
+class SpectralObjective:
+    """The step of the mask-regression objectives "mse_mask", "mse_signal" and "msa" (``ops.spectral_loss`` on
+    sigmoid(logits), summed over the batch like the BCE).  ``prepare`` is ``wav_pair_step`` -- or ``step``, ``mix_step``
+    with ``waves`` and ``peak`` -- and keeps what the loss needs:
+      "mse_mask", "mse_signal": the step's own label -- the IBM of the clean wave, or the noise-aware mask / IRM of a mixture;
+      "mse_signal", "msa":      X = ``ops.stft_complex`` of the peak-normalised mixture, the one the features come from;
+      "msa":                    S = ``ops.stft_complex`` of the clean wave over the MIXTURE's peak, not its own, so that S
+                                and X are on one scale (the reference's metrics script scales ``s_t / norm_max`` the same
+                                way).  For a mixture made in the step that peak is ``ops.mix``'s ``info["peak"]`` and the
+                                clean wave is the one the noise was added to; for a wav pair it is the noisy file's
+                                ``abs_max`` and the clean wave is the clean file as read.
+    The spectra's frame count must be the features' (``_pair_tail``'s check).  ``loss`` returns the summed loss and the
+    batch's mean per-utterance loss for the log line."""
+
+    def __init__(self, objective, device, labels, stats, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, step=None):
+        self.kind = SPECTRAL_OBJECTIVES[objective]
+        self.name = objective
+        self.device, self.labels, self.stats = device, labels, stats      # stats: a callable, read at every step
+        self.fs, self.wlen_sec, self.hop_percent = fs, wlen_sec, hop_percent
+        self.n_fft = int(wlen_sec * fs)
+        self.hop = int(hop_percent * self.n_fft)
+        self.step = step                  # (batch, stats) -> mix_step's four values with the peak; None: wav pairs
+        self.mix = self.speech = None
+
+    def _spectrum(self, wave, T):
+        spec = ops.stft_complex(wave, self.n_fft, self.hop, pad_at_end=True, fs=self.fs)
+        if spec.shape[1] != T:
+            raise RuntimeError("spectrum frames %d != label frames %d" % (spec.shape[1], T))
+        return spec
+
+    def prepare(self, batch):
+        if self.step is not None:
+            frames, x, target, (noisy, clean, _lens, _noise, peak) = self.step(batch, self.stats())
+        else:
+            lens, noisy, clean = batch
+            noisy, clean = noisy.to(self.device, non_blocking=True), clean.to(self.device, non_blocking=True)
+            peak = ops.peak(noisy)
+            frames, x, target, (noisy, _clean, _lens) = _pair_tail(
+                lens, ops.peak_normalize(noisy), ops.peak_normalize(clean), self.device, self.labels, self.stats(), self.fs,
+                self.wlen_sec, self.hop_percent, EPS, True)
+        T = target.shape[1]
+        self.mix = self._spectrum(noisy, T) if self.kind != "mask" else None
+        self.speech = None
+        if self.kind == "spectrum":         # (a silent mixture has nothing to scale by: its clean wave stays as it is)
+            scale = torch.where(peak > 0, 1.0 / peak, torch.ones_like(peak))
+            self.speech = self._spectrum(clean * scale[:, None], T)
+        return frames, x, target
+
+    def loss(self, logits, y, lengths):
+        loss, rows = ops.spectral_loss(logits, self.kind, target=y if self.kind != "spectrum" else None, mix=self.mix,
+                                       speech=self.speech, lengths=lengths, pred_mode=2, return_rows=True)
+        return loss, "  %s/utt %.4f" % (self.name, float(rows.mean()))
 
 
 def rank_shard(n, rank, world):
@@ -634,7 +700,11 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
 
     ``objective``: "bce" (the summed masked BCE against the labels) or, with ``wav_pairs`` and a y_dim 513 head, "si_sdr":
     minus the SI-SDR of the noisy file resynthesised through sigmoid(logits) against the clean file (``SiSdrObjective``);
-    the F1 figures against the IBM label stay in the log.  AVVAD_OBJECTIVE overrides it.
+    the F1 figures against the IBM label stay in the log.  Under the same conditions (``wav_pairs``, or ``clean_wavs`` with
+    ``noise_wavs``; a y_dim 513 head) the mask-regression objectives of ``ops.spectral_loss`` on sigmoid(logits)
+    (``SpectralObjective``): "mse_mask", the squared error against the step's label; "mse_signal", that error weighted by
+    the mixture's magnitude; "msa", the complex spectrum approximation ``|S - m X|^2`` of the clean spectrum by the masked
+    mixture.  Validation reports the same loss.  AVVAD_OBJECTIVE overrides it.
 
     ``clean_wavs`` + ``noise_wavs`` (audio network, spectrogram input, both objectives; instead of ``wav_pairs``): lists
     or text files of clean utterances (``CleanWavs``) and of noise clips (``read_noise_bank``).  Every batch is mixed on
@@ -647,7 +717,8 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     ``mix_labels`` (with ``clean_wavs`` + ``noise_wavs`` and a y_dim 513 head): "clean" (the default) labels the clean
     utterance alone, as wav pairs are labelled; "noise_aware" trains against the speech mask of the reference's
     ``noise_aware_IBM`` and "irm" against the ideal ratio mask, both computed in the step from the clean wave and the
-    noise that was just added (``mix_step``).  With ``objective="si_sdr"`` the label feeds the F1 log line only."""
+    noise that was just added (``mix_step``).  With ``objective="si_sdr"`` or "msa" the label feeds the F1 log line only;
+    "mse_mask" and "mse_signal" regress onto it."""
     objective = os.environ.get("AVVAD_OBJECTIVE", objective)
     check_objective(objective, kind, waveform, wav_pairs, clean_wavs=clean_wavs)
     check_mix_labels(mix_labels, clean_wavs is not None and noise_wavs is not None)
@@ -698,6 +769,11 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
                                   step=lambda batch, st: mix_step(batch, device, labels, bank, mixer, st, waves=True,
                                                                    mix_labels=mix_labels))
             prepare, loss_fn = step.prepare, step.loss
+        elif objective in SPECTRAL_OBJECTIVES:
+            step = SpectralObjective(objective, device, labels, lambda: stats,
+                                     step=lambda batch, st: mix_step(batch, device, labels, bank, mixer, st, waves=True,
+                                                                      mix_labels=mix_labels, peak=True))
+            prepare, loss_fn = step.prepare, step.loss
     elif av_files is not None:
         pairs = AVFiles(av_files)
         labels = labels_for_ydim(model.y_dim)
@@ -720,6 +796,9 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         prepare = lambda batch: wav_pair_step(batch, device, labels, stats)   # noqa: E731
         if objective == "si_sdr":
             step = SiSdrObjective(device, labels, lambda: stats)
+            prepare, loss_fn = step.prepare, step.loss
+        elif objective in SPECTRAL_OBJECTIVES:
+            step = SpectralObjective(objective, device, labels, lambda: stats)
             prepare, loss_fn = step.prepare, step.loss
     mk = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=batch_size // world or 1, shuffle=sh, collate_fn=collate)
     out_dir = out_dir or os.path.join("models", model_name)

@@ -1,7 +1,8 @@
 """Drop-in for the hot-path members of ``packages/models/utils.py``: ``binary_cross_entropy`` (``:108-113``),
 ``binary_cross_entropy_2classes`` (``:115-116``), ``f1_loss`` (``:164-203``), ``method3`` (``:36-55``),
-``weights_init_normal`` (``:5-26``).  The VAE-era helpers
-of that file are not on the path and are not provided."""
+``weights_init_normal`` (``:5-26``), and the mask-regression losses ``mean_square_error_signal`` (``:151-154``),
+``mean_square_error_mask`` (``:156-158``) and ``magnitude_spectrum_approxiamation_loss`` (``:160-162``).  The VAE-era
+helpers of that file (the Itakura-Saito and KL terms) are not on the path and are not provided."""
 import torch
 
 from avvad import ops
@@ -31,6 +32,31 @@ def binary_cross_entropy_2classes(r1, r2, x, eps):
     """-mean(sum(x log(r1+eps) + (1-x) log(r2+eps), dim=-1)) on two probability outputs (reference ``:115-116``,
     imported by ``scripts/train_video_net.py:18``) -- HIP loss kernel, value and both gradients."""
     return ops.Bce2ClassesFn.apply(r1, r2, x, eps)
+
+
+def _as_complex(t):
+    """a complex (T, F) spectrum as ``ops.spectral_loss`` takes it; a real one (a magnitude) gets a zero imaginary part"""
+    if t.is_complex():
+        return t.to(torch.complex64)
+    return torch.complex(t.to(torch.float32), torch.zeros_like(t, dtype=torch.float32))
+
+
+def mean_square_error_mask(y, y_hat):
+    """mean(sum((y - y_hat)^2, axis=-1)) of one utterance's (T, F) mask probabilities ``y_hat`` against the label ``y``
+    (reference ``:156-158``) -- HIP loss kernel, value and the gradient in ``y_hat``."""
+    return ops.spectral_loss(y_hat, "mask", target=y.to(torch.float32), pred_mode=1)
+
+
+def mean_square_error_signal(x, y, y_hat):
+    """mean(sum(((y - y_hat) x)^2, axis=-1)) (reference ``:151-154``): ``x`` (T, F) is the mixture's spectrum, complex
+    (its magnitude is taken) or already a magnitude."""
+    return ops.spectral_loss(y_hat, "signal", target=y.to(torch.float32), mix=_as_complex(x), pred_mode=1)
+
+
+def magnitude_spectrum_approxiamation_loss(x, s, y_hat):
+    """mean(sum(real((s - y_hat x) conj(s - y_hat x)), axis=-1)) (reference ``:160-162``, its spelling): ``x`` and ``s``
+    are the complex (T, F) spectra of the mixture and of the clean speech."""
+    return ops.spectral_loss(y_hat, "spectrum", mix=_as_complex(x), speech=_as_complex(s), pred_mode=1)
 
 
 def batch_binary_cross_entropy(logits, targets, lengths, eps):

@@ -31,7 +31,10 @@ wav_pairs = None          # text file with one "noisy.wav clean.wav" pair per li
 compute_stats = False     # with wav_pairs and no trainset_audio_*.npy yet: compute the train-set mean / std over the pairs on
                           # the GPU before the first epoch and save them in models/<model_name> (the evaluate scripts' stats_dir)
 objective = 'bce'         # 'si_sdr' (wav_pairs, y_dim 513): minus the SI-SDR of the noisy file resynthesised through the
-                          # sigmoid of the logits, against the clean file; the F1 figures against the IBM stay in the log
+                          # sigmoid of the logits, against the clean file; the F1 figures against the IBM stay in the log.
+                          # 'mse_mask' | 'mse_signal' | 'msa' (same conditions): the mask-regression losses on the sigmoid of
+                          # the logits -- squared error against the label, that error weighted by the mixture's magnitude,
+                          # the complex spectrum approximation |S - m X|^2 (avvad.train.SpectralObjective)
 wavenet_params = dict(filter_width=2, quantization_channel=1, dilations=[2 ** i for i in range(10)] * 2,
                       en_residual_channel=32, en_dilation_channel=32, en_bottleneck_width=256,
                       en_pool_kernel_size=16, use_bias=True)

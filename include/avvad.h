@@ -86,7 +86,8 @@ typedef void* avvad_stream_t; /* hipStream_t */
                                  library exactly for every symbol it binds.  The avvad_stats_* section is such an addition, and so
                                  are the avvad_score_* / avvad_confusion_* scores, and avvad_istft_bwd / avvad_resynth_bwd /
                                  avvad_si_sdr_loss, and avvad_mix_workspace / avvad_mix, and the
-                                 avvad_target_noise_aware* masks. */
+                                 avvad_target_noise_aware* masks, and avvad_spectral_loss_workspace /
+                                 avvad_spectral_loss. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -683,6 +684,43 @@ int avvad_si_sdr_loss(const float* est, long ld_est, const float* ref, long ld_r
  * not read. */
 int avvad_confusion_accumulate(const float* pred, int pred_mode, const float* target, const int* lengths,
                                long long* counts /* [B][4], added to */, int B, int T, int Y, avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Mask-regression training losses of a (B, T, F) mask head: mask MSE, signal approximation, spectrum approximation
+ * Replaces: packages/models/utils.py:151-162 (mean_square_error_signal, mean_square_error_mask,
+ *   magnitude_spectrum_approxiamation_loss), each a torch composition over one utterance.
+ * pred [B][T][F] contiguous.  pred_mode 1: pred is the mask m itself and dpred the gradient in the mask; 2: m =
+ * sigmoid(pred) and dpred the gradient in the logits (the numbers of avvad_istft_desc.mask_mode).  Per cell (b, t, f):
+ *   kind 0 (mask):      (y - m)^2                          y = target[b][t][f]
+ *   kind 1 (signal):    ((y - m) x)^2                      x = |X|, the magnitude of the mixture's complex bin
+ *   kind 2 (spectrum):  |S - m X|^2                        the complex difference, real(d conj(d))
+ *   row_b = (1 / len_b) sum_{t < len_b} sum_f term         (the reference's mean(sum(., axis=-1)) over the valid frames)
+ *   loss[0] = sum_b row_b                                  (a fixed order that depends on B alone, in double, rounded once to float)
+ *   dpred = d loss / d pred, exact zeros on frames t >= len_b; the whole [B][T][F] buffer is written (NULL: skipped)
+ * len_b = n_frames[b] clamped to [0, T] (NULL: T each); a row with len_b == 0 adds nothing and divides by nothing.
+ * Terms and gradients are evaluated in float32, every sum is in double.  row_loss: NULL or [B] doubles, 8-byte aligned.
+ * target [B][T][F] contiguous (kind 0, 1; not read for kind 2 and may be NULL).  mix (kind 1, 2) and speech (kind 2) hold
+ * interleaved (re, im) float pairs, bin (b, t, f) at p[b * stride_b + t * stride_t + f * stride_f] (float strides: even,
+ * stride_t and stride_f positive, stride_b positive unless B == 1; the pointer 8-byte aligned) -- a [B][T][F][2] tensor,
+ * the legacy [F][T][2] view of one utterance and a complex (F, T) tensor go in as they are.  Nothing of pred, target or
+ * the spectra at or behind len_b is read.  pred / target / dpred: any 4-byte aligned float pointers.
+ * A row's T * F cells are cut into chunks of AVVAD_SPECTRAL_CHUNK cells (a function of (T, F) alone), one workgroup per
+ * chunk and row; per-chunk double partials are summed in a fixed lane and wave order, then a second launch adds a row's
+ * partials in a fixed order that depends on its chunk count alone.
+ * Guarantees: no floating-point atomics; the same bits from run to run; a row's row_loss and dpred bits are the same at
+ * B = 1 and inside any batch; the loss bits do not depend on whether dpred is asked for.
+ * ws: 16-byte aligned.  A bad shape (B outside 1..65535, T or F < 1, T * F > 2^30), a needed pointer that is NULL, an
+ * unknown kind or pred_mode, bad strides or alignment: AVVAD_EINVAL; a workspace below the query: AVVAD_EWORKSPACE; both
+ * before anything is launched or written.
+ * ---------------------------------------------------------------------- */
+#define AVVAD_SPECTRAL_CHUNK 2048
+size_t avvad_spectral_loss_workspace(int B, int T, int F);     /* 0 on a bad shape */
+int avvad_spectral_loss(const float* pred, int pred_mode /* 1 mask, 2 logits */, int kind /* 0 mask, 1 signal, 2 spectrum */,
+                        const float* target /* [B][T][F]: kind 0, 1; NULL for kind 2 */,
+                        const float* mix, long mb, long mt, long mf /* complex (re,im) pairs, strides in floats: kind 1, 2 */,
+                        const float* speech, long sb, long st, long sf /* kind 2 */,
+                        const int* n_frames /* NULL: T each */, float* loss /* [1] */, double* row_loss /* [B] or NULL */,
+                        float* dpred /* [B][T][F] or NULL */, int B, int T, int F, void* ws, size_t ws_bytes, avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Mixing clean speech and noise at a target SNR, for training

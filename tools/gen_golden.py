@@ -2,7 +2,8 @@
 """Generate tests/golden/*.npz by RUNNING THE REFERENCE in the build container.
 
     python tools/gen_golden.py [group ...]   # needs /root/reference (absent on the GPU box); groups: wavenet audio
-                                             # video av misc metrics eval targets scores noise_aware (default: all)
+                                             # video av misc metrics eval targets scores noise_aware spectral_loss
+                                             # (default: all)
 
 The reference's own classes/functions are imported from /root/reference and run
 on seeded inputs; only inputs, (small) weights and outputs are written -- data,
@@ -416,7 +417,29 @@ def gen_noise_aware():
          noise=np.packbits(noise.astype(bool)), threshold=np.packbits(thr.astype(bool)), voiced=voiced, unvoiced=unvoiced)
 
 
+# ------------------------------------------------------------------ mask-regression losses (packages/models/utils.py:151-162)
+# The reference's own mean_square_error_mask / mean_square_error_signal / magnitude_spectrum_approxiamation_loss in float64
+# on one seeded utterance per shape: complex x and s, a label y in [0, 1] and mask probabilities y_hat in (0, 1).  Every
+# input is a float32 value widened to float64, so a float32 implementation reads exactly these numbers.
+# mean_square_error_signal takes x as the magnitude |x|.  Inputs and the three scalars only; writes spectral_loss.npz.
+def gen_spectral_loss():
+    arrs = {}
+    for tag, (T, F) in (("a", (5, 9)), ("b", (3, 513))):
+        g = torch.Generator().manual_seed(1000 * T + F)
+        wide = lambda t: t.to(torch.float32).to(torch.float64)      # noqa: E731
+        x = torch.complex(wide(torch.randn(T, F, generator=g)), wide(torch.randn(T, F, generator=g)))
+        y = wide(torch.rand(T, F, generator=g))
+        y_hat = wide(torch.rand(T, F, generator=g) * 0.98 + 0.01)
+        s = torch.complex(wide(y * x.real + 0.1 * torch.randn(T, F, generator=g)), wide(y * x.imag + 0.1 * torch.randn(T, F, generator=g)))
+        out = np.array([float(ref_mutils.mean_square_error_mask(y, y_hat)), float(ref_mutils.mean_square_error_signal(x.abs(), y, y_hat)),
+                        float(ref_mutils.magnitude_spectrum_approxiamation_loss(x, s, y_hat))], dtype=np.float64)
+        arrs.update({tag + "_x": npy(x).astype(np.complex64), tag + "_s": npy(s).astype(np.complex64),        # (exact: float32 values)
+                     tag + "_y": npy(y).astype(np.float32), tag + "_y_hat": npy(y_hat).astype(np.float32), tag + "_loss": out})
+    save("spectral_loss", **arrs)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["wavenet", "audio", "video", "av", "misc", "metrics", "eval", "targets", "scores", "noise_aware"]
+    which = sys.argv[1:] or ["wavenet", "audio", "video", "av", "misc", "metrics", "eval", "targets", "scores", "noise_aware",
+                             "spectral_loss"]
     for w in which:
         globals()["gen_" + w]()
