@@ -145,7 +145,7 @@ __global__ void is_ola_kernel(const OlaArgs a) {
 }
 
 bool is_desc_ok(const avvad_istft_stream_desc* d) {
-  return d && d->B > 0 && d->T >= 0 && d->L >= 0 && frames::ok_n_fft(d->n_fft) && d->hop >= 1 &&
+  return d && d->B > 0 && d->T >= 0 && d->L >= 0 && frames::ok_n_fft(d->n_fft) && d->n_fft <= sp::K_MAX && d->hop >= 1 &&
          d->hop <= d->n_fft && d->M >= 0 && d->mask_mode >= 0 && d->mask_mode <= 3 && (long)d->T * d->hop < (1L << 30) &&
          (long)d->B * d->T < (1L << 31) - 64 && (long)d->B * ((long)d->L + d->n_fft) < (1L << 40);
 }
@@ -156,7 +156,7 @@ size_t is_basis_floats(int n_fft) { return (size_t)n_fft * n_fft; }
 }  // namespace
 
 extern "C" size_t avvad_istft_stream_basis_bytes(int n_fft) {
-  if (!frames::ok_n_fft(n_fft) || !is_plan(n_fft, 1).NG) return 0;
+  if (!frames::ok_n_fft(n_fft) || n_fft > sp::K_MAX || !is_plan(n_fft, 1).NG) return 0;
   return is_basis_floats(n_fft) * sizeof(float) + (size_t)n_fft * sizeof(double);
 }
 

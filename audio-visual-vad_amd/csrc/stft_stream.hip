@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(sp::NT) ss_fwd_kernel(const SsArgs a) {
 }
 
 bool ss_desc_ok(const avvad_stft_stream_desc* d) {
-  return d && d->B > 0 && d->L >= 1 && frames::ok_n_fft(d->n_fft) && d->hop >= 1 && d->hop <= d->n_fft && d->T >= 0 &&
+  return d && d->B > 0 && d->L >= 1 && frames::ok_n_fft(d->n_fft) && d->n_fft <= sp::K_MAX && d->hop >= 1 && d->hop <= d->n_fft && d->T >= 0 &&
          d->M >= 0 && (long)d->T * d->hop < (1L << 30) && (long)d->B * d->L < (1L << 40) &&
          (long)d->B * d->T < (1L << 31) - 64;
 }
@@ -184,13 +184,13 @@ int ss_forward(const float* chunk, const int* n_valid, const int* n_pending, con
 }  // namespace
 
 extern "C" size_t avvad_stft_stream_basis_bytes(int n_fft) {
-  if (!frames::ok_n_fft(n_fft)) return 0;
+  if (!frames::ok_n_fft(n_fft) || n_fft > sp::K_MAX) return 0;
   return (size_t)ss_bin_blocks(n_fft) * 2 * 16 * n_fft * sizeof(float);
 }
 
 extern "C" int avvad_stft_stream_basis(int n_fft, float* out, avvad_stream_t sv) {
   AVVAD_ENTER();
-  if (!out || !frames::ok_n_fft(n_fft) || ((uintptr_t)out & 15)) return AVVAD_EINVAL;
+  if (!out || !avvad_stft_stream_basis_bytes(n_fft) || ((uintptr_t)out & 15)) return AVVAD_EINVAL;
   const long n = (long)(avvad_stft_stream_basis_bytes(n_fft) / sizeof(float));
   hipLaunchKernelGGL(ss_basis_kernel, dim3(frames::grid1(n)), dim3(256), 0, (hipStream_t)sv, out, n_fft, n_fft / 2 + 1, n);
   AVVAD_LAUNCH_CHECK();

@@ -22,6 +22,7 @@ constexpr int NT = 512;             // threads per workgroup: 8 waves over K
 constexpr int NW = NT / 64;
 constexpr int PAD = 4;              // frame pitch K + 4 floats: the 16 frames of a ds_read_b128 lane group sit on 16 different slots
 constexpr size_t LDS_MAX = 150 * 1024;
+constexpr int K_MAX = 2048;        // the documented limit of both transforms (include/avvad.h); plan() alone would take what LDS takes, 2368
 
 // index within K that lane-quarter q reads in MFMA j of group kk: both operands use it, so the product is a plain sum
 __device__ __forceinline__ int operand_index(int K, int kk, int q, int j) { return (K >> 2) * q + 4 * kk + j; }

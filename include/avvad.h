@@ -443,7 +443,9 @@ int avvad_stft_features(const float* wave, const float* mean, const float* std_,
  * state_in / state_out: plain float [B][n_fft], different buffers (every workgroup reads tails while others are written:
  * the caller swaps, as for h / c); all zeros with n_pending 0 is "start of utterance".  chunk [B][L] is never written.
  * n_valid / n_pending / n_frames / pad_frames: device int32 [B]; the counts are the caller's bookkeeping (frames after N
- * samples: max(0, (N - n_fft) / hop + 1)); the kernel clamps them so that wrong ones cannot leave a buffer.  d->M is the
+ * samples: max(0, (N - n_fft) / hop + 1)); the kernel clamps them so that wrong ones cannot leave a buffer: n_valid to
+ * [0, d->L], n_pending to [0, n_fft], n_frames to [0, min(d->T, the complete frames of the n_pending + n_valid samples,
+ * plus one where pad_frames[b] != 0)].  d->M is the
  * HOST's sum of n_frames (0: unknown, B T is assumed); it sizes the grid and selects nothing that changes a value.
  * basis: avvad_stft_stream_basis_bytes(n_fft) bytes filled ONCE by avvad_stft_stream_basis (16-byte aligned) -- the
  * windowed basis of avvad_stft (periodic Hann, exact phase reduction, evaluated in double) packed per block of 16 bins,
