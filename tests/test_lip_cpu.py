@@ -1,6 +1,9 @@
 """CPU tests of the video front-end's host side: the frame-rate map (``ops.lip_out_frames`` / ``lip_frame_starts``) against
 a float-free brute-force restatement and the frame counts recorded in the reference's data, the float64 restatement
-(tests/lip_ref.py) against the literal scipy expression of the reference, and the exported symbols."""
+(tests/lip_ref.py) against the literal scipy expression of the reference, and the exported symbols.  The oracles of
+test_lip_gpu.py's cases past one loop trip: the one-hot utterance's closed form, its derived bound (1.368e-4 level) held by
+a float32 stand-in (2.39e-5) and broken by four planted mistakes, the 600-frame utterance against restatements that stop
+after one or two trips, the loops and grids the many-utterance cases reach, and rates that drop frames."""
 import os
 
 import numpy as np
@@ -140,6 +143,107 @@ def test_symbols_are_exported_and_declared():
     from avvad import train as TR
     for name in ("AVFiles", "av_file_step", "read_av_files", "av_file_stats"):
         assert hasattr(TR, name)
+
+
+# ------------------------------------------------------------------------------------------ the oracles of test_lip_gpu.py
+def test_onehot_utterance_closed_form_bound_and_mutants():
+    """The one-hot utterance of test_lip_gpu.py: its closed form is the restatement, the derived bound (1.37e-4 level) holds
+    for a float32 stand-in of the kernel's formula and not for four planted mistakes."""
+    coef, pairs, amp = R.onehot_coef()
+    N = len(pairs)
+    assert N == 189 and N % 4 == 1 and coef.shape == (N, 67 * 67) and (coef != 0).sum() == N
+    assert {a for a, _ in pairs} == {b for _, b in pairs} == set(range(67))
+    assert {(a, b) for a in R.TILE_EDGES for b in R.TILE_EDGES} <= set(pairs) and pairs[-1] == (0, 0)
+    exact = R.onehot_frames64(pairs, amp)
+    # the index convention: A[ii][j] = x C[ii][b] C[66 - j][a] is what the restatement computes from the coefficients
+    assert np.abs(exact - R.frames(coef, quantize=False)).max() <= 1e-9
+    dc = exact[-1]
+    assert np.ptp(dc) <= 1e-9 and 0 < dc.mean() < 255 and exact.min() == 0.0 and exact.max() > 254.0   # constant, utterance not
+    bound = R.onehot_bound(pairs, amp)
+    got = R.onehot_float32(coef)
+    err = np.abs(got - exact).max()
+    print("one-hot: float32 stand-in max |d| = %.3e level, derived bound %.3e" % (err, bound))
+    assert 1.0e-4 < bound < 2.0e-4 and 0 < err <= bound
+    for mutant in ("entry", "reverse", "pad", "transpose"):
+        bad = np.abs(R.onehot_float32(coef, mutant) - exact).max()
+        print("  mutant %-9s max |d| = %.3e" % (mutant, bad))
+        assert bad > 100 * bound, mutant
+    # quantised: the float64 reference alone excuses well under the 3 % cap, and the stand-in passes the excuse rule
+    near = np.abs(exact - np.rint(exact)) <= bound
+    print("one-hot: %.4f %% of the pixels excusable" % (100 * near.mean()))
+    assert near.mean() <= 0.03
+    differ = R.quantise(got) != R.quantise(exact)
+    assert np.all(near[differ])
+    assert np.any((R.quantise(R.onehot_float32(coef, "entry")) != R.quantise(exact)) & ~near)
+
+
+def test_long_utterance_needs_every_trip_of_the_frame_loop():
+    coef = R.long_utterance()
+    A = R.idct2(coef)
+    lo, rg = A.min(axis=(-2, -1)), A.max(axis=(-2, -1)) - A.min(axis=(-2, -1))
+    assert A.shape[0] == 600 and int(lo.argmin()) == R.LONG_LO >= 256 and int(rg.argmax()) == R.LONG_RANGE >= 512
+    assert lo[:256].min() > lo.min() and rg[:256].max() < rg.max()
+    assert np.delete(lo, R.LONG_LO).min() > lo.min() and np.delete(rg, R.LONG_RANGE).max() < rg.max()
+    ref = R.decode(coef, quantize=False, **R.ONE)
+    assert ref.shape[0] == 600 and ref.min() == 0.0 and (ref <= 255.0).mean() > 0.9                # the clip does not hide the levels
+    tol = R.tolerance(coef)
+    assert 0 < tol <= 0.01
+    for first in (256, 512):                                     # one trip, two trips
+        bad = R.decode_first_frames_only(coef, first, **R.ONE)
+        assert np.abs(bad - ref).max() > 100 * tol
+        near = np.abs(ref - np.rint(ref)) <= tol
+        assert ((R.quantise(bad) != R.quantise(ref)) & ~near).any()
+
+
+def grid_x(n_max, B, cus=256):
+    """lip_frames' grid: workgroups per utterance (csrc/lip.hip, avvad_lip_decode)"""
+    return max(1, min(-(-n_max // 4), cus // B))
+
+
+def test_many_utterance_cases_reach_their_loops():
+    # statistics add: utterances in three trips of the wave loop, frames in three trips of the lane loop
+    n_in = R.stats_add_counts()
+    sums = np.arange(1, sum(n_in) + 1, dtype=np.float64)         # any per-frame partials
+    whole = R.add_model(sums, n_in)
+    assert whole == sums.sum()
+    assert R.add_model(sums, n_in, max_waves=16) != whole and R.add_model(sums, n_in, max_waves=32) != whole
+    assert R.add_model(sums, n_in, max_lane_trips=1) != whole and R.add_model(sums, n_in, max_lane_trips=2) != whole
+    # count loop: more utterances than lip_add has threads, and no CU left per utterance
+    n_in = R.count_counts()
+    assert len(n_in) == 1030 > 1024 and set(n_in) == {1, 2} and grid_x(max(n_in), len(n_in)) == 1 and 256 // len(n_in) == 0
+    assert sum(n_in[:1024]) != sum(n_in)
+    # ragged multi-trip: two workgroups, stride 8, two trips, none of them whole
+    n_in = R.ragged_counts()
+    assert len(n_in) == 128 and set(n_in) == {9, 10, 11, 12, 13} and grid_x(max(n_in), 128) == 2
+    assert all(-(-n // 8) == 2 and n % 8 for n in n_in)
+    # the one-hot batch under a cap of 4 CUs: one workgroup per utterance, 48 trips with a prefetch each
+    assert grid_x(189, 4, cus=4) == 1 and -(-189 // 4) == 48
+
+
+@pytest.mark.parametrize("fps_in", R.RATES)
+def test_rates_below_one_drop_frames_that_still_normalise(fps_in):
+    from avvad import ops
+    p, q = R.rate(hop=256, fps_in=fps_in)
+    assert (p, q) == ops.lip_rate(16000, 256, fps_in) == {25: (5, 2), 50: (5, 4), 100: (5, 8), 125: (1, 2)}[fps_in]
+    for N in (0, 1, 2, 37, 50):
+        s = R.frame_starts(N, hop=256, fps_in=fps_in)
+        assert s == [brute_start(i, p, q) for i in range(N + 1)] == ops.lip_frame_starts(N, 16000, 256, fps_in)
+        fm = R.frame_map(N, hop=256, fps_in=fps_in)
+        assert len(fm) == s[N] == ops.lip_out_frames(N, 16000, 256, fps_in) and np.all(np.diff(fm) >= 0)
+    if fps_in == 125:
+        assert R.frame_starts(4, hop=256, fps_in=125) == [0, 1, 1, 2, 2]          # 0.5 -> 1, 1.5 -> 2: ties away from zero
+    for coef in R.rate_utterances(fps_in):
+        N = coef.shape[0]
+        gone = R.dropped_frames(N, hop=256, fps_in=fps_in)
+        assert (len(gone) > 0) == (p < q)
+        if p >= q:
+            continue
+        A = R.idct2(coef)
+        lo, rg = A.min(axis=(-2, -1)), A.max(axis=(-2, -1)) - A.min(axis=(-2, -1))
+        assert int(lo.argmin()) in gone and int(rg.argmax()) in gone and int(lo.argmin()) != int(rg.argmax())
+        ref = R.decode(coef, quantize=False, hop=256, fps_in=fps_in)
+        bad = R.decode_seen_frames_only(coef, hop=256, fps_in=fps_in)
+        assert np.abs(bad - ref).max() > 100 * R.tolerance(coef)
 
 
 def test_cpu_tensors_raise():

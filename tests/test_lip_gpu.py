@@ -2,7 +2,25 @@
 tests/lip_ref.py: unquantised and quantised frames, the frame map and lengths of ragged batches, constant utterances, the
 fused statistics and standardisation, and video / AV training and scoring from files.
 
-Measured on the MI355X (40-frame synthetic utterance): see the docstrings of the first two tests."""
+Measured on the MI355X (40-frame synthetic utterance): see the docstrings of the first two tests.
+
+Past one loop trip (the second half of the file; inputs and oracles in tests/lip_ref.py, their mutants in
+tests/test_lip_cpu.py):
+* a one-hot utterance -- one nonzero coefficient per frame, so every pixel is ONE product of two table entries and no
+  summation order enters -- covering every row and column, all pairs of the MFMA tile edges and the DC frame, staged from
+  all four alignments packed and padded: held to ``lip_ref.onehot_bound``, 1.368e-4 level, derived by counting roundings
+  (observed on the MI355X: 2.39e-5, the value of the float32 numpy stand-in), the same bits under a cap of 4 CUs (48
+  trips with prefetch), quantised levels exact outside the bound;
+* 600 frames with the minimum in frame 300 and the largest range in frame 550 (lip_utt's ``i += 256``; observed 2.48e-4
+  against a tolerance of 9.11e-4);
+* B = 35 utterances of 0..130 frames and B = 1030 of one or two with ``acc=`` (lip_add's wave, lane and count loops, a
+  grid of one workgroup per utterance): sums and pixel count equal to the host's integers;
+* B = 128 utterances of 9..13 frames (two workgroups per utterance, two ragged trips) against float64 (observed 0.29 of
+  the tolerance);
+* 25, 50, 100 and 125 input frames/s at hop 256: the frame map bit for bit, and where frames get no slot (p < q) the
+  minimum and the largest range lie in such frames.
+These use ``lip_ref.tolerance``: the rule of ``tolerance`` below with the float32 evaluation written out term by term
+(the same arithmetic on every host, milliseconds per frame); on the 40-frame utterance it is 6.7e-4 against 4.28e-3."""
 import os
 
 import numpy as np
@@ -184,6 +202,202 @@ def test_fused_standardisation_equals_stats_video():
         assert not fused[b, n:].any()                            # padding stays zero, it is not standardised
     with pytest.raises(Exception):
         decode(coef, n_in, mean=st.get("video_mean", torch.device(DEV)))
+
+
+# ------------------------------------------------------------------------------------------ past one loop trip
+def log_line(msg):
+    """print and append to the parity log of tests/test_gpu_parity.py"""
+    from test_gpu_parity import OUT
+    print(msg)
+    try:
+        os.makedirs(OUT, exist_ok=True)
+        with open(os.path.join(OUT, "parity.log"), "a") as f:
+            f.write(msg + "\n")
+    except OSError:
+        pass
+
+
+def check_quantised(got, exact, tol, what):
+    """The excuse rule of test_quantised_levels_against_float64: integer levels in 0..255; a pixel may differ from the
+    reference's level, by exactly 1, only where the float64 value lies within ``tol`` of an integer; a test that excuses
+    more than 3 % fails whatever the values."""
+    ref = R.quantise(exact)
+    assert got.shape == ref.shape and np.array_equal(got, np.trunc(got)) and got.min() >= 0 and got.max() <= 255
+    near = np.abs(exact - np.rint(exact)) <= tol
+    differ = got != ref
+    print("%s: %.4f %% of the pixels differ, %.4f %% excusable at tolerance %.3e" % (what, 100 * differ.mean(), 100 * near.mean(), np.max(tol)))
+    assert near.mean() <= 0.03 and differ.mean() <= 0.03
+    assert np.all(near[differ])
+    assert np.all(np.abs(got - ref)[differ] == 1.0)
+
+
+def host_sums(video, lens):
+    """[sum, sumsq, count] of the written frames in float64 on the host: exact for quantised frames (integers, < 2^53)"""
+    v = video.cpu().numpy().astype(np.float64)
+    vals = np.concatenate([v[b, :n].reshape(-1) for b, n in enumerate(lens)])
+    host = [float(vals.sum()), float((vals * vals).sum()), float(vals.size)]
+    assert host[1] < 2.0 ** 53
+    return host
+
+
+def onehot_batches():
+    """the one-hot utterance four times, packed (starts 0, 189, 378, 567) and padded to a pitch of 191 frames (starts 0,
+    191, 382, 573): every frame is staged from all four alignments of ``load_raw``, behind nonzero starts"""
+    coef, pairs, amp = R.onehot_coef()
+    N = coef.shape[0]
+    packed = np.concatenate([coef] * 4)
+    padded = np.full((4, N + 2, NPIX), 1e6, np.float32)          # what lies behind an utterance is never read
+    padded[:, :N] = coef
+    assert sorted(s & 3 for s in (0, N, 2 * N, 3 * N)) == sorted(s & 3 for s in (0, N + 2, 2 * N + 4, 3 * N + 6)) == [0, 1, 2, 3]
+    return (("packed", packed), ("padded", padded)), pairs, amp
+
+
+def test_onehot_frames_within_the_counted_roundings(lib_options):
+    """One nonzero coefficient per frame: every pixel is one product of two table entries, so an index, transpose,
+    reversal or pad mistake is an error of order 1 and the float32 error is bounded by counting roundings
+    (lip_ref.onehot_bound: 1.368e-4 level).  MI355X: largest deviation 2.4e-5 level, packed and padded alike; the same
+    bits under a cap of 4 CUs (one workgroup per utterance, 48 trips with prefetch)."""
+    batches, pairs, amp = onehot_batches()
+    N = len(pairs)
+    exact = R.onehot_frames64(pairs, amp)
+    bound = R.onehot_bound(pairs, amp)
+    assert 1.0e-4 < bound < 2.0e-4
+    videos = {}
+    for name, coef in batches:
+        video, lens = decode(coef, [N] * 4, quantize=False, **R.ONE)
+        assert lens.tolist() == [N] * 4 and tuple(video.shape) == (4, N, 67, 67)
+        got = video.cpu().numpy().astype(np.float64)
+        err = [float(np.abs(got[b] - exact).max()) for b in range(4)]
+        log_line("lip one-hot %-6s max |gpu - float64| = %.3e level (per alignment %s), derived bound %.3e"
+                 % (name, max(err), " ".join("%.2e" % e for e in err), bound))
+        assert max(err) <= bound
+        videos[name] = video
+    lib_options("max_cus", 4)
+    for name, coef in batches:
+        assert torch.equal(decode(coef, [N] * 4, quantize=False, **R.ONE)[0], videos[name])
+
+
+def test_onehot_levels_are_exact_outside_the_bound():
+    """Quantised one-hot frames: every pixel whose float64 value lies farther than the derived bound from an integer has
+    exactly the reference's level (0.05 % of the pixels are excusable)."""
+    batches, pairs, amp = onehot_batches()
+    N = len(pairs)
+    exact = R.onehot_frames64(pairs, amp)
+    bound = R.onehot_bound(pairs, amp)
+    for name, coef in batches:
+        video, _ = decode(coef, [N] * 4, **R.ONE)
+        got = video.cpu().numpy().astype(np.float64)
+        for b in range(4):
+            check_quantised(got[b], exact, bound, "one-hot %s, utterance %d" % (name, b))
+
+
+def test_frame_loop_of_a_long_utterance():
+    """600 frames, the global minimum in frame 300 and the largest range in frame 550: lip_utt's loop takes three trips."""
+    coef = R.long_utterance()
+    exact = R.decode(coef, quantize=False, **R.ONE)
+    tol = R.tolerance(coef)
+    video, lens = decode(coef, [R.LONG_N], quantize=False, **R.ONE)
+    assert lens.tolist() == [R.LONG_N]
+    err = np.abs(video[0].cpu().numpy().astype(np.float64) - exact).max()
+    log_line("lip 600 frames: max |gpu - float64| = %.3e level, tolerance %.3e" % (err, tol))
+    assert 0 < tol <= 0.01 and err <= tol
+    video, _ = decode(coef, [R.LONG_N], **R.ONE)
+    check_quantised(video[0].cpu().numpy().astype(np.float64), exact, tol, "600 frames")
+
+
+def test_statistics_add_over_many_utterances_and_frames():
+    """B = 35 utterances of 0..130 frames: lip_add's wave loop and lane loop take three trips each.  Quantised levels are
+    integers, so the accumulator equals the host's float64 sums and ``ops.accumulate_stats`` bit for bit."""
+    from avvad import ops
+    n_in = R.stats_add_counts()
+    coef = R.batch_of(n_in, seed=41)
+    acc = ops.stats_new(1, DEV)
+    video, lens = decode(coef, n_in, acc=acc, **R.ONE)
+    assert lens.tolist() == n_in and tuple(video.shape) == (35, 130, 67, 67)
+    assert acc.tolist() == host_sums(video, n_in)
+    other = ops.accumulate_stats(ops.stats_new(1, DEV), video.view(35, -1, NPIX), lens, nstat=1)
+    assert torch.equal(acc, other)
+    for b in (0, 9, 34):                                         # and the frames are the single utterances'
+        assert torch.equal(video[b, :n_in[b]], decode(R.split(coef, n_in)[b], [n_in[b]], **R.ONE)[0][0])
+    assert not video[2].any() and not video[1, 3:].any()
+
+
+def test_count_loop_and_one_workgroup_per_utterance():
+    """B = 1030 utterances of one or two frames: the second trip of lip_add's count loop, and 256 / B == 0 workgroups per
+    utterance (a grid of one)."""
+    from avvad import ops
+    n_in = R.count_counts()
+    coef = R.batch_of(n_in, seed=43)
+    acc = ops.stats_new(1, DEV)
+    video, lens = decode(coef, n_in, acc=acc, **R.ONE)
+    assert lens.tolist() == n_in and tuple(video.shape) == (1030, 2, 67, 67)
+    host = host_sums(video, n_in)
+    assert host[2] == sum(n_in) * NPIX and acc.tolist() == host
+    utts = R.split(coef, n_in)
+    for b in (0, 1, 2, 3, 255, 256, 257, 511, 512, 767, 1023, 1024, 1025, 1027, 1028, 1029):
+        single, _ = decode(utts[b], [n_in[b]], **R.ONE)
+        assert torch.equal(video[b, :n_in[b]], single[0]) and not video[b, n_in[b]:].any()
+        check = R.decode(utts[b], **R.ONE)
+        assert np.abs(single[0].cpu().numpy() - check).max() <= 1.0
+
+
+def test_ragged_utterances_over_two_trips_of_two_workgroups():
+    """B = 128 utterances of 9..13 frames, uncapped: lip_frames runs two workgroups per utterance, eight frames per trip,
+    two trips with ragged ends -- against the float64 restatement, utterance by utterance."""
+    n_in = R.ragged_counts()
+    coef = R.batch_of(n_in, seed=47)
+    utts = R.split(coef, n_in)
+    raw, lens = decode(coef, n_in, quantize=False, **R.ONE)
+    lev, _ = decode(coef, n_in, **R.ONE)
+    assert lens.tolist() == n_in
+    raw, lev = raw.cpu().numpy().astype(np.float64), lev.cpu().numpy().astype(np.float64)
+    worst = 0.0
+    exacts, tols = [], []
+    for b, n in enumerate(n_in):
+        exact = R.decode(utts[b], quantize=False, **R.ONE)
+        tol = R.tolerance(utts[b])
+        err = np.abs(raw[b, :n] - exact).max()
+        worst = max(worst, err / tol)
+        assert 0 < tol <= 0.01 and err <= tol, (b, err, tol)
+        assert not raw[b, n:].any() and not lev[b, n:].any()
+        exacts.append(exact), tols.append(np.full(exact.shape, tol))
+    log_line("lip 128 ragged utterances: worst |gpu - float64| / tolerance = %.4f" % worst)
+    check_quantised(np.concatenate([lev[b, :n] for b, n in enumerate(n_in)]), np.concatenate(exacts), np.concatenate(tols), "128 ragged")
+
+
+@pytest.mark.parametrize("fps_in", R.RATES)
+def test_rates_above_and_below_one(fps_in):
+    """hop 256 at 25, 50, 100 and 125 input frames/s (p / q = 5/2, 5/4, 5/8, 1/2): lengths and frame map against
+    lip_ref.frame_map through a gather from the 1:1 decode (bit exact).  Below one, frames without an output slot hold the
+    utterance's minimum and its largest range: the normalisation must see them, the statistics must not."""
+    from avvad import ops
+    rate = dict(fs=16000, hop=256, fps_in=fps_in)
+    utts = R.rate_utterances(fps_in)
+    n_in = [u.shape[0] for u in utts]
+    want = [len(R.frame_map(n, hop=256, fps_in=fps_in)) for n in n_in]
+    coef = np.concatenate(utts)
+    for quantize in (True, False):
+        acc = ops.stats_new(1, DEV)
+        video, lens = decode(coef, n_in, quantize=quantize, acc=acc, **rate)
+        assert lens.tolist() == want and tuple(video.shape) == (2, max(want), 67, 67)
+        for b, n in enumerate(n_in):
+            one, _ = decode(utts[b], [n], quantize=quantize, **R.ONE)
+            fm = torch.from_numpy(R.frame_map(n, hop=256, fps_in=fps_in)).to(DEV)
+            assert torch.equal(video[b, :want[b]], one[0][fm]) and not video[b, want[b]:].any()
+            exact = R.decode(utts[b], quantize=False, hop=256, fps_in=fps_in)
+            got = video[b, :want[b]].cpu().numpy().astype(np.float64)
+            tol = R.tolerance(utts[b])
+            if quantize:
+                check_quantised(got, exact, tol, "%d frames/s, utterance %d" % (fps_in, b))
+            else:
+                err = np.abs(got - exact).max()
+                log_line("lip %3d frames/s utterance %d: max |gpu - float64| = %.3e level, tolerance %.3e" % (fps_in, b, err, tol))
+                assert err <= tol
+        if quantize:                                             # the sums are of the written frames only
+            assert acc.tolist() == host_sums(video, want)
+            assert torch.equal(acc, ops.accumulate_stats(ops.stats_new(1, DEV), video.view(2, -1, NPIX), lens, nstat=1))
+        else:
+            assert float(acc[2]) == sum(want) * NPIX
 
 
 def av_fixture(tmp_path, n_utts=3):

@@ -1,7 +1,16 @@
 """GPU tests of the train-set statistics (csrc/stats.hip through avvad.ops / avvad.train): the reduction against a float64
 host reduction of the very features ``ops.stft`` returns, against the float64 restatement from the waveform
 (tests/stats_ref.py), ragged batches against single utterances and materialised features, reproducibility, the scalar
-(video) form, degenerate inputs, and the wav-pair path of the train / evaluate loops."""
+(video) form, degenerate inputs, and the wav-pair path of the train / evaluate loops.
+
+On exact operands (``stats_ref.EXACT_CASES``: integer-valued float32, |x| <= 2^10, every sum an integer below 2^53) the
+accumulator must equal the host's float64 sums bit for bit: F = 1, 63, 64, 65, 129 (column-block tails), T = 1, 3, 5, 33
+(several utterance boundaries inside an eight-row group), lengths of 0, T, T + 7 and -2, 151 chunks (add_partials'
+eight-way body and remainder loop in every segment, 19 trips of the count loop), the scalar form at F = 2 .. 20000 (both
+sides of its F >= 16384 and F < 256 branches) and at B = 1030, and twice the sums after a second call.  The spectrum
+loader runs at n_fft = 64, 96, 256 (F = 33, 49, 129) against the features of ``ops.stft`` within ``stats_ref.sum_bound``
+(observed on the MI355X: at most 0.036 of the bound).  tests/test_stats_cpu.py shows that each case reaches its branch
+and that a host model of the kernels with one planted mistake fails it."""
 import os
 
 import numpy as np
@@ -206,6 +215,60 @@ def test_degenerate_inputs():
     assert torch.all(zm == c)
     assert torch.isfinite(zs).all() and float(zs.min()) >= 0 and float(zs.max()) <= 1e-6
     assert torch.isfinite(ops.stft(zeros, mode=0, mean=zm, std=zs)).all()
+
+
+# ------------------------------------------------------------------------------------------ exact operands, every tail
+@pytest.mark.parametrize("name", [c[0] for c in R.EXACT_CASES])
+def test_exact_operands_give_the_hosts_integers(name):
+    """Integer-valued float32 inputs (|x| <= 2^10): sum and sum of squares are integers below 2^53, exact in double in any
+    order, so the accumulator must equal the host's float64 sums bit for bit -- at column-block tails (F = 1, 63, 64, 65,
+    129), utterance boundaries inside an eight-row group (T = 1, 3, 5), lengths of 0, T, T + 7 and -2, 150 chunks plus 37
+    rows (add_partials' eight-way body and remainder loop), and the scalar form on both sides of its F >= 16384 and F < 256
+    branches and past 1024 utterances.  Accumulating the batch a second time must give exactly twice the sums."""
+    from avvad import ops
+    x, lens, nstat = R.exact_case(name)
+    want = R.host_sums(x, lens, nstat)
+    assert want.max() < 2.0 ** 52
+    xd = torch.from_numpy(x).to(DEV)
+    acc = ops.accumulate_stats(ops.stats_new(nstat, DEV), xd, lens)
+    got = acc.cpu().numpy()
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, (name, bad[:8], got[bad[:8]], want[bad[:8]])
+    if lens is not None:                                         # a tensor of lengths is the list
+        assert torch.equal(acc, ops.accumulate_stats(ops.stats_new(nstat, DEV), xd, torch.LongTensor(lens)))
+    ops.accumulate_stats(acc, xd, lens)
+    assert np.array_equal(acc.cpu().numpy(), 2.0 * want)
+
+
+@pytest.mark.parametrize("n_fft", [64, 96, 256])
+def test_spectrum_loader_at_other_transform_sizes(n_fft):
+    """``ops.stft_stats`` at F = 33, 49 and 129 (the two-bins-per-lane loader's tails: 17, 25 and 1 lane of the last
+    block, the second bin of the last lane a pad column) on a ragged batch, against a host float64 sum of the float32
+    features ``ops.stft`` returns for the same waveform.  Both sides add the same doubles in different orders: the bound is
+    stats_ref.sum_bound, 2 (n - 1) 2^-53 sum|x| per bin, n the counted rows."""
+    from avvad import ops
+    Fb, hop = n_fft // 2 + 1, n_fft // 4
+    g = torch.Generator().manual_seed(n_fft)
+    lens = [hop * 130 + 17, hop * 97, hop // 2, hop * 61 + n_fft]           # ragged; the third is shorter than a frame
+    wave = torch.zeros(4, max(lens))
+    for b, n in enumerate(lens):
+        wave[b, :n] = torch.randn(n, generator=g) * (0.05 + 0.1 * b)
+    wave = wave.to(DEV)
+    frames = [max(0, ops.n_frames(n, n_fft, hop)) for n in lens]
+    x = ops.stft(wave, n_fft=n_fft, hop=hop, mode=0)
+    assert x.shape[2] == Fb and x.shape[1] == max(frames) and frames[2] == 0 and x.numel() < 2 ** 20
+    acc = ops.stft_stats(ops.stats_new(Fb, DEV), wave, lens, n_fft=n_fft, hop=hop)
+    xh = x.cpu().numpy().astype(np.float64)
+    rows = np.concatenate([xh[b, :n] for b, n in enumerate(frames)])
+    n = rows.shape[0]
+    got = acc.cpu().numpy()
+    assert got[-1] == n == sum(frames) and n > 128                # more than one chunk
+    d_sum, b_sum = np.abs(got[:Fb] - rows.sum(axis=0)), R.sum_bound(rows, n)
+    d_sq, b_sq = np.abs(got[Fb:2 * Fb] - (rows * rows).sum(axis=0)), R.sum_bound(rows * rows, n)
+    print("n_fft %d: %d rows, sum |d| / bound %.3f, sumsq |d| / bound %.3f" % (n_fft, n, (d_sum / b_sum).max(), (d_sq / b_sq).max()))
+    assert np.all(d_sum <= b_sum) and np.all(d_sq <= b_sq)
+    # counting the padded rows would be far outside
+    assert np.abs(xh.reshape(-1, Fb).sum(axis=0) - rows.sum(axis=0)).min() > 1e6 * b_sum.max()
 
 
 def pair_files(tmp_path):
