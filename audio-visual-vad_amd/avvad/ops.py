@@ -1331,6 +1331,53 @@ def energy_ratios(est, ref, noise=None, mixture=None, lengths=None, return_alpha
     return score_finalize(acc, "noise" if noise is not None else "mixture" if mixture is not None else "none", return_alpha)
 
 
+# --------------------------------------------------------------------------- STOI / ESTOI (csrc/stoi.hip, no gradient)
+_STOI_TAPS = {}
+
+
+def stoi_taps():
+    """The resampler's host table: the 161 float64 taps ``5 * firwin(161, 1/8, window=('kaiser', 5.0))`` that
+    ``scipy.signal.resample_poly(x, 5, 8)`` uses by default, built with numpy alone (windowed sinc, DC gain 1, times 5)."""
+    import numpy as np
+    m = np.arange(161, dtype=np.float64) - 80.0
+    h = 0.125 * np.sinc(0.125 * m) * np.kaiser(161, 5.0)
+    return 5.0 * (h / h.sum())
+
+
+def stoi(clean, processed, lengths=None, fs=16000, extended=False, both=False, return_info=False):
+    """STOI (``extended``: ESTOI) of a ragged batch on the GPU (avvad_stoi): clean and processed (B, L) (or (L,)) float32,
+    cropped to ``lengths`` (nothing at or behind a row's length is read).  ``fs`` 16000 (resampled to 10 kHz) or 10000.
+    Returns float64 (B,) on the GPU, or (B, 2) ``(stoi, estoi)`` with ``both``; a row with fewer than 30 frames after the
+    silent-frame removal scores 1e-5.  ``return_info``: also int32 (B, 3) ``(frames, kept frames, segments)``."""
+    if int(fs) not in (16000, 10000):
+        raise L.AvvadError("stoi: fs must be 16000 or 10000, got %r" % (fs,))
+    if not isinstance(clean, torch.Tensor) or clean.dim() not in (1, 2) or not isinstance(processed, torch.Tensor) \
+            or processed.dim() != clean.dim() or processed.shape != clean.shape:
+        raise L.AvvadError("stoi: clean and processed must be GPU tensors of one shape (B, L) or (L,), got %s and %s"
+                           % (tuple(getattr(clean, "shape", ())), tuple(getattr(processed, "shape", ()))))
+    B, Ls = (1, clean.shape[0]) if clean.dim() == 1 else clean.shape
+    x, ld_x = _score_rows(clean, "clean", B, Ls)
+    y, ld_y = _score_rows(processed, "processed", B, Ls)
+    lens32 = None
+    if lengths is not None:
+        lens32 = lengths_i32(lengths, x.device)
+        if lens32.numel() != B:
+            raise L.AvvadError("lengths must hold %d values" % B)
+    taps = None
+    if int(fs) == 16000:
+        taps = _STOI_TAPS.get(x.device)
+        if taps is None:
+            taps = _STOI_TAPS[x.device] = torch.from_numpy(stoi_taps()).to(x.device)
+    which = 3 if both else 2 if extended else 1
+    d = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    info = torch.empty((B, 3), dtype=torch.int32, device=x.device)
+    ws = _ws(L.lib().avvad_stoi_workspace(B, Ls, int(fs)), x.device)
+    L.check(L.lib().avvad_stoi(L.ptr(x), ld_x, L.ptr(y), ld_y, L.ptr(lens32), L.ptr(taps), B, Ls, int(fs), which, L.ptr(d),
+                               L.ptr(info), L.ptr(ws), ws.numel() * 4, _stream()), "avvad_stoi")
+    out = d if both else d[:, 1] if extended else d[:, 0]
+    return (out, info) if return_info else out
+
+
 # --------------------------------------------------------------------------- SI-SDR loss (csrc/scores.hip)
 class SiSdrLossFn(torch.autograd.Function):
     """-sum_b SI-SDR_b over each row's window, and its gradient in the estimate from the same call (avvad_si_sdr_loss)."""

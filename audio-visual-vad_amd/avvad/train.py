@@ -988,11 +988,24 @@ def score_utt(enhanced, clean, noisy):
 
 
 SCORE_KEYS = ("si_sdr", "si_sir", "si_sar", "input_si_sdr")
+INTELLIGIBILITY_KEYS = ("stoi", "estoi", "input_stoi", "input_estoi")
+
+
+def intelligibility_utt(enhanced, clean, noisy):
+    """Intelligibility scores of one 16 kHz utterance on the GPU: a dict of Python floats ``stoi``, ``estoi`` (the enhanced
+    signal against the clean one) and ``input_stoi``, ``input_estoi`` (the noisy signal itself).  One two-row ``ops.stoi``
+    call: rows ``enhanced`` and ``noisy`` against the same ``clean``.  The three (L,) GPU signals are cropped to their
+    common length."""
+    n = min(enhanced.numel(), clean.numel(), noisy.numel())
+    e, c, x = (t.reshape(-1)[:n] for t in (enhanced, clean, noisy))
+    d = ops.stoi(torch.stack([c, c]), torch.stack([e, x]), fs=16000, both=True).tolist()
+    return {"stoi": d[0][0], "estoi": d[0][1], "input_stoi": d[1][0], "input_estoi": d[1][1]}
 
 
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
                   stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None, chunk_samples=None,
-                  resynth_dir=None, resynth_hard=True, resynth_chunked=False, score_dir=None):
+                  resynth_dir=None, resynth_hard=True, resynth_chunked=False, score_dir=None,
+                  intelligibility=False):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
@@ -1019,7 +1032,11 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
     ``score_dir`` (``wav_list`` with ``clean_of``): every utterance is scored on the GPU and ``<base>_scores.pt`` is
     written there, a dict of Python numbers: the classifier's ``tp, tn, fp, fn`` (``ops.confusion_counts`` on the logits
     the predictions come from and the GPU labels) and, with ``resynth_dir``, ``score_utt`` of the enhanced waveform
-    against the clean file cropped to the common length.  ``None`` writes nothing and changes nothing."""
+    against the clean file cropped to the common length.  ``None`` writes nothing and changes nothing.
+    ``intelligibility`` (with ``resynth_dir`` and ``score_dir``): ``intelligibility_utt``'s four keys ``stoi``, ``estoi``,
+    ``input_stoi``, ``input_estoi`` join that dict; ``False`` leaves the file exactly as it was."""
+    if intelligibility and (resynth_dir is None or score_dir is None):
+        raise ValueError("intelligibility scores the enhanced utterances: it needs resynth_dir and score_dir")
     if score_dir is not None and (wav_list is None or clean_of is None):
         raise ValueError("score_dir scores the utterances of wav_list against their clean files: it needs clean_of")
     _one_chunking(chunk_frames, chunk_samples)
@@ -1110,6 +1127,8 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                     if scores is not None:
                         clean, _ = load_waveform(clean_of[wav_list[i]])
                         scores.update(score_utt(enhanced, clean.to(device), x_t.to(device)))
+                        if intelligibility:
+                            scores.update(intelligibility_utt(enhanced, clean.to(device), x_t.to(device)))
                 if scores is not None:
                     torch.save(scores, os.path.join(score_dir, os.path.basename(base) + "_scores.pt"))
     else:
@@ -1127,13 +1146,14 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
         print("Finished in {:.2f} seconds".format(time.perf_counter() - t0))
 
 
-def metrics_main(out_dir="eval_out", confidence=0.95, eps=1e-8, score_dir=None):
+def metrics_main(out_dir="eval_out", confidence=0.95, eps=1e-8, score_dir=None, intelligibility=False):
     """The body of ``scripts/run_metrics_dnn_classif.py`` (``:102-300``) for the classifier outputs: per utterance
     ``f1_loss(y_hat_hard, y)`` -> (accuracy, precision, recall, F1), then ``compute_stats`` tables with Student-t
     confidence intervals.  Reads the ``*_y_hat_hard.pt`` / ``*_label.pt`` pairs that ``evaluate_main`` wrote.
     ``score_dir``: a second table over the four enhancement scores of the ``*_scores.pt`` files that
     ``evaluate_main(resynth_dir=..., score_dir=...)`` wrote there; both tables are then returned as
-    ``{"classifier": ..., "enhancement": ...}``."""
+    ``{"classifier": ..., "enhancement": ...}``.  ``intelligibility``: the enhancement table also holds the four
+    ``INTELLIGIBILITY_KEYS`` that ``evaluate_main(..., intelligibility=True)`` wrote."""
     import glob
     from packages.metrics import compute_stats
     from packages.models.utils import f1_loss
@@ -1149,8 +1169,9 @@ def metrics_main(out_dir="eval_out", confidence=0.95, eps=1e-8, score_dir=None):
     if score_dir is None:
         return table
     scored = [torch.load(path, weights_only=True) for path in sorted(glob.glob(os.path.join(score_dir, "*_scores.pt")))]
-    scored = [tuple(d[k] for k in SCORE_KEYS) for d in scored if all(k in d for k in SCORE_KEYS)]
+    keys = SCORE_KEYS + (INTELLIGIBILITY_KEYS if intelligibility else ())
+    scored = [tuple(d[k] for k in keys) for d in scored if all(k in d for k in keys)]
     if len(scored) < 2:
         raise SystemExit("need at least two scored utterances in %s (evaluate_main with resynth_dir and score_dir)" % score_dir)
-    return {"classifier": table, "enhancement": compute_stats(metrics_keys=list(SCORE_KEYS), all_metrics=scored,
+    return {"classifier": table, "enhancement": compute_stats(metrics_keys=list(keys), all_metrics=scored,
                                                               model_data_dir=score_dir, confidence=confidence)}

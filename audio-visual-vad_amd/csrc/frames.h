@@ -82,4 +82,24 @@ static inline SpecWs spec_ws(int n_fft, size_t M, size_t base = 0) {
 // ws + w.S [B*T][ld] = framed, windowed DFT of wave [B][L]; w = spec_ws(n_fft, B*T, ...) within the workspace ws
 int framed_dft(const float* wave, long L, int B, int T, int n_fft, int hop, float* ws, const SpecWs& w, hipStream_t s);
 
+// ---- the second basis formula (stoi.hip): a window of W samples under an N-point transform, W <= N, some of its bins.
+// The symmetric Hann of W samples without its two zero end points (numpy.hanning(W + 2)[1:-1]), in double like hann()
+__device__ __forceinline__ double hann_sym(int k, int W) { return 0.5 - 0.5 * cospi(2.0 * (double)(k + 1) / (double)(W + 1)); }
+// element (k, 2j | 2j + 1) of the banded basis, bin f = f0 + j: win cos(2 pi f k / N) | -win sin(2 pi f k / N) with the
+// same exactly reduced phase, formed in double and rounded once
+__device__ __forceinline__ float banded_element(int k, int f, bool imag, int W, int N) {
+  const double win = hann_sym(k, W);
+  const Phase ph = phase(f, k, N);
+  return (float)(imag ? -win * ph.sin() : win * ph.cos());
+}
+// row pitch (floats) of the banded spectrum: 2 nf interleaved (re, im) columns rounded up to a float4
+static inline int banded_ld(int nf) { return (2 * nf + 3) / 4 * 4; }
+// S [R*T][ld] (ld = banded_ld(nf)): row (r, t) = the n_fft-point real DFT of frame t of rows[r] (win samples from t * hop,
+// under hann_sym, zero-extended), bins f0 .. f0 + nf - 1, column 2 (f - f0) + {re, im}.  rows: R rows of pitch ld_rows floats;
+// every frame lies within its row ((T - 1) hop + win <= ld_rows).  W: win x ld floats for the basis.  The same engine
+// product as framed_dft, always scheduled in whole tiles: every value is one ordered fmaf chain over the win samples, so
+// a row's bits depend neither on how many rows the product has nor on the CU cap.
+int banded_dft(const float* rows, long ld_rows, int R, int T, int win, int n_fft, int hop, int f0, int nf, float* W, float* S,
+               hipStream_t s);
+
 }  // namespace frames

@@ -107,6 +107,50 @@ int frames::framed_dft(const float* wave, long L, int B, int T, int n_fft, int h
   return igemm::launch<128, 128>(a, b, e, M, ld, n_fft, 1, s, ws + w.slab, /*allow_bf16=*/false);
 }
 
+// ---- the banded transform (frames.h): the same product with rows of their own pitch and the second basis formula
+namespace {
+// A[m = (r,t)][k] = rows[r][t*hop + k]; every frame lies within its row (checked by banded_dft)
+struct PitchedFrameRows {
+  static constexpr bool KCONTIG = true;
+  static constexpr int VEC = 1;
+  typedef igemm::NoCtx Ctx;
+  const float* p;
+  long ld;
+  int X, K, T, hop;
+  __device__ __forceinline__ Ctx prep(int) const { return Ctx(); }
+  __device__ __forceinline__ void load(const Ctx&, int x, int k0, int kin, float* v) const {
+    const int k = k0 + kin;
+    float t = 0.f;
+    if (x < X && k < K) {
+      const int r = x / T, fr = x - r * T;
+      t = p[(long)r * ld + (long)fr * hop + k];
+    }
+    v[0] = t;
+  }
+};
+// basis[k][c] = frames::banded_element(k, f0 + c / 2, c odd); columns >= 2 nf are zero
+__global__ void banded_basis(float* __restrict__ W, int win, int N, int f0, int nf, int ld) {
+  const long n = (long)win * ld;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int k = (int)(i / ld), c = (int)(i % ld);
+    W[i] = c < 2 * nf ? frames::banded_element(k, f0 + (c >> 1), c & 1, win, N) : 0.f;
+  }
+}
+}  // namespace
+
+int frames::banded_dft(const float* rows, long ld_rows, int R, int T, int win, int n_fft, int hop, int f0, int nf, float* W,
+                       float* S, hipStream_t s) {
+  const int ld = banded_ld(nf);
+  if (R <= 0 || T <= 0 || win < 32 || win % 32 || win > n_fft || hop <= 0 || f0 < 0 || nf <= 0 || f0 + nf > n_fft / 2 + 1) return AVVAD_EINVAL;
+  if ((long)(T - 1) * hop + win > ld_rows || (double)R * T * ld >= 2147483648.0) return AVVAD_EINVAL;
+  const int M = R * T;
+  hipLaunchKernelGGL(banded_basis, dim3(grid1((long)win * ld)), dim3(256), 0, s, W, win, n_fft, f0, nf, ld);
+  PitchedFrameRows a{rows, ld_rows, M, win, T, hop};
+  igemm::ColPlain<4> b{W, ld, ld, win, 0};
+  igemm::EpiStore e{S, ld, nullptr, 0};
+  return igemm::launch<128, 128>(a, b, e, M, ld, win, 1, s, /*slab=*/nullptr, /*allow_bf16=*/false);
+}
+
 extern "C" size_t avvad_stft_workspace(const avvad_stft_desc* d) { return ok_desc(d) ? ws_of(d).total * sizeof(float) : 0; }
 
 static int stft_impl(const float* wave, float* out, const avvad_stft_desc* d, int mode, const float* mean, const float* stdv,

@@ -1,0 +1,375 @@
+// stoi.hip -- intelligibility scores of the enhanced speech on the GPU: STOI (Taal et al. 2011) and its extended form
+// ESTOI (Jensen & Taal 2016) of a ragged batch of (clean, processed) waveform pairs.
+//
+// Replaces: nothing the reference has -- its papers report the two scores from a host-side Python package.  The definition
+// is include/avvad.h's (avvad_stoi) and tests/stoi_ref.py restates it in float64, stage by stage.
+//
+// Passes (every constant is fixed: 10 kHz, frames of 256 at hop 128, 512-point DFT, 15 third-octave bands, 30-frame segments):
+//   resample     fs 16000 only.  Polyphase 5/8 with the caller's 161 double taps: one output sample per thread, its 32 or 33
+//                products widened to double, summed in tap order, rounded once to float32.  Both signals, grid (chunk, row, signal).
+//   keep_frames  one workgroup of 16 waves per row.  The clean row's frame energies in double (a wave per frame: four samples per lane in
+//                sample order, the fixed butterfly), e = 20 log10(|w x| + eps) to the workspace; the row maximum (a NaN
+//                propagates, as numpy.max has it); keep flags (max - 40) - e < 0 and their exclusive scan by wave ballots into
+//                the kept-frame list; info = (frames, kept, segments).
+//   overlap_add  x_sil / y_sil materialised: sample j is the sum, in double and in frame order, of the one or two kept
+//                windowed frames that cover it, rounded once; exact zeros behind the row's own end.
+//   banded_dft   (frames.h) the 256-sample frames of x_sil / y_sil under the symmetric Hann as ONE fp32-MFMA product against
+//                the 256 x 424 basis of bins 7 .. 218 of a 512-point DFT.
+//   band_norms   one thread per (frame, band): sum of re^2 + im^2 over the band's bins in bin order, widened to double, sqrt.
+//   segments     one wave per (row, segment) on the 15 x 30 block in LDS, all in double: STOI's clipped, normalised row
+//                correlations (lane = band) and ESTOI's row-then-column normalisation (lane = band, then lane = frame);
+//                per-segment partials to the workspace.
+//   finalize     one thread per row: the partials in ascending segment order, d = sum / (15 S) and sum / S; a row with fewer
+//                than 30 frames after removal scores 1e-5.
+// No floating-point atomics; every sum has a fixed order that depends on the row alone; the product is scheduled in whole
+// tiles (an ordered fmaf chain per value), so a row's bits do not depend on its batch, on the CU cap or on the run.
+// Nothing at or behind lengths[b] (clamped to [0, L]) is read.
+#include <math.h>
+
+#include "frames.h"
+
+namespace {
+
+constexpr int FRAME = 256, HOP = 128, NFFT = 512, F0 = 7, NBIN = 212, NBAND = 15, SEG = 30, NTAP = 161, HALF = 80;
+constexpr int UP = 5, DOWN = 8;
+constexpr double EPS = 2.220446049250313e-16;      // 2^-52
+constexpr double DYN_RANGE = 40.0;
+constexpr double DEGENERATE = 1e-5;                // score of a row without a segment
+// first bin of band j (and, at j = 15, the end of the last band): the bins nearest 150 * 2^((2j - 1) / 6) Hz on the grid k * 10000 / 512
+__device__ const int BAND_EDGE[NBAND + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
+static_assert(F0 + NBIN == 219, "bins 7 .. 218");
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// numpy.minimum: a NaN on either side propagates
+__device__ __forceinline__ double min_nan(double a, double b) { return (a != a || b != b) ? a + b : (a < b ? a : b); }
+
+__host__ __device__ inline long resampled(long len) { return (UP * len + DOWN - 1) / DOWN; }
+__host__ __device__ inline long frame_count(long len) { return len > FRAME ? (len - FRAME + HOP - 1) / HOP : 0; }   // starts i < len - 256
+// samples of row b in the 10 kHz domain
+__device__ __forceinline__ long row_len(const int* lengths, int b, long L, int rate16) {
+  long len = L;
+  if (lengths) {
+    const int v = lengths[b];
+    len = v < 0 ? 0 : (v > L ? L : v);
+  }
+  return rate16 ? resampled(len) : len;
+}
+__device__ __forceinline__ int segments_of(int kept) {
+  const int M = kept > 0 ? kept - 1 : 0;
+  return M >= SEG ? M - SEG + 1 : 0;
+}
+
+// out[(sig, b)][n] = sum_t taps[t] xup[8 n + 80 - t], xup[5 m] = x[m]: scipy.signal.resample_poly(x, 5, 8)'s centring
+__global__ void __launch_bounds__(256)
+    resample(const float* __restrict__ x, long ldx, const float* __restrict__ y, long ldy, const int* __restrict__ lengths, long L,
+             const double* __restrict__ taps, float* __restrict__ out, long ld_out) {
+  const int b = blockIdx.y, sig = blockIdx.z;
+  long len = L;
+  if (lengths) {
+    const int v = lengths[b];
+    len = v < 0 ? 0 : (v > L ? L : v);
+  }
+  const long n = (long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= resampled(len)) return;
+  const float* src = sig ? y + b * ldy : x + b * ldx;
+  const long c = DOWN * n + HALF;
+  double acc = 0.0;
+  for (int t = (int)(c % UP); t < NTAP; t += UP) {
+    const long m = (c - t) / UP;
+    if (m >= 0 && m < len) acc += taps[t] * (double)src[m];
+  }
+  out[((long)sig * gridDim.y + b) * ld_out + n] = (float)acc;
+}
+
+// one workgroup of KEEP_WAVES waves per row of the clean signal x [B][ldx]; en [B][nf_p], idx [B][nf_p], nk [B], info [B][3]
+constexpr int KEEP_WAVES = 16, KEEP_THREADS = 64 * KEEP_WAVES;
+__global__ void __launch_bounds__(KEEP_THREADS)
+    keep_frames(const float* __restrict__ x, long ldx, const int* __restrict__ lengths, long L, int rate16, double* __restrict__ en,
+                int* __restrict__ idx, int nf_p, int* __restrict__ nk, int* __restrict__ info) {
+  __shared__ double w[FRAME];
+  __shared__ double wmax[KEEP_WAVES];
+  __shared__ int wnan[KEEP_WAVES], wcnt[KEEP_WAVES];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int nf = (int)frame_count(row_len(lengths, b, L, rate16));
+  const float* xr = x + b * ldx;
+  double* e = en + (long)b * nf_p;
+  int* ix = idx + (long)b * nf_p;
+  if (tid < FRAME) w[tid] = frames::hann_sym(tid, FRAME);
+  __syncthreads();
+  for (int i = wv; i < nf; i += KEEP_WAVES) {
+    const float* f = xr + (long)i * HOP;
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = lane + 64 * u;
+      const double v = w[k] * (double)f[k];
+      s += v * v;
+    }
+    s = wave_sum_d(s);
+    if (lane == 0) e[i] = 20.0 * log10(sqrt(s) + EPS);
+  }
+  __syncthreads();
+  double m = -INFINITY;
+  int nan = 0;
+  for (int i = tid; i < nf; i += KEEP_THREADS) {
+    const double v = e[i];
+    if (v != v) nan = 1;
+    else m = v > m ? v : m;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double t = __shfl_xor(m, o, 64);
+    m = t > m ? t : m;
+  }
+  nan = __any(nan);
+  if (lane == 0) wmax[wv] = m, wnan[wv] = nan;
+  __syncthreads();
+  nan = 0;
+  for (int k = 0; k < KEEP_WAVES; ++k) {
+    m = wmax[k] > m ? wmax[k] : m;
+    nan |= wnan[k];
+  }
+  const double thr = nan ? __builtin_nan("") : m - DYN_RANGE;
+  int base = 0;
+  for (int i0 = 0; i0 < nf; i0 += KEEP_THREADS) {
+    const int i = i0 + tid;
+    const bool keep = i < nf && (thr - e[i] < 0.0);
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wcnt[wv] = __popcll(mask);
+    __syncthreads();
+    int off = base;
+    for (int k = 0; k < KEEP_WAVES; ++k) {
+      if (k == wv) off = base;
+      base += wcnt[k];
+    }
+    if (keep) ix[off + __popcll(mask & ((1ull << lane) - 1ull))] = i;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    nk[b] = base;
+    info[b * 3 + 0] = nf;
+    info[b * 3 + 1] = base;
+    info[b * 3 + 2] = segments_of(base);
+  }
+}
+
+// sil[(sig, b)][j] = the kept windowed frames overlap-added at hop 128; grid (chunk of ld_sil, row, signal)
+__global__ void __launch_bounds__(256)
+    overlap_add(const float* __restrict__ x, long ldx, const float* __restrict__ y, long ldy, const int* __restrict__ idx, int nf_p,
+                int nf, const int* __restrict__ nk, float* __restrict__ sil, long ld_sil) {
+  __shared__ double w[FRAME];
+  const int b = blockIdx.y, sig = blockIdx.z;
+  w[threadIdx.x] = frames::hann_sym(threadIdx.x, FRAME);
+  __syncthreads();
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= ld_sil) return;
+  const float* src = sig ? y + b * ldy : x + b * ldx;
+  const int* ix = idx + (long)b * nf_p;
+  const int n = clamp_count(nk[b], nf);         // (nf: the most frames a row of this call has, so every read stays in its row)
+  const long q = j / HOP;
+  const int r = (int)(j - q * HOP);
+  double v = 0.0;
+  if (q >= 1 && q - 1 < n) v += w[r + HOP] * (double)src[(long)clamp_count(ix[q - 1], nf - 1) * HOP + r + HOP];
+  if (q < n) v += w[r] * (double)src[(long)clamp_count(ix[q], nf - 1) * HOP + r];
+  sil[((long)sig * gridDim.y + b) * ld_sil + j] = (float)v;
+}
+
+// band[m][j] = sqrt(sum over the band's bins of re^2 + im^2), m over all frames of all rows of both signals
+__global__ void __launch_bounds__(256) band_norms(const float* __restrict__ S, int ld, long n_frames, double* __restrict__ band) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_frames * NBAND) return;
+  const long m = i / NBAND;
+  const int j = (int)(i - m * NBAND);
+  const float* row = S + m * ld;
+  double s = 0.0;
+  for (int f = BAND_EDGE[j]; f < BAND_EDGE[j + 1]; ++f) {
+    const float2 c = *reinterpret_cast<const float2*>(row + 2 * (f - F0));
+    s += (double)c.x * (double)c.x + (double)c.y * (double)c.y;
+  }
+  band[i] = sqrt(s);
+}
+
+// v[0 .. n) (stride st) -> (v - mean) / (|v - mean| + eps) in place, sums in index order
+__device__ __forceinline__ void normalise(double* v, int n, int st) {
+  double mean = 0.0;
+  for (int t = 0; t < n; ++t) mean += v[t * st];
+  mean /= (double)n;
+  double ss = 0.0;
+  for (int t = 0; t < n; ++t) {
+    const double c = v[t * st] - mean;
+    v[t * st] = c;
+    ss += c * c;
+  }
+  const double inv = sqrt(ss) + EPS;
+  for (int t = 0; t < n; ++t) v[t * st] /= inv;
+}
+
+// one wave per (segment, row); band [2][B][mf][15]; part [B][ns][2] = (sum over the bands of STOI's correlations, ESTOI's sum / 30)
+__global__ void __launch_bounds__(64)
+    segments(const double* __restrict__ band, const int* __restrict__ nk, int B, int mf, int ns, int which, double* __restrict__ part) {
+  constexpr int LD = SEG + 1;
+  __shared__ double X[NBAND * LD], Y[NBAND * LD], P[NBAND * LD], red[SEG];
+  const int b = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
+  if (s >= segments_of(clamp_count(nk[b], mf + 1))) return;      // (uniform: nobody waits at a barrier below)
+  for (int e = tid; e < NBAND * SEG; e += 64) {
+    const int t = e / NBAND, j = e - t * NBAND;
+    X[j * LD + t] = band[((long)b * mf + s + t) * NBAND + j];
+    Y[j * LD + t] = band[(((long)B + b) * mf + s + t) * NBAND + j];
+  }
+  __syncthreads();
+  double stoi = 0.0, estoi = 0.0;
+  if (which & 1) {
+    if (tid < NBAND) {
+      const double *x = X + tid * LD, *y = Y + tid * LD;
+      double *p = P + tid * LD;
+      double nx = 0.0, ny = 0.0;
+      for (int t = 0; t < SEG; ++t) nx += x[t] * x[t], ny += y[t] * y[t];
+      const double alpha = sqrt(nx) / (sqrt(ny) + EPS);
+      const double clip = 1.0 + 5.623413251903491;             // 1 + 10^(15 / 20)
+      double mx = 0.0, mp = 0.0;
+      for (int t = 0; t < SEG; ++t) {
+        p[t] = min_nan(alpha * y[t], x[t] * clip);
+        mx += x[t], mp += p[t];
+      }
+      mx /= (double)SEG, mp /= (double)SEG;
+      double sx = 0.0, sp = 0.0, sxp = 0.0;
+      for (int t = 0; t < SEG; ++t) {
+        const double cx = x[t] - mx, cp = p[t] - mp;
+        sx += cx * cx, sp += cp * cp;
+      }
+      const double ix = sqrt(sx) + EPS, ip = sqrt(sp) + EPS;
+      for (int t = 0; t < SEG; ++t) sxp += ((x[t] - mx) / ix) * ((p[t] - mp) / ip);
+      red[tid] = sxp;
+    }
+    __syncthreads();
+    if (tid == 0)
+      for (int j = 0; j < NBAND; ++j) stoi += red[j];
+    __syncthreads();
+  }
+  if (which & 2) {
+    if (tid < NBAND) normalise(X + tid * LD, SEG, 1), normalise(Y + tid * LD, SEG, 1);
+    __syncthreads();
+    if (tid < SEG) {
+      normalise(X + tid, NBAND, LD), normalise(Y + tid, NBAND, LD);
+      double c = 0.0;
+      for (int j = 0; j < NBAND; ++j) c += X[j * LD + tid] * Y[j * LD + tid];
+      red[tid] = c;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int t = 0; t < SEG; ++t) estoi += red[t];
+      estoi /= (double)SEG;
+    }
+  }
+  if (tid == 0) part[((long)b * ns + s) * 2 + 0] = stoi, part[((long)b * ns + s) * 2 + 1] = estoi;
+}
+
+// d[b] = (STOI, ESTOI); a score that was not asked for is NaN
+__global__ void finalize(const double* __restrict__ part, const int* __restrict__ nk, int B, int mf, int ns, int which,
+                         double* __restrict__ d) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int n = segments_of(clamp_count(nk[b], mf + 1));
+  double s0 = 0.0, s1 = 0.0;
+  const double* p = part + (long)b * ns * 2;
+  int s = 0;
+  for (; s + 8 <= n; s += 8) {                 // eight segments' loads in flight, added in segment order
+    double2 t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[u] = *reinterpret_cast<const double2*>(p + 2 * (s + u));
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s0 += t[u].x, s1 += t[u].y;
+  }
+  for (; s < n; ++s) s0 += p[2 * s], s1 += p[2 * s + 1];
+  const double nan = __builtin_nan("");
+  d[b * 2 + 0] = (which & 1) ? (n ? s0 / ((double)NBAND * n) : DEGENERATE) : nan;
+  d[b * 2 + 1] = (which & 2) ? (n ? s1 / (double)n : DEGENERATE) : nan;
+}
+
+// The workspace, byte offsets (each a multiple of 256): [rs 2 B x ld_rs floats, fs 16000 only][en B x nf_p doubles]
+// [idx B x nf_p ints][nk B ints][sil 2 B x ld_sil floats][W 256 x ldS floats][S 2 B mf x ldS floats][band 2 B mf x 15 doubles]
+// [part B x ns x 2 doubles]; everything behind nk only when a row can have a segment (mf >= 30)
+struct Plan {
+  int rate16, nf, nf_p, mf, ns, ldS;
+  long Lr, ld_rs, ld_sil;
+  size_t rs, en, idx, nk, sil, W, S, band, part, total;
+};
+inline bool plan(int B, long L, int fs, Plan& p) {
+  if (B <= 0 || B > 32767 || L <= 0 || L > (1L << 30) || (fs != 16000 && fs != 10000)) return false;
+  p.rate16 = fs == 16000;
+  p.Lr = p.rate16 ? resampled(L) : L;
+  p.nf = (int)frame_count(p.Lr);
+  p.nf_p = (int)align_up((size_t)(p.nf > 0 ? p.nf : 1), 64);
+  p.mf = p.nf > 0 ? p.nf - 1 : 0;
+  p.ns = p.mf >= SEG ? p.mf - SEG + 1 : 0;
+  p.ldS = frames::banded_ld(NBIN);
+  p.ld_rs = (long)align_up((size_t)p.Lr, 64);
+  p.ld_sil = (long)p.nf * HOP + HOP;                 // (nf - 1) 128 + 256: every frame kept
+  if (p.ns > 0 && (double)2 * B * p.mf * p.ldS >= 2147483648.0) return false;
+  size_t o = 0;
+  p.rs = o, o += p.rate16 ? align_up((size_t)2 * B * p.ld_rs * sizeof(float), 256) : 0;
+  p.en = o, o += align_up((size_t)B * p.nf_p * sizeof(double), 256);
+  p.idx = o, o += align_up((size_t)B * p.nf_p * sizeof(int), 256);
+  p.nk = o, o += align_up((size_t)B * sizeof(int), 256);
+  p.sil = p.W = p.S = p.band = p.part = o;
+  if (p.ns > 0) {
+    p.sil = o, o += align_up((size_t)2 * B * p.ld_sil * sizeof(float), 256);
+    p.W = o, o += align_up((size_t)FRAME * p.ldS * sizeof(float), 256);
+    p.S = o, o += align_up((size_t)2 * B * p.mf * p.ldS * sizeof(float), 256);
+    p.band = o, o += align_up((size_t)2 * B * p.mf * NBAND * sizeof(double), 256);
+    p.part = o, o += align_up((size_t)B * p.ns * 2 * sizeof(double), 256);
+  }
+  p.total = o;
+  return true;
+}
+
+}  // namespace
+
+extern "C" size_t avvad_stoi_workspace(int B, long L, int fs) {
+  Plan p;
+  return plan(B, L, fs, p) ? p.total : 0;
+}
+
+extern "C" int avvad_stoi(const float* clean, long ld_clean, const float* proc, long ld_proc, const int* lengths, const double* taps,
+                          int B, long L, int fs, int which, double* d, int* info, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  Plan p;
+  if (!clean || !proc || !d || !info || !wsv || which < 1 || which > 3 || !plan(B, L, fs, p)) return AVVAD_EINVAL;
+  if (ld_clean < L || ld_proc < L || (p.rate16 && !taps)) return AVVAD_EINVAL;
+  if (ws_misaligned(wsv) || ((uintptr_t)d & 7) || ((uintptr_t)taps & 7) || ((uintptr_t)info & 3)) return AVVAD_EINVAL;
+  if (ws_bytes < p.total) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  char* ws = (char*)wsv;
+  double* en = (double*)(ws + p.en);
+  int* idx = (int*)(ws + p.idx);
+  int* nk = (int*)(ws + p.nk);
+  const float *x = clean, *y = proc;
+  long ldx = ld_clean, ldy = ld_proc;
+  if (p.rate16) {
+    float* rs = (float*)(ws + p.rs);
+    hipLaunchKernelGGL(resample, dim3(cdiv(p.Lr, 256), B, 2), dim3(256), 0, s, clean, ld_clean, proc, ld_proc, lengths, L, taps, rs,
+                       p.ld_rs);
+    x = rs, y = rs + (long)B * p.ld_rs, ldx = ldy = p.ld_rs;
+  }
+  hipLaunchKernelGGL(keep_frames, dim3(B), dim3(KEEP_THREADS), 0, s, x, ldx, lengths, L, p.rate16, en, idx, p.nf_p, nk, info);
+  double* part = (double*)(ws + p.part);
+  if (p.ns > 0) {
+    float* sil = (float*)(ws + p.sil);
+    float* S = (float*)(ws + p.S);
+    double* band = (double*)(ws + p.band);
+    hipLaunchKernelGGL(overlap_add, dim3(cdiv(p.ld_sil, 256), B, 2), dim3(256), 0, s, x, ldx, y, ldy, idx, p.nf_p, p.nf, nk, sil,
+                       p.ld_sil);
+    const int rc = frames::banded_dft(sil, p.ld_sil, 2 * B, p.mf, FRAME, NFFT, HOP, F0, NBIN, (float*)(ws + p.W), S, s);
+    if (rc) return rc;
+    const long n_frames = (long)2 * B * p.mf;
+    hipLaunchKernelGGL(band_norms, dim3(cdiv(n_frames * NBAND, 256)), dim3(256), 0, s, S, p.ldS, n_frames, band);
+    hipLaunchKernelGGL(segments, dim3(p.ns, B), dim3(64), 0, s, band, nk, B, p.mf, p.ns, which, part);
+  }
+  hipLaunchKernelGGL(finalize, dim3(cdiv(B, 64)), dim3(64), 0, s, part, nk, B, p.mf, p.ns, which, d);
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}

@@ -55,6 +55,17 @@ def energy_ratios(s_hat, s, n):
     return tuple(float(x) for x in ratios.tolist())
 
 
+def stoi(x, y, fs_sig=16000, extended=False):
+    """STOI (``extended``: ESTOI) of the processed signal ``y`` against the clean ``x``, the call of the Python package the
+    field uses: numpy arrays in, a Python float out.  Runs on the GPU (``avvad.ops.stoi``, csrc/stoi.hip); ``fs_sig`` is
+    16000 or 10000."""
+    from avvad import ops
+    c, p = _on_gpu(x, y)
+    if c.numel() != p.numel():
+        raise ValueError("x and y should have the same length, found %d and %d" % (c.numel(), p.numel()))
+    return float(ops.stoi(c, p, fs=fs_sig, extended=extended)[0])
+
+
 def mean_confidence_interval(data, confidence=0.95, round=3):
     """(mean, half-width of the two-sided Student-t interval), both rounded to 3 decimals -- the reference
     ignores its ``round`` argument (``:10``) and so does this."""

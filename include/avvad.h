@@ -37,6 +37,7 @@
  *           float64 statistics and score accumulators, score ratios, int64 confusion counts  8 bytes
  *           ratio / energies / clip_off of avvad_mix                                        8 bytes
  *           c_speech / c_noise and the spectra of avvad_target_noise_aware*                 8 bytes
+ *           d and taps of avvad_stoi                                                        8 bytes
  *           int64 / int32 index arrays      their natural alignment
  *           bf16 operands, avvad_lip_decode's coef, the avvad_stft_stream basis,
  *           (checked by avvad_stft_stream_fwd / _fwd_spec), the avvad_istft_stream
@@ -87,7 +88,7 @@ typedef void* avvad_stream_t; /* hipStream_t */
                                  are the avvad_score_* / avvad_confusion_* scores, and avvad_istft_bwd / avvad_resynth_bwd /
                                  avvad_si_sdr_loss, and avvad_mix_workspace / avvad_mix, and the
                                  avvad_target_noise_aware* masks, and avvad_spectral_loss_workspace /
-                                 avvad_spectral_loss. */
+                                 avvad_spectral_loss, and avvad_stoi_workspace / avvad_stoi. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -686,6 +687,38 @@ int avvad_si_sdr_loss(const float* est, long ld_est, const float* ref, long ld_r
  * not read. */
 int avvad_confusion_accumulate(const float* pred, int pred_mode, const float* target, const int* lengths,
                                long long* counts /* [B][4], added to */, int B, int T, int Y, avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Intelligibility: STOI and ESTOI of the enhanced speech (csrc/stoi.hip)
+ * Replaces: nothing the reference has; the papers of this model family report both scores from a host-side package.
+ * Signal order: clean x, processed y, both cropped to the row's length.  Every constant is fixed:
+ *   1. fs 16000: both are resampled to 10 kHz, polyphase up 5 / down 8 with the 161 taps the caller uploads (doubles;
+ *      avvad.ops.stoi_taps(): 5 firwin(161, 1/8, kaiser 5.0)), zero-extended edges, ceil(5 len / 8) samples centred as
+ *      scipy.signal.resample_poly centres them; each sample is a double sum in tap order rounded once to float32.
+ *      fs 10000 skips the stage; any other rate is refused.
+ *   2. frames of 256 at hop 128 with starts i < len - 256 (strict), window w = hanning(258)[1:-1];
+ *      e_i = 20 log10(|w x_i| + 2^-52) of the CLEAN signal in double; frame i is kept iff (max e - 40) - e_i < 0; the kept
+ *      windowed frames of both signals are overlap-added at hop 128 (double sum, rounded once).
+ *   3. the result is framed again by the same rule and window (M = kept - 1 frames), 512-point real DFT as one fp32-MFMA
+ *      product, and the 15 third-octave band magnitudes sqrt(sum |.|^2) over bins (7,9) (9,11) (11,14) (14,17) (17,22) (22,27)
+ *      (27,34) (34,43) (43,55) (55,69) (69,87) (87,109) (109,138) (138,174) (174,219), upper bin excluded, in double.
+ *   4. for m = 30 .. M the 15 x 30 blocks of frames m - 30 .. m - 1, in double.  STOI per band row: a = |x| / (|y| + eps),
+ *      y' = min(a y, x (1 + 10^(15/20))), both rows' means removed, each divided by (its norm + eps), products summed;
+ *      d = mean over bands and segments.  ESTOI: rows normalised the same way over time, then columns over bands;
+ *      d = mean over segments of sum(x_n y_n) / 30.
+ *   5. a row with fewer than 30 frames after removal (or no full frame) scores 1e-5 with 0 segments; anything else
+ *      propagates as IEEE arithmetic gives it.
+ * d [B][2] = (STOI, ESTOI); the one `which` does not ask for is NaN.  info [B][3] = (frames, kept frames, segments).
+ * clean / proc: B rows with their own pitches in floats (ld_* >= L), any 4-byte aligned float pointers; lengths: device int32
+ * [B], clamped to [0, L], nothing at or behind a row's length is read (NULL: L each).  taps: 8-byte aligned device doubles
+ * [161] (may be NULL at fs 10000); d: 8-byte aligned; ws: 16-byte aligned.  No floating-point atomics and every sum in a
+ * fixed order of the row alone: bit-identical run to run, a row's bits independent of its batch and of "max_cus".
+ * ---------------------------------------------------------------------- */
+size_t avvad_stoi_workspace(int B, long L, int fs);                /* 0 on a bad shape (B outside 1..32767, L < 1) or rate */
+int avvad_stoi(const float* clean, long ld_clean, const float* proc, long ld_proc, const int* lengths /* NULL: L each */,
+               const double* taps /* [161] */, int B, long L, int fs, int which /* 1 STOI, 2 ESTOI, 3 both */,
+               double* d /* [B][2] */, int* info /* [B][3]: frames, kept, segments */, void* ws, size_t ws_bytes,
+               avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Mask-regression training losses of a (B, T, F) mask head: mask MSE, signal approximation, spectrum approximation
