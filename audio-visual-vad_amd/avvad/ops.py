@@ -11,6 +11,7 @@ import os
 import torch
 
 from . import _lib as L
+from ._lib import AvvadError         # by name too: target_frames takes the utterance length as ``L``
 
 
 def _stream():
@@ -1597,7 +1598,7 @@ def target_frames(L, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, center=False, pa
         n += hop
     total = n + (2 * (nfft // 2) if center else 0)
     if total < nfft:
-        raise L.AvvadError("utterance of %d samples is shorter than one %d-sample frame" % (L, nfft))
+        raise AvvadError("utterance of %d samples is shorter than one %d-sample frame" % (int(L), nfft))
     return n, 1 + (total - nfft) // hop
 
 

@@ -111,6 +111,38 @@ def test_exact_from_spectra():
         _check_exact(ops.noise_aware_from_spectrum(Xd, Nd, outputs=(k,)), X, N, "only " + k)
 
 
+def test_exact_past_one_grid_stride_trip():
+    """noise_aware_mask on B * T * F = 2 * 8201 * 513 = 8,414,226 outputs: two trips of the grid-stride loop (8192
+    workgroups x 256 threads x 4 outputs a trip).  With n_frames = [8201, 5000] the second trip (row 1 from frame 8151 on)
+    writes zeros behind the row's frames; with [5000, 8201] it decides live cells.  Both bit for bit, all three outputs,
+    with a peak per row; the reference one row at a time."""
+    import target_ref as TR
+    ops = _ops()
+    assert TR.trips(TR.NA_B * TR.NA_T * F, TR.MASK_TRIP) == 2
+    rows = [TR.noise_aware_row(b) for b in range(TR.NA_B)]
+    Xd = torch.from_numpy(np.stack([r[0] for r in rows])).to(DEV)
+    Nd = torch.from_numpy(np.stack([r[1] for r in rows])).to(DEV)
+    peak = torch.tensor([0.37, 2.5], device=DEV)
+    pk = peak.cpu().numpy()
+    for counts in ([8201, 5000], [5000, 8201]):
+        got = ops.noise_aware_from_spectrum(Xd, Nd, n_frames=counts, peak=peak, outputs=NAMES)
+        for b in range(TR.NA_B):
+            _check_exact({k: v[b:b + 1] for k, v in got.items()}, rows[b][0][None], rows[b][1][None], "n_frames %r row %d" % (counts, b),
+                         peak=pk[b:b + 1], n_frames=counts[b:b + 1])
+            assert all(not got[k][b, counts[b]:].any() for k in NAMES), (counts, b)
+        print("noise-aware %r: %d outputs a mask, 0 excluded (bit for bit)" % (counts, got["speech"].numel()))
+        del got
+
+
+def test_a_row_shorter_than_a_frame_is_refused():
+    """ops.target_frames raises AvvadError for such a row, so noise_aware_targets returns before any launch"""
+    from avvad._lib import AvvadError
+    ops = _ops()
+    wave = torch.zeros(2, 5000, device=DEV)
+    with pytest.raises(AvvadError, match="shorter than one"):
+        ops.noise_aware_targets(wave, wave, [5000, 500])
+
+
 def _ragged():
     """four rows, width 4000: one frame, an end pad, the longest, and an all-zero row"""
     rng = np.random.default_rng(23)

@@ -1,7 +1,8 @@
 """GPU tests of the training labels (csrc/target.hip through avvad.ops and the drop-in packages/processing/target.py):
 against the reference's results (tests/golden/targets.npz) outside the stated rounding bands, against the float64
-restatement (tests/target_ref.py), ragged batches against single calls, degenerate inputs, reproducibility, and the
-real-audio data path of the train / evaluate loops."""
+restatement (tests/target_ref.py), ragged batches against single calls, degenerate inputs, reproducibility, every
+framing form and every loop of the label kernels past its first trip, and the real-audio data path of the train /
+evaluate loops."""
 import os
 
 import numpy as np
@@ -10,7 +11,7 @@ import torch
 
 import target_ref as R
 from conftest import GOLDEN, load_golden
-from test_targets_cpu import CFGS, IBM_DELTA, ibm_band, sa1, vad_band
+from test_targets_cpu import CFGS, IBM_DELTA, ibm_band, ibm_case, sa1, spectrum_case, vad_band
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -156,6 +157,158 @@ def test_bit_identical_run_to_run():
         a = ops.speech_targets(wave, lens, labels, robust=True)[1]
         b = ops.speech_targets(wave, lens, labels, robust=True)[1]
         assert torch.equal(a, b)
+
+
+# ------------------------------------------------------------------ past one loop trip and in every framing form
+# The cases come from tests/target_ref.py; tests/test_targets_cpu.py asserts from the float64 reference that each one can
+# fail: the ones shares, the empty tie bands, and the labels a minimum or maximum lost between trips would change.
+def run_vad_case(name, mode=None):
+    """one call of ops.speech_targets for the case; every row against vad_energy of that row alone, exact outside TIE"""
+    from avvad import ops
+    case = R.vad_cases()[name]
+    wave, lens = R.batch_of(case["rows"])
+    frames, out = ops.speech_targets(torch.from_numpy(wave).to(DEV), lens, "vad_labels", center=mode is not None,
+                                     pad_mode=mode or "reflect", **R.framing(case["n_fft"], case["hop"]))
+    assert frames.tolist() == case["T"] and out.shape == (len(lens), max(case["T"]), 1)
+    got = out.cpu().numpy()[:, :, 0]
+    assert np.isin(got, (0.0, 1.0)).all()
+    for b, T in enumerate(case["T"]):
+        E, c = R.vad_reference(case, b, mode)
+        thr = c * E.min()
+        tie = np.abs(E - thr) <= TIE * thr
+        bad = (got[b, :T].astype(bool) != (E > thr)) & ~tie
+        print("VAD %s %s row %d: T %d, %d frames excluded, %d differ" % (name, mode or "", b, T, tie.sum(), bad.sum()))
+        assert not bad.any(), (name, mode, b, np.flatnonzero(bad)[:8])
+        assert not got[b, T:].any(), (name, mode, b)
+
+
+def test_vad_vector_store_past_1024_frames():
+    """vad_decide at T = 1028: five trips of the minimum loop (256 frames a trip; the quietest frame lies in the fourth),
+    two of the float4 store loop (1024 frames a trip).  segment_energy, hop-block form (R = 4, seg = 16): 33 workgroups
+    of 32 segments, eight trips of each wave's segment loop, one of the k loop."""
+    run_vad_case("vec_store_T1028")
+
+
+def test_vad_scalar_store_with_the_minimum_in_the_last_quad():
+    """vad_decide at T = 1027 (T % 4 != 0): five trips of the minimum loop and five of the scalar store loop; the quietest
+    frame is the last: the fifth trip, which has three live threads, reads it, and the fifth store trip writes 1, 1, 0."""
+    run_vad_case("scalar_store_T1027")
+
+
+@pytest.mark.parametrize("name", ["whole_frame_vec", "whole_frame_scalar"])
+def test_vad_whole_frame_form(name):
+    """segment_energy in the whole-frame form (n_fft = 1024, hop = 307: R = 1, seg = 1024, stride 307): four trips of the k
+    loop per frame, eight of the segment loop; with L % 4 == 0 the float4 loads are on and taken by every fourth frame
+    only ((s0 & 3) == 0), with L % 4 != 0 every load is scalar.  vad_decide at T = 257: two trips of the minimum loop.
+    Every frame's label is decided by one loud sample, which lies in another k trip from frame to frame and, for every
+    eighth frame, in the last three samples that a load from an aligned address would miss."""
+    run_vad_case(name)
+
+
+@pytest.mark.parametrize("name", ["ragged_quad_whole_frame", "ragged_quad_hop_block"])
+def test_vad_guarded_last_quad(name):
+    """segment_energy with seg % 4 == 2: the last quad of a segment is loaded sample by sample behind the k + q < seg
+    guards, in the whole-frame form (seg = n_fft = 1002, four k trips) and in the hop-block form (n_fft = 1000: R = 4,
+    seg = hop = 250, one k trip).  vad_decide: one trip.  Loud single samples sit in the two guarded places of a segment
+    and in the two just behind it: dropping the former or adding the latter changes labels."""
+    run_vad_case(name)
+
+
+def test_vad_hop_block_form_with_a_segment_past_256_samples():
+    """segment_energy in the hop-block form with seg = hop = 512 (n_fft = 1024, R = 2): two trips of the k loop;
+    vad_decide adds two blocks per frame, one trip.  Loud single samples lie in the second half of some blocks and in the
+    first half of others, so either k trip alone gives other labels."""
+    run_vad_case("hop_block_seg512")
+
+
+@pytest.mark.parametrize("mode", ["reflect", "constant"])
+def test_vad_centred_ragged_batch(mode):
+    """segment_energy through sample_at on a centred ragged batch (n_fft = 64, hop 16, three rows; nseg = 130 for the
+    longest: five workgroups, eight trips of each wave's segment loop, one of the k loop; vad_decide: one trip): the
+    reflection point 2 (n - 1) - s is each row's own, row 0 fills the pitch so its end pad and part of its reflection
+    lie past the row (n > nread), rows 1 and 2 differ in the end-pad decision; 'constant' is the zero-padding mode.
+    Single loud samples decide the first and last frames: the two modes, a reflection about another row's end or about
+    the length without the end pad, and a read past the row's width each give other labels (test_targets_cpu.py)."""
+    run_vad_case("centred_ragged", mode)
+
+
+def test_vad_long_and_short_rows_in_one_call():
+    """vad_decide with T = 1028 and T = 185 in one launch, 100x apart in level: the long row's workgroup runs five trips
+    of the minimum loop (its quietest frame in the fourth), the short row's one; the store loops run to Tp = 1028 for
+    both (two float4 trips), zeros past the short row's frames."""
+    run_vad_case("long_and_short")
+
+
+def test_ibm_batch_past_one_grid_stride_trip():
+    """ibm_mask on B * T * 513 = 4 * 4101 * 513 = 8,415,252 outputs: two trips of the grid-stride loop (8192 workgroups
+    x 256 threads x 4 outputs a trip), the second in live frames of the last row; T odd, so quads cross rows and
+    utterances.  spectrum_max: every row ends in a partial slab (T_b % 8 != 0), and rows 1 and 3 have their loudest bin
+    there.  robust: segment_energy (R = 4, seg = 256, one k trip) and vad_decide at T = 4101 (17 trips of the minimum loop
+    and of the scalar store loop for the longest row)."""
+    from avvad import ops
+    rows, ref = ibm_case()
+    wave, lens = R.batch_of(rows)
+    w = torch.from_numpy(wave).to(DEV)
+    frames, plain = ops.speech_targets(w, lens, "ibm_labels")
+    _, robust = ops.speech_targets(w, lens, "ibm_labels", robust=True)
+    _, vad = ops.speech_targets(w, lens, "vad_labels")
+    Tp = max(R.IBM_FRAMES)
+    assert frames.tolist() == list(R.IBM_FRAMES) and plain.shape == robust.shape == (len(rows), Tp, 513) and vad.shape == (len(rows), Tp, 1)
+    assert torch.equal(robust, plain * vad)
+    got, v = plain.cpu().numpy(), vad.cpu().numpy()[:, :, 0]
+    assert np.isin(got, (0.0, 1.0)).all()
+    for b, T in enumerate(R.IBM_FRAMES):
+        bad = (got[b, :T].astype(bool) != ref[b]["mask"]) & ~ref[b]["band"]
+        print("IBM batch row %d: T %d, %d of %d bins excluded (delta %.0e), %d differ"
+              % (b, T, ref[b]["band"].sum(), bad.size, IBM_DELTA, bad.sum()))
+        assert not bad.any(), (b, np.argwhere(bad)[:8])
+        assert not got[b, T:].any() and not v[b, T:].any(), b
+        E, thr = ref[b]["E"], ref[b]["vad_thr"]
+        tie = np.abs(E - thr) <= TIE * thr
+        assert np.array_equal(v[b, :T].astype(bool)[~tie], (E > thr)[~tie]), b
+
+
+def test_ibm_from_spectrum_past_one_trip_in_every_layout():
+    """spectrum_max_strided on 513 x 8200 = 4,206,600 bins: 17 trips of the grid-stride loop (1024 workgroups x 256
+    threads a trip), the maximum in the thirteenth; ibm_mask_strided: two trips (4096 workgroups x 256 threads x 4 outputs
+    a trip).  Four layouts, each without and with a vad vector, against the kernel's arithmetic restated in float64."""
+    from avvad import ops
+    S, vad, mask, undecided = spectrum_case()
+    F, T = S.shape
+    Sd = torch.from_numpy(S).to(DEV)
+    vd = torch.from_numpy(vad).to(DEV)
+
+    def layouts():
+        yield "complex", Sd, None
+        yield "legacy view", torch.view_as_real(Sd), (2 * T, 2, 1)
+        yield "transposed storage", torch.view_as_real(Sd.T.contiguous()).permute(1, 0, 2), (2, 2 * F, 1)
+        wide = torch.full((F, T + 7), float("nan"), dtype=torch.complex64, device=DEV)
+        wide[:, 3:3 + T] = Sd
+        yield "column slice", wide[:, 3:3 + T], None
+    keep = ~undecided
+    for name, spec, strides in layouts():
+        if strides:
+            assert spec.stride() == strides, name
+        for with_vad in (False, True):
+            got = ops.ibm_from_spectrum(spec, vad=vd if with_vad else None).cpu().numpy()
+            want = mask & (vad != 0)[None, :] if with_vad else mask
+            bad = (got != want.astype(np.float32)) & keep
+            print("IBM from a spectrum, %s%s: %d of %d bins excluded, %d differ"
+                  % (name, " with vad" if with_vad else "", undecided.sum(), got.size, bad.sum()))
+            assert got.shape == (F, T) and not bad.any(), (name, with_vad, np.argwhere(bad)[:8])
+        del spec
+
+
+def test_a_row_shorter_than_a_frame_is_refused():
+    """ops.target_frames raises AvvadError for such a row, so speech_targets returns before any launch"""
+    from avvad import ops
+    from avvad._lib import AvvadError
+    wave = torch.zeros(2, 5000, device=DEV)
+    for labels in ("vad_labels", "ibm_labels"):
+        with pytest.raises(AvvadError, match="shorter than one"):
+            ops.speech_targets(wave, [5000, 500], labels)
+    with pytest.raises(AvvadError, match="shorter than one"):
+        ops.speech_targets(wave, [5000, 600], "vad_labels", pad_at_end=False)
 
 
 # ------------------------------------------------------------------ the real-audio data path
