@@ -180,6 +180,9 @@ SIGNATURES = {
     "avvad_confusion_accumulate": (C.c_int, [FP, C.c_int, FP, FP, FP, C.c_int, C.c_int, C.c_int, FP]),
     "avvad_stoi_workspace": (C.c_size_t, [C.c_int, C.c_long, C.c_int]),
     "avvad_stoi": (C.c_int, [FP, C.c_long, FP, C.c_long, FP, FP, C.c_int, C.c_long, C.c_int, C.c_int, FP, FP, FP, C.c_size_t, FP]),
+    "avvad_stoi_loss_workspace": (C.c_size_t, [C.c_int, C.c_long, C.c_int]),
+    "avvad_stoi_loss": (C.c_int, [FP, C.c_long, FP, C.c_long, FP, FP, C.c_int, C.c_long, C.c_int, C.c_int, FP, FP, FP, FP, C.c_long,
+                                  FP, C.c_size_t, FP]),
     "avvad_spectral_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "avvad_spectral_loss": (C.c_int, [FP, C.c_int, C.c_int, FP, FP, C.c_long, C.c_long, C.c_long, FP, C.c_long, C.c_long, C.c_long,
                                       FP, FP, FP, FP, C.c_int, C.c_int, C.c_int, FP, C.c_size_t, FP]),

@@ -1345,6 +1345,13 @@ def stoi_taps():
     return 5.0 * (h / h.sum())
 
 
+def _stoi_taps_on(device):
+    taps = _STOI_TAPS.get(device)
+    if taps is None:
+        taps = _STOI_TAPS[device] = torch.from_numpy(stoi_taps()).to(device)
+    return taps
+
+
 def stoi(clean, processed, lengths=None, fs=16000, extended=False, both=False, return_info=False):
     """STOI (``extended``: ESTOI) of a ragged batch on the GPU (avvad_stoi): clean and processed (B, L) (or (L,)) float32,
     cropped to ``lengths`` (nothing at or behind a row's length is read).  ``fs`` 16000 (resampled to 10 kHz) or 10000.
@@ -1364,11 +1371,7 @@ def stoi(clean, processed, lengths=None, fs=16000, extended=False, both=False, r
         lens32 = lengths_i32(lengths, x.device)
         if lens32.numel() != B:
             raise L.AvvadError("lengths must hold %d values" % B)
-    taps = None
-    if int(fs) == 16000:
-        taps = _STOI_TAPS.get(x.device)
-        if taps is None:
-            taps = _STOI_TAPS[x.device] = torch.from_numpy(stoi_taps()).to(x.device)
+    taps = _stoi_taps_on(x.device) if int(fs) == 16000 else None
     which = 3 if both else 2 if extended else 1
     d = torch.empty((B, 2), dtype=torch.float64, device=x.device)
     info = torch.empty((B, 3), dtype=torch.int32, device=x.device)
@@ -1377,6 +1380,65 @@ def stoi(clean, processed, lengths=None, fs=16000, extended=False, both=False, r
                                L.ptr(info), L.ptr(ws), ws.numel() * 4, _stream()), "avvad_stoi")
     out = d if both else d[:, 1] if extended else d[:, 0]
     return (out, info) if return_info else out
+
+
+class StoiLossFn(torch.autograd.Function):
+    """-sum_b d_b (STOI or ESTOI) and its gradient in the processed signal from the same call (avvad_stoi_loss)."""
+
+    @staticmethod
+    def forward(ctx, proc, ld_proc, clean, ld_clean, lens32, fs, which):
+        B, Ls = proc.shape
+        loss = torch.empty(1, dtype=torch.float32, device=proc.device)
+        d = torch.empty(B, dtype=torch.float64, device=proc.device)
+        dproc = torch.empty(B, Ls, dtype=torch.float32, device=proc.device)
+        taps = _stoi_taps_on(proc.device) if fs == 16000 else None
+        ws = _ws(L.lib().avvad_stoi_loss_workspace(B, Ls, fs), proc.device)
+        L.check(L.lib().avvad_stoi_loss(L.ptr(clean), ld_clean, L.ptr(proc.detach()), ld_proc, L.ptr(lens32), L.ptr(taps), B, Ls, fs,
+                                        which, L.ptr(loss), L.ptr(d), None, L.ptr(dproc), Ls, L.ptr(ws), ws.numel() * 4, _stream()),
+                "avvad_stoi_loss")
+        ctx.save_for_backward(dproc)
+        ctx.mark_non_differentiable(d)
+        return loss.view(()), d
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss, _dd):
+        (dproc,) = ctx.saved_tensors
+        g = dproc.clone()
+        L.check(L.lib().avvad_scale_by_device_scalar(L.ptr(g), L.ptr(_dev(dloss, "dloss").view(1)), g.numel(), _stream()),
+                "avvad_scale_by_device_scalar")
+        return g, None, None, None, None, None, None
+
+
+def stoi_loss(processed, clean, lengths=None, fs=16000, extended=False, return_scores=False):
+    """``-sum_b STOI_b`` (``extended``: ESTOI) of a ragged batch as a float32 scalar, differentiable in ``processed`` only:
+    processed, clean (B, L) (or (L,)) float32 on the GPU, read through their row pitches, cropped to ``lengths``.  The scores
+    are ``ops.stoi``'s bit for bit; the keep decision is made from the clean signal and is a constant of the backward, a
+    row without a segment scores 1e-5 and has a zero gradient, and the gradient is zero at and behind a row's length.  A
+    ``clean`` that requires grad is refused; there is no double backward.  Bit-identical run to run.  ``return_scores``: also
+    the (B,) float64 scores."""
+    if int(fs) not in (16000, 10000):
+        raise L.AvvadError("stoi_loss: fs must be 16000 or 10000, got %r" % (fs,))
+    if not isinstance(clean, torch.Tensor) or clean.dim() not in (1, 2) or not isinstance(processed, torch.Tensor) \
+            or processed.shape != clean.shape:
+        raise L.AvvadError("stoi_loss: processed and clean must be GPU tensors of one shape (B, L) or (L,), got %s and %s"
+                           % (tuple(getattr(processed, "shape", ())), tuple(getattr(clean, "shape", ()))))
+    if clean.requires_grad:
+        raise L.AvvadError("stoi_loss: the clean signal gets no gradient (the keep decision is made from it); detach it")
+    if not processed.is_cuda or processed.dtype != torch.float32:
+        raise L.AvvadError("processed must be a float32 GPU tensor: the AV-VAD hot path has no CPU fallback")
+    y = processed.view(1, -1) if processed.dim() == 1 else processed
+    B, Ls = y.shape
+    if y.stride(1) != 1 or (B > 1 and y.stride(0) < Ls):
+        y = y.contiguous()
+    x, ld_x = _score_rows(clean, "clean", B, Ls)
+    lens32 = None
+    if lengths is not None:
+        lens32 = lengths_i32(lengths, y.device)
+        if lens32.numel() != B:
+            raise L.AvvadError("lengths must hold %d values" % B)
+    loss, d = StoiLossFn.apply(y, y.stride(0) if B > 1 else Ls, x, ld_x, lens32, int(fs), 2 if extended else 1)
+    return (loss, d) if return_scores else loss
 
 
 # --------------------------------------------------------------------------- SI-SDR loss (csrc/scores.hip)

@@ -352,13 +352,14 @@ def mix_step(batch, device, labels, bank, draw, stats=None, fs=16e3, wlen_sec=64
 
 
 SPECTRAL_OBJECTIVES = {"mse_mask": "mask", "mse_signal": "signal", "msa": "spectrum"}      # -> the kind of ops.spectral_loss
-OBJECTIVES = ("bce", "si_sdr") + tuple(SPECTRAL_OBJECTIVES)
+STOI_OBJECTIVES = {"stoi": False, "estoi": True}                                            # -> ops.stoi_loss's ``extended``
+OBJECTIVES = ("bce", "si_sdr") + tuple(SPECTRAL_OBJECTIVES) + tuple(STOI_OBJECTIVES)
 
 
 def check_objective(objective, kind, waveform, wav_pairs, y_dim=None, clean_wavs=None):
     """``objective`` "si_sdr" trains a 513-bin mask model of the audio network on wav pairs, or on clean utterances mixed
     with noise in the step (``clean_wavs``), and so do the mask-regression objectives "mse_mask", "mse_signal" and "msa";
-    anything else is a ValueError (``y_dim`` None: not known yet)."""
+    "stoi" and "estoi" train under the conditions of "si_sdr"; anything else is a ValueError (``y_dim`` None: not known yet)."""
     if objective not in OBJECTIVES:
         raise ValueError("objective %r: one of %s" % (objective, ", ".join(OBJECTIVES)))
     if objective in SPECTRAL_OBJECTIVES:
@@ -373,6 +374,12 @@ def check_objective(objective, kind, waveform, wav_pairs, y_dim=None, clean_wavs
                              "the noisy file through the model's mask")
         if y_dim is not None and y_dim != 513:
             raise ValueError("objective 'si_sdr' needs a 513-bin mask head (y_dim 513), got y_dim %d" % y_dim)
+    if objective in STOI_OBJECTIVES:
+        if kind != "audio" or waveform or (wav_pairs is None and clean_wavs is None):
+            raise ValueError("objective %r trains the audio network on spectrograms of wav_pairs, or of clean_wavs mixed with "
+                             "noise_wavs: it resynthesises the noisy wave through the model's mask" % objective)
+        if y_dim is not None and y_dim != 513:
+            raise ValueError("objective %r needs a 513-bin mask head (y_dim 513), got y_dim %d" % (objective, y_dim))
 
 
 class SiSdrObjective:
@@ -398,12 +405,36 @@ class SiSdrObjective:
                                                           self.hop_percent, waves=True)
         return frames, x, target
 
+    def estimate(self, logits):
+        noisy, _, lens = self.waves[:3]
+        return ops.resynth(noisy, logits, mask_mode=2, n_fft=self.n_fft, hop=self.hop, sample_lengths=lens, pad_at_end=True, fs=self.fs)
+
     def loss(self, logits, y, lengths):
-        noisy, clean, lens = self.waves[:3]
-        est = ops.resynth(noisy, logits, mask_mode=2, n_fft=self.n_fft, hop=self.hop, sample_lengths=lens, pad_at_end=True, fs=self.fs)
+        _, clean, lens = self.waves[:3]
+        est = self.estimate(logits)
         skip = self.n_fft - self.hop
         loss, ratios = ops.si_sdr_loss(est, clean, lens, skip, skip, return_ratios=True)
         return loss, "  si-sdr %.2f dB" % float(torch.nanmean(ratios))
+
+
+class StoiObjective(SiSdrObjective):
+    """The step of ``objective="stoi"`` / ``"estoi"``: ``SiSdrObjective``'s ``prepare`` and resynthesis, then minus the summed
+    STOI (``extended``: ESTOI) of the estimate against the clean wave (``ops.stoi_loss``), and the batch's mean score for the
+    log line.  The same first and last ``n_fft - hop`` samples stay out, for ``SiSdrObjective``'s reason: the two waves are
+    sliced (the op takes pitched views) and every length loses both margins."""
+
+    def __init__(self, objective, device, labels, stats, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, step=None):
+        super().__init__(device, labels, stats, fs, wlen_sec, hop_percent, step)
+        self.name, self.extended = objective, STOI_OBJECTIVES[objective]
+
+    def loss(self, logits, y, lengths):
+        _, clean, lens = self.waves[:3]
+        est = self.estimate(logits)
+        skip = self.n_fft - self.hop
+        n = min(est.shape[1], clean.shape[1])
+        inner = [max(0, min(int(v), n) - 2 * skip) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+        loss, d = ops.stoi_loss(est[:, skip:n], clean[:, skip:n], inner, fs=int(self.fs), extended=self.extended, return_scores=True)
+        return loss, "  %s %.6f" % (self.name, float(d.mean()))
 
 
 class SpectralObjective:
@@ -704,7 +735,9 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     ``noise_wavs``; a y_dim 513 head) the mask-regression objectives of ``ops.spectral_loss`` on sigmoid(logits)
     (``SpectralObjective``): "mse_mask", the squared error against the step's label; "mse_signal", that error weighted by
     the mixture's magnitude; "msa", the complex spectrum approximation ``|S - m X|^2`` of the clean spectrum by the masked
-    mixture.  Validation reports the same loss.  AVVAD_OBJECTIVE overrides it.
+    mixture.  And under the conditions of "si_sdr", "stoi" / "estoi": minus the summed STOI / ESTOI of the resynthesised
+    wave against the clean one (``StoiObjective``, ``ops.stoi_loss``), the batch's mean score in the log line.
+    Validation reports the same loss.  AVVAD_OBJECTIVE overrides it.
 
     ``clean_wavs`` + ``noise_wavs`` (audio network, spectrogram input, both objectives; instead of ``wav_pairs``): lists
     or text files of clean utterances (``CleanWavs``) and of noise clips (``read_noise_bank``).  Every batch is mixed on
@@ -769,6 +802,11 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
                                   step=lambda batch, st: mix_step(batch, device, labels, bank, mixer, st, waves=True,
                                                                    mix_labels=mix_labels))
             prepare, loss_fn = step.prepare, step.loss
+        elif objective in STOI_OBJECTIVES:
+            step = StoiObjective(objective, device, labels, lambda: stats,
+                                 step=lambda batch, st: mix_step(batch, device, labels, bank, mixer, st, waves=True,
+                                                                  mix_labels=mix_labels))
+            prepare, loss_fn = step.prepare, step.loss
         elif objective in SPECTRAL_OBJECTIVES:
             step = SpectralObjective(objective, device, labels, lambda: stats,
                                      step=lambda batch, st: mix_step(batch, device, labels, bank, mixer, st, waves=True,
@@ -796,6 +834,9 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         prepare = lambda batch: wav_pair_step(batch, device, labels, stats)   # noqa: E731
         if objective == "si_sdr":
             step = SiSdrObjective(device, labels, lambda: stats)
+            prepare, loss_fn = step.prepare, step.loss
+        elif objective in STOI_OBJECTIVES:
+            step = StoiObjective(objective, device, labels, lambda: stats)
             prepare, loss_fn = step.prepare, step.loss
         elif objective in SPECTRAL_OBJECTIVES:
             step = SpectralObjective(objective, device, labels, lambda: stats)

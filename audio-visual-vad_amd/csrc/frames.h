@@ -101,5 +101,9 @@ static inline int banded_ld(int nf) { return (2 * nf + 3) / 4 * 4; }
 // a row's bits depend neither on how many rows the product has nor on the CU cap.
 int banded_dft(const float* rows, long ld_rows, int R, int T, int win, int n_fft, int hop, int f0, int nf, float* W, float* S,
                hipStream_t s);
+// The adjoint of banded_dft's product in its frames: dframes [M][win] = dS [M][ld] . basis^T, M = R * T rows, with W the
+// basis banded_dft left (the window is inside it).  One engine product over K = 2 nf (the gathers guard k < K), whole
+// tiles again: every value is one ordered fmaf chain over the 2 nf columns, independent of M and of the CU cap.
+int banded_dft_adjoint(const float* dS, int M, int win, int nf, const float* W, float* dframes, hipStream_t s);
 
 }  // namespace frames

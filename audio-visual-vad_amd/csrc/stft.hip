@@ -151,6 +151,15 @@ int frames::banded_dft(const float* rows, long ld_rows, int R, int T, int win, i
   return igemm::launch<128, 128>(a, b, e, M, ld, win, 1, s, /*slab=*/nullptr, /*allow_bf16=*/false);
 }
 
+int frames::banded_dft_adjoint(const float* dS, int M, int win, int nf, const float* W, float* dframes, hipStream_t s) {
+  const int ld = banded_ld(nf);
+  if (M <= 0 || win < 32 || win % 32 || nf <= 0 || (double)M * ld >= 2147483648.0) return AVVAD_EINVAL;
+  igemm::RowPlain a{dS, ld, M, 2 * nf, 0};
+  igemm::RowPlain b{W, ld, win, 2 * nf, 0};        // element (k, n) = basis[n][k]: the basis as it is stored, read along its rows
+  igemm::EpiStore e{dframes, win, nullptr, 0};
+  return igemm::launch<128, 128>(a, b, e, M, win, 2 * nf, 1, s, /*slab=*/nullptr, /*allow_bf16=*/false);
+}
+
 extern "C" size_t avvad_stft_workspace(const avvad_stft_desc* d) { return ok_desc(d) ? ws_of(d).total * sizeof(float) : 0; }
 
 static int stft_impl(const float* wave, float* out, const avvad_stft_desc* d, int mode, const float* mean, const float* stdv,

@@ -24,6 +24,20 @@
 // No floating-point atomics; every sum has a fixed order that depends on the row alone; the product is scheduled in whole
 // tiles (an ordered fmaf chain per value), so a row's bits do not depend on its batch, on the CU cap or on the run.
 // Nothing at or behind lengths[b] (clamped to [0, L]) is read.
+//
+// The training loss (avvad_stoi_loss) runs the same passes, then their adjoints in the processed signal, stage by stage,
+// every one a gather with fixed-order double sums (the keep decision and the kept-frame list are constants of the backward):
+//   segments_grad     one wave per (row, segment): the gradient of -d in the segment's 15 x 30 block of processed band
+//                     magnitudes -- STOI through the strictly unclipped elements and through alpha, ESTOI through the two
+//                     unit maps in reverse -- to a block of its own in the workspace.
+//   band_grad         one thread per (frame, band): the blocks of the up to 30 segments that hold the frame, in ascending
+//                     segment order; dS = dY S / Y (0 where Y is 0) over the band's bins, rounded to the float32 operand of
+//   banded_dft_adjoint  (frames.h) dframes = dS . basis^T, ONE fp32-MFMA product in whole tiles.
+//   invert_kept       frame -> position in the kept list, or -1.
+//   ola_adjoint       one thread per 10 kHz sample: the one or two kept frames that cover it, each through the one or two
+//                     frames of the second framing, under the window, in double; float32 at fs 10000, else kept as doubles for
+//   resample_adjoint  one thread per 16 kHz sample: its about 20 taps in ascending output order, in double, rounded once.
+//   loss_sum          one thread: -sum_b d_b in ascending row order, rounded once.
 #include <math.h>
 
 #include "frames.h"
@@ -290,6 +304,222 @@ __global__ void finalize(const double* __restrict__ part, const int* __restrict_
   d[b * 2 + 1] = (which & 2) ? (n ? s1 / (double)n : DEGENERATE) : nan;
 }
 
+// ---- the gradient of -d in the processed signal (avvad_stoi_loss)
+// The adjoint of normalise(): v[0 .. n) (stride st) the map's input, g its output's cotangent, overwritten with the input's:
+// c = v - mean, nn = |c|, dc = g / (nn + eps) - c (g.c) / (nn (nn + eps)^2) (the second term 0 when nn == 0), dv = dc - mean(dc)
+__device__ __forceinline__ void unit_backward(const double* v, double* g, int n, int st) {
+  double mean = 0.0;
+  for (int t = 0; t < n; ++t) mean += v[t * st];
+  mean /= (double)n;
+  double ss = 0.0, gc = 0.0;
+  for (int t = 0; t < n; ++t) {
+    const double c = v[t * st] - mean;
+    ss += c * c;
+    gc += g[t * st] * c;
+  }
+  const double nn = sqrt(ss), inv = nn + EPS;
+  const double k = nn != 0.0 ? gc / (nn * inv * inv) : 0.0;
+  double md = 0.0;
+  for (int t = 0; t < n; ++t) {
+    const double dc = g[t * st] / inv - (nn != 0.0 ? (v[t * st] - mean) * k : 0.0);
+    g[t * st] = dc;
+    md += dc;
+  }
+  md /= (double)n;
+  for (int t = 0; t < n; ++t) g[t * st] -= md;
+}
+
+// one wave per (segment, row), `which` 1 or 2; gblk [B][ns][15][30] = d(-d_b) / d(the segment's processed band magnitudes)
+__global__ void __launch_bounds__(64)
+    segments_grad(const double* __restrict__ band, const int* __restrict__ nk, int B, int mf, int ns, int which,
+                  double* __restrict__ gblk) {
+  constexpr int LD = SEG + 1;
+  __shared__ double X[NBAND * LD], Y[NBAND * LD], P[NBAND * LD], G[NBAND * LD];
+  const int b = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
+  const int nseg = segments_of(clamp_count(nk[b], mf + 1));
+  if (s >= nseg) return;                                           // (uniform: nobody waits at a barrier below)
+  for (int e = tid; e < NBAND * SEG; e += 64) {
+    const int t = e / NBAND, j = e - t * NBAND;
+    X[j * LD + t] = band[((long)b * mf + s + t) * NBAND + j];
+    Y[j * LD + t] = band[(((long)B + b) * mf + s + t) * NBAND + j];
+  }
+  __syncthreads();
+  if (which == 1) {
+    if (tid < NBAND) {
+      const double *x = X + tid * LD, *y = Y + tid * LD;
+      double *p = P + tid * LD, *g = G + tid * LD;
+      double nx = 0.0, ny = 0.0;
+      for (int t = 0; t < SEG; ++t) nx += x[t] * x[t], ny += y[t] * y[t];
+      const double sqx = sqrt(nx), sqy = sqrt(ny);
+      const double alpha = sqx / (sqy + EPS);
+      const double clip = 1.0 + 5.623413251903491;             // 1 + 10^(15 / 20)
+      double mx = 0.0;
+      for (int t = 0; t < SEG; ++t) {
+        p[t] = min_nan(alpha * y[t], x[t] * clip);
+        mx += x[t];
+      }
+      mx /= (double)SEG;
+      double sx = 0.0;
+      for (int t = 0; t < SEG; ++t) sx += (x[t] - mx) * (x[t] - mx);
+      const double ix = sqrt(sx) + EPS, scale = -1.0 / ((double)NBAND * nseg);
+      for (int t = 0; t < SEG; ++t) g[t] = scale * ((x[t] - mx) / ix);
+      unit_backward(p, g, SEG, 1);                             // g: the cotangent of p
+      // the tie went to the clip branch (min_nan), so only alpha y < C x carries a gradient: directly, and through alpha
+      double dot = 0.0;
+      for (int t = 0; t < SEG; ++t)
+        if (alpha * y[t] < x[t] * clip) dot += g[t] * y[t];
+      const double k = sqy != 0.0 ? sqx / (sqy * (sqy + EPS) * (sqy + EPS)) * dot : 0.0;
+      for (int t = 0; t < SEG; ++t) g[t] = (alpha * y[t] < x[t] * clip ? alpha * g[t] : 0.0) - (sqy != 0.0 ? k * y[t] : 0.0);
+    }
+  } else {
+    if (tid < NBAND) {
+      for (int t = 0; t < SEG; ++t) P[tid * LD + t] = Y[tid * LD + t];
+      normalise(X + tid * LD, SEG, 1), normalise(P + tid * LD, SEG, 1);     // P: the rows normalised over time
+    }
+    __syncthreads();
+    if (tid < SEG) {
+      normalise(X + tid, NBAND, LD);
+      const double scale = -1.0 / ((double)SEG * nseg);
+      for (int j = 0; j < NBAND; ++j) G[j * LD + tid] = scale * X[j * LD + tid];
+      unit_backward(P + tid, G + tid, NBAND, LD);              // over the bands ...
+    }
+    __syncthreads();
+    if (tid < NBAND) unit_backward(Y + tid * LD, G + tid * LD, SEG, 1);    // ... then over time
+  }
+  __syncthreads();
+  double* out = gblk + ((long)b * ns + s) * (NBAND * SEG);
+  for (int e = tid; e < NBAND * SEG; e += 64) {
+    const int j = e / SEG, t = e - j * SEG;
+    out[e] = G[j * LD + t];
+  }
+}
+
+// one thread per (row, frame, band): dY[m][j] = the blocks of segments max(0, m - 29) .. min(S - 1, m) in ascending order, then
+// dS[m][2 (f - 7) + {re, im}] = dY S / Y over the band's bins (0 where Y == 0, and on frames no segment holds).
+// S, band: the processed half of the forward's; dS [B mf][ld]
+__global__ void __launch_bounds__(256)
+    band_grad(const double* __restrict__ gblk, const float* __restrict__ S, const double* __restrict__ band, const int* __restrict__ nk,
+              int B, int mf, int ns, int ld, float* __restrict__ dS) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * mf * NBAND) return;
+  const long fr = i / NBAND;
+  const int j = (int)(i - fr * NBAND), b = (int)(fr / mf), m = (int)(fr - (long)b * mf);
+  const int kept = clamp_count(nk[b], mf + 1), nseg = segments_of(kept);
+  double dy = 0.0, yv = 0.0;
+  if (nseg > 0 && m < kept - 1) {
+    const int s0 = m - (SEG - 1) > 0 ? m - (SEG - 1) : 0, s1 = m < nseg - 1 ? m : nseg - 1;
+    for (int s = s0; s <= s1; ++s) dy += gblk[(((long)b * ns + s) * NBAND + j) * SEG + (m - s)];
+    yv = band[(((long)B + b) * mf + m) * NBAND + j];
+  }
+  const float* src = S + (((long)B + b) * mf + m) * ld;
+  float* dst = dS + fr * ld;
+  for (int f = BAND_EDGE[j]; f < BAND_EDGE[j + 1]; ++f) {
+    float2 o = make_float2(0.f, 0.f);
+    if (yv != 0.0) {
+      const float2 c = *reinterpret_cast<const float2*>(src + 2 * (f - F0));
+      o = make_float2((float)(dy * (double)c.x / yv), (float)(dy * (double)c.y / yv));
+    }
+    *reinterpret_cast<float2*>(dst + 2 * (f - F0)) = o;
+  }
+}
+
+// pos[b][f] = the position of frame f in row b's kept list (ascending, so a binary search), or -1; grid (chunk of nf_p, row)
+__global__ void __launch_bounds__(256)
+    invert_kept(const int* __restrict__ idx, int nf_p, int nf, const int* __restrict__ nk, int* __restrict__ pos) {
+  const int b = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= nf_p) return;
+  const int* ix = idx + (long)b * nf_p;
+  int lo = 0, hi = clamp_count(nk[b], nf);
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (ix[mid] < f) lo = mid + 1;
+    else hi = mid;
+  }
+  pos[(long)b * nf_p + f] = (lo < clamp_count(nk[b], nf) && ix[lo] == f) ? lo : -1;
+}
+
+// The adjoints of the second framing, the kept-frame overlap-add and the first framing's window in one gather: sample i of
+// the 10 kHz domain lies in frames i / 128 - 1 and i / 128; a kept one at position q put w[k] x[i] at sample 128 q + k of the
+// overlap-added signal, which frames j - 1 and j (j = that sample / 128) of the second framing read (the second window is in the
+// basis).  Up to four terms, in ascending frame order, in double; T = float writes the gradient itself (fs 10000), T = double
+// the resampler adjoint's input.  Zeros at and behind the row's length, in rows without a segment and when !live.
+// dfr [B][mf][256]; grid (chunk of ncols, row)
+template <typename T>
+__global__ void __launch_bounds__(256)
+    ola_adjoint(const float* __restrict__ dfr, const int* __restrict__ pos, int nf_p, const int* __restrict__ nk,
+                const int* __restrict__ lengths, long L, int rate16, int mf, int live, T* __restrict__ out, long ld_out, long ncols) {
+  __shared__ double w[FRAME];
+  w[threadIdx.x] = frames::hann_sym(threadIdx.x, FRAME);
+  __syncthreads();
+  const int b = blockIdx.y;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= ncols) return;
+  double v = 0.0;
+  if (live) {
+    const long len = row_len(lengths, b, L, rate16);
+    const long nfb = frame_count(len);
+    const int kept = clamp_count(nk[b], mf + 1), M = kept > 0 ? kept - 1 : 0;
+    if (i < len && segments_of(kept) > 0) {
+      const float* d = dfr + (long)b * mf * FRAME;
+      const int* ps = pos + (long)b * nf_p;
+      // the cotangent of sample 128 q + k (k < 256) of the overlap-added signal
+      auto dsil = [&](int q, int k) -> double {
+        const int j = q + (k >= HOP ? 1 : 0), r = k >= HOP ? k - HOP : k;
+        double s = 0.0;
+        if (j >= 1 && j - 1 < M) s += (double)d[(long)(j - 1) * FRAME + r + HOP];
+        if (j < M) s += (double)d[(long)j * FRAME + r];
+        return s;
+      };
+      const long f = i / HOP;
+      const int r = (int)(i - f * HOP);
+      if (f >= 1 && f - 1 < nfb) {
+        const int q = ps[f - 1];
+        if (q >= 0 && q < kept) v += w[r + HOP] * dsil(q, r + HOP);
+      }
+      if (f < nfb) {
+        const int q = ps[f];
+        if (q >= 0 && q < kept) v += w[r] * dsil(q, r);
+      }
+    }
+  }
+  out[(long)b * ld_out + i] = (T)v;
+}
+
+// The adjoint of resample(): dproc[b][m] = sum_n taps[8 n + 80 - 5 m] dy[b][n] over the outputs n whose tap index lies in
+// 0 .. 160, in ascending n, in double, rounded once; zeros at and behind the row's length and when !live.  grid (chunk of L, row)
+__global__ void __launch_bounds__(256)
+    resample_adjoint(const double* __restrict__ dy, long ld_dy, const int* __restrict__ lengths, long L, const double* __restrict__ taps,
+                     int live, float* __restrict__ dproc, long ld) {
+  const int b = blockIdx.y;
+  const long m = (long)blockIdx.x * 256 + threadIdx.x;
+  if (m >= L) return;
+  long len = L;
+  if (lengths) {
+    const int v = lengths[b];
+    len = v < 0 ? 0 : (v > L ? L : v);
+  }
+  double acc = 0.0;
+  if (live && m < len) {
+    const long lo = UP * m - HALF, last = resampled(len) - 1;
+    long n0 = lo > 0 ? (lo + DOWN - 1) / DOWN : 0, n1 = (UP * m + HALF) / DOWN;
+    if (n1 > last) n1 = last;
+    const double* row = dy + b * ld_dy;
+    for (long n = n0; n <= n1; ++n) acc += taps[DOWN * n + HALF - UP * m] * row[n];
+  }
+  dproc[b * ld + m] = (float)acc;
+}
+
+// loss = -(sum_b d2[b][which - 1]) in ascending row order by one thread, rounded once; d[b] = the row's score
+__global__ void __launch_bounds__(64) loss_sum(const double* __restrict__ d2, int B, int which, float* __restrict__ loss, double* __restrict__ d) {
+  if (d)
+    for (int b = threadIdx.x; b < B; b += 64) d[b] = d2[2 * b + which - 1];
+  if (threadIdx.x == 0) {
+    double sum = 0.0;
+    for (int b = 0; b < B; ++b) sum += d2[2 * b + which - 1];
+    loss[0] = (float)-sum;
+  }
+}
+
 // The workspace, byte offsets (each a multiple of 256): [rs 2 B x ld_rs floats, fs 16000 only][en B x nf_p doubles]
 // [idx B x nf_p ints][nk B ints][sil 2 B x ld_sil floats][W 256 x ldS floats][S 2 B mf x ldS floats][band 2 B mf x 15 doubles]
 // [part B x ns x 2 doubles]; everything behind nk only when a row can have a segment (mf >= 30)
@@ -327,23 +557,32 @@ inline bool plan(int B, long L, int fs, Plan& p) {
   return true;
 }
 
-}  // namespace
-
-extern "C" size_t avvad_stoi_workspace(int B, long L, int fs) {
-  Plan p;
-  return plan(B, L, fs, p) ? p.total : 0;
+// The loss's workspace: the forward's, then [pos B x nf_p ints][d2 B x 2 doubles][info B x 3 ints] and, when a row can have a
+// segment, [gblk B x ns x 450 doubles][dfr B mf x 256 floats][dy10 B x ld_rs doubles, fs 16000 only].  dS takes the clean half
+// of S, which band_norms has consumed by then.
+struct LossPlan {
+  Plan f;
+  size_t pos, d2, info, gblk, dfr, dy10, total;
+};
+inline bool loss_plan(int B, long L, int fs, LossPlan& p) {
+  if (!plan(B, L, fs, p.f)) return false;
+  size_t o = p.f.total;
+  p.pos = o, o += align_up((size_t)B * p.f.nf_p * sizeof(int), 256);
+  p.d2 = o, o += align_up((size_t)B * 2 * sizeof(double), 256);
+  p.info = o, o += align_up((size_t)B * 3 * sizeof(int), 256);
+  p.gblk = p.dfr = p.dy10 = o;
+  if (p.f.ns > 0) {
+    p.gblk = o, o += align_up((size_t)B * p.f.ns * NBAND * SEG * sizeof(double), 256);
+    p.dfr = o, o += align_up((size_t)B * p.f.mf * FRAME * sizeof(float), 256);
+    p.dy10 = o, o += p.f.rate16 ? align_up((size_t)B * p.f.ld_rs * sizeof(double), 256) : 0;
+  }
+  p.total = o;
+  return true;
 }
 
-extern "C" int avvad_stoi(const float* clean, long ld_clean, const float* proc, long ld_proc, const int* lengths, const double* taps,
-                          int B, long L, int fs, int which, double* d, int* info, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
-  AVVAD_ENTER();
-  Plan p;
-  if (!clean || !proc || !d || !info || !wsv || which < 1 || which > 3 || !plan(B, L, fs, p)) return AVVAD_EINVAL;
-  if (ld_clean < L || ld_proc < L || (p.rate16 && !taps)) return AVVAD_EINVAL;
-  if (ws_misaligned(wsv) || ((uintptr_t)d & 7) || ((uintptr_t)taps & 7) || ((uintptr_t)info & 3)) return AVVAD_EINVAL;
-  if (ws_bytes < p.total) return AVVAD_EWORKSPACE;
-  hipStream_t s = (hipStream_t)sv;
-  char* ws = (char*)wsv;
+// the forward passes of avvad_stoi within ws (carved by p); d [B][2], info [B][3]
+int forward(const float* clean, long ld_clean, const float* proc, long ld_proc, const int* lengths, const double* taps, int B, long L,
+            int which, double* d, int* info, char* ws, const Plan& p, hipStream_t s) {
   double* en = (double*)(ws + p.en);
   int* idx = (int*)(ws + p.idx);
   int* nk = (int*)(ws + p.nk);
@@ -370,6 +609,77 @@ extern "C" int avvad_stoi(const float* clean, long ld_clean, const float* proc, 
     hipLaunchKernelGGL(segments, dim3(p.ns, B), dim3(64), 0, s, band, nk, B, p.mf, p.ns, which, part);
   }
   hipLaunchKernelGGL(finalize, dim3(cdiv(B, 64)), dim3(64), 0, s, part, nk, B, p.mf, p.ns, which, d);
+  return AVVAD_OK;
+}
+
+}  // namespace
+
+extern "C" size_t avvad_stoi_workspace(int B, long L, int fs) {
+  Plan p;
+  return plan(B, L, fs, p) ? p.total : 0;
+}
+
+extern "C" int avvad_stoi(const float* clean, long ld_clean, const float* proc, long ld_proc, const int* lengths, const double* taps,
+                          int B, long L, int fs, int which, double* d, int* info, void* wsv, size_t ws_bytes, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  Plan p;
+  if (!clean || !proc || !d || !info || !wsv || which < 1 || which > 3 || !plan(B, L, fs, p)) return AVVAD_EINVAL;
+  if (ld_clean < L || ld_proc < L || (p.rate16 && !taps)) return AVVAD_EINVAL;
+  if (ws_misaligned(wsv) || ((uintptr_t)d & 7) || ((uintptr_t)taps & 7) || ((uintptr_t)info & 3)) return AVVAD_EINVAL;
+  if (ws_bytes < p.total) return AVVAD_EWORKSPACE;
+  const int rc = forward(clean, ld_clean, proc, ld_proc, lengths, taps, B, L, which, d, info, (char*)wsv, p, (hipStream_t)sv);
+  if (rc) return rc;
+  AVVAD_LAUNCH_CHECK();
+  return AVVAD_OK;
+}
+
+extern "C" size_t avvad_stoi_loss_workspace(int B, long L, int fs) {
+  LossPlan p;
+  return loss_plan(B, L, fs, p) ? p.total : 0;
+}
+
+extern "C" int avvad_stoi_loss(const float* clean, long ld_clean, const float* proc, long ld_proc, const int* lengths, const double* taps,
+                               int B, long L, int fs, int which, float* loss, double* d, int* info, float* dproc, long ld_dproc,
+                               void* wsv, size_t ws_bytes, avvad_stream_t sv) {
+  AVVAD_ENTER();
+  LossPlan lp;
+  if (!clean || !proc || !loss || !dproc || !wsv || which < 1 || which > 2 || !loss_plan(B, L, fs, lp)) return AVVAD_EINVAL;
+  const Plan& p = lp.f;
+  if (ld_clean < L || ld_proc < L || ld_dproc < L || (p.rate16 && !taps)) return AVVAD_EINVAL;
+  if (ws_misaligned(wsv) || ((uintptr_t)d & 7) || ((uintptr_t)taps & 7) || ((uintptr_t)info & 3)) return AVVAD_EINVAL;
+  if (ws_bytes < lp.total) return AVVAD_EWORKSPACE;
+  hipStream_t s = (hipStream_t)sv;
+  char* ws = (char*)wsv;
+  double* d2 = (double*)(ws + lp.d2);
+  if (!info) info = (int*)(ws + lp.info);
+  int rc = forward(clean, ld_clean, proc, ld_proc, lengths, taps, B, L, which, d2, info, ws, p, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(loss_sum, dim3(1), dim3(64), 0, s, d2, B, which, loss, d);
+  const int* nk = (const int*)(ws + p.nk);
+  int* pos = (int*)(ws + lp.pos);
+  float* dfr = (float*)(ws + lp.dfr);
+  const int live = p.ns > 0;
+  if (live) {
+    float* S = (float*)(ws + p.S);
+    const double* band = (const double*)(ws + p.band);
+    double* gblk = (double*)(ws + lp.gblk);
+    float* dS = S;                                    // the clean half: consumed by band_norms
+    hipLaunchKernelGGL(segments_grad, dim3(p.ns, B), dim3(64), 0, s, band, nk, B, p.mf, p.ns, which, gblk);
+    hipLaunchKernelGGL(band_grad, dim3(cdiv((long)B * p.mf * NBAND, 256)), dim3(256), 0, s, gblk, S, band, nk, B, p.mf, p.ns, p.ldS, dS);
+    rc = frames::banded_dft_adjoint(dS, B * p.mf, FRAME, NBIN, (const float*)(ws + p.W), dfr, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(invert_kept, dim3(cdiv(p.nf_p, 256), B), dim3(256), 0, s, (const int*)(ws + p.idx), p.nf_p, p.nf, nk, pos);
+  }
+  if (p.rate16) {
+    double* dy10 = (double*)(ws + lp.dy10);
+    if (live)
+      hipLaunchKernelGGL(ola_adjoint<double>, dim3(cdiv(p.Lr, 256), B), dim3(256), 0, s, dfr, pos, p.nf_p, nk, lengths, L, 1, p.mf, 1,
+                         dy10, p.ld_rs, p.Lr);
+    hipLaunchKernelGGL(resample_adjoint, dim3(cdiv(L, 256), B), dim3(256), 0, s, dy10, p.ld_rs, lengths, L, taps, live, dproc, ld_dproc);
+  } else {
+    hipLaunchKernelGGL(ola_adjoint<float>, dim3(cdiv(L, 256), B), dim3(256), 0, s, dfr, pos, p.nf_p, nk, lengths, L, 0, p.mf, live,
+                       dproc, ld_dproc, L);
+  }
   AVVAD_LAUNCH_CHECK();
   return AVVAD_OK;
 }

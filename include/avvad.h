@@ -37,7 +37,7 @@
  *           float64 statistics and score accumulators, score ratios, int64 confusion counts  8 bytes
  *           ratio / energies / clip_off of avvad_mix                                        8 bytes
  *           c_speech / c_noise and the spectra of avvad_target_noise_aware*                 8 bytes
- *           d and taps of avvad_stoi                                                        8 bytes
+ *           d and taps of avvad_stoi and avvad_stoi_loss                                    8 bytes
  *           int64 / int32 index arrays      their natural alignment
  *           bf16 operands, avvad_lip_decode's coef, the avvad_stft_stream basis,
  *           (checked by avvad_stft_stream_fwd / _fwd_spec), the avvad_istft_stream
@@ -88,7 +88,8 @@ typedef void* avvad_stream_t; /* hipStream_t */
                                  are the avvad_score_* / avvad_confusion_* scores, and avvad_istft_bwd / avvad_resynth_bwd /
                                  avvad_si_sdr_loss, and avvad_mix_workspace / avvad_mix, and the
                                  avvad_target_noise_aware* masks, and avvad_spectral_loss_workspace /
-                                 avvad_spectral_loss, and avvad_stoi_workspace / avvad_stoi. */
+                                 avvad_spectral_loss, and avvad_stoi_workspace / avvad_stoi, and
+                                 avvad_stoi_loss_workspace / avvad_stoi_loss. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -719,6 +720,40 @@ int avvad_stoi(const float* clean, long ld_clean, const float* proc, long ld_pro
                const double* taps /* [161] */, int B, long L, int fs, int which /* 1 STOI, 2 ESTOI, 3 both */,
                double* d /* [B][2] */, int* info /* [B][3]: frames, kept, segments */, void* ws, size_t ws_bytes,
                avvad_stream_t s);
+/* STOI / ESTOI as a training loss: the row loss is -d_b, with d_b avvad_stoi's STOI (which 1) or ESTOI (which 2) bit for
+ * bit (the same forward passes in the same order), and dproc its gradient in the PROCESSED signal.  The clean signal gets
+ * no gradient; the 40 dB keep decision is made from the clean signal alone, so it and the kept-frame list are constants of
+ * the backward.  The chain resample -> overlap-add of the kept windowed frames -> frame, window, banded DFT -> band
+ * magnitudes -> segments is differentiated stage by stage, every adjoint a gather with fixed-order sums, in double where
+ * the forward sums in double; no float atomics; a row's sums depend on the row alone.
+ *   unit map u(v) = c / (n + eps), c = v - mean(v), n = |c|, cotangent g on u:
+ *       dc = g / (n + eps) - c (g.c) / (n (n + eps)^2)   (second term 0 when n == 0),   dv = dc - mean(dc)
+ *   STOI, per band row of a segment: a = |x| / (|y| + eps), p_t = a y_t where a y_t < C x_t, else C x_t (C = 1 + 10^(15/20);
+ *       the tie goes to the clip branch as the forward's minimum has it, so m_t = [a y_t < C x_t] strictly).  g_p = the unit
+ *       map's dv for u(p) under the cotangent u(x) / (15 S);
+ *       dy_t = a m_t g_p,t - (|x| y_t / (|y| (|y| + eps)^2)) sum_k m_k g_p,k y_k   (second term 0 when |y| == 0)
+ *   ESTOI: the unit map over time, then over bands; its adjoint twice in reverse, from the cotangent x_n / (30 S).
+ *   (the loss is -d: both cotangents enter with a minus sign)
+ *   segments: frame m belongs to segments max(0, m - 29) .. min(S - 1, m); their contributions to dY[m][j] are summed in
+ *       ascending segment order (each segment writes a 15 x 30 block of its own, then a gather).
+ *   band magnitude: dS[m][f] = dY[m][band(f)] S[m][f] / Y[m][band(f)], 0 where the magnitude is 0; the 15 bands tile bins
+ *       7 .. 218, so this is one pass that writes the float32 operand of
+ *   the banded DFT's adjoint: ONE fp32-MFMA product dframes [M x 256] = dS [M x 424] . basis^T (the window is in the
+ *       basis), in whole tiles: a row's bits depend neither on its batch nor on "max_cus".
+ *   framing, kept-frame overlap-add (through the inverse of the kept list: frame -> position, or dropped) and the 5/8
+ *       resampler: each sample gathers the one or two frames, or the about 20 taps, that touch it, in ascending order, in
+ *       double, rounded once.  fs 10000 skips the resampler, as the forward does.
+ * dproc [B][ld_dproc] float32 is overwritten in columns 0 .. L - 1, with exact zeros at and behind lengths[b]; nothing of
+ * either input there is read.  A row without a segment scores 1e-5 and has an all-zero gradient.
+ * loss[0] = -sum_b d_b, summed in double in ascending row order and rounded once to float (as avvad_si_sdr_loss).
+ * d: NULL or [B] doubles, d_b; info: NULL or [B][3] as avvad_stoi's.  Non-finite inputs propagate as IEEE arithmetic
+ * gives them.  Pointers, pitches (ld_dproc >= L too), alignments and return codes as for avvad_stoi; loss and dproc: any
+ * 4-byte aligned float pointers.  The workspace is the caller's; nothing is allocated and nothing synchronises. */
+size_t avvad_stoi_loss_workspace(int B, long L, int fs);           /* 0 on a bad shape or rate, as avvad_stoi_workspace */
+int avvad_stoi_loss(const float* clean, long ld_clean, const float* proc, long ld_proc, const int* lengths /* NULL: L each */,
+                    const double* taps /* [161] */, int B, long L, int fs, int which /* 1 STOI, 2 ESTOI */,
+                    float* loss /* [1] */, double* d /* [B] or NULL */, int* info /* [B][3] or NULL */, float* dproc,
+                    long ld_dproc, void* ws, size_t ws_bytes, avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Mask-regression training losses of a (B, T, F) mask head: mask MSE, signal approximation, spectrum approximation
