@@ -13,6 +13,7 @@
 // w_f / N times the forward one, so the adjoint of the inverse GEMM is frames::framed_dft applied to the normalised cotangent
 // q (overlap_add_adjoint), followed by one epilogue pass (mask_gradient); the spectrum is data and has no gradient.
 #include "frames.h"
+#include "reduce.h"
 
 namespace {
 
@@ -61,7 +62,7 @@ __global__ void overlap_add(const float* __restrict__ Y, const double* __restric
   const long n_el = (long)B * pitch;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
     const int b = (int)(i / pitch), s = (int)(i % pitch);
-    const int nf = n_frames ? clamp_count(n_frames[b], T) : T;
+    const int nf = row_count(n_frames, b, T);
     int len = out_len ? out_len[b] : pitch;
     len = len > pitch ? pitch : len;
     const long natural = nf > 0 ? (long)N + (long)hop * (nf - 1) - start : 0;
@@ -104,7 +105,7 @@ __global__ void overlap_add_adjoint(const float* __restrict__ dout, const double
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
     const int b = (int)(i / Lq);
     const long sp = i % Lq, s = sp - start;
-    const int nf = n_frames ? clamp_count(n_frames[b], T) : T;
+    const int nf = row_count(n_frames, b, T);
     int len = out_len ? out_len[b] : pitch;
     len = len > pitch ? pitch : len;
     const long natural = nf > 0 ? (long)N + (long)hop * (nf - 1) - start : 0;
@@ -131,7 +132,7 @@ __global__ void mask_gradient(const float* __restrict__ G, int ld, const float* 
   const long n_el = (long)B * T * F;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_el; i += (long)gridDim.x * blockDim.x) {
     const unsigned f = (unsigned)(i % F), x = (unsigned)(i / F), b = x / (unsigned)T, t = x - b * (unsigned)T;
-    const int nf = n_frames ? clamp_count(n_frames[b], T) : T;
+    const int nf = row_count(n_frames, b, T);
     float r = 0.f;
     if ((int)t < nf) {
       const float2 g = *reinterpret_cast<const float2*>(G + (long)x * ld + 2 * f);

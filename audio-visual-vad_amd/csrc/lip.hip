@@ -32,7 +32,7 @@
 // No floating-point atomics; the partials are per input frame, so results do not depend on the grid ("max_cus").
 #include <math.h>
 
-#include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (ti * 16 + 4 * l4 + r < W && tj * 16 + l15 < W) mn = fminf(mn, acc[ti][tj][r]), mx = fmaxf(mx, acc[ti][tj][r]);
-    for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o)), mx = fmaxf(mx, __shfl_xor(mx, o));
+    mn = wave_fold(mn, fminf), mx = wave_fold(mx, fmaxf);
     if (lane == 0) flo[row] = mn, fhi[row] = mx;
     wave_sync();                         // Z is read; the frame takes its place, row-major with pitch 67, for whole-line stores
 #pragma unroll
@@ -201,12 +201,13 @@ __global__ void __launch_bounds__(256)
     mn = fminf(mn, lo);
     rg = fmax(rg, (double)hi - (double)lo);
   }
-  for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o)), rg = fmax(rg, __shfl_xor(rg, o));
-  if ((threadIdx.x & 63) == 0) smn[threadIdx.x >> 6] = mn, srg[threadIdx.x >> 6] = rg;
+  const auto most = [](double a, double b) { return fmax(a, b); };
+  fold4_put(smn, mn, fminf);
+  fold4_put(srg, rg, most);
   __syncthreads();
   if (threadIdx.x == 0) {
-    mn = fminf(fminf(smn[0], smn[1]), fminf(smn[2], smn[3]));
-    rg = fmax(fmax(srg[0], srg[1]), fmax(srg[2], srg[3]));
+    mn = fold4_get(smn, fminf);
+    rg = fold4_get(srg, most);
     gmin[b] = n > 0 ? mn : 0.f;
     inv[b] = rg > 0.0 ? (float)(255.0 / rg) : 0.f;               // R == 0 (constant frames): the frames are written as 0
     long len = frame_start(n, p, q);
@@ -247,12 +248,12 @@ __global__ void __launch_bounds__(256)
     for (int k = 0; k < k1 - k0; ++k) dst[(long)k * NPIX + e] = v;
   }
   if (!part) return;                     // statistics of what is stored, before the standardisation
-  for (int o = 32; o > 0; o >>= 1) s1 += __shfl_xor(s1, o), s2 += __shfl_xor(s2, o);
-  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s1, red[1][threadIdx.x >> 6] = s2;
+  const double s[2] = {s1, s2};
+  fold4_put(red, s, Add());
   __syncthreads();
   if (threadIdx.x == 0) {
-    part[2 * row] = (double)(k1 - k0) * (((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]);
-    part[2 * row + 1] = (double)(k1 - k0) * (((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]);
+    part[2 * row] = (double)(k1 - k0) * fold4_get(red[0], Add());
+    part[2 * row + 1] = (double)(k1 - k0) * fold4_get(red[1], Add());
   }
 }
 
@@ -264,8 +265,8 @@ __global__ void __launch_bounds__(256) lip_pad(const int* __restrict__ out_len, 
 }
 
 // acc += (sum, sumsq) of the frames' partials, count += written pixels.  Wave w takes the utterances w, w + 16, ..., lane l
-// their frames l, l + 64, ... in ascending order; the lanes are added by butterflies and the sixteen waves in ascending
-// order.  (One utterance after the other over the whole workgroup is a chain of B dependent load rounds: 34 us for B = 64.)
+// their frames l, l + 64, ... in ascending order; the lanes are added by butterflies (reduce.h) and the sixteen waves in
+// ascending order.  (One utterance after the other over the whole workgroup is a chain of B dependent load rounds: 34 us for B = 64.)
 __global__ void __launch_bounds__(1024)
     lip_add(const double* __restrict__ part, const int* __restrict__ starts, const int* __restrict__ n_in, const int* __restrict__ out_len,
             long rows, int B, double* __restrict__ acc) {
@@ -283,7 +284,7 @@ __global__ void __launch_bounds__(1024)
     }
   }
   for (int b = threadIdx.x; b < B; b += 1024) c += (long long)out_len[b] * NPIX;
-  for (int o = 32; o > 0; o >>= 1) s1 += __shfl_xor(s1, o), s2 += __shfl_xor(s2, o), c += __shfl_xor(c, o);
+  s1 = wave_sum(s1), s2 = wave_sum(s2), c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s1, red[1][threadIdx.x >> 6] = s2, cnt[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -15,8 +15,8 @@
 // Kernel forms (memory-bound, and at a training batch's size launch-bound):
 //   mix_energies: rows are cut into chunks of AVVAD_MIX_CHUNK samples; workgroup (chunk, row) has four waves whose 256
 //        lanes stride over the chunk (plain dword loads: the row bases are only 4-byte aligned), cross-lane sums by a fixed
-//        butterfly, the four waves added in wave order; the workgroup stores one (Es, En) partial.  A workgroup whose chunk
-//        lies past the row's length exits and stores nothing.
+//        butterfly, the four waves added in wave order (reduce.h); the workgroup stores one (Es, En) partial.  A workgroup
+//        whose chunk lies past the row's length exits and stores nothing.
 //   mix_gain: one thread per row adds the row's partials in ascending chunk order (only the chunks below the row's length
 //        are read), forms g_b, and zeroes peak[b].
 //   mix_apply: the same grid over [0, L): the mixture, the scaled noise, the zeros behind the length; the workgroup's
@@ -32,25 +32,13 @@
 // is cut there, and start is taken mod the clip's length.
 #include <math.h>
 
-#include "common.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int CHUNK = AVVAD_MIX_CHUNK;     // samples of one partial
 constexpr int UN = 8;                      // samples in flight per lane in the energy pass (as scores.hip)
 static_assert(CHUNK % (256 * UN) == 0, "a chunk is a whole number of unrolled workgroup strides");
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ long row_len(const int* __restrict__ n_samples, int b, long L) {
-  if (!n_samples) return L;
-  const int v = n_samples[b];
-  return v < 0 ? 0 : (v > L ? L : v);
-}
 
 // The row's clip as the kernels read it: `base` points at its first sample, `len` samples lie inside the bank (0: silent,
 // nothing is read), `pos` is the clip position of row sample i0.  Uniform for the workgroup.
@@ -110,14 +98,12 @@ __global__ void __launch_bounds__(256)
       en += dn * dn;
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  es = wave_sum_d(es);
-  en = wave_sum_d(en);
-  if (lane == 0) red[0][wv] = es, red[1][wv] = en;
+  const double e[2] = {es, en};
+  fold4_put(red, e, Add());
   __syncthreads();
   if (threadIdx.x < 2) {
     const int q = threadIdx.x;
-    part[((long)b * gridDim.x + blockIdx.x) * 2 + q] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
+    part[((long)b * gridDim.x + blockIdx.x) * 2 + q] = fold4_get(red[q], Add());
   }
 }
 
@@ -128,7 +114,7 @@ __global__ void __launch_bounds__(64)
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const long len = row_len(n_samples, b, L);
-  const int n = (int)((len + CHUNK - 1) / CHUNK);      // <= nchunks
+  const int n = (int)chunks_of(len, CHUNK);            // <= nchunks
   const double* p = part + (long)b * nchunks * 2;
   double es = 0.0, en = 0.0;
   for (int k = 0; k < n; ++k) es += p[2 * k], en += p[2 * k + 1];
@@ -176,18 +162,16 @@ __global__ void __launch_bounds__(256)
     m = fmaxf(m, fabsf(v));
   }
   if (!peak) return;                      // (uniform)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  fold4_put(red, m, fmaxf);
   __syncthreads();
   if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    m = fold4_get(red, fmaxf);
     // m >= 0 and not a NaN (fmaxf from 0 drops NaN, as avvad_abs_max does): its bits order like the value
     if (m > 0.f) atomicMax((unsigned int*)peak + b, __builtin_bit_cast(unsigned int, m));
   }
 }
 
-inline long n_chunks(long L) { return (L + CHUNK - 1) / CHUNK; }
+inline long n_chunks(long L) { return chunks_of(L, CHUNK); }
 inline bool ok_shape(int B, long L) {
   return B > 0 && B <= 65535 && L > 0 && L < (1L << 40) && n_chunks(L) * B < (1L << 31) / 2;
 }

@@ -22,8 +22,8 @@
 //   gram_partials<MODE>: rows are cut into chunks of AVVAD_SCORE_CHUNK samples; workgroup (chunk, row) has four waves whose
 //        256 lanes stride over the chunk (a wave reads 256 consecutive bytes per signal and load, UN samples of each signal
 //        in flight per lane: plain dword loads, since the three row bases are only 4-byte aligned and differently so);
-//        cross-lane sums by a fixed butterfly, the four waves added in wave order; the workgroup stores one 6-double partial.
-//        A workgroup whose chunk lies past the row's length exits and stores nothing.
+//        cross-lane sums by a fixed butterfly, the four waves added in wave order (reduce.h); the workgroup stores one
+//        6-double partial.  A workgroup whose chunk lies past the row's length exits and stores nothing.
 //   gram_add: acc[row][c] += the row's partials in ascending chunk order (lane c < 6 of one wave per row); only the
 //        chunks below the row's length are read.
 //   gram_finalize: one thread per row, acc -> the three ratios in dB (and the two alpha).
@@ -37,7 +37,7 @@
 // CU cap.  Nothing at or behind lengths[b] (clamped to [0, L]) is read.
 #include <math.h>
 
-#include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -45,12 +45,6 @@ constexpr int CHUNK = AVVAD_SCORE_CHUNK;   // samples of one partial
 constexpr int UN = 8;                      // samples of each signal in flight per lane (measured: tools/lab/score_lab.hip)
 constexpr int CONF_CHUNK = 4096;           // values of one confusion workgroup
 static_assert(CHUNK % (256 * UN) == 0, "a chunk is a whole number of unrolled workgroup strides");
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // part[row][chunk][6], chunk < nchunks(L).  MODE 0: no third signal (its three products stay 0), 1: noise, 2: mixture.
 template <int MODE>
@@ -60,11 +54,7 @@ __global__ void __launch_bounds__(256)
                   double* __restrict__ part) {
   __shared__ double red[6][4];
   const int b = blockIdx.y;
-  long len = L;
-  if (lengths) {
-    const int v = lengths[b];
-    len = v < 0 ? 0 : (v > L ? L : v);
-  }
+  const long len = row_len(lengths, b, L);
   const long i0 = (long)blockIdx.x * CHUNK;
   if (i0 >= len) return;                  // (uniform for the workgroup: nothing is waiting at the barrier below)
   const long i1 = min(len, i0 + CHUNK);
@@ -96,16 +86,12 @@ __global__ void __launch_bounds__(256)
       }
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    const double s = wave_sum_d(g[c]);
-    if (lane == 0) red[c][wv] = s;
-  }
+  for (int c = 0; c < 6; ++c) fold4_put(red[c], g[c], Add());
   __syncthreads();
   if (threadIdx.x < 6) {
     const int c = threadIdx.x;
-    part[((long)b * gridDim.x + blockIdx.x) * 6 + c] = ((red[c][0] + red[c][1]) + red[c][2]) + red[c][3];
+    part[((long)b * gridDim.x + blockIdx.x) * 6 + c] = fold4_get(red[c], Add());
   }
 }
 
@@ -114,24 +100,10 @@ __global__ void __launch_bounds__(64)
     gram_add(const double* __restrict__ part, int nchunks, const int* __restrict__ lengths, long L, double* __restrict__ acc) {
   const int b = blockIdx.x, c = threadIdx.x;
   if (c >= 6) return;
-  long len = L;
-  if (lengths) {
-    const int v = lengths[b];
-    len = v < 0 ? 0 : (v > L ? L : v);
-  }
-  const int n = (int)((len + CHUNK - 1) / CHUNK);      // <= nchunks
+  const long len = row_len(lengths, b, L);
+  const int n = (int)chunks_of(len, CHUNK);            // <= nchunks
   const double* p = part + (long)b * nchunks * 6 + c;
-  double a = acc[b * 6 + c];
-  int k = 0;
-  for (; k + 8 <= n; k += 8) {
-    double t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = p[(long)(k + u) * 6];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) a += t[u];
-  }
-  for (; k < n; ++k) a += p[(long)k * 6];
-  acc[b * 6 + c] = a;
+  acc[b * 6 + c] = add_ascending<8>(acc[b * 6 + c], p, 6, 0, n);
 }
 
 // 10 log10(num / den) with the reference's IEEE behaviour: den == 0 gives inf (0 / 0: NaN), and a den that cancellation
@@ -164,7 +136,7 @@ __global__ void __launch_bounds__(256)
                        const int* __restrict__ lengths, int T, int Y, unsigned long long* __restrict__ counts) {
   __shared__ int red[4][4];
   const int b = blockIdx.y;
-  const long n = (long)(lengths ? clamp_count(lengths[b], T) : T) * Y;
+  const long n = (long)row_count(lengths, b, T) * Y;
   const long i0 = (long)blockIdx.x * CONF_CHUNK;
   if (i0 >= n) return;
   const long i1 = min(n, i0 + CONF_CHUNK);
@@ -179,18 +151,12 @@ __global__ void __launch_bounds__(256)
     c[2] += hp & (hy ^ 1);
     c[3] += (hp ^ 1) & hy;
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int v = c[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) red[k][wv] = v;
-  }
+  for (int k = 0; k < 4; ++k) fold4_put(red[k], c[k], Add());
   __syncthreads();
   if (threadIdx.x < 4) {
     const int k = threadIdx.x;
-    const int v = red[k][0] + red[k][1] + red[k][2] + red[k][3];
+    const int v = fold4_get(red[k], Add());
     if (v) atomicAdd(counts + (long)b * 4 + k, (unsigned long long)v);
   }
 }
@@ -209,11 +175,7 @@ __global__ void __launch_bounds__(256)
     sisdr_coefficients(const double* __restrict__ acc, const int* __restrict__ lengths, long L, int B, double* __restrict__ sdr,
                        double* __restrict__ ratios, float* __restrict__ coef, float* __restrict__ loss) {
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    long len = L;
-    if (lengths) {
-      const int v = lengths[b];
-      len = v < 0 ? 0 : (v > L ? L : v);
-    }
+    const long len = row_len(lengths, b, L);
     const double ee = acc[b * 6 + 0], er = acc[b * 6 + 1], rr = acc[b * 6 + 3];
     const double target = (er / rr) * er, D = ee - target;
     const double k = 20.0 / log(10.0);
@@ -238,11 +200,7 @@ __global__ void __launch_bounds__(256)
     sisdr_gradient(const float* __restrict__ est, long ld_est, const float* __restrict__ ref, long ld_ref,
                    const int* __restrict__ lengths, long L, const float* __restrict__ coef, float* __restrict__ dest, long ld_dest) {
   const int b = blockIdx.y;
-  long len = L;
-  if (lengths) {
-    const int v = lengths[b];
-    len = v < 0 ? 0 : (v > L ? L : v);
-  }
+  const long len = row_len(lengths, b, L);
   const long i0 = (long)blockIdx.x * CHUNK, i1 = min(L, i0 + CHUNK);
   const float c1 = coef[2 * b], c2 = coef[2 * b + 1];
   const float* e = est + b * ld_est;
@@ -251,7 +209,7 @@ __global__ void __launch_bounds__(256)
   for (long i = i0 + threadIdx.x; i < i1; i += 256) d[i] = i < len ? c1 * r[i] + c2 * e[i] : 0.f;
 }
 
-inline long n_chunks(long L) { return (L + CHUNK - 1) / CHUNK; }
+inline long n_chunks(long L) { return chunks_of(L, CHUNK); }
 inline bool ok_shape(int B, long L) {
   return B > 0 && B <= 65535 && L > 0 && L < (1L << 40) && n_chunks(L) * B < (1L << 31) / 6;
 }
@@ -310,7 +268,7 @@ extern "C" int avvad_confusion_accumulate(const float* pred, int pred_mode, cons
                                           long long* counts, int B, int T, int Y, avvad_stream_t sv) {
   AVVAD_ENTER();
   if (!pred || !target || !counts || pred_mode < 0 || pred_mode > 1 || B <= 0 || B > 65535 || T <= 0 || Y <= 0) return AVVAD_EINVAL;
-  const long chunks = ((long)T * Y + CONF_CHUNK - 1) / CONF_CHUNK;
+  const long chunks = chunks_of((long)T * Y, CONF_CHUNK);
   if (chunks >= (1L << 31) || ((uintptr_t)counts & 7)) return AVVAD_EINVAL;
   hipLaunchKernelGGL(confusion_partials, dim3((unsigned)chunks, B), dim3(256), 0, (hipStream_t)sv, pred, pred_mode, target, lengths,
                      T, Y, (unsigned long long*)counts);

@@ -19,7 +19,7 @@
 //        bytes; F is odd, so a row of [T][F] floats is 16-byte aligned only by accident and nothing wider is assumed); a
 //        complex bin is one 8-byte load through the spectrum's strides.  A lane finds (t, f) of its first cell by one
 //        division and steps from there by 256 cells with a compare-and-subtract.  Cross-lane sum by a fixed butterfly,
-//        the four waves added in wave order, one double partial per workgroup.  Cells at or behind len_b * F get an
+//        the four waves added in wave order (reduce.h), one double partial per workgroup.  Cells at or behind len_b * F get an
 //        exact zero gradient and nothing of the inputs there is read; a workgroup wholly behind them stores no partial.
 //   spectral_finish: one workgroup; a wave per row adds the row's partials (only the chunks below the row's length) in a
 //        fixed lane order and butterfly, divides by len_b in double; then one wave adds the rows the same way.
@@ -27,19 +27,13 @@
 // row_loss and dpred bits are the same alone and inside any batch.
 #include <math.h>
 
-#include "common.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int CHUNK = AVVAD_SPECTRAL_CHUNK;   // cells of one partial
 constexpr int UN = 4;                         // cells in flight per lane
 static_assert(CHUNK % (256 * UN) == 0, "a chunk is a whole number of unrolled workgroup strides");
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 struct Spec { const float* p; long sb, st, sf; };
 
@@ -50,7 +44,7 @@ __global__ void __launch_bounds__(256)
                   const int* __restrict__ n_frames, int T, int F, double* __restrict__ part, float* dpred) {
   __shared__ double red[4];
   const int b = blockIdx.y;
-  const int len = n_frames ? clamp_count(n_frames[b], T) : T;
+  const int len = row_count(n_frames, b, T);
   const int n_row = T * F, n_valid = len * F;                // (< 2^30: launch precondition)
   const int i0 = blockIdx.x * CHUNK, i1 = min(n_row, i0 + CHUNK);
   const long base = (long)b * n_row;
@@ -108,11 +102,9 @@ __global__ void __launch_bounds__(256)
       if (dq && j < i1) dq[j] = valid ? g * inv : 0.f;
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  acc = wave_sum_d(acc);
-  if (lane == 0) red[wv] = acc;
+  fold4_put(red, acc, Add());
   __syncthreads();
-  if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = fold4_get(red, Add());
 }
 
 // One workgroup of FIN_WAVES waves.  A wave per row (rows b = wave, wave + FIN_WAVES, ...): lane l adds the row's partials
@@ -126,12 +118,12 @@ __global__ void __launch_bounds__(64 * FIN_WAVES)
                     double* __restrict__ rows, double* __restrict__ row_loss, float* __restrict__ loss) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int b = wv; b < B; b += FIN_WAVES) {
-    const int len = n_frames ? clamp_count(n_frames[b], T) : T;
-    const int n = (int)(((long)len * F + CHUNK - 1) / CHUNK);      // <= nchunks
+    const int len = row_count(n_frames, b, T);
+    const int n = (int)chunks_of((long)len * F, CHUNK);            // <= nchunks
     const double* p = part + (long)b * nchunks;
     double a = 0.0;
     for (int k = lane; k < n; k += 64) a += p[k];
-    a = wave_sum_d(a);
+    a = wave_sum(a);
     const double r = len > 0 ? a / (double)len : 0.0;
     if (lane == 0) {
       rows[b] = r;
@@ -142,12 +134,12 @@ __global__ void __launch_bounds__(64 * FIN_WAVES)
   if (wv == 0) {
     double sum = 0.0;
     for (int b = lane; b < B; b += 64) sum += rows[b];
-    sum = wave_sum_d(sum);
+    sum = wave_sum(sum);
     if (lane == 0) loss[0] = (float)sum;
   }
 }
 
-inline long n_chunks(int T, int F) { return ((long)T * F + CHUNK - 1) / CHUNK; }
+inline long n_chunks(int T, int F) { return chunks_of((long)T * F, CHUNK); }
 inline bool ok_shape(int B, int T, int F) {
   return B > 0 && B <= 65535 && T > 0 && F > 0 && (long)T * F <= (1L << 30) && n_chunks(T, F) * B < (1L << 31);
 }

@@ -18,7 +18,7 @@
 //        GEMM's S [rows][ld] as (re, im) pairs and forms log(re^2 + im^2 + eps) as stft.hip's power_log does -- the
 //        [B][T][F] feature tensor is never written; Load = PlainFeature reads materialised features x [rows][F].
 //   scalar_partials: nstat == 1 (video): a chunk of rows is one workgroup; lanes stride over a row's F values, cross-lane
-//        and cross-wave sums in a fixed order.
+//        and cross-wave sums in a fixed order (reduce.h).
 //   add_partials: adds the chunks' partials into the accumulator in a fixed order (sixteen contiguous segments of chunks,
 //        each ascending, then the segments ascending); one extra workgroup counts the valid rows (integers).
 // No floating-point atomics, and the chunking depends on the shape alone: results are bit-identical run to run and
@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include "frames.h"
+#include "reduce.h"
 
 namespace {
 
@@ -130,7 +131,6 @@ __global__ void __launch_bounds__(256)
     scalar_partials(const float* __restrict__ x, long M, int T, int F, int rows_per_chunk, const int* __restrict__ lengths,
                     double* __restrict__ part) {
   __shared__ double red[2][4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long m0 = (long)blockIdx.x * rows_per_chunk, m1 = min(M, m0 + rows_per_chunk);
   double s = 0.0, q = 0.0;
   for (long m = m0; m < m1; ++m) {
@@ -142,12 +142,12 @@ __global__ void __launch_bounds__(256)
       q += v * v;
     }
   }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o), q += __shfl_xor(q, o);
-  if (lane == 0) red[0][wv] = s, red[1][wv] = q;
+  const double sq[2] = {s, q};
+  fold4_put(red, sq, Add());
   __syncthreads();
   if (threadIdx.x == 0) {
-    part[2 * (long)blockIdx.x] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-    part[2 * (long)blockIdx.x + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    part[2 * (long)blockIdx.x] = fold4_get(red[0], Add());
+    part[2 * (long)blockIdx.x + 1] = fold4_get(red[1], Add());
   }
 }
 
@@ -169,18 +169,7 @@ __global__ void __launch_bounds__(64 * ADD_WAVES)
     const int per = (nchunks + ADD_WAVES - 1) / ADD_WAVES;
     const int k0 = wv * per, k1 = min(nchunks, k0 + per);
     double v = 0.0;
-    if (c < ncol) {
-      const double* p = part + c;
-      int k = k0;
-      for (; k + ADD_UNROLL <= k1; k += ADD_UNROLL) {
-        double t[ADD_UNROLL];
-#pragma unroll
-        for (int u = 0; u < ADD_UNROLL; ++u) t[u] = p[(long)(k + u) * ncol];
-#pragma unroll
-        for (int u = 0; u < ADD_UNROLL; ++u) v += t[u];
-      }
-      for (; k < k1; ++k) v += p[(long)k * ncol];
-    }
+    if (c < ncol) v = add_ascending<ADD_UNROLL>(0.0, part + c, ncol, k0, k1);
     seg[wv][lane] = v;
     __syncthreads();
     if (wv == 0 && c < ncol) {
@@ -196,7 +185,7 @@ __global__ void __launch_bounds__(64 * ADD_WAVES)
   if (lengths)
     for (int b = threadIdx.x; b < B; b += 64 * ADD_WAVES) n += min(max(lengths[b], 0), T);
   else if (threadIdx.x == 0) n = (long long)B * T;
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  n = wave_sum(n);
   if (lane == 0) red[wv] = n;
   __syncthreads();
   if (threadIdx.x == 0) {

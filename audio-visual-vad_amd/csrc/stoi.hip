@@ -8,7 +8,7 @@
 //   resample     fs 16000 only.  Polyphase 5/8 with the caller's 161 double taps: one output sample per thread, its 32 or 33
 //                products widened to double, summed in tap order, rounded once to float32.  Both signals, grid (chunk, row, signal).
 //   keep_frames  one workgroup of 16 waves per row.  The clean row's frame energies in double (a wave per frame: four samples per lane in
-//                sample order, the fixed butterfly), e = 20 log10(|w x| + eps) to the workspace; the row maximum (a NaN
+//                sample order, the fixed butterfly of reduce.h), e = 20 log10(|w x| + eps) to the workspace; the row maximum (a NaN
 //                propagates, as numpy.max has it); keep flags (max - 40) - e < 0 and their exclusive scan by wave ballots into
 //                the kept-frame list; info = (frames, kept, segments).
 //   overlap_add  x_sil / y_sil materialised: sample j is the sum, in double and in frame order, of the one or two kept
@@ -41,6 +41,7 @@
 #include <math.h>
 
 #include "frames.h"
+#include "reduce.h"
 
 namespace {
 
@@ -53,23 +54,14 @@ constexpr double DEGENERATE = 1e-5;                // score of a row without a s
 __device__ const int BAND_EDGE[NBAND + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
 static_assert(F0 + NBIN == 219, "bins 7 .. 218");
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // numpy.minimum: a NaN on either side propagates
 __device__ __forceinline__ double min_nan(double a, double b) { return (a != a || b != b) ? a + b : (a < b ? a : b); }
 
 __host__ __device__ inline long resampled(long len) { return (UP * len + DOWN - 1) / DOWN; }
 __host__ __device__ inline long frame_count(long len) { return len > FRAME ? (len - FRAME + HOP - 1) / HOP : 0; }   // starts i < len - 256
 // samples of row b in the 10 kHz domain
-__device__ __forceinline__ long row_len(const int* lengths, int b, long L, int rate16) {
-  long len = L;
-  if (lengths) {
-    const int v = lengths[b];
-    len = v < 0 ? 0 : (v > L ? L : v);
-  }
+__device__ __forceinline__ long row_len_10k(const int* lengths, int b, long L, int rate16) {
+  const long len = row_len(lengths, b, L);
   return rate16 ? resampled(len) : len;
 }
 __device__ __forceinline__ int segments_of(int kept) {
@@ -82,11 +74,7 @@ __global__ void __launch_bounds__(256)
     resample(const float* __restrict__ x, long ldx, const float* __restrict__ y, long ldy, const int* __restrict__ lengths, long L,
              const double* __restrict__ taps, float* __restrict__ out, long ld_out) {
   const int b = blockIdx.y, sig = blockIdx.z;
-  long len = L;
-  if (lengths) {
-    const int v = lengths[b];
-    len = v < 0 ? 0 : (v > L ? L : v);
-  }
+  const long len = row_len(lengths, b, L);
   const long n = (long)blockIdx.x * 256 + threadIdx.x;
   if (n >= resampled(len)) return;
   const float* src = sig ? y + b * ldy : x + b * ldx;
@@ -108,7 +96,7 @@ __global__ void __launch_bounds__(KEEP_THREADS)
   __shared__ double wmax[KEEP_WAVES];
   __shared__ int wnan[KEEP_WAVES], wcnt[KEEP_WAVES];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int nf = (int)frame_count(row_len(lengths, b, L, rate16));
+  const int nf = (int)frame_count(row_len_10k(lengths, b, L, rate16));
   const float* xr = x + b * ldx;
   double* e = en + (long)b * nf_p;
   int* ix = idx + (long)b * nf_p;
@@ -123,7 +111,7 @@ __global__ void __launch_bounds__(KEEP_THREADS)
       const double v = w[k] * (double)f[k];
       s += v * v;
     }
-    s = wave_sum_d(s);
+    s = wave_sum(s);
     if (lane == 0) e[i] = 20.0 * log10(sqrt(s) + EPS);
   }
   __syncthreads();
@@ -134,11 +122,7 @@ __global__ void __launch_bounds__(KEEP_THREADS)
     if (v != v) nan = 1;
     else m = v > m ? v : m;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double t = __shfl_xor(m, o, 64);
-    m = t > m ? t : m;
-  }
+  m = wave_fold(m, [](double m, double t) { return t > m ? t : m; });
   nan = __any(nan);
   if (lane == 0) wmax[wv] = m, wnan[wv] = nan;
   __syncthreads();
@@ -456,7 +440,7 @@ __global__ void __launch_bounds__(256)
   if (i >= ncols) return;
   double v = 0.0;
   if (live) {
-    const long len = row_len(lengths, b, L, rate16);
+    const long len = row_len_10k(lengths, b, L, rate16);
     const long nfb = frame_count(len);
     const int kept = clamp_count(nk[b], mf + 1), M = kept > 0 ? kept - 1 : 0;
     if (i < len && segments_of(kept) > 0) {
@@ -493,11 +477,7 @@ __global__ void __launch_bounds__(256)
   const int b = blockIdx.y;
   const long m = (long)blockIdx.x * 256 + threadIdx.x;
   if (m >= L) return;
-  long len = L;
-  if (lengths) {
-    const int v = lengths[b];
-    len = v < 0 ? 0 : (v > L ? L : v);
-  }
+  const long len = row_len(lengths, b, L);
   double acc = 0.0;
   if (live && m < len) {
     const long lo = UP * m - HALF, last = resampled(len) - 1;

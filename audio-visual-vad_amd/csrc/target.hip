@@ -17,7 +17,8 @@
 //        n_fft % hop == 0 -- each sample is read once -- or over whole frames otherwise, one wave per segment with
 //        float4 loads on the interior of the signal and the framing functor (centre offset, reflect / zero padding,
 //        zero past the utterance) at its edges; vad_decide (one workgroup per utterance) adds R = n_fft/hop blocks per
-//        frame in a fixed order, takes the minimum through cross-lane + LDS reductions and thresholds in double.
+//        frame in a fixed order, takes the minimum through cross-lane + LDS reductions (reduce.h) and thresholds in
+//        double.
 //   IBM: the DFT is the STFT front-end's GEMM (frames.h); spectrum_max takes the per-utterance maximum of |X|^2 in one
 //        pass over S (float4 loads, block reduction, one integer atomicMax per workgroup on the bit pattern of a
 //        non-negative double: order-independent, so bit-reproducible); ibm_mask thresholds every bin in a second pass
@@ -28,6 +29,7 @@
 #include <math.h>
 
 #include "frames.h"
+#include "reduce.h"
 
 namespace {
 
@@ -51,7 +53,7 @@ __global__ void __launch_bounds__(256)
                    int Tp, int off, int mode, int seg, int stride, int R, int nseg_pitch, int vec, double* __restrict__ E) {
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int T = min(n_frames[b], Tp);
+  const int T = row_count(n_frames, b, Tp);
   const int nseg = T > 0 ? T + R - 1 : 0;
   const long n = n_samples[b], nread = min(n, pitch);
   const float* row = wave + (long)b * pitch;
@@ -76,7 +78,7 @@ __global__ void __launch_bounds__(256)
       acc += (double)v2 * v2;
       acc += (double)v3 * v3;
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = wave_sum(acc);
     if (lane == 0) E[(long)b * nseg_pitch + j] = acc;
   }
 }
@@ -93,14 +95,14 @@ __global__ void __launch_bounds__(256)
                float* __restrict__ vad) {
   __shared__ double red[4];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int T = min(n_frames[b], Tp);
+  const int T = row_count(n_frames, b, Tp);
   const double* e = E + (long)b * nseg_pitch;
   double mn = __builtin_huge_val();
   for (int t = tid; t < T; t += 256) mn = fmin(mn, frame_energy(e, t, R));
-  for (int o = 32; o > 0; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o));
-  if ((tid & 63) == 0) red[tid >> 6] = mn;
+  const auto least = [](double a, double b) { return fmin(a, b); };
+  fold4_put(red, mn, least);
   __syncthreads();
-  const double thr = coef * fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
+  const double thr = coef * fold4_get(red, least);
   float* out = vad + (long)b * Tp;
   if (vec) {                                               // Tp % 4 == 0 and a 16-byte aligned output
     for (int t4 = tid * 4; t4 < Tp; t4 += 1024) {
@@ -116,10 +118,10 @@ __global__ void __launch_bounds__(256)
 
 __device__ __forceinline__ double block_max_256(double mx) {
   __shared__ double red[4];
-  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  const auto most = [](double a, double b) { return fmax(a, b); };
+  fold4_put(red, mx, most);
   __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  return fold4_get(red, most);
 }
 
 // maxbits[b] = max over the rows t < T_b of S [B*Tp][ld] of re^2 + im^2 (the zero pad columns add nothing)
@@ -127,7 +129,7 @@ __global__ void __launch_bounds__(256)
     spectrum_max(const float* __restrict__ S, int ld, int Tp, const int* __restrict__ n_frames, unsigned long long* __restrict__ maxbits) {
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * MAX_ROWS;
-  const int nr = min(min(n_frames[b], Tp) - t0, MAX_ROWS);
+  const int nr = min(row_count(n_frames, b, Tp) - t0, MAX_ROWS);
   if (nr <= 0) return;                                     // uniform across the workgroup
   const int n4 = ld >> 2;
   const float4* p = reinterpret_cast<const float4*>(S + ((long)b * Tp + t0) * ld);   // nr contiguous rows
@@ -159,12 +161,13 @@ __global__ void __launch_bounds__(256)
     long m = i / F;
     int f = (int)(i - m * F);
     int b = (int)(m / Tp), t = (int)(m - (long)b * Tp);
+    int Tb = row_count(n_frames, b, Tp);
     double tau = mask_tau(maxbits, b, coef, eps);
     float v[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       float r = 0.f;
-      if (i + q < n && t < n_frames[b]) {
+      if (i + q < n && t < Tb) {
         const float2 c = *reinterpret_cast<const float2*>(S + m * ld + 2 * f);
         r = mask_bit(c.x, c.y, tau);
         if (vad) r *= vad[(long)b * Tp + t];
@@ -172,7 +175,7 @@ __global__ void __launch_bounds__(256)
       v[q] = r;
       if (++f == F) {                                      // next spectrum row (and maybe the next utterance)
         f = 0, ++m;
-        if (++t == Tp && i + q + 1 < n) t = 0, ++b, tau = mask_tau(maxbits, b, coef, eps);
+        if (++t == Tp && i + q + 1 < n) t = 0, ++b, Tb = row_count(n_frames, b, Tp), tau = mask_tau(maxbits, b, coef, eps);
       }
     }
     if (vec && i + 3 < n) *reinterpret_cast<float4*>(out + i) = make_float4(v[0], v[1], v[2], v[3]);
@@ -250,7 +253,7 @@ __global__ void __launch_bounds__(256)
     const long m = i / F;
     int f = (int)(i - m * F);
     int b = (int)(m / Tp), t = (int)(m - (long)b * Tp);
-    int Tb = n_frames ? clamp_count(n_frames[b], Tp) : Tp;
+    int Tb = row_count(n_frames, b, Tp);
     double p2 = peak_sq(peak, b);
     float vs[4], vn[4], vr[4];
 #pragma unroll
@@ -271,7 +274,7 @@ __global__ void __launch_bounds__(256)
         f = 0;
         if (++t == Tp && i + q + 1 < n) {
           t = 0, ++b;
-          Tb = n_frames ? clamp_count(n_frames[b], Tp) : Tp;
+          Tb = row_count(n_frames, b, Tp);
           p2 = peak_sq(peak, b);
         }
       }
