@@ -19,6 +19,8 @@ TRUNK_NCONV = 20
 ABI_VERSION = 3          # include/avvad.h AVVAD_ABI_VERSION: the signatures below describe exactly this version
 SCORE_CHUNK = 4096       # include/avvad.h AVVAD_SCORE_CHUNK: samples of one partial of avvad_score_accumulate
 MIX_CHUNK = 4096         # include/avvad.h AVVAD_MIX_CHUNK: samples of one energy partial of avvad_mix
+RESAMPLE_TILE = 256      # include/avvad.h AVVAD_RESAMPLE_TILE: outputs of one workgroup of avvad_resample
+RESAMPLE_MAX_RATE = 1024 # include/avvad.h AVVAD_RESAMPLE_MAX_RATE: largest up and down of avvad_resample
 SPECTRAL_CHUNK = 2048    # include/avvad.h AVVAD_SPECTRAL_CHUNK: cells of one partial of avvad_spectral_loss
 _ERR = {-1: "AVVAD_EINVAL (bad descriptor / unsupported shape)", -2: "AVVAD_EWORKSPACE (workspace too small)",
         -3: "AVVAD_ELAUNCH (kernel launch failed)"}
@@ -189,6 +191,11 @@ SIGNATURES = {
     "avvad_mix_workspace": (C.c_size_t, [C.c_int, C.c_long]),
     "avvad_mix": (C.c_int, [FP, C.c_long, FP, FP, C.c_long, FP, FP, C.c_int, FP, FP, FP, FP, C.c_long, FP, C.c_long, FP, FP, FP,
                             C.c_int, C.c_long, FP, C.c_size_t, FP]),
+    "avvad_resample_length": (C.c_long, [C.c_long, C.c_int, C.c_int]),
+    "avvad_resample_taps_len": (C.c_long, [C.c_int, C.c_int]),
+    "avvad_resample_hist": (C.c_int, [C.c_int, C.c_int]),
+    "avvad_resample": (C.c_int, [FP, C.c_long, FP, FP, C.c_int, C.c_int, FP, C.c_long, FP, C.c_int, C.c_long, FP]),
+    "avvad_resample_stream": (C.c_int, [FP, C.c_long] + [FP] * 7 + [C.c_int, C.c_int, FP, C.c_long, C.c_int, C.c_int, C.c_int, FP]),
     "avvad_target_workspace": (C.c_size_t, [C.POINTER(TargetDesc)]),
     "avvad_target_vad": (C.c_int, [FP, FP, FP, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),
     "avvad_target_ibm": (C.c_int, [FP, FP, FP, C.c_int, FP, C.POINTER(TargetDesc), FP, C.c_size_t, FP]),

@@ -1169,6 +1169,167 @@ def istft_stream(spec, frames, clock, state, basis, mask=None, mask_mode=None, s
     return out, n_out
 
 
+# --------------------------------------------------------------------------- resampling (csrc/resample.hip)
+_RESAMPLE_TAPS = {}
+
+
+def resample_ratio(fs_in, fs_out=16000):
+    """(up, down) of the rates ``fs_in -> fs_out`` in lowest terms; integer rates >= 1 whose reduced ratio stays within
+    ``AVVAD_RESAMPLE_MAX_RATE``."""
+    if any(isinstance(f, bool) or int(f) != f or int(f) < 1 for f in (fs_in, fs_out)):
+        raise L.AvvadError("resample: rates must be integers >= 1, got %r -> %r" % (fs_in, fs_out))
+    fs_in, fs_out = int(fs_in), int(fs_out)
+    g = math.gcd(fs_in, fs_out)
+    up, down = fs_out // g, fs_in // g
+    if max(up, down) > L.RESAMPLE_MAX_RATE:
+        raise L.AvvadError("resample: %d -> %d Hz is the ratio %d/%d, beyond %d" % (fs_in, fs_out, up, down, L.RESAMPLE_MAX_RATE))
+    return up, down
+
+
+def _ratio_check(up, down):
+    if isinstance(up, bool) or isinstance(down, bool) or int(up) != up or int(down) != down:
+        raise L.AvvadError("resample: up and down must be integers, got %r/%r" % (up, down))
+    up, down = int(up), int(down)
+    if up < 1 or down < 1 or max(up, down) > L.RESAMPLE_MAX_RATE or math.gcd(up, down) != 1 or up == down:
+        raise L.AvvadError("resample: the ratio must be in lowest terms within 1..%d and not 1/1, got %d/%d"
+                           % (L.RESAMPLE_MAX_RATE, up, down))
+    return up, down
+
+
+def resample_taps(up, down):
+    """The resampler's host table: the ``2 * half + 1`` float64 taps (``half = 10 * max(up, down)``)
+    ``up * firwin(2 * half + 1, 1 / max(up, down), window=('kaiser', 5.0))`` that ``scipy.signal.resample_poly(x, up, down)``
+    uses by default, built with numpy alone (windowed sinc, DC gain 1, times ``up``).  ``resample_taps(5, 8)`` is
+    ``stoi_taps()`` bit for bit."""
+    import numpy as np
+    up, down = _ratio_check(up, down)
+    m = max(up, down)
+    half = 10 * m
+    fc = 1.0 / m
+    k = np.arange(2 * half + 1, dtype=np.float64) - float(half)
+    h = fc * np.sinc(fc * k) * np.kaiser(2 * half + 1, 5.0)
+    return float(up) * (h / h.sum())
+
+
+def resample_taps_phase_major(up, down):
+    """``resample_taps`` in the kernel's layout (include/avvad.h): ``T = 2 * half // up + 1`` taps per phase,
+    ``taps[p * T + j] = h[p + j * up]`` and 0 behind the last tap."""
+    import numpy as np
+    h = resample_taps(up, down)
+    up = int(up)
+    T = (len(h) - 1) // up + 1
+    tp = np.zeros((up, T), dtype=np.float64)
+    for p in range(up):
+        col = h[p::up]
+        tp[p, :len(col)] = col
+    return tp.reshape(-1)
+
+
+def resample_taps_on(up, down, device):
+    """The phase-major taps of a ratio on ``device``: built once per (ratio, device), what ``resample_stream`` takes."""
+    up, down = _ratio_check(up, down)
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (up, down, device)
+    taps = _RESAMPLE_TAPS.get(key)
+    if taps is None:
+        taps = _RESAMPLE_TAPS[key] = torch.from_numpy(resample_taps_phase_major(up, down)).to(device)
+    return taps
+
+
+def resample_length(n, up, down):
+    """Samples ``n`` inputs give: ``ceil(n * up / down)``."""
+    up, down = _ratio_check(up, down)
+    if int(n) < 0:
+        raise L.AvvadError("resample_length: negative sample count %r" % (n,))
+    return (int(n) * up + down - 1) // down
+
+
+def resample(wave, lengths=None, fs_in=None, fs_out=16000):
+    """A ragged batch from ``fs_in`` to ``fs_out`` on the GPU (avvad_resample), with ``scipy.signal.resample_poly``'s default
+    filter: wave (B, L) (or (L,)) float32, row b's first ``lengths[b]`` samples real (nothing behind them is read; None: all).
+    -> (out (B, Lout) -- (Lout,) for a 1-D wave -- with ``Lout = resample_length(L)`` and zeros behind a row's samples,
+    samples per row (list)).  ``fs_in == fs_out`` returns the input itself.  Every sample is a double sum in a fixed order
+    rounded once: the same bits from run to run, at any batch, and as ``resample_stream`` gives for any split."""
+    if fs_in is None:
+        raise L.AvvadError("resample: fs_in is required")
+    up, down = resample_ratio(fs_in, fs_out)
+    if not isinstance(wave, torch.Tensor) or wave.dim() not in (1, 2) or (wave.numel() == 0 and up != down):
+        raise L.AvvadError("resample: wave must be a GPU tensor (B, L) or (L,) with L >= 1, got %s"
+                           % (tuple(getattr(wave, "shape", ())),))
+    B, Ls = (1, wave.shape[0]) if wave.dim() == 1 else wave.shape
+    lens = [Ls] * B if lengths is None else _ints(lengths, B, Ls, "lengths must hold %d values within 0..%d" % (B, Ls))
+    if up == down:
+        return wave, lens
+    x, ld_x = _score_rows(wave, "wave", B, Ls)
+    lens32 = None if lengths is None else torch.tensor(lens, dtype=torch.int32).to(x.device)
+    taps = resample_taps_on(up, down, x.device)
+    Lout = resample_length(Ls, up, down)
+    out = torch.empty(B, Lout, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().avvad_resample(L.ptr(x), ld_x, L.ptr(lens32), L.ptr(taps), up, down, L.ptr(out), Lout, None, B, Ls,
+                                       _stream()), "avvad_resample")
+    return (out[0] if wave.dim() == 1 else out), [resample_length(n, up, down) for n in lens]
+
+
+def resample_stream_state(B, up, down, device):
+    """Zeroed resampler state (B, H), ``H = 2 * half // up + 2``: the last inputs of each row, which later outputs still
+    need; with a fresh ``RateClock`` it is "start of utterance" whatever it holds."""
+    up, down = _ratio_check(up, down)
+    if int(B) < 1:
+        raise L.AvvadError("B must be >= 1")
+    return torch.zeros(int(B), L.lib().avvad_resample_hist(up, down), dtype=torch.float32, device=device)
+
+
+def resample_stream(chunk, n_valid, clock, state, taps, final=None, out_state=None):
+    """The next samples of ``B`` rows through the resampler (avvad_resample_stream): one kernel launch.
+
+    chunk (B, n) float32 on the GPU at the input rate, of which row b's first ``n_valid[b]`` samples are real (None: all n).
+    ``clock`` is the rows' :class:`avvad.stream.RateClock` (the ratio and the per-row counts); it is advanced by this call.
+    ``state`` (B, H) from ``resample_stream_state``; the new tails go to ``out_state`` -- a spare tensor the caller swaps with
+    ``state`` -- or, with ``out_state`` None or ``state`` itself, back into ``state``.  ``taps``: ``resample_taps_on`` of the
+    clock's ratio.  ``final``: rows that end with this call; they also yield the outputs whose later taps never came and
+    must be reset on the clock before they take samples again.
+    -> (out (B, nmax) with zeros behind a row's count, samples per row (list)).  A row that goes on has emitted
+    ``floor((N * up - 1 - half) / down) + 1`` samples after N inputs; a stream of N samples yields exactly ``resample``'s.
+    Every argument is checked before the clock or a state changes.  Any split of a stream into calls gives the same bits."""
+    chunk = _dev(chunk, "chunk")
+    if chunk.dim() != 2 or chunk.shape[0] < 1:
+        raise L.AvvadError("chunk must be (B, n) samples, got %s" % (tuple(chunk.shape),))
+    B, n = chunk.shape
+    up, down = _ratio_check(clock.up, clock.down)
+    H = L.lib().avvad_resample_hist(up, down)
+    nv = [n] * B if n_valid is None else _ints(n_valid)
+    if len(nv) != B or any(x < 0 or x > n for x in nv):
+        raise L.AvvadError("n_valid must hold one count in [0, %d] per row (%d rows), got %s" % (n, B, nv))
+
+    def st(t, what):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
+                tuple(t.shape) != (B, H) or t.device != chunk.device:
+            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of resample_stream_state(%d, %d, %d, device)"
+                               % (what, B, up, down))
+    st(state, "state")
+    if out_state is not None and out_state is not state:
+        st(out_state, "out_state")
+    in_place = out_state is None or out_state.data_ptr() == state.data_ptr()
+    new = torch.empty_like(state) if in_place else out_state
+    if not isinstance(taps, torch.Tensor) or not taps.is_cuda or taps.dtype != torch.float64 or taps.device != chunk.device or \
+            not taps.is_contiguous() or taps.numel() != L.lib().avvad_resample_taps_len(up, down):
+        raise L.AvvadError("taps must be resample_taps_on(%d, %d, device)" % (up, down))
+    in_before, out_before, n_emit = clock.advance(nv, final=() if final is None else final)   # raises before it changes anything
+    nmax = max(n_emit)
+    counts = torch.tensor([nv, in_before, out_before, n_emit], dtype=torch.int64).to(chunk.device, non_blocking=False)
+    out = torch.empty(B, nmax, dtype=torch.float32, device=chunk.device)
+    with torch.cuda.device(chunk.device):
+        L.check(L.lib().avvad_resample_stream(L.ptr(chunk) if n else None, n, L.ptr(counts[0]), L.ptr(counts[1]), L.ptr(counts[2]),
+                                              L.ptr(counts[3]), L.ptr(state), L.ptr(new), L.ptr(taps), up, down,
+                                              L.ptr(out) if nmax else None, nmax, B, n, nmax, _stream()), "avvad_resample_stream")
+    if in_place:
+        state.copy_(new)
+    return out, n_emit
+
+
 # --------------------------------------------------------------------------- train-set statistics (no gradient)
 def stats_new(nstat, device):
     """A zeroed statistics accumulator: float64 ``[sum (nstat), sumsq (nstat), count]`` on the GPU (include/avvad.h,

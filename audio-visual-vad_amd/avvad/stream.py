@@ -135,6 +135,88 @@ class SampleClock:
         return frames, used, pad
 
 
+class RateClock:
+    """Host-side bookkeeping of the streaming resampler (``ops.resample_stream``), per row, beside :class:`SampleClock`:
+    ``total`` input samples taken since the reset, ``emitted`` output samples, and ``pending`` -- the inputs the next output
+    still needs of those that came, at most ``H - 2`` of the ``H = 2 * half // up + 2`` the state holds.  With
+    ``half = 10 * max(up, down)``, a row that goes on has emitted ``floor((N * up - 1 - half) / down) + 1`` samples after N
+    inputs (0 while ``N * up - 1 - half < 0``): the outputs whose every tap has arrived.  A row named in ``final`` ends with
+    that call and emits up to ``ceil(N * up / down)``, so a stream of N samples yields the whole-utterance call's count; it
+    must be ``reset`` before it takes samples again.  ``total`` (with ``emitted`` to match, see ``preset``) may be set ahead
+    for a test of large positions."""
+
+    def __init__(self, batch, up, down):
+        self.up, self.down = ops._ratio_check(up, down)
+        if int(batch) < 1:
+            raise L.AvvadError("RateClock needs batch >= 1")
+        self.half = 10 * max(self.up, self.down)
+        self.total = [0] * int(batch)
+        self.emitted = [0] * int(batch)
+        self.pending = [0] * int(batch)
+        self.ended = [False] * int(batch)
+
+    def reset(self, rows=None):
+        for b in (range(len(self.total)) if rows is None else rows):
+            self.total[b] = self.emitted[b] = self.pending[b] = 0
+            self.ended[b] = False
+
+    def count(self, N):
+        """outputs a row that goes on has emitted after N inputs"""
+        a = int(N) * self.up - 1 - self.half
+        return a // self.down + 1 if a >= 0 else 0
+
+    def _held(self, N, e):
+        """inputs of the first N that output e (the next one) still needs"""
+        first = max(0, -((self.half - e * self.down) // self.up))      # ceil((e down - half) / up)
+        return max(N - first, 0)
+
+    def preset(self, row, total):
+        """Puts ``row`` where a stream stands after ``total`` inputs (a test of positions beyond 2^31 costs nothing)."""
+        self.total[row] = int(total)
+        self.emitted[row] = self.count(total)
+        self.pending[row] = self._held(self.total[row], self.emitted[row])
+        self.ended[row] = False
+
+    def _plan(self, n, final):
+        B = len(self.total)
+        n = ops._ints(n)
+        if len(n) != B:
+            raise L.AvvadError("one sample count per row expected (%d), got %d" % (B, len(n)))
+        final = set(ops._ints(final))
+        if any(b < 0 or b >= B for b in final):
+            raise L.AvvadError("final rows must be in [0, %d)" % B)
+        n_emit, state = [], []
+        for b, nb in enumerate(n):
+            if nb < 0:
+                raise L.AvvadError("row %d: negative sample count" % b)
+            if self.ended[b] and (nb > 0 or b in final):
+                raise L.AvvadError("row %d ended with a final call: reset it before it takes samples again" % b)
+            if self.ended[b]:                       # idles until its reset
+                n_emit.append(0)
+                state.append((self.total[b], self.emitted[b], self.pending[b], True))
+                continue
+            N = self.total[b] + nb
+            e = (N * self.up + self.down - 1) // self.down if b in final else self.count(N)
+            e = max(e, self.emitted[b])
+            n_emit.append(e - self.emitted[b])
+            state.append((N, e, self._held(N, e), b in final))
+        return n, n_emit, state
+
+    def plan(self, n, final=()):
+        """Samples each row emits from ``n[b]`` more inputs (rows in ``final`` end with them); raises :class:`AvvadError`
+        when a count is negative or a row that ended is fed again.  Changes nothing."""
+        return self._plan(n, final)[1]
+
+    def advance(self, n, final=()):
+        """``plan`` and then consume: -> (inputs each row had behind it, outputs it had emitted, outputs of THIS call)."""
+        _, n_emit, state = self._plan(n, final)
+        before = (list(self.total), list(self.emitted))
+        for b, (N, e, p, end) in enumerate(state):
+            self.total[b], self.emitted[b], self.pending[b] = N, e, p
+            self.ended[b] = self.ended[b] or end
+        return before[0], before[1], n_emit
+
+
 class OlaClock:
     """Host-side bookkeeping of the streaming overlap-add (``ops.istft_stream``), per row, beside :class:`SampleClock`:
     ``emitted`` frames taken and ``written`` samples returned since the reset.  A row that goes on writes
@@ -254,7 +336,9 @@ class Session:
         # the streaming resynthesis (step_enhance): overlap-add state, its spare and the inverse basis, built with the front-end
         self.ola_clock = self.ola_state = self._ola_spare = self._inv_basis = None
         self._route = [None] * self.batch          # per row: "wave" / "enhance" once it has taken samples since its reset
-        self._frontend = dict(stats=None, eps=1e-8, n_fft=1024, hop=256)
+        self._frontend = dict(stats=None, eps=1e-8, n_fft=1024, hop=256, fs_in=16000)
+        # the resampler in front of the STFT (set_frontend(fs_in=...)): its clock, state, spare and taps; None at 16 kHz
+        self.rate_clock = self.rs_state = self._rs_spare = self._rs_taps = None
         if self.kind != "video" and self.enc is None:
             self.sample_clock = SampleClock(self.batch, 1024, 256)
             self.ola_clock = OlaClock(self.batch, 1024, 256)
@@ -283,6 +367,10 @@ class Session:
             self.ola_clock.reset(rows)
         if self.ola_state is not None:
             self.ola_state.index_fill_(0, idx, 0.0)
+        if self.rate_clock is not None:
+            self.rate_clock.reset(rows)
+        if self.rs_state is not None:
+            self.rs_state.index_fill_(0, idx, 0.0)
         for r in rows:
             self._route[r] = None
 
@@ -292,21 +380,27 @@ class Session:
             raise L.AvvadError("step_wave feeds the STFT front-end of DeepVAD_audio / DeepVAD_AV without the encoder; "
                                "a model with the encoder takes samples through step(), the video model takes none")
 
-    def set_frontend(self, stats=None, eps=1e-8, n_fft=1024, hop=256):
+    def set_frontend(self, stats=None, eps=1e-8, n_fft=1024, hop=256, fs_in=16000):
         """Configuration of ``step_wave``'s front-end: ``stats`` (``train.Stats``-like: ``get("audio_mean" /
-        "audio_std", device)`` and ``.eps``) standardises the log-power features, ``eps`` is the log's.  Changing
-        ``n_fft`` / ``hop`` starts every row's front-end over."""
+        "audio_std", device)`` and ``.eps``) standardises the log-power features, ``eps`` is the log's.  ``fs_in``: the rate
+        of the samples ``step_wave`` / ``step_enhance`` take; another rate than 16000 goes through the streaming resampler
+        (``ops.resample_stream``) into the same 16 kHz front-end, and the logits are those of ``ops.resample`` of the whole
+        utterance fed at 16 kHz, bit for bit.  Changing ``n_fft`` / ``hop`` / ``fs_in`` starts every row's front-end over."""
         self._wave_check()
         n_fft, hop = ops._n_fft_check(n_fft), int(hop)
         if hop < 1 or hop > n_fft:
             raise L.AvvadError("hop must be in [1, n_fft]")
-        if (n_fft, hop) != (self.sample_clock.n_fft, self.sample_clock.hop):
+        up, down = ops.resample_ratio(fs_in, 16000)
+        fs_in = int(fs_in)
+        if (n_fft, hop) != (self.sample_clock.n_fft, self.sample_clock.hop) or fs_in != self._frontend["fs_in"]:
+            self.rs_state = self._rs_spare = self._rs_taps = None
+            self.rate_clock = RateClock(self.batch, up, down) if up != down else None
             self.stft_state = self._stft_spare = self._basis = None
             self.ola_state = self._ola_spare = self._inv_basis = None
             self.sample_clock = SampleClock(self.batch, n_fft, hop)
             self.ola_clock = OlaClock(self.batch, n_fft, hop)
             self._route = [None] * self.batch
-        self._frontend = dict(stats=stats, eps=float(eps), n_fft=n_fft, hop=hop)
+        self._frontend = dict(stats=stats, eps=float(eps), n_fft=n_fft, hop=hop, fs_in=fs_in)
 
     def prepare_frontend(self):
         """Builds what ``step_wave`` needs on the GPU -- the windowed basis, ``stft_state`` and its spare -- if it is not
@@ -318,10 +412,24 @@ class Session:
             self._basis = ops.stft_stream_basis(f["n_fft"], self.device)
             self.stft_state = ops.stft_stream_state(self.batch, f["n_fft"], self.device)
             self._stft_spare = torch.zeros_like(self.stft_state)
+        if self.rate_clock is not None and self.rs_state is None:
+            self._rs_taps = ops.resample_taps_on(self.rate_clock.up, self.rate_clock.down, self.device)
+            self.rs_state = ops.resample_stream_state(self.batch, self.rate_clock.up, self.rate_clock.down, self.device)
+            self._rs_spare = torch.zeros_like(self.rs_state)
         if self.ola_state is None and self.linear.out_features == f["n_fft"] // 2 + 1:
             self._inv_basis = ops.istft_stream_basis(f["n_fft"], self.device)
             self.ola_state = ops.istft_stream_state(self.batch, f["n_fft"], self.device)
             self._ola_spare = torch.zeros_like(self.ola_state)
+
+    def plan_wave(self, samples, final=()):
+        """Frames each row yields from ``samples[b]`` more samples at ``fs_in`` (rows in ``final`` end with them): the
+        resampler's clock composed with the STFT's, which is what tells an AV caller how many lip frames a packet needs.
+        Changes nothing."""
+        self._wave_check()
+        n = ops._ints(samples)
+        if self.rate_clock is not None:
+            n = self.rate_clock.plan(n, final)
+        return self.sample_clock.plan(n, final)
 
     def step_wave(self, wave, samples=None, video=None, final=None):
         """The next SAMPLES of every row of a spectrogram model: wave (B, n) float32 on the GPU, of which row b's first
@@ -329,7 +437,8 @@ class Session:
         ``self.peak[b]``; the frames the samples complete go through the STFT front-end (``set_frontend``) and the model.
         ``final``: rows whose utterance ends with this call (they also yield the reference's zero-padded last frame;
         ``reset`` them before they take samples again).  For the AV model ``video`` must hold exactly
-        ``max(self.sample_clock.plan(samples, final))`` lip frames (None when that is 0).
+        ``max(self.plan_wave(samples, final))`` lip frames (None when that is 0).  With ``set_frontend(fs_in=...)`` the
+        samples are at that rate.
         -> (logits (B, tmax, y_dim), frames per row); (B, 0, y_dim) when no row completes a frame."""
         return self._step_samples(wave, samples, video, final, None)
 
@@ -339,7 +448,8 @@ class Session:
         the evaluators' sigmoid > 0.5; else ``sigmoid(logit)``), and the streaming inverse STFT (``ops.istft_stream``) turns
         it back into samples, multiplied by ``self.peak[b]``.  A sample comes out once no later frame can cover it, up to
         ``n_fft - 1`` samples after it went in; a row in ``final`` returns all that is left, so a stream of N samples
-        returns exactly N.  The cost of a call does not depend on the position in the utterance, and any split of a stream
+        returns exactly N (at ``fs_in`` other than 16000: the enhanced samples are 16 kHz, ``ops.resample_length(N)`` of
+        them).  The cost of a call does not depend on the position in the utterance, and any split of a stream
         into packets gives the same samples bit for bit (given the same logits).  A row goes through ONE of ``step_wave`` /
         ``step_enhance`` from its reset to its end.
         -> (logits (B, tmax, y_dim), frames per row, enhanced (B, nmax) with zeros behind a row's count, samples per row)."""
@@ -360,11 +470,14 @@ class Session:
         n = _int_list(samples, B, "samples", wave.shape[1])
         self.prepare_frontend()
         final = () if final is None else final
+        n_in = n
+        if self.rate_clock is not None:             # the samples are at fs_in: the 16 kHz counts they resample to
+            n = self.rate_clock.plan(n_in, final)
         frames = self.sample_clock.plan(n, final)
         tmax = max(frames)
         route = "enhance" if enhance else "wave"
         fin = set(ops._ints(final))
-        live = [b for b in range(B) if n[b] > 0 or b in fin]
+        live = [b for b in range(B) if n_in[b] > 0 or b in fin]
         for b in live:
             if self._route[b] not in (None, route):
                 raise L.AvvadError("row %d went through step_%s since its reset: a row stays with one of step_wave / "
@@ -385,6 +498,9 @@ class Session:
             mean = std = None
             if f["stats"] is not None:
                 mean, std = f["stats"].get("audio_mean", self.device), f["stats"].get("audio_std", self.device)
+            if self.rate_clock is not None:
+                wave, n = ops.resample_stream(wave, n_in, self.rate_clock, self.rs_state, self._rs_taps, final, self._rs_spare)
+                self.rs_state, self._rs_spare = self._rs_spare, self.rs_state
             res = ops.stft_stream(wave, n, self.sample_clock, self.stft_state, self._basis, self.peak, mean, std, final,
                                   self._stft_spare, eps=f["eps"],
                                   norm_eps=f["stats"].eps if f["stats"] is not None else f["eps"], return_spec=enhance)
@@ -541,7 +657,7 @@ def forward_chunked(model, audio=None, video=None, lengths=None, chunk_frames=1,
     return torch.cat(outs, dim=1)
 
 
-def _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop):
+def _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop, fs_in=16000):
     """the shared opening of ``forward_wave_chunked`` / ``enhance_wave_chunked``: the arguments checked, a session with its
     front-end built and ``peak`` set.  -> (chunk_samples, wave (B, Lmax), lengths (list), session)"""
     c = int(chunk_samples)
@@ -553,7 +669,7 @@ def _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_
     B, Lmax = w.shape
     lens = _int_list(lengths, B, "lengths", Lmax)
     sess = open(model, B)
-    sess.set_frontend(stats, eps, n_fft, hop)
+    sess.set_frontend(stats, eps, n_fft, hop, fs_in)
     sess.prepare_frontend()
     if peak is not None:
         sess.peak.copy_(ops._row_vector(peak, B, "peak"))
@@ -561,23 +677,28 @@ def _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_
 
 
 def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=256, stats=None, peak=None, eps=1e-8,
-                         n_fft=1024, hop=256, max_frames=None):
+                         n_fft=1024, hop=256, max_frames=None, fs_in=16000):
     """A spectrogram model (``DeepVAD_audio`` / concat ``DeepVAD_AV`` without the encoder, in ``eval()`` mode) scored
     from RAW SAMPLES through a session: wave (B, Lmax) on the GPU, row b's first ``lengths[b]`` samples real, fed in
     packets of ``chunk_samples`` with each row's last packet ``final``.  ``peak`` (B,) is what every sample is divided by
     (``ops.peak(wave)`` reproduces the evaluators' x / max|x|; None: 1), ``stats`` standardises the features, ``video``
     (B, T, 67, 67) holds the lip frames already decoded and standardised.  ``max_frames[b]`` ends row b after that many
     frames (the evaluators' crop to the label length).  -> logits (B, T, y_dim), T = the longest row's frame count
-    (``ops.n_frames``, capped by ``max_frames``); positions behind a row's frames hold the Linear layer's bias."""
-    c, w, lens, sess = _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop)
+    (``ops.n_frames``, capped by ``max_frames``); positions behind a row's frames hold the Linear layer's bias.
+    ``fs_in``: the rate of ``wave`` and of the packets (``Session.set_frontend``); the frames are those of the utterance
+    resampled to 16 kHz, and ``peak`` is what the samples are divided by behind the resampler."""
+    c, w, lens, sess = _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop, fs_in)
     B, Lmax = w.shape
-    total = [max(ops.n_frames(l, n_fft, hop), 0) for l in lens]
+    rc = sess.rate_clock
+    total = [max(ops.n_frames(l if rc is None else ops.resample_length(l, rc.up, rc.down), n_fft, hop), 0) for l in lens]
     ends = [True] * B                                   # the row ends with its last sample (and may owe the padded frame)
     if max_frames is not None:
         for b, mf in enumerate(_int_list(max_frames, B, "max_frames", 1 << 30)):
-            if mf < total[b]:                           # exactly mf frames: the samples they need and no end
+            if mf < total[b] and rc is None:            # exactly mf frames: the samples they need and no end
                 total[b], ends[b] = mf, False
                 lens[b] = (mf - 1) * hop + n_fft if mf > 0 else 0
+            elif mf < total[b]:                         # at another rate the row runs to its end and the frames past mf are dropped
+                total[b] = mf
     T = max(total)
     if sess.kind == "av" and (video is None or video.dim() != 4 or video.shape[0] != B or video.shape[1] < T):
         raise L.AvvadError("the AV model needs video (B, >= %d, H, W)" % T)
@@ -588,31 +709,36 @@ def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=25
         n = [min(max(l - s0, 0), c) for l in lens]
         fin = [b for b in range(B) if ends[b] and b not in ended and s0 + c >= lens[b]]
         ended.update(fin)
-        frames = sess.sample_clock.plan(n, fin)
+        frames = sess.plan_wave(n, fin)
         tl = max(frames)
         v = None
         if sess.kind == "av" and tl > 0:                # every row's next lip frames start where its own frames stand
             v = video.new_zeros((B, tl) + tuple(video.shape[2:]))
             for b, f in enumerate(frames):
-                if f:
+                f = min(f, video.shape[1] - done[b])
+                if f > 0:
                     v[b, :f] = video[b, done[b]:done[b] + f]
         y, frames = sess.step_wave(w[:, s0:s0 + c].contiguous(), n, v, fin)
         for b, f in enumerate(frames):
-            if f:
+            f = min(f, total[b] - done[b])
+            if f > 0:
                 out[b, done[b]:done[b] + f] = y[b, :f]
                 done[b] += f
     return out
 
 
 def enhance_wave_chunked(model, wave, lengths=None, chunk_samples=256, stats=None, peak=None, hard=True, eps=1e-8, n_fft=1024,
-                         hop=256):
+                         hop=256, fs_in=16000):
     """The twin of ``forward_wave_chunked`` for a mask-predicting ``DeepVAD_audio(y_dim=n_fft // 2 + 1)``: wave (B, Lmax) on
     the GPU, row b's first ``lengths[b]`` samples real, fed through ``Session.step_enhance`` in packets of ``chunk_samples``
     with each row's last packet ``final``.  ``peak`` (B,): what every sample is divided by on the way in and multiplied by
-    on the way out (None: 1).  -> enhanced samples (B, Lmax), row b's first ``lengths[b]`` real, zeros behind them."""
-    c, w, lens, sess = _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop)
+    on the way out (None: 1).  -> enhanced samples (B, Lmax), row b's first ``lengths[b]`` real, zeros behind them.
+    ``fs_in``: the rate of ``wave``; the enhanced samples are 16 kHz, (B, ``resample_length(Lmax)``) with
+    ``resample_length(lengths[b])`` real ones per row."""
+    c, w, lens, sess = _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_fft, hop, fs_in)
     B, Lmax = w.shape
-    out = w.new_zeros(B, Lmax)
+    rc = sess.rate_clock
+    out = w.new_zeros(B, Lmax if rc is None else ops.resample_length(Lmax, rc.up, rc.down))
     done, ended = [0] * B, set()
     for s0 in range(0, max(max(lens), 1), c):
         n = [min(max(l - s0, 0), c) for l in lens]

@@ -120,10 +120,13 @@ class WavPairs(torch.utils.data.Dataset):
     ``NoisyWavWholeSequenceSpectrogramLabeledFrames`` reads (``data_handling.py:231-320``), with the labels computed from
     the clean file in the training step (``wav_pair_step``) instead of read from HDF5.  ``pairs``: a list of
     (noisy path, clean path) or a text file with one "noisy clean" pair per line.  Items: (noisy (L,), clean (L,), L),
-    both cropped to their common length."""
+    both cropped to their common length.  ``resample``: files of other rates are allowed (the two of a pair may differ);
+    items are then (noisy (Ln,), clean (Lc,), Ln, Lc, noisy rate, clean rate) as read, and the training step resamples them
+    on the GPU (``to_16k``) before it crops them to their common length."""
 
-    def __init__(self, pairs):
+    def __init__(self, pairs, resample=False):
         self.pairs = read_wav_pairs(pairs) if isinstance(pairs, str) else [tuple(p) for p in pairs]
+        self.resample = bool(resample)
 
     def __len__(self):
         return len(self.pairs)
@@ -132,6 +135,8 @@ class WavPairs(torch.utils.data.Dataset):
         noisy_path, clean_path = self.pairs[i]
         noisy, fs_n = load_waveform(noisy_path)
         clean, fs_c = load_waveform(clean_path)
+        if self.resample:
+            return noisy, clean, noisy.numel(), clean.numel(), int(fs_n), int(fs_c)
         if fs_n != 16000 or fs_c != 16000:
             raise ValueError("%s / %s: expected 16 kHz audio, got %d / %d Hz" % (noisy_path, clean_path, fs_n, fs_c))
         n = min(noisy.numel(), clean.numel())
@@ -139,7 +144,17 @@ class WavPairs(torch.utils.data.Dataset):
 
     @staticmethod
     def collate(batch):
-        """-> (sample lengths LongTensor (B,), noisy (B, Lmax), clean (B, Lmax)), rows zero-padded."""
+        """-> (sample lengths LongTensor (B,), noisy (B, Lmax), clean (B, Lmax)), rows zero-padded.  Items that carry
+        their rates (``resample=True``): lengths (B, 2) -- noisy, clean -- each signal padded to its own longest row, and a
+        trailing ``rates`` LongTensor (B, 2)."""
+        if len(batch[0]) == 6:
+            noisy = torch.zeros(len(batch), max(item[2] for item in batch))
+            clean = torch.zeros(len(batch), max(item[3] for item in batch))
+            for i, item in enumerate(batch):
+                noisy[i, :item[2]] = item[0]
+                clean[i, :item[3]] = item[1]
+            return (torch.LongTensor([[item[2], item[3]] for item in batch]), noisy, clean,
+                    torch.LongTensor([[item[4], item[5]] for item in batch]))
         lens = [item[2] for item in batch]
         noisy = torch.zeros(len(batch), max(lens))
         clean = torch.zeros(len(batch), max(lens))
@@ -177,10 +192,74 @@ def wav_pair_step(batch, device, labels, stats=None, fs=16e3, wlen_sec=64e-3, ho
     pipeline's settings (64 ms, hop 0.25, ``center=False``, end pad; create_audio_train_files.py:44-60) and the same
     frame counts.  ``waves``: a fourth value, (peak-normalised noisy (B, L), clean (B, L), sample lengths), what a loss on
     the resynthesised waveform needs."""
-    lens, noisy, clean = batch
-    noisy = ops.peak_normalize(noisy.to(device, non_blocking=True))
-    clean = ops.peak_normalize(clean.to(device, non_blocking=True))
+    lens, noisy, clean = pair_waves(batch, device)
+    noisy = ops.peak_normalize(noisy)
+    clean = ops.peak_normalize(clean)
     return _pair_tail(lens, noisy, clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves)
+
+
+def to_16k(waves, lens, rates, device):
+    """A ragged batch of mixed rates -> (waves16 (B, Lmax16) on the GPU, lens16 (list)): waves (B, Lmax) float32 (host or
+    GPU), row b holding ``lens[b]`` samples at ``rates[b]`` Hz.  One ragged ``ops.resample`` call per distinct rate in the
+    batch; 16 kHz rows are copied; the rows go back in their order, zeros behind each row's samples."""
+    lens, rates = [int(v) for v in lens], [int(r) for r in rates]
+    B = len(lens)
+    if len(rates) != B or tuple(waves.shape[:1]) != (B,) or waves.dim() != 2:
+        raise ValueError("to_16k: waves (B, Lmax) with one length and one rate per row, got %s, %d lengths, %d rates"
+                         % (tuple(waves.shape), B, len(rates)))
+    w = waves.to(device, non_blocking=True)
+    groups = {}
+    for b, r in enumerate(rates):
+        groups.setdefault(r, []).append(b)
+    lens16, parts = list(lens), []
+    for r, rows in groups.items():
+        Lg = max(lens[b] for b in rows)
+        if r == 16000 or Lg == 0:
+            parts.append((rows, w[rows][:, :Lg] if len(rows) < B else w[:, :Lg]))
+            continue
+        out, n = ops.resample(w[rows][:, :Lg] if len(rows) < B else w[:, :Lg], [lens[b] for b in rows], fs_in=r)
+        for b, k in zip(rows, n):
+            lens16[b] = k
+        parts.append((rows, out))
+    if len(parts) == 1 and parts[0][1].shape[1] == max(lens16):
+        return parts[0][1], lens16
+    out16 = torch.zeros(B, max(lens16), dtype=torch.float32, device=w.device)
+    for rows, part in parts:
+        k = min(part.shape[1], out16.shape[1])
+        out16[torch.tensor(rows, device=w.device), :k] = part[:, :k]
+    return out16, lens16
+
+
+def _crop_rows(w, lens, n):
+    """w (B, >= max(n)) whose row b holds lens[b] samples -> (B, max(n)) with zeros from n[b] <= lens[b] on"""
+    w = w[:, :max(n)]
+    if all(a == b for a, b in zip(lens, n)):
+        return w.contiguous()
+    keep = torch.arange(w.shape[1], device=w.device)[None, :] < torch.tensor(n, device=w.device)[:, None]
+    return torch.where(keep, w, torch.zeros((), dtype=w.dtype, device=w.device))
+
+
+def pair_waves(batch, device):
+    """A ``WavPairs.collate`` batch on the GPU -> (sample lengths (LongTensor), noisy (B, L), clean (B, L)).  A batch
+    that carries rates is resampled (``to_16k``) and each pair cropped to its common length first."""
+    if len(batch) == 3:
+        lens, noisy, clean = batch
+        return lens, noisy.to(device, non_blocking=True), clean.to(device, non_blocking=True)
+    lens, noisy, clean, rates = batch
+    noisy, ln = to_16k(noisy, lens[:, 0], rates[:, 0], device)
+    clean, lc = to_16k(clean, lens[:, 1], rates[:, 1], device)
+    n = [min(a, b) for a, b in zip(ln, lc)]
+    return torch.LongTensor(n), _crop_rows(noisy, ln, n), _crop_rows(clean, lc, n)
+
+
+def clean_waves(batch, device):
+    """A ``CleanWavs.collate`` batch on the GPU -> (sample lengths (LongTensor), clean (B, L)), resampled (``to_16k``) when
+    the batch carries rates."""
+    if len(batch) == 2:
+        return batch[0], batch[1].to(device, non_blocking=True)
+    lens, clean, rates = batch
+    clean, n = to_16k(clean, lens, rates, device)
+    return torch.LongTensor(n), clean
 
 
 def _pair_tail(lens, noisy, clean, device, labels, stats, fs, wlen_sec, hop_percent, eps, waves, more=(), made=None):
@@ -205,27 +284,35 @@ def _pair_tail(lens, noisy, clean, device, labels, stats, fs, wlen_sec, hop_perc
 
 class CleanWavs(torch.utils.data.Dataset):
     """Clean 16 kHz utterances to be mixed with noise in the training step (``mix_step``).  ``paths``: a list of paths or
-    a text file with one path per line (blank lines and # comments skipped).  Items: (clean (L,), L)."""
+    a text file with one path per line (blank lines and # comments skipped).  Items: (clean (L,), L).  ``resample``:
+    files of other rates are allowed; items are then (clean (L,), L, rate) as read and ``mix_step`` resamples them on the
+    GPU (``to_16k``)."""
 
-    def __init__(self, paths):
+    def __init__(self, paths, resample=False):
         self.paths = read_path_list(paths) if isinstance(paths, str) else [str(p) for p in paths]
+        self.resample = bool(resample)
 
     def __len__(self):
         return len(self.paths)
 
     def __getitem__(self, i):
         clean, fs = load_waveform(self.paths[i])
+        if self.resample:
+            return clean, clean.numel(), int(fs)
         if fs != 16000:
             raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (self.paths[i], fs))
         return clean, clean.numel()
 
     @staticmethod
     def collate(batch):
-        """-> (sample lengths LongTensor (B,), clean (B, Lmax)), rows zero-padded."""
+        """-> (sample lengths LongTensor (B,), clean (B, Lmax)), rows zero-padded; a trailing ``rates`` LongTensor (B,)
+        when the items carry their rate (``resample=True``)."""
         lens = [item[1] for item in batch]
         clean = torch.zeros(len(batch), max(lens))
-        for i, (cl, n) in enumerate(batch):
-            clean[i, :n] = cl
+        for i, item in enumerate(batch):
+            clean[i, :item[1]] = item[0]
+        if len(batch[0]) == 3:
+            return torch.LongTensor(lens), clean, torch.LongTensor([item[2] for item in batch])
         return torch.LongTensor(lens), clean
 
 
@@ -235,13 +322,16 @@ def read_path_list(path):
         return [line for line in (raw.split("#", 1)[0].strip() for raw in f) if line]
 
 
-def read_noise_bank(paths, device):
+def read_noise_bank(paths, device, resample=False):
     """The noise clips of ``paths`` (a list, or a text file with one path per line) as an ``ops.NoiseBank`` on ``device``:
-    every file read with ``load_waveform``, 16 kHz enforced, not normalised (the mix sets each row's gain)."""
+    every file read with ``load_waveform``, 16 kHz enforced, not normalised (the mix sets each row's gain).  ``resample``:
+    a clip of another rate is resampled on the GPU (``ops.resample``) once, before it enters the bank."""
     clips = []
     for p in (read_path_list(paths) if isinstance(paths, str) else list(paths)):
         x, fs = load_waveform(str(p))
-        if fs != 16000:
+        if fs != 16000 and resample:
+            x = ops.resample(x.to(device), fs_in=fs)[0]
+        elif fs != 16000:
             raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (p, fs))
         clips.append(x)
     return ops.NoiseBank(clips, device)
@@ -331,8 +421,8 @@ def mix_step(batch, device, labels, bank, draw, stats=None, fs=16e3, wlen_sec=64
     check_mix_labels(mix_labels, True)
     if mix_labels != "clean" and labels != "ibm_labels":
         raise ValueError("mix_labels %r are 513-bin masks: they go with labels 'ibm_labels', got %r" % (mix_labels, labels))
-    lens, clean = batch
-    clean = ops.peak_normalize(clean.to(device, non_blocking=True))
+    lens, clean = clean_waves(batch, device)
+    clean = ops.peak_normalize(clean)
     n = [int(v) for v in lens]
     clip, start, snr = draw(n)
     made = None
@@ -471,8 +561,7 @@ class SpectralObjective:
         if self.step is not None:
             frames, x, target, (noisy, clean, _lens, _noise, peak) = self.step(batch, self.stats())
         else:
-            lens, noisy, clean = batch
-            noisy, clean = noisy.to(self.device, non_blocking=True), clean.to(self.device, non_blocking=True)
+            lens, noisy, clean = pair_waves(batch, self.device)
             peak = ops.peak(noisy)
             frames, x, target, (noisy, _clean, _lens) = _pair_tail(
                 lens, ops.peak_normalize(noisy), ops.peak_normalize(clean), self.device, self.labels, self.stats(), self.fs,
@@ -506,24 +595,25 @@ def merge_stats(accs):
     return out
 
 
-def wav_pair_stats(pairs, device, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS):
+def wav_pair_stats(pairs, device, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS, resample=False):
     """Train-set statistics of the audio features over (noisy, clean) wav pairs -> ``Stats`` (audio (513, 1) mean / std):
     what ``create_audio_train_files.py:196-214, 340-392`` computes offline.  ``pairs``: a ``WavPairs``, a list of pairs or
     a text file of them.  Every noisy file is peak-normalised as ``wav_pair_step`` does and its log-power STFT frames --
     the frame counts ``wav_pair_step`` uses -- are accumulated on the GPU without materialising the features
     (``ops.stft_stats``).  With ``torch.distributed`` initialised every rank takes ``rank_shard`` of the pairs and the
-    float64 accumulators are summed by one all-reduce."""
+    float64 accumulators are summed by one all-reduce.  ``resample``: as ``WavPairs``'s (a ``WavPairs`` brings its own)."""
     import torch.distributed as dist
     if not isinstance(pairs, WavPairs):
-        pairs = WavPairs(pairs)
+        pairs = WavPairs(pairs, resample)
     multi = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     nfft = int(wlen_sec * fs)
     acc = ops.stats_new(nfft // 2 + 1, device)
     loader = torch.utils.data.DataLoader(torch.utils.data.Subset(pairs, rank_shard(len(pairs), rank, world)),
                                          batch_size=batch_size, shuffle=False, collate_fn=WavPairs.collate)
-    for lens, noisy, _ in loader:
-        noisy = ops.peak_normalize(noisy.to(device, non_blocking=True))
+    for batch in loader:
+        lens, noisy, _ = pair_waves(batch, device)
+        noisy = ops.peak_normalize(noisy)
         ops.stft_stats(acc, noisy, lens, nfft, int(hop_percent * nfft), eps=eps, pad_at_end=True, fs=fs)
     if multi:
         dist.all_reduce(acc)                 # the merge across ranks: merge_stats of the ranks' accumulators
@@ -531,23 +621,25 @@ def wav_pair_stats(pairs, device, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_pe
     return Stats(audio_mean=mean.cpu().numpy().reshape(-1, 1), audio_std=std.cpu().numpy().reshape(-1, 1), eps=eps)
 
 
-def mix_stats(clean, bank, device, draw, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS):
+def mix_stats(clean, bank, device, draw, batch_size=16, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, eps=EPS, resample=False):
     """``wav_pair_stats`` over mixtures made on the fly: one pass over the clean utterances (``clean``: a ``CleanWavs``, a
     list of paths or a text file of them), every batch mixed as ``mix_step`` mixes it with ``draw(lengths)`` -- a seeded
-    ``MixDraw`` makes the pass reproducible -- peak-normalised and accumulated with ``ops.stft_stats``."""
+    ``MixDraw`` makes the pass reproducible -- peak-normalised and accumulated with ``ops.stft_stats``.  ``resample``: as
+    ``CleanWavs``'s (a ``CleanWavs`` brings its own)."""
     import torch.distributed as dist
     if not isinstance(clean, CleanWavs):
-        clean = CleanWavs(clean)
+        clean = CleanWavs(clean, resample)
     multi = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     nfft = int(wlen_sec * fs)
     acc = ops.stats_new(nfft // 2 + 1, device)
     loader = torch.utils.data.DataLoader(torch.utils.data.Subset(clean, rank_shard(len(clean), rank, world)),
                                          batch_size=batch_size, shuffle=False, collate_fn=CleanWavs.collate)
-    for lens, wave in loader:
+    for batch in loader:
+        lens, wave = clean_waves(batch, device)
         n = [int(v) for v in lens]
         clip, start, snr = draw(n)
-        noisy = ops.mix(ops.peak_normalize(wave.to(device, non_blocking=True)), n, bank, clip, start, snr)
+        noisy = ops.mix(ops.peak_normalize(wave), n, bank, clip, start, snr)
         ops.stft_stats(acc, ops.peak_normalize(noisy), lens, nfft, int(hop_percent * nfft), eps=eps, pad_at_end=True, fs=fs)
     if multi:
         dist.all_reduce(acc)
@@ -713,7 +805,8 @@ def run_epoch(model, kind, loader, device, waveform, opt=None, reducer=None, log
 
 def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_size=16, n_items=64, lr=1e-4,
                freeze_features=False, out_dir=None, stats=None, wav_pairs=None, compute_stats=False, av_files=None,
-               objective="bce", clean_wavs=None, noise_wavs=None, snr_db=(-5.0, 20.0), mix_seed=0, mix_labels="clean"):
+               objective="bce", clean_wavs=None, noise_wavs=None, snr_db=(-5.0, 20.0), mix_seed=0, mix_labels="clean",
+               resample=False):
     """The body of ``scripts/train_{audio,video,AV}_net.py``; settings come from the caller's module-level constants
     (the reference's "config system") and may be overridden by AVVAD_* environment variables.
 
@@ -751,7 +844,11 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
     utterance alone, as wav pairs are labelled; "noise_aware" trains against the speech mask of the reference's
     ``noise_aware_IBM`` and "irm" against the ideal ratio mask, both computed in the step from the clean wave and the
     noise that was just added (``mix_step``).  With ``objective="si_sdr"`` or "msa" the label feeds the F1 log line only;
-    "mse_mask" and "mse_signal" regress onto it."""
+    "mse_mask" and "mse_signal" regress onto it.
+
+    ``resample`` (with ``wav_pairs``, or ``clean_wavs`` + ``noise_wavs``): files of other rates than 16 kHz are allowed and
+    resampled on the GPU -- the utterances in the step (``to_16k``), the noise clips once when the bank is read, and the
+    same in the statistics passes.  The default refuses them."""
     objective = os.environ.get("AVVAD_OBJECTIVE", objective)
     check_objective(objective, kind, waveform, wav_pairs, clean_wavs=clean_wavs)
     check_mix_labels(mix_labels, clean_wavs is not None and noise_wavs is not None)
@@ -790,8 +887,8 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
                                 names=[n for n, q in model.named_parameters() if q.requires_grad]) if world > 1 else None
     prepare = loss_fn = mixer = None
     if clean_wavs is not None:
-        pairs = CleanWavs(clean_wavs)
-        bank = read_noise_bank(noise_wavs, device)
+        pairs = CleanWavs(clean_wavs, resample)
+        bank = read_noise_bank(noise_wavs, device, resample)
         mixer = MixDraw(bank, snr_db, mix_seed, rank)
         labels = labels_for_ydim(model.y_dim)
         collate = CleanWavs.collate
@@ -827,7 +924,7 @@ def train_main(kind, make_model, model_name, waveform=False, epochs=1, batch_siz
         ds_train = SyntheticAV(per_rank, kind, waveform=waveform, seed=1 + rank)
         ds_valid = SyntheticAV(max(per_rank // 4, batch_size), kind, waveform=waveform, seed=1000 + rank)
     else:
-        pairs = WavPairs(wav_pairs)
+        pairs = WavPairs(wav_pairs, resample)
         labels = labels_for_ydim(model.y_dim)
         collate = WavPairs.collate
         ds_train = ds_valid = torch.utils.data.Subset(pairs, range(rank, len(pairs), world))
@@ -935,12 +1032,20 @@ def audio_features(x_t, stats=None, n_label_frames=None, fs=16e3, wlen_sec=64e-3
     return x
 
 
-def clean_vad_labels(clean_path, n_noisy, device, fs=16e3, wlen_sec=64e-3, hop_percent=0.25):
+def load_16k(path, device, resample=False):
+    """``load_waveform`` onto the GPU at 16 kHz -> (L,): a file of another rate is resampled there (``ops.resample``) with
+    ``resample``, and refused without it."""
+    x, fs = load_waveform(path)
+    if fs != 16000 and not resample:
+        raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (path, fs))
+    return ops.resample(x.to(device), fs_in=fs)[0]
+
+
+def clean_vad_labels(clean_path, n_noisy, device, fs=16e3, wlen_sec=64e-3, hop_percent=0.25, resample=False):
     """VAD labels (1, T) of a clean file, cropped to the noisy file's length first (the evaluator's counterpart of
-    ``WavPairs``): peak normalisation, then ``clean_speech_VAD`` with the training pipeline's framing, on the GPU."""
-    c, fs_c = load_waveform(clean_path)
-    if fs_c != 16000:
-        raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (clean_path, fs_c))
+    ``WavPairs``): peak normalisation, then ``clean_speech_VAD`` with the training pipeline's framing, on the GPU.
+    ``resample``: a clean file of another rate is resampled to 16 kHz first (``n_noisy`` counts 16 kHz samples)."""
+    c = load_16k(clean_path, device, resample)
     n = min(c.numel(), int(n_noisy))
     c = ops.peak_normalize(c[:n].to(device).view(1, -1))
     _, vad = ops.speech_targets(c, [n], "vad_labels", fs=fs, wlen_sec=wlen_sec, hop_percent=hop_percent, center=False,
@@ -954,33 +1059,36 @@ def _one_chunking(chunk_frames, chunk_samples):
 
 
 def process_utt(classifier, x_t, stats=None, n_label_frames=None, video=None, eps=EPS, std_norm=True, chunk_frames=None,
-                chunk_samples=None):
+                chunk_samples=None, fs_in=16000):
     """One utterance through the reference's evaluator (``evaluate_audio_net.py:107-180``; with ``video`` (T,67,67) the AV
     variant ``evaluate_AV_net.py:148-250``): returns (y_hat_soft, y_hat_hard) on the CPU, shaped (1, T) like the
     reference's ``y_hat_soft[..., 0]``.  ``chunk_frames``: score through a streaming session (``avvad.stream``), that
     many frames per step; the features are still formed from the whole utterance.  ``chunk_samples``: the RAW samples go
     through the session in packets of that many (``stream.forward_wave_chunked``): the peak -- the one statistic of the
-    whole utterance -- is one reduction up front, everything behind it is streamed."""
+    whole utterance -- is one reduction up front, everything behind it is streamed.  ``fs_in``: the rate of ``x_t``; another
+    rate than 16000 is resampled on the GPU first (``ops.resample``), and with ``chunk_samples`` the packets are taken at
+    ``fs_in`` and resampled inside the session."""
     soft = torch.sigmoid(utt_logits(classifier, x_t, stats, n_label_frames, video, eps, std_norm, chunk_frames,
-                                    chunk_samples)[..., 0].detach().cpu())
+                                    chunk_samples, fs_in)[..., 0].detach().cpu())
     return soft, (soft > 0.5).int()
 
 
 def utt_logits(classifier, x_t, stats=None, n_label_frames=None, video=None, eps=EPS, std_norm=True, chunk_frames=None,
-               chunk_samples=None):
+               chunk_samples=None, fs_in=16000):
     """The logits (1, T, y_dim) of ``process_utt``, on the GPU (arguments as there)."""
     _one_chunking(chunk_frames, chunk_samples)
+    x16 = ops.resample(x_t.reshape(-1), fs_in=fs_in)[0]          # x_t itself at 16 kHz
     if chunk_samples is not None:
         w = x_t.reshape(1, -1)
-        T = ops.n_frames(w.shape[1], 1024, 256)
+        T = ops.n_frames(x16.numel(), 1024, 256)
         T = T if n_label_frames is None else min(T, int(n_label_frames))
         v = None
         if video is not None:
             v = video[None, :T].contiguous()
             v = stats.video(v) if (stats is not None and std_norm) else v
-        return stream.forward_wave_chunked(classifier, w, None, v, chunk_samples, stats if std_norm else None, ops.peak(w),
-                                           eps=eps, max_frames=[T])
-    x = audio_features(x_t, stats, n_label_frames, eps=eps, std_norm=std_norm)
+        return stream.forward_wave_chunked(classifier, w, None, v, chunk_samples, stats if std_norm else None,
+                                           ops.peak(x16.view(1, -1)), eps=eps, max_frames=[T], fs_in=fs_in)
+    x = audio_features(x16, stats, n_label_frames, eps=eps, std_norm=std_norm)
     lengths = [x.shape[1]]
     v = None
     if video is not None:
@@ -995,23 +1103,25 @@ def utt_logits(classifier, x_t, stats=None, n_label_frames=None, video=None, eps
     return y
 
 
-def resynth_utt(classifier, x_t, stats=None, hard=True, eps=EPS, std_norm=True, chunk_samples=None):
+def resynth_utt(classifier, x_t, stats=None, hard=True, eps=EPS, std_norm=True, chunk_samples=None, fs_in=16000):
     """Enhanced waveform of one utterance from a mask-predicting audio model (``y_dim = n_fft/2 + 1 = 513``): peak
     normalisation -> features -> model as in ``process_utt``, then the logits go straight in as the mask of
     ``ops.resynth`` on the peak-normalised wave -- ``hard``: ``logit > 0`` (the evaluator's ``sigmoid > 0.5``), else
     ``sigmoid(logit)`` -- with the peak as the output scale, so the result is in the input's scale.  x_t (L,) on the GPU
     -> (L,) on the GPU.  ``chunk_samples``: the raw samples go through a streaming session in packets of that many and the
     enhanced samples come out of it per packet (``stream.enhance_wave_chunked``) -- the same values up to summation order
-    (with ``hard``, a logit next to 0 may fall on the other side)."""
+    (with ``hard``, a logit next to 0 may fall on the other side).  ``fs_in``: the rate of ``x_t``; the enhanced samples
+    are 16 kHz, ``ops.resample_length(L)`` of them (resampling back is out of scope)."""
     n_fft = 1024
     if getattr(classifier, "y_dim", None) != n_fft // 2 + 1:
         raise ValueError("resynthesis needs a model that predicts a %d-bin mask (y_dim = %d), got y_dim = %r"
                          % (n_fft // 2 + 1, n_fft // 2 + 1, getattr(classifier, "y_dim", None)))
-    w = x_t.reshape(1, -1)
+    x16 = ops.resample(x_t.reshape(-1), fs_in=fs_in)[0]
     if chunk_samples is not None:
-        return stream.enhance_wave_chunked(classifier, w, None, chunk_samples, stats if std_norm else None, ops.peak(w), hard,
-                                           eps, n_fft, 256).view(-1)
-    x = audio_features(x_t, stats, None, eps=eps, std_norm=std_norm)
+        return stream.enhance_wave_chunked(classifier, x_t.reshape(1, -1), None, chunk_samples, stats if std_norm else None,
+                                           ops.peak(x16.view(1, -1)), hard, eps, n_fft, 256, fs_in).view(-1)
+    w = x16.view(1, -1)
+    x = audio_features(x16, stats, None, eps=eps, std_norm=std_norm)
     logits = classifier(x, [x.shape[1]]).detach().contiguous()
     out = ops.resynth(ops.peak_normalize(w), logits, mask_mode=3 if hard else 2, n_fft=n_fft, hop=256, scale=ops.peak(w))
     return out.view(-1)
@@ -1046,7 +1156,7 @@ def intelligibility_utt(enhanced, clean, noisy):
 def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16, out_dir="eval_out", wav_list=None,
                   stats=None, labels=None, clean_of=None, av_files=None, chunk_frames=None, chunk_samples=None,
                   resynth_dir=None, resynth_hard=True, resynth_chunked=False, score_dir=None,
-                  intelligibility=False):
+                  intelligibility=False, resample=False):
     """The body of ``scripts/evaluate_*_net.py``: per-utterance forward, sigmoid, threshold, save
     ``*_y_hat_soft.pt`` / ``*_y_hat_hard.pt`` (``evaluate_AV_net.py:236-250``); utterances are split across ranks
     (the reference's 4-process pool, ``:329-339``).
@@ -1075,7 +1185,12 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
     the predictions come from and the GPU labels) and, with ``resynth_dir``, ``score_utt`` of the enhanced waveform
     against the clean file cropped to the common length.  ``None`` writes nothing and changes nothing.
     ``intelligibility`` (with ``resynth_dir`` and ``score_dir``): ``intelligibility_utt``'s four keys ``stoi``, ``estoi``,
-    ``input_stoi``, ``input_estoi`` join that dict; ``False`` leaves the file exactly as it was."""
+    ``input_stoi``, ``input_estoi`` join that dict; ``False`` leaves the file exactly as it was.
+
+    ``resample`` (``wav_list``): an utterance (or its clean file) of another rate than 16 kHz is resampled on the GPU
+    (``ops.resample``) and then scored as a 16 kHz one -- predictions, labels, ``resynth_dir`` and ``score_dir`` outputs are
+    all 16 kHz; with ``chunk_samples`` the packets are taken at the file's rate and resampled inside the session
+    (``Session.set_frontend(fs_in=...)``).  The default refuses such a file."""
     if intelligibility and (resynth_dir is None or score_dir is None):
         raise ValueError("intelligibility scores the enhanced utterances: it needs resynth_dir and score_dir")
     if score_dir is not None and (wav_list is None or clean_of is None):
@@ -1138,14 +1253,16 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
         with torch.no_grad():
             for i in range(rank, len(wav_list), world):
                 x_t, fs = load_waveform(wav_list[i])
-                if fs != 16000:
+                if fs != 16000 and not resample:
                     raise ValueError("%s: expected 16 kHz audio, got %d Hz" % (wav_list[i], fs))
+                x_in = x_t.to(device)                             # as read, at the file's rate: what the packets are cut from
+                x_t = ops.resample(x_in, fs_in=fs)[0]             # at 16 kHz (the tensor itself when it is)
                 if clean_of is not None:
-                    y = clean_vad_labels(clean_of[wav_list[i]], x_t.numel(), device)
+                    y = clean_vad_labels(clean_of[wav_list[i]], x_t.numel(), device, resample=resample)
                 else:
                     y = labels.get(wav_list[i]) if labels else None
-                logits = utt_logits(model, x_t.to(device), stats, None if y is None else y.shape[-1],
-                                    chunk_frames=chunk_frames, chunk_samples=chunk_samples)
+                logits = utt_logits(model, x_in, stats, None if y is None else y.shape[-1],
+                                    chunk_frames=chunk_frames, chunk_samples=chunk_samples, fs_in=fs)
                 soft = torch.sigmoid(logits[..., 0].detach().cpu())                      # process_utt's outputs
                 hard = (soft > 0.5).int()
                 scores = None
@@ -1161,15 +1278,15 @@ def evaluate_main(kind, make_model, checkpoint=None, waveform=False, n_items=16,
                     torch.save(y.int().cpu(), base + "_label.pt")
                 if resynth_dir is not None:
                     from scipy.io import wavfile
-                    enhanced = resynth_utt(model, x_t.to(device), stats, hard=resynth_hard,
-                                           chunk_samples=chunk_samples if resynth_chunked else None)
+                    enhanced = resynth_utt(model, x_in, stats, hard=resynth_hard,
+                                           chunk_samples=chunk_samples if resynth_chunked else None, fs_in=fs)
                     wavfile.write(os.path.join(resynth_dir, os.path.basename(base) + "_enhanced.wav"), 16000,
                                   enhanced.cpu().numpy())
                     if scores is not None:
-                        clean, _ = load_waveform(clean_of[wav_list[i]])
-                        scores.update(score_utt(enhanced, clean.to(device), x_t.to(device)))
+                        clean = load_16k(clean_of[wav_list[i]], device, resample)
+                        scores.update(score_utt(enhanced, clean, x_t))
                         if intelligibility:
-                            scores.update(intelligibility_utt(enhanced, clean.to(device), x_t.to(device)))
+                            scores.update(intelligibility_utt(enhanced, clean, x_t))
                 if scores is not None:
                     torch.save(scores, os.path.join(score_dir, os.path.basename(base) + "_scores.pt"))
     else:

@@ -6,7 +6,7 @@ OUT="$HERE/../lib"
 mkdir -p "$OUT" "$HERE/_obj"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$HERE/../../include -I$HERE $*"
 # every source once: compiled in parallel, then linked
-SRCS="gemm trunk lstm misc wavenet mcb stft target stats scores stoi spectral_loss mix lip stream stft_stream istft istft_stream"
+SRCS="gemm trunk lstm misc wavenet mcb stft target stats scores stoi spectral_loss mix lip stream stft_stream istft istft_stream resample"
 pids=()
 objs=()
 for f in $SRCS; do

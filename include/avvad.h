@@ -37,7 +37,7 @@
  *           float64 statistics and score accumulators, score ratios, int64 confusion counts  8 bytes
  *           ratio / energies / clip_off of avvad_mix                                        8 bytes
  *           c_speech / c_noise and the spectra of avvad_target_noise_aware*                 8 bytes
- *           d and taps of avvad_stoi and avvad_stoi_loss                                    8 bytes
+ *           d and taps of avvad_stoi and avvad_stoi_loss, taps of avvad_resample*           8 bytes
  *           int64 / int32 index arrays      their natural alignment
  *           bf16 operands, avvad_lip_decode's coef, the avvad_stft_stream basis,
  *           (checked by avvad_stft_stream_fwd / _fwd_spec), the avvad_istft_stream
@@ -89,7 +89,7 @@ typedef void* avvad_stream_t; /* hipStream_t */
                                  avvad_si_sdr_loss, and avvad_mix_workspace / avvad_mix, and the
                                  avvad_target_noise_aware* masks, and avvad_spectral_loss_workspace /
                                  avvad_spectral_loss, and avvad_stoi_workspace / avvad_stoi, and
-                                 avvad_stoi_loss_workspace / avvad_stoi_loss. */
+                                 avvad_stoi_loss_workspace / avvad_stoi_loss, and the avvad_resample* entries. */
 const char* avvad_version(void);
 int avvad_abi_version(void);
 
@@ -834,6 +834,51 @@ int avvad_mix(const float* clean, long ld_clean, const int* n_samples /* NULL: L
               float* noisy, long ld_noisy, float* noise_out /* or NULL */, long ld_noise,
               float* gain, double* energies, float* peak,      /* each NULL or as above */
               int B, long L, void* ws, size_t ws_bytes, avvad_stream_t s);
+
+/* ------------------------------------------------------------------------
+ * Rational-rate resampling: waveforms and streams of any rate into the 16 kHz signal chain (csrc/resample.hip)
+ * Replaces: nothing the reference has -- its corpus scripts read audio that was resampled offline.
+ * For rates fs_in -> fs_out: g = gcd, up = fs_out / g, down = fs_in / g, m = max(up, down), half = 10 m.  The filter is
+ * scipy.signal.resample_poly's default, h[t] = up w[t] / sum(w), w[t] = (1/m) sinc((t - half) / m) kaiser(2 half + 1, 5.0)[t],
+ * built on the host in float64 (avvad.ops.resample_taps).  Per row of len inputs x:
+ *   out[n] = (float) sum_m h[n down + half - m up] x[m],   0 <= n < ceil(len up / down),
+ *   m ascending over max(0, ceil((n down - half) / up)) .. min(len - 1, floor((n down + half) / up)):
+ * inputs that do not exist are skipped, not multiplied; every product and the chain are double fma, rounded to float once.
+ * A value depends on its own inputs alone: not on the tile, the row, the batch, "max_cus", the form of the kernel or how a
+ * stream was split into calls.  No atomics, no workspace.
+ * taps: 8-byte aligned device doubles, avvad_resample_taps_len(up, down) = up T of them with T = 2 half / up + 1, PHASE-MAJOR:
+ *   taps[p T + j] = h[p + j up], and 0 where p + j up > 2 half (never read).
+ * avvad_resample: x [B][ld_x], row b holding lengths[b] (device int32, clamped to [0, L]; NULL: L each) samples, any
+ *   4-byte aligned float pointer; nothing at or behind a row's length is read.  out [B][ld_out]: columns
+ *   0 .. avvad_resample_length(L, up, down) - 1 are written, +0 from the row's own count on; columns from there to the pitch
+ *   are not touched.  n_out: NULL or device int32 [B], the rows' counts ceil(len up / down).
+ * avvad_resample_stream: row b has taken in_before[b] inputs and emitted out_before[b] outputs since its reset, takes the
+ *   first n_valid[b] samples of chunk [B][ld_chunk] (n_in columns; chunk may be NULL when n_in == 0) and writes its outputs
+ *   out_before[b] .. out_before[b] + n_emit[b] - 1 to out [B][ld_out]; columns n_emit[b] .. n_max - 1 are +0 (out may be NULL
+ *   when n_max == 0).  The four count arrays are device int64 [B] (a stream that runs for hours passes 2^31), clamped in the
+ *   kernel (to n_in, to n_max, to [0, 2^50]) so that wrong counts cannot leave a buffer.  The host decides n_emit: a row that
+ *   goes on emits the outputs whose every tap has arrived, E(N) = floor((N up - 1 - half) / down) + 1 of them after N inputs
+ *   (0 while N up - 1 - half < 0); a row that ENDS with the call emits up to ceil(N up / down), the inputs that never came
+ *   skipped like those behind a whole utterance's end -- so a stream of N samples yields avvad_resample's samples and count.
+ *   state_in / state_out: float [B][H], H = avvad_resample_hist(up, down) = 2 half / up + 2, different buffers:
+ *   state_out[b] = the last H of (state_in[b] ++ chunk[b][:n_valid[b]]), so a row with nothing to do copies its state.  Inputs
+ *   in front of a row's reset are never read: any state content is "start of utterance" when in_before[b] == 0.
+ * Refused (AVVAD_EINVAL) before anything is launched: up or down < 1 or > AVVAD_RESAMPLE_MAX_RATE, gcd(up, down) != 1,
+ * up == down == 1 (16 kHz passes through untouched in the Python layer), B outside 1..65535, L < 1 or L or the output
+ * length >= 2^31, a pitch below its row, taps not 8-byte aligned, NULL where a buffer is needed, state_in == state_out.
+ * The three queries return 0 on a bad ratio.
+ * ---------------------------------------------------------------------- */
+#define AVVAD_RESAMPLE_TILE 256       /* outputs of one workgroup */
+#define AVVAD_RESAMPLE_MAX_RATE 1024  /* largest up and down */
+long avvad_resample_length(long L, int up, int down);      /* ceil(L up / down) */
+long avvad_resample_taps_len(int up, int down);            /* doubles of the phase-major table */
+int avvad_resample_hist(int up, int down);                 /* H: floats per row of the stream state */
+int avvad_resample(const float* x, long ld_x, const int* lengths /* NULL: L each */, const double* taps, int up, int down,
+                   float* out, long ld_out, int* n_out /* int32 [B] or NULL */, int B, long L, avvad_stream_t s);
+int avvad_resample_stream(const float* chunk, long ld_chunk, const long long* n_valid, const long long* in_before,
+                          const long long* out_before, const long long* n_emit, const float* state_in, float* state_out,
+                          const double* taps, int up, int down, float* out, long ld_out, int B, int n_in, int n_max,
+                          avvad_stream_t s);
 
 /* ------------------------------------------------------------------------
  * Training labels from clean speech: framed-energy VAD and ideal binary mask (IBM)
