@@ -171,7 +171,8 @@ def istft_case(n_fft, hop, frames, mode, center, seed, lengths=None, scale=None,
     in the padding frames either way), a mask in [0, 1) (mode 1) or logits
     (mode 2) with NaN in the padding, a normal cotangent with NaN behind each row's length -- with ``center`` a full one,
     without it zero in the first and last n_fft - hop samples of every row, where the window sum of squares falls to
-    1e-10.  Holds the float64 reference and the float32 yardstick of dmask."""
+    1e-10.  A row of 0 frames is all padding, has length 0 and a zero row in the reference.  Holds the float64 reference
+    and the float32 yardstick of dmask."""
     rng = np.random.default_rng(seed)
     B, T, F = len(frames), max(frames), n_fft // 2 + 1
     start = n_fft // 2 if center else 0
@@ -182,8 +183,9 @@ def istft_case(n_fft, hop, frames, mode, center, seed, lengths=None, scale=None,
     dout = np.full((B, max(lens)), np.nan, dtype=np.float32)
     for b, nf in enumerate(frames):
         if spec_rows is None:
-            S = R.random_spectrum(rng, nf, n_fft)
-            spec[b, :nf, :, 0], spec[b, :nf, :, 1] = S.real, S.imag
+            if nf > 0:                                          # (a row of 0 frames is all padding: NaN, and a zero row of dmask)
+                S = R.random_spectrum(rng, nf, n_fft)
+                spec[b, :nf, :, 0], spec[b, :nf, :, 1] = S.real, S.imag
         else:
             spec[b, :nf] = spec_rows[b][:nf]
         mask[b, :nf] = rng.random((nf, F)) if mode == 1 else rng.standard_normal((nf, F)) * 2.0
