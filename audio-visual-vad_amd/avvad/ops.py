@@ -87,12 +87,15 @@ def _wave2d(wave):
     return w, (w.view(1, -1) if w.dim() == 1 else w)
 
 
-def _ints(v, B=None, hi=None, msg=None):
-    """Host list of ints from a tensor or a sequence.  With ``msg``: B values within 0..hi (``hi`` None: no upper bound),
-    or AvvadError(msg)."""
+def _ints(v, B=None, hi=None, msg=None, default=None, what=None):
+    """Host list of ints from a tensor or a sequence: THE per-row list check.  With ``msg``, or ``what`` (the argument's
+    name, for the usual message, made only when it is needed): B values within 0..hi (``hi`` None: no upper bound), or
+    AvvadError.  With ``default``: None stands for B times that value."""
+    if v is None and default is not None:
+        return [default] * B
     vals = [int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
-    if msg is not None and (len(vals) != B or any(n < 0 or (hi is not None and n > hi) for n in vals)):
-        raise L.AvvadError(msg)
+    if (msg or what) and (len(vals) != B or any(n < 0 or (hi is not None and n > hi) for n in vals)):
+        raise L.AvvadError(msg or "%s must hold one value in [0, %s] per row (%d rows), got %s" % (what, hi, B, vals))
     return vals
 
 
@@ -1017,28 +1020,47 @@ def _stream_basis(which, n_fft, device):
     return out
 
 
-def _stream_state(B, n_fft, device):
+def _stream_state(B, width, device):
+    """zeroed per-row state (B, width) of a streaming stage"""
     if int(B) < 1:
         raise L.AvvadError("B must be >= 1")
-    return torch.zeros(int(B), _n_fft_check(n_fft), dtype=torch.float32, device=device)
+    return torch.zeros(int(B), width, dtype=torch.float32, device=device)
 
 
-def _stream_buffers(which, state, out_state, basis, B, n_fft, device):
-    """Checks ``state`` / ``out_state`` / ``basis`` of ``<which>`` (stft_stream / istft_stream).  -> (in_place, the tensor
-    the kernel writes the new state to): with ``out_state`` None or ``state`` itself a temporary, which the caller copies
-    back into ``state`` after the launch."""
+def _stream_chunk(chunk, n_valid):
+    """The samples of a streaming call -> (chunk (B, n), B, n, the real samples per row (``n_valid`` None: all n))."""
+    chunk = _dev(chunk, "chunk")
+    if chunk.dim() != 2 or chunk.shape[0] < 1:
+        raise L.AvvadError("chunk must be (B, n) samples, got %s" % (tuple(chunk.shape),))
+    B, n = chunk.shape
+    return chunk, B, n, _ints(n_valid, B, n, default=n, what="n_valid")
+
+
+def _stream_buffers(state, out_state, shape, device, made_by, *args):
+    """Checks ``state`` / ``out_state`` of a streaming stage against the ``shape`` of ``made_by % args`` (the ``*_state(...)``
+    call the message quotes).  -> (in_place, the tensor the kernel writes the new state to): with ``out_state`` None or
+    ``state`` itself a temporary, which ``_stream_commit`` copies back into ``state`` after the launch."""
     def st(t, what):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
-                tuple(t.shape) != (B, n_fft) or t.device != device:
-            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of %s_state(%d, %d, device)" % (what, which, B, n_fft))
+                tuple(t.shape) != shape or t.device != device:
+            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of %s" % (what, made_by % args))
     st(state, "state")
     if out_state is not None and out_state is not state:
         st(out_state, "out_state")
     in_place = out_state is None or out_state.data_ptr() == state.data_ptr()
-    if not isinstance(basis, torch.Tensor) or not basis.is_cuda or basis.dtype != torch.float32 or \
-            basis.numel() * 4 != getattr(L.lib(), "avvad_%s_basis_bytes" % which)(n_fft) or basis.device != device:
-        raise L.AvvadError("basis must be %s_basis(%d, device)" % (which, n_fft))
     return in_place, torch.empty_like(state) if in_place else out_state
+
+
+def _stream_commit(in_place, state, new):
+    if in_place:
+        state.copy_(new)
+
+
+def _stream_table(t, what, dtype, numel, device, made_by, *args):
+    """Checks a table built once per stream (a packed basis, the resampler's taps): dtype, device and size."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.device != device or \
+            not t.is_contiguous() or t.numel() != numel:
+        raise L.AvvadError("%s must be %s" % (what, made_by % args))
 
 
 def stft_stream_basis(n_fft, device):
@@ -1050,7 +1072,7 @@ def stft_stream_basis(n_fft, device):
 def stft_stream_state(B, n_fft, device):
     """Zeroed front-end state (B, n_fft) -- each row's pending samples; all zeros with a count of 0 (a fresh
     ``SampleClock``) is "start of utterance"."""
-    return _stream_state(B, n_fft, device)
+    return _stream_state(B, _n_fft_check(n_fft), device)
 
 
 def _row_vector(v, B, name):
@@ -1075,16 +1097,12 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
     ``return_spec``: -> (features, frames, spec (B, tmax, F, 2)), the complex spectrum (re, im) of the samples / peak that
     the same launch holds anyway (zeros behind a row's frames); the features keep their bits.  What ``istft_stream`` takes.
     Every argument is checked before the clock or a state changes.  Any split of a stream into calls gives the same bits."""
-    chunk = _dev(chunk, "chunk")
-    if chunk.dim() != 2 or chunk.shape[0] < 1:
-        raise L.AvvadError("chunk must be (B, n) samples, got %s" % (tuple(chunk.shape),))
-    B, n = chunk.shape
+    chunk, B, n, nv = _stream_chunk(chunk, n_valid)
     n_fft, hop = _n_fft_check(clock.n_fft), int(clock.hop)
     F = n_fft // 2 + 1
-    nv = [n] * B if n_valid is None else _ints(n_valid)
-    if len(nv) != B or any(x < 0 or x > n for x in nv):
-        raise L.AvvadError("n_valid must hold one count in [0, %d] per row (%d rows), got %s" % (n, B, nv))
-    in_place, new = _stream_buffers("stft_stream", state, out_state, basis, B, n_fft, chunk.device)
+    in_place, new = _stream_buffers(state, out_state, (B, n_fft), chunk.device, "stft_stream_state(%d, %d, device)", B, n_fft)
+    _stream_table(basis, "basis", torch.float32, L.lib().avvad_stft_stream_basis_bytes(n_fft) // 4, chunk.device,
+                  "stft_stream_basis(%d, device)", n_fft)
     pk = None if peak is None else _row_vector(peak, B, "peak")
     if (mean is None) != (std is None):
         raise L.AvvadError("standardisation needs both mean and std")
@@ -1105,8 +1123,7 @@ def stft_stream(chunk, n_valid, clock, state, basis, peak=None, mean=None, std=N
                     "avvad_stft_stream_fwd_spec")
         else:
             L.check(L.lib().avvad_stft_stream_fwd(*args, C.byref(d), _stream()), "avvad_stft_stream_fwd")
-    if in_place:
-        state.copy_(new)
+    _stream_commit(in_place, state, new)
     return (out, frames, spec) if return_spec else (out, frames)
 
 
@@ -1120,7 +1137,7 @@ def istft_stream_basis(n_fft, device):
 def istft_stream_state(B, n_fft, device):
     """Zeroed overlap-add state (B, n_fft) -- each row's unfinished sums of the samples later frames still cover; all
     zeros (a fresh ``OlaClock``) is "start of utterance"."""
-    return _stream_state(B, n_fft, device)
+    return _stream_state(B, _n_fft_check(n_fft), device)
 
 
 def istft_stream(spec, frames, clock, state, basis, mask=None, mask_mode=None, scale=None, final_samples=None, out_state=None):
@@ -1151,7 +1168,9 @@ def istft_stream(spec, frames, clock, state, basis, mask=None, mask_mode=None, s
         m, mode = _mask_args(mask, mask_mode, B, T, F)
     else:
         m, mode = None, 0                                         # no row has a frame: there is nothing to mask
-    in_place, new = _stream_buffers("istft_stream", state, out_state, basis, B, n_fft, spec.device)
+    in_place, new = _stream_buffers(state, out_state, (B, n_fft), spec.device, "istft_stream_state(%d, %d, device)", B, n_fft)
+    _stream_table(basis, "basis", torch.float32, L.lib().avvad_istft_stream_basis_bytes(n_fft) // 4, spec.device,
+                  "istft_stream_basis(%d, device)", n_fft)
     sc = None if scale is None else _row_vector(scale, B, "scale")
     n_before, n_out = clock.advance(nf, final_samples)           # raises before it changes anything
     nmax = max(n_out)
@@ -1164,8 +1183,7 @@ def istft_stream(spec, frames, clock, state, basis, mask=None, mask_mode=None, s
                                            L.ptr(counts[2]), L.ptr(sc), L.ptr(state), L.ptr(new), L.ptr(basis),
                                            L.ptr(out) if nmax else None, C.byref(d), L.ptr(ws), ws.numel() * 4, _stream()),
                 "avvad_istft_stream")
-    if in_place:
-        state.copy_(new)
+    _stream_commit(in_place, state, new)
     return out, n_out
 
 
@@ -1276,10 +1294,7 @@ def resample(wave, lengths=None, fs_in=None, fs_out=16000):
 def resample_stream_state(B, up, down, device):
     """Zeroed resampler state (B, H), ``H = 2 * half // up + 2``: the last inputs of each row, which later outputs still
     need; with a fresh ``RateClock`` it is "start of utterance" whatever it holds."""
-    up, down = _ratio_check(up, down)
-    if int(B) < 1:
-        raise L.AvvadError("B must be >= 1")
-    return torch.zeros(int(B), L.lib().avvad_resample_hist(up, down), dtype=torch.float32, device=device)
+    return _stream_state(B, L.lib().avvad_resample_hist(*_ratio_check(up, down)), device)
 
 
 def resample_stream(chunk, n_valid, clock, state, taps, final=None, out_state=None):
@@ -1294,29 +1309,12 @@ def resample_stream(chunk, n_valid, clock, state, taps, final=None, out_state=No
     -> (out (B, nmax) with zeros behind a row's count, samples per row (list)).  A row that goes on has emitted
     ``floor((N * up - 1 - half) / down) + 1`` samples after N inputs; a stream of N samples yields exactly ``resample``'s.
     Every argument is checked before the clock or a state changes.  Any split of a stream into calls gives the same bits."""
-    chunk = _dev(chunk, "chunk")
-    if chunk.dim() != 2 or chunk.shape[0] < 1:
-        raise L.AvvadError("chunk must be (B, n) samples, got %s" % (tuple(chunk.shape),))
-    B, n = chunk.shape
+    chunk, B, n, nv = _stream_chunk(chunk, n_valid)
     up, down = _ratio_check(clock.up, clock.down)
-    H = L.lib().avvad_resample_hist(up, down)
-    nv = [n] * B if n_valid is None else _ints(n_valid)
-    if len(nv) != B or any(x < 0 or x > n for x in nv):
-        raise L.AvvadError("n_valid must hold one count in [0, %d] per row (%d rows), got %s" % (n, B, nv))
-
-    def st(t, what):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
-                tuple(t.shape) != (B, H) or t.device != chunk.device:
-            raise L.AvvadError("%s must be the contiguous float32 GPU tensor of resample_stream_state(%d, %d, %d, device)"
-                               % (what, B, up, down))
-    st(state, "state")
-    if out_state is not None and out_state is not state:
-        st(out_state, "out_state")
-    in_place = out_state is None or out_state.data_ptr() == state.data_ptr()
-    new = torch.empty_like(state) if in_place else out_state
-    if not isinstance(taps, torch.Tensor) or not taps.is_cuda or taps.dtype != torch.float64 or taps.device != chunk.device or \
-            not taps.is_contiguous() or taps.numel() != L.lib().avvad_resample_taps_len(up, down):
-        raise L.AvvadError("taps must be resample_taps_on(%d, %d, device)" % (up, down))
+    in_place, new = _stream_buffers(state, out_state, (B, L.lib().avvad_resample_hist(up, down)), chunk.device,
+                                    "resample_stream_state(%d, %d, %d, device)", B, up, down)
+    _stream_table(taps, "taps", torch.float64, L.lib().avvad_resample_taps_len(up, down), chunk.device,
+                  "resample_taps_on(%d, %d, device)", up, down)
     in_before, out_before, n_emit = clock.advance(nv, final=() if final is None else final)   # raises before it changes anything
     nmax = max(n_emit)
     counts = torch.tensor([nv, in_before, out_before, n_emit], dtype=torch.int64).to(chunk.device, non_blocking=False)
@@ -1325,8 +1323,7 @@ def resample_stream(chunk, n_valid, clock, state, taps, final=None, out_state=No
         L.check(L.lib().avvad_resample_stream(L.ptr(chunk) if n else None, n, L.ptr(counts[0]), L.ptr(counts[1]), L.ptr(counts[2]),
                                               L.ptr(counts[3]), L.ptr(state), L.ptr(new), L.ptr(taps), up, down,
                                               L.ptr(out) if nmax else None, nmax, B, n, nmax, _stream()), "avvad_resample_stream")
-    if in_place:
-        state.copy_(new)
+    _stream_commit(in_place, state, new)
     return out, n_emit
 
 

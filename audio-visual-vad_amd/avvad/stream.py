@@ -65,7 +65,71 @@ class FrameClock:
         return frames, used
 
 
-class SampleClock:
+class _RowClock:
+    """What the clocks of the streaming stages share: the per-row lists named in ``_lists`` and ``ended``, ``reset``, the
+    checks every call gets, and -- for a stage that turns ``total`` items taken into ``emitted`` items given, with
+    ``pending`` of them held in its state -- the ``plan`` / ``advance`` pair.  Such a clock supplies ``_emitted`` and
+    ``_held``; ``advance``'s return value is each clock's own."""
+    _lists = ("total", "emitted", "pending")
+    _unit = "sample"
+
+    def _rows(self, batch):
+        for k in self._lists:
+            setattr(self, k, [0] * int(batch))
+        self.ended = [False] * int(batch)
+
+    def reset(self, rows=None):
+        for b in (range(len(self.ended)) if rows is None else rows):
+            for k in self._lists:
+                getattr(self, k)[b] = 0
+            self.ended[b] = False
+
+    def _final(self, final, B):
+        return set(ops._ints(final))
+
+    def _checked(self, n, final):
+        """-> (counts per row, the rows that end): one count >= 0 per row, ``final`` within the rows, and a row that ended
+        neither fed nor ended again before its reset."""
+        B = len(self.ended)
+        n = ops._ints(n)
+        if len(n) != B or (n and min(n) < 0):
+            raise L.AvvadError("one %s count >= 0 per row expected (%d), got %s" % (self._unit, B, n))
+        final = self._final(final, B)
+        if final and (min(final) < 0 or max(final) >= B):
+            raise L.AvvadError("final rows must be in [0, %d)" % B)
+        for b in (range(B) if True in self.ended else ()):
+            if self.ended[b] and (n[b] > 0 or b in final):
+                raise L.AvvadError("row %d ended with a final call: reset it before it takes %ss again" % (b, self._unit))
+        return n, final
+
+    def _plan(self, n, final):
+        """-> per row (total, emitted, pending, ended) after the call; a row that ended idles until its reset"""
+        n, final = self._checked(n, final)
+        after = []
+        for b, nb in enumerate(n):
+            if self.ended[b]:
+                after.append((self.total[b], self.emitted[b], self.pending[b], True))
+            else:
+                N, last = self.total[b] + nb, b in final
+                e = self._emitted(b, N, last)
+                after.append((N, e, self._held(N, e), last))
+        return after
+
+    def plan(self, n, final=()):
+        """Items each row emits from ``n[b]`` more (rows in ``final`` end with them); raises :class:`AvvadError` when a
+        count is negative or a row that ended is fed again.  Changes nothing."""
+        return [row[1] - e for row, e in zip(self._plan(n, final), self.emitted)]
+
+    def _advance(self, n, final):
+        """``plan`` and then commit: -> (total, emitted, pending, ended as they applied to THIS call, items each row emits)"""
+        after = self._plan(n, final)
+        before = (list(self.total), list(self.emitted), list(self.pending), list(self.ended))
+        for b, row in enumerate(after):
+            self.total[b], self.emitted[b], self.pending[b], self.ended[b] = row
+        return before + ([e - e0 for e, e0 in zip(self.emitted, before[1])],)
+
+
+class SampleClock(_RowClock):
     """Host-side bookkeeping of the streaming STFT front-end, per row, beside :class:`FrameClock`: ``total`` samples
     taken since the reset, ``emitted`` frames, and ``pending`` = total - emitted * hop < n_fft samples held in the
     front-end state (they completed no frame yet, or later frames still overlap them).  After N samples a row has
@@ -78,64 +142,35 @@ class SampleClock:
         if int(batch) < 1 or int(n_fft) < 1 or int(hop) < 1 or int(hop) > int(n_fft):
             raise L.AvvadError("SampleClock needs batch >= 1 and 1 <= hop <= n_fft")
         self.n_fft, self.hop = int(n_fft), int(hop)
-        self.total = [0] * int(batch)
-        self.emitted = [0] * int(batch)
-        self.pending = [0] * int(batch)
-        self.ended = [False] * int(batch)
+        self._rows(batch)
 
-    def reset(self, rows=None):
-        for b in (range(len(self.total)) if rows is None else rows):
-            self.total[b] = self.emitted[b] = self.pending[b] = 0
-            self.ended[b] = False
+    def _going(self, N):
+        """frames a row that goes on has emitted after N samples"""
+        return max(0, (N - self.n_fft) // self.hop + 1)
 
-    def _plan(self, n, final):
-        B = len(self.total)
-        n = ops._ints(n)
-        if len(n) != B:
-            raise L.AvvadError("one sample count per row expected (%d), got %d" % (B, len(n)))
-        final = set(ops._ints(final))
-        if any(b < 0 or b >= B for b in final):
-            raise L.AvvadError("final rows must be in [0, %d)" % B)
-        frames, pad, state = [], [], []
-        for b, nb in enumerate(n):
-            if nb < 0:
-                raise L.AvvadError("row %d: negative sample count" % b)
-            if self.ended[b] and (nb > 0 or b in final):
-                raise L.AvvadError("row %d ended with a final call: reset it before it takes samples again" % b)
-            if self.ended[b]:                       # idles until its reset
-                frames.append(0)
-                pad.append(0)
-                state.append((self.total[b], self.emitted[b], self.pending[b], True))
-                continue
-            N = self.total[b] + nb
-            e = max(0, (N - self.n_fft) // self.hop + 1)
-            extra = 0
-            if b in final:
-                extra = max(ops.n_frames(N, self.n_fft, self.hop), 0) - e
-                if extra < 0 or extra > 1:          # cannot happen for the reference's framing; never emit a wrong count
-                    raise L.AvvadError("row %d: %d samples end %d frames away from the reference's count" % (b, N, extra))
-            frames.append(e - self.emitted[b] + extra)
-            pad.append(extra)
-            state.append((N, e + extra, max(N - (e + extra) * self.hop, 0), b in final))
-        return n, frames, pad, state
+    def _emitted(self, b, N, last):
+        if not last:
+            return max(0, (N - self.n_fft) // self.hop + 1)
+        e = max(ops.n_frames(N, self.n_fft, self.hop), 0)
+        if not 0 <= e - self._going(N) <= 1:        # cannot happen for the reference's framing; never emit a wrong count
+            raise L.AvvadError("row %d: %d samples end %d frames away from the reference's count" % (b, N, e - self._going(N)))
+        return e
 
-    def plan(self, n, final=()):
-        """Frames each row yields from ``n[b]`` more samples (rows in ``final`` end with them); raises
-        :class:`AvvadError` when a count is negative or a row that ended is fed again.  Changes nothing."""
-        return self._plan(n, final)[1]
+    def _held(self, N, e):
+        return max(N - e * self.hop, 0)
 
     def advance(self, n, final=()):
         """``plan`` and then consume: -> (frames per row, the pending counts that applied to THIS call, per row 1 where
         the last frame is the zero-padded one)."""
-        _, frames, pad, state = self._plan(n, final)
-        used = list(self.pending)
-        for b, (N, e, p, end) in enumerate(state):
-            self.total[b], self.emitted[b], self.pending[b] = N, e, p
-            self.ended[b] = self.ended[b] or end
+        _, _, used, was_ended, frames = self._advance(n, final)
+        pad = [0] * len(frames)
+        for b in (range(len(pad)) if self.ended != was_ended else ()):      # the rows that ended with this call
+            if not was_ended[b]:
+                pad[b] = self.emitted[b] - self._going(self.total[b])
         return frames, used, pad
 
 
-class RateClock:
+class RateClock(_RowClock):
     """Host-side bookkeeping of the streaming resampler (``ops.resample_stream``), per row, beside :class:`SampleClock`:
     ``total`` input samples taken since the reset, ``emitted`` output samples, and ``pending`` -- the inputs the next output
     still needs of those that came, at most ``H - 2`` of the ``H = 2 * half // up + 2`` the state holds.  With
@@ -150,15 +185,7 @@ class RateClock:
         if int(batch) < 1:
             raise L.AvvadError("RateClock needs batch >= 1")
         self.half = 10 * max(self.up, self.down)
-        self.total = [0] * int(batch)
-        self.emitted = [0] * int(batch)
-        self.pending = [0] * int(batch)
-        self.ended = [False] * int(batch)
-
-    def reset(self, rows=None):
-        for b in (range(len(self.total)) if rows is None else rows):
-            self.total[b] = self.emitted[b] = self.pending[b] = 0
-            self.ended[b] = False
+        self._rows(batch)
 
     def count(self, N):
         """outputs a row that goes on has emitted after N inputs"""
@@ -177,105 +204,57 @@ class RateClock:
         self.pending[row] = self._held(self.total[row], self.emitted[row])
         self.ended[row] = False
 
-    def _plan(self, n, final):
-        B = len(self.total)
-        n = ops._ints(n)
-        if len(n) != B:
-            raise L.AvvadError("one sample count per row expected (%d), got %d" % (B, len(n)))
-        final = set(ops._ints(final))
-        if any(b < 0 or b >= B for b in final):
-            raise L.AvvadError("final rows must be in [0, %d)" % B)
-        n_emit, state = [], []
-        for b, nb in enumerate(n):
-            if nb < 0:
-                raise L.AvvadError("row %d: negative sample count" % b)
-            if self.ended[b] and (nb > 0 or b in final):
-                raise L.AvvadError("row %d ended with a final call: reset it before it takes samples again" % b)
-            if self.ended[b]:                       # idles until its reset
-                n_emit.append(0)
-                state.append((self.total[b], self.emitted[b], self.pending[b], True))
-                continue
-            N = self.total[b] + nb
-            e = (N * self.up + self.down - 1) // self.down if b in final else self.count(N)
-            e = max(e, self.emitted[b])
-            n_emit.append(e - self.emitted[b])
-            state.append((N, e, self._held(N, e), b in final))
-        return n, n_emit, state
-
-    def plan(self, n, final=()):
-        """Samples each row emits from ``n[b]`` more inputs (rows in ``final`` end with them); raises :class:`AvvadError`
-        when a count is negative or a row that ended is fed again.  Changes nothing."""
-        return self._plan(n, final)[1]
+    def _emitted(self, b, N, last):
+        return max((N * self.up + self.down - 1) // self.down if last else self.count(N), self.emitted[b])
 
     def advance(self, n, final=()):
         """``plan`` and then consume: -> (inputs each row had behind it, outputs it had emitted, outputs of THIS call)."""
-        _, n_emit, state = self._plan(n, final)
-        before = (list(self.total), list(self.emitted))
-        for b, (N, e, p, end) in enumerate(state):
-            self.total[b], self.emitted[b], self.pending[b] = N, e, p
-            self.ended[b] = self.ended[b] or end
-        return before[0], before[1], n_emit
+        total, emitted, _, _, n_emit = self._advance(n, final)
+        return total, emitted, n_emit
 
 
-class OlaClock:
+class OlaClock(_RowClock):
     """Host-side bookkeeping of the streaming overlap-add (``ops.istft_stream``), per row, beside :class:`SampleClock`:
     ``emitted`` frames taken and ``written`` samples returned since the reset.  A row that goes on writes
     ``frames[b] * hop`` samples per call -- those no later frame can cover -- so ``written = emitted * hop``.  A row that
     ends with N input samples (``final_totals``) writes the ``N - written[b]`` that are left: a stream of N samples
     yields exactly N, as ``ops.resynth`` returns exactly L_b, and a row that never completes a frame yields N zeros at
     its end.  It must be ``reset`` before it takes frames again."""
+    _lists = ("emitted", "written")
+    _unit = "frame"
 
     def __init__(self, batch, n_fft=1024, hop=256):
         if int(batch) < 1 or int(n_fft) < 1 or int(hop) < 1 or int(hop) > int(n_fft):
             raise L.AvvadError("OlaClock needs batch >= 1 and 1 <= hop <= n_fft")
         self.n_fft, self.hop = int(n_fft), int(hop)
-        self.emitted = [0] * int(batch)
-        self.written = [0] * int(batch)
-        self.ended = [False] * int(batch)
+        self._rows(batch)
 
-    def reset(self, rows=None):
-        for b in (range(len(self.emitted)) if rows is None else rows):
-            self.emitted[b] = self.written[b] = 0
-            self.ended[b] = False
-
-    def _plan(self, frames, final_totals):
-        B = len(self.emitted)
-        frames = ops._ints(frames)
-        if len(frames) != B:
-            raise L.AvvadError("one frame count per row expected (%d), got %d" % (B, len(frames)))
+    def _final(self, final_totals, B):
         if final_totals is None:
-            final_totals = {}
-        elif not isinstance(final_totals, dict):
+            return {}
+        if not isinstance(final_totals, dict):
             if len(final_totals) != B:
                 raise L.AvvadError("final_totals must be {row: samples} or hold one entry (None: the row goes on) per row")
             final_totals = {b: n for b, n in enumerate(final_totals) if n is not None}
-        final_totals = {int(b): int(n) for b, n in final_totals.items()}
-        if any(b < 0 or b >= B for b in final_totals):
-            raise L.AvvadError("final rows must be in [0, %d)" % B)
-        n_out = []
-        for b, f in enumerate(frames):
-            if f < 0:
-                raise L.AvvadError("row %d: negative frame count" % b)
-            if self.ended[b] and (f > 0 or b in final_totals):
-                raise L.AvvadError("row %d ended with a final call: reset it before it takes frames again" % b)
-            if b in final_totals:
-                if final_totals[b] < self.written[b]:
-                    raise L.AvvadError("row %d: a stream of %d samples cannot end after %d were written"
-                                       % (b, final_totals[b], self.written[b]))
-                n_out.append(final_totals[b] - self.written[b])
-            else:
-                n_out.append(f * self.hop)
-        return frames, list(self.emitted), n_out, final_totals
+        return {int(b): int(n) for b, n in final_totals.items()}
+
+    def _plan(self, frames, final_totals):
+        frames, fin = self._checked(frames, final_totals)
+        for b, n in fin.items():
+            if n < self.written[b]:
+                raise L.AvvadError("row %d: a stream of %d samples cannot end after %d were written" % (b, n, self.written[b]))
+        return frames, [fin[b] - self.written[b] if b in fin else f * self.hop for b, f in enumerate(frames)], fin
 
     def plan(self, frames, final_totals=None):
         """-> (frames each row has behind it, samples each row writes) for a call with ``frames[b]`` more frames, rows in
         ``final_totals`` ({row: N input samples}, or a list with None for rows that go on) ending with it; raises
         :class:`AvvadError` when a count is negative or a row that ended is fed again.  Changes nothing."""
-        return self._plan(frames, final_totals)[1:3]
+        return list(self.emitted), self._plan(frames, final_totals)[1]
 
     def advance(self, frames, final_totals=None):
         """``plan`` and then consume: -> (n_before, n_out)."""
-        frames, before, n_out, fin = self._plan(frames, final_totals)
+        frames, n_out, fin = self._plan(frames, final_totals)
+        before = list(self.emitted)
         for b, f in enumerate(frames):
             self.emitted[b] += f
             self.written[b] += n_out[b]
@@ -284,12 +263,39 @@ class OlaClock:
 
 
 def _int_list(v, B, what, hi):
-    if v is None:
-        return [hi] * B
-    v = ops._ints(v)
-    if len(v) != B or any(x < 0 or x > hi for x in v):
-        raise L.AvvadError("%s must hold one value in [0, %d] per row (%d rows), got %s" % (what, hi, B, v))
-    return v
+    """``ops._ints``: one value in [0, hi] per row, None standing for hi"""
+    return ops._ints(v, B, hi, default=hi, what=what)
+
+
+class _Stage:
+    """One streaming stage of a session's waveform front-end: its host ``clock`` (None: the stage is not in the path) and,
+    once ``build`` ran, its table on the GPU (basis or taps), its ``state`` and the ``spare`` a call writes the new state
+    to before the two swap."""
+
+    def __init__(self, clock=None):
+        self.clock = clock
+        self.table = self.state = self.spare = None
+
+    @property
+    def built(self):
+        return self.state is not None
+
+    def build(self, table, state):
+        self.table, self.state, self.spare = table, state, torch.zeros_like(state)
+
+    def reset(self, rows, idx):
+        if self.clock is not None:
+            self.clock.reset(rows)
+        if self.state is not None:
+            self.state.index_fill_(0, idx, 0.0)
+
+    def swap(self):
+        self.state, self.spare = self.spare, self.state
+
+
+def _stage_attr(stage, field):
+    """a session attribute that lives in one of its stages: readable and assignable, as callers save and restore them"""
+    return property(lambda s: getattr(getattr(s, stage), field), lambda s, v: setattr(getattr(s, stage), field, v))
 
 
 class Session:
@@ -298,6 +304,12 @@ class Session:
     encoder; all zeros = start of utterance) and ``clock.skip`` (host list: remaining warm-up samples per row).  A step
     writes the new LSTM state into a spare pair of tensors and swaps, so read ``h`` / ``c`` from the session after each
     step, not from a reference taken earlier."""
+    # the waveform front-end of the spectrogram models: the STFT (step_wave), the overlap-add behind it (step_enhance) and
+    # the resampler in front of it (set_frontend(fs_in=...); no clock at 16 kHz).  The clocks are host bookkeeping and
+    # exist from the start; the GPU side is built by prepare_frontend on first use.
+    sample_clock, stft_state = _stage_attr("_stft", "clock"), _stage_attr("_stft", "state")
+    ola_clock, ola_state = _stage_attr("_ola", "clock"), _stage_attr("_ola", "state")
+    rate_clock, rs_state = _stage_attr("_rs", "clock"), _stage_attr("_rs", "state")
 
     def __init__(self, model, batch, samples_per_frame=256):
         from packages.models.Audio_Net import DeepVAD_audio
@@ -330,22 +342,19 @@ class Session:
         self.c = torch.zeros_like(self.h)
         self._spare = (torch.zeros_like(self.h), torch.zeros_like(self.h))   # a step writes here, then the pairs swap
         self.enc_state = self.clock = None
-        # the waveform front-end of the spectrogram models (step_wave), built on first use
-        # (sample_clock is host bookkeeping and exists from the start; the GPU side is built by prepare_frontend)
-        self.sample_clock = self.stft_state = self._stft_spare = self._basis = None
-        # the streaming resynthesis (step_enhance): overlap-add state, its spare and the inverse basis, built with the front-end
-        self.ola_clock = self.ola_state = self._ola_spare = self._inv_basis = None
         self._route = [None] * self.batch          # per row: "wave" / "enhance" once it has taken samples since its reset
         self._frontend = dict(stats=None, eps=1e-8, n_fft=1024, hop=256, fs_in=16000)
-        # the resampler in front of the STFT (set_frontend(fs_in=...)): its clock, state, spare and taps; None at 16 kHz
-        self.rate_clock = self.rs_state = self._rs_spare = self._rs_taps = None
-        if self.kind != "video" and self.enc is None:
-            self.sample_clock = SampleClock(self.batch, 1024, 256)
-            self.ola_clock = OlaClock(self.batch, 1024, 256)
+        self._stages(1024, 256, 1, 1, self.kind != "video" and self.enc is None)
         self.peak = torch.ones(self.batch, dtype=torch.float32, device=dev)
         if self.enc is not None:
             self.clock = FrameClock(self.batch, self.enc.receptive_field, samples_per_frame)
             self.enc_state = ops.wavenet_stream_state(self.enc, self.batch, dev)
+
+    def _stages(self, n_fft, hop, up, down, wave=True):
+        """fresh front-end stages (``wave`` False: a model that takes no waveform this way has none of the clocks)"""
+        self._stft = _Stage(SampleClock(self.batch, n_fft, hop) if wave else None)
+        self._ola = _Stage(OlaClock(self.batch, n_fft, hop) if wave else None)
+        self._rs = _Stage(RateClock(self.batch, up, down) if wave and up != down else None)
 
     def reset(self, rows=None):
         """Start a new utterance on ``rows`` (all when None)."""
@@ -359,18 +368,8 @@ class Session:
             self.enc_state.index_fill_(0, idx, 0.0)
             self.clock.reset(rows)
         self.peak.index_fill_(0, idx, 1.0)
-        if self.sample_clock is not None:
-            self.sample_clock.reset(rows)
-        if self.stft_state is not None:
-            self.stft_state.index_fill_(0, idx, 0.0)
-        if self.ola_clock is not None:
-            self.ola_clock.reset(rows)
-        if self.ola_state is not None:
-            self.ola_state.index_fill_(0, idx, 0.0)
-        if self.rate_clock is not None:
-            self.rate_clock.reset(rows)
-        if self.rs_state is not None:
-            self.rs_state.index_fill_(0, idx, 0.0)
+        for stage in (self._stft, self._ola, self._rs):
+            stage.reset(rows, idx)
         for r in rows:
             self._route[r] = None
 
@@ -393,12 +392,7 @@ class Session:
         up, down = ops.resample_ratio(fs_in, 16000)
         fs_in = int(fs_in)
         if (n_fft, hop) != (self.sample_clock.n_fft, self.sample_clock.hop) or fs_in != self._frontend["fs_in"]:
-            self.rs_state = self._rs_spare = self._rs_taps = None
-            self.rate_clock = RateClock(self.batch, up, down) if up != down else None
-            self.stft_state = self._stft_spare = self._basis = None
-            self.ola_state = self._ola_spare = self._inv_basis = None
-            self.sample_clock = SampleClock(self.batch, n_fft, hop)
-            self.ola_clock = OlaClock(self.batch, n_fft, hop)
+            self._stages(n_fft, hop, up, down)
             self._route = [None] * self.batch
         self._frontend = dict(stats=stats, eps=float(eps), n_fft=n_fft, hop=hop, fs_in=fs_in)
 
@@ -407,19 +401,13 @@ class Session:
         there yet (``step_wave`` does it on first use; a caller that restores a saved ``stft_state`` does it first).  For a
         model that predicts a mask over the bins (``step_enhance``) also the inverse basis, ``ola_state`` and its spare."""
         self._wave_check()
-        f = self._frontend
-        if self.stft_state is None:
-            self._basis = ops.stft_stream_basis(f["n_fft"], self.device)
-            self.stft_state = ops.stft_stream_state(self.batch, f["n_fft"], self.device)
-            self._stft_spare = torch.zeros_like(self.stft_state)
-        if self.rate_clock is not None and self.rs_state is None:
-            self._rs_taps = ops.resample_taps_on(self.rate_clock.up, self.rate_clock.down, self.device)
-            self.rs_state = ops.resample_stream_state(self.batch, self.rate_clock.up, self.rate_clock.down, self.device)
-            self._rs_spare = torch.zeros_like(self.rs_state)
-        if self.ola_state is None and self.linear.out_features == f["n_fft"] // 2 + 1:
-            self._inv_basis = ops.istft_stream_basis(f["n_fft"], self.device)
-            self.ola_state = ops.istft_stream_state(self.batch, f["n_fft"], self.device)
-            self._ola_spare = torch.zeros_like(self.ola_state)
+        B, n_fft, dev, rc = self.batch, self._frontend["n_fft"], self.device, self._rs.clock
+        if not self._stft.built:
+            self._stft.build(ops.stft_stream_basis(n_fft, dev), ops.stft_stream_state(B, n_fft, dev))
+        if rc is not None and not self._rs.built:
+            self._rs.build(ops.resample_taps_on(rc.up, rc.down, dev), ops.resample_stream_state(B, rc.up, rc.down, dev))
+        if not self._ola.built and self.linear.out_features == n_fft // 2 + 1:
+            self._ola.build(ops.istft_stream_basis(n_fft, dev), ops.istft_stream_state(B, n_fft, dev))
 
     def plan_wave(self, samples, final=()):
         """Frames each row yields from ``samples[b]`` more samples at ``fs_in`` (rows in ``final`` end with them): the
@@ -469,11 +457,12 @@ class Session:
             raise L.AvvadError("wave must be (%d, n) float32 samples, got %s %s" % (B, wave.dtype, tuple(wave.shape)))
         n = _int_list(samples, B, "samples", wave.shape[1])
         self.prepare_frontend()
+        rs, stft, ola = self._rs, self._stft, self._ola
         final = () if final is None else final
         n_in = n
-        if self.rate_clock is not None:             # the samples are at fs_in: the 16 kHz counts they resample to
-            n = self.rate_clock.plan(n_in, final)
-        frames = self.sample_clock.plan(n, final)
+        if rs.clock is not None:                    # the samples are at fs_in: the 16 kHz counts they resample to
+            n = rs.clock.plan(n_in, final)
+        frames = stft.clock.plan(n, final)
         tmax = max(frames)
         route = "enhance" if enhance else "wave"
         fin = set(ops._ints(final))
@@ -482,9 +471,9 @@ class Session:
             if self._route[b] not in (None, route):
                 raise L.AvvadError("row %d went through step_%s since its reset: a row stays with one of step_wave / "
                                    "step_enhance until its end" % (b, self._route[b]))
-        totals = {b: self.sample_clock.total[b] + n[b] for b in fin}
+        totals = {b: stft.clock.total[b] + n[b] for b in fin}
         if enhance:
-            self.ola_clock.plan(frames, totals)
+            ola.clock.plan(frames, totals)
         with torch.no_grad():
             vfeats = None
             if self.kind == "av":
@@ -498,14 +487,14 @@ class Session:
             mean = std = None
             if f["stats"] is not None:
                 mean, std = f["stats"].get("audio_mean", self.device), f["stats"].get("audio_std", self.device)
-            if self.rate_clock is not None:
-                wave, n = ops.resample_stream(wave, n_in, self.rate_clock, self.rs_state, self._rs_taps, final, self._rs_spare)
-                self.rs_state, self._rs_spare = self._rs_spare, self.rs_state
-            res = ops.stft_stream(wave, n, self.sample_clock, self.stft_state, self._basis, self.peak, mean, std, final,
-                                  self._stft_spare, eps=f["eps"],
-                                  norm_eps=f["stats"].eps if f["stats"] is not None else f["eps"], return_spec=enhance)
+            if rs.clock is not None:
+                wave, n = ops.resample_stream(wave, n_in, rs.clock, rs.state, rs.table, final, rs.spare)
+                rs.swap()
+            res = ops.stft_stream(wave, n, stft.clock, stft.state, stft.table, self.peak, mean, std, final, stft.spare,
+                                  eps=f["eps"], norm_eps=f["stats"].eps if f["stats"] is not None else f["eps"],
+                                  return_spec=enhance)
             x, frames = res[0], res[1]
-            self.stft_state, self._stft_spare = self._stft_spare, self.stft_state
+            stft.swap()
             for b in live:
                 self._route[b] = route
             if tmax == 0:
@@ -521,9 +510,9 @@ class Session:
                 return logits, frames
             if tmax == 0 and not fin:                   # no row has a frame or ends: nothing comes out, no state moves
                 return logits, frames, torch.zeros(B, 0, dtype=torch.float32, device=self.device), [0] * B
-            enhanced, n_out = ops.istft_stream(res[2], frames, self.ola_clock, self.ola_state, self._inv_basis,
-                                               logits if tmax else None, 3 if hard else 2, self.peak, totals, self._ola_spare)
-            self.ola_state, self._ola_spare = self._ola_spare, self.ola_state
+            enhanced, n_out = ops.istft_stream(res[2], frames, ola.clock, ola.state, ola.table, logits if tmax else None,
+                                               3 if hard else 2, self.peak, totals, ola.spare)
+            ola.swap()
             return logits, frames, enhanced, n_out
 
     def _audio_frames(self, audio, lengths, samples, video=None, with_video=False):
@@ -676,6 +665,24 @@ def _open_wave_chunked(model, wave, lengths, chunk_samples, stats, peak, eps, n_
     return c, w, lens, sess
 
 
+def _packets(lens, c, ends):
+    """The packets of ``c`` samples that feed rows of ``lens`` samples: yields (s0, samples per row, the rows of ``ends``
+    whose last sample the packet holds -- each once, in the first packet that reaches its end)."""
+    ended = set()
+    for s0 in range(0, max(max(lens), 1), c):
+        fin = [b for b in range(len(lens)) if ends[b] and b not in ended and s0 + c >= lens[b]]
+        ended.update(fin)
+        yield s0, [min(max(l - s0, 0), c) for l in lens], fin
+
+
+def _scatter(out, done, y, counts):
+    """row b's first ``counts[b]`` items of ``y`` go behind the ``done[b]`` it has in ``out``"""
+    for b, k in enumerate(counts):
+        if k > 0:
+            out[b, done[b]:done[b] + k] = y[b, :k]
+            done[b] += k
+
+
 def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=256, stats=None, peak=None, eps=1e-8,
                          n_fft=1024, hop=256, max_frames=None, fs_in=16000):
     """A spectrogram model (``DeepVAD_audio`` / concat ``DeepVAD_AV`` without the encoder, in ``eval()`` mode) scored
@@ -704,11 +711,8 @@ def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=25
         raise L.AvvadError("the AV model needs video (B, >= %d, H, W)" % T)
     bias = sess.linear.bias.detach()
     out = bias.expand(B, T, bias.numel()).clone()
-    done, ended = [0] * B, set()
-    for s0 in range(0, max(max(lens), 1), c):
-        n = [min(max(l - s0, 0), c) for l in lens]
-        fin = [b for b in range(B) if ends[b] and b not in ended and s0 + c >= lens[b]]
-        ended.update(fin)
+    done = [0] * B
+    for s0, n, fin in _packets(lens, c, ends):
         frames = sess.plan_wave(n, fin)
         tl = max(frames)
         v = None
@@ -719,11 +723,7 @@ def forward_wave_chunked(model, wave, lengths=None, video=None, chunk_samples=25
                 if f > 0:
                     v[b, :f] = video[b, done[b]:done[b] + f]
         y, frames = sess.step_wave(w[:, s0:s0 + c].contiguous(), n, v, fin)
-        for b, f in enumerate(frames):
-            f = min(f, total[b] - done[b])
-            if f > 0:
-                out[b, done[b]:done[b] + f] = y[b, :f]
-                done[b] += f
+        _scatter(out, done, y, [min(f, total[b] - done[b]) for b, f in enumerate(frames)])
     return out
 
 
@@ -739,14 +739,8 @@ def enhance_wave_chunked(model, wave, lengths=None, chunk_samples=256, stats=Non
     B, Lmax = w.shape
     rc = sess.rate_clock
     out = w.new_zeros(B, Lmax if rc is None else ops.resample_length(Lmax, rc.up, rc.down))
-    done, ended = [0] * B, set()
-    for s0 in range(0, max(max(lens), 1), c):
-        n = [min(max(l - s0, 0), c) for l in lens]
-        fin = [b for b in range(B) if b not in ended and s0 + c >= lens[b]]
-        ended.update(fin)
+    done = [0] * B
+    for s0, n, fin in _packets(lens, c, [True] * B):
         _, _, y, n_out = sess.step_enhance(w[:, s0:s0 + c].contiguous(), n, None, fin, hard)
-        for b, k in enumerate(n_out):
-            if k:
-                out[b, done[b]:done[b] + k] = y[b, :k]
-                done[b] += k
+        _scatter(out, done, y, n_out)
     return out
