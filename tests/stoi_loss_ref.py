@@ -36,6 +36,15 @@ NCOL = 2 * (R.F1 - R.F0)                      # 424 interleaved (re, im) columns
 
 MEASURED_STANDIN_GRAD = 2.9e-6               # largest stand-in error over the gradient cases: 2.88e-6 (STOI of k16_11270), rounded up
 GPU_GRAD_BOUND = 8 * MEASURED_STANDIN_GRAD
+# The cases past one trip (stoi_ref.LONG_CASE_NAMES) have a constant of their own, by the same rule: the two 16 kHz rows of
+# more than 1100 frames exceed the figure above (tests/test_stoi_long_cpu.py measures and prints every row).
+MEASURED_STANDIN_GRAD_LONG = 3.3e-6          # largest stand-in error over the long cases: 3.26e-6 (STOI of k16_345004_both_sides), rounded up
+GPU_GRAD_BOUND_LONG = 8 * MEASURED_STANDIN_GRAD_LONG
+
+
+def grad_bound(name):
+    """the GPU's bound on a case's gradient error"""
+    return GPU_GRAD_BOUND_LONG if name in R.LONG_CASE_NAMES else GPU_GRAD_BOUND
 
 
 # ---------------------------------------------------------------------------------------------- constants of the chain
@@ -193,6 +202,10 @@ def clip_stats(X, Y):
 
 # ---------------------------------------------------------------------------------------------- the hand-written chain
 MUTANTS = ("no_clip_mask", "alpha_constant", "mean_kept", "segment_left_out", "resampler_shifted", "dropped_not_skipped")
+# invert_kept answers -1 for frames >= 256 (its first workgroup alone ran): those frames lose their gradient in the
+# overlap-add adjoint.  Only a row of more than 256 frames can tell.
+LONG_MUTANTS = ("positions_of_one_block",)
+INVERT_BLOCK = 256
 
 
 def _chain32(A, Bm):
@@ -202,7 +215,7 @@ def _chain32(A, Bm):
 
 def manual_grad(x, y, fs, which, f32=False, mutant=None):
     """the gradient of -d in y by the closed forms and hand-written adjoints; ``f32``: the float32 stand-in"""
-    assert mutant is None or mutant in MUTANTS
+    assert mutant is None or mutant in MUTANTS or mutant in LONG_MUTANTS
     r32 = (lambda v: v.astype(np.float32).astype(np.float64)) if f32 else (lambda v: v)
     y = np.asarray(y, dtype=np.float64)
     mask, X, n10 = clean_side(x, fs, f32)
@@ -240,6 +253,8 @@ def manual_grad(x, y, fs, which, f32=False, mutant=None):
     np.add.at(dsil, st2[:, None] + k[None, :], dfr)
     dkept = dsil[np.arange(kept.size)[:, None] * R.HOP + k[None, :]] * w[None, :]
     dy10 = np.zeros(n10)
+    if mutant == "positions_of_one_block":
+        dkept[kept >= INVERT_BLOCK * R.HOP] = 0.0
     target = starts[:kept.size] if mutant == "dropped_not_skipped" else kept
     np.add.at(dy10, target[:, None] + k[None, :], dkept)
     if fs == 16000:
@@ -282,10 +297,30 @@ def has_segment(name):
     return R.reference(name)["segments"] > 0
 
 
-def grad_cases(which):
+def grad_cases(which, names=R.CASE_NAMES):
     """the cases whose gradient is compared: every case with a segment for ESTOI; for STOI those whose clip gap allows it"""
-    out = [n for n in R.CASE_NAMES if has_segment(n)]
+    out = [n for n in names if has_segment(n)]
     return [n for n in out if case_clip(n)[0] >= MIN_CLIP_GAP] if which == 1 else out
+
+
+def check_gradient(name, which, g):
+    """What the GPU tests assert of a case's gradient g (L,) of -d: its shape, finite, exact zeros without a segment, and the
+    error against float64 within grad_bound(name) wherever the gradient is compared.  -> the error, or None where it is not;
+    the CPU tests hand it a mutant's gradient to show that it can fail."""
+    g64 = reference(name, which)[1]
+    g = np.asarray(g)
+    key = "stoi" if which == 1 else "estoi"
+    assert g.shape == g64.shape and np.isfinite(g).all()
+    if not has_segment(name):
+        assert not g.any()
+        return None
+    if name not in grad_cases(which, (name,)):
+        print("%-22s %-5s gradient not compared: clip gap %.3g below %.3g" % (name, key, case_clip(name)[0], MIN_CLIP_GAP))
+        return None
+    e = err(g, g64)
+    print("%-22s %-5s gradient error %.3g (bound %.3g), clipped %d of %d" % ((name, key, e, grad_bound(name)) + case_clip(name)[1:]))
+    assert e <= grad_bound(name)
+    return e
 
 
 # ---------------------------------------------------------------------------------------------- the chain from the logits

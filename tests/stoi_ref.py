@@ -10,6 +10,11 @@ The bound.  MEASURED_STANDIN is the float32 stand-in's largest |d - d_float64| o
 on the CPU by tests/test_stoi_cpu.py, which prints the figure and holds the stand-in to GPU_BOUND / 8 = MEASURED_STANDIN
 rounded up to two digits.  GPU_BOUND is 8 times that: the margin this project gives a kernel over its stand-in.  The
 yardstick is always the float64 reference.
+
+Past one trip.  ``LONG_CASE_NAMES`` is a second table of inputs, of more than 256 and more than 1024 frames, for the loops
+and grids of csrc/stoi.hip that the 15 inputs above leave at one trip; ``LONG_MUTANTS`` restates how a kept-frame pass goes
+wrong there.  tests/test_stoi_long_cpu.py holds their conditions and measures the stand-in over them (it stays within
+MEASURED_STANDIN, so they keep GPU_BOUND); ``check_scores`` is what every GPU test asserts of a case's result.
 """
 import functools
 import os
@@ -31,6 +36,7 @@ EDGES = ((7, 9), (9, 11), (11, 14), (14, 17), (17, 22), (22, 27), (27, 34), (34,
 MEASURED_STANDIN = 3.0e-8             # largest |stand-in - float64| over CASE_NAMES: 2.97e-8 (ESTOI of k16_9218), rounded up
 GPU_BOUND = 8 * MEASURED_STANDIN
 MIN_MARGIN_DB = 0.01
+KEEP_TRIP = 1024                      # frames that keep_frames' one workgroup of 1024 threads takes per loop trip
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -83,11 +89,18 @@ def energies(x, periodic=False, take_last=False):
     return 20.0 * np.log10(np.linalg.norm(f, axis=1) + EPS)
 
 
-def keep_mask(x, dyn=DYN_RANGE, **kw):
+def keep_mask(x, dyn=DYN_RANGE, trip=None, **kw):
+    """``trip`` (the mutants of LONG_MUTANTS): a kept-frame pass that goes wrong behind its first KEEP_TRIP frames"""
     e = energies(x, **kw)
     if e.size == 0:
         return np.zeros(0, dtype=bool)
-    return (np.max(e) - dyn - e) < 0
+    top = np.max(e[:KEEP_TRIP]) if trip == "max_of_first_trip" else np.max(e)
+    mask = (top - dyn - e) < 0
+    if trip == "frames_of_one_trip":
+        mask[KEEP_TRIP:] = False
+    if trip == "scan_not_carried":                          # the last trip's frames from position 0, the count its own
+        mask[:(e.size - 1) // KEEP_TRIP * KEEP_TRIP] = False
+    return mask
 
 
 def margin_10k(x):
@@ -113,10 +126,10 @@ def overlap_add(fr):
     return out
 
 
-def remove_silent(x, y, dyn=DYN_RANGE, periodic=False, take_last=False, decide_from_y=False, f32=False):
+def remove_silent(x, y, dyn=DYN_RANGE, periodic=False, take_last=False, decide_from_y=False, f32=False, trip=None):
     """-> x_sil, y_sil, frames, kept"""
     w = window(periodic)
-    mask = keep_mask(y if decide_from_y else x, dyn, periodic=periodic, take_last=take_last)
+    mask = keep_mask(y if decide_from_y else x, dyn, trip, periodic=periodic, take_last=take_last)
     xs = overlap_add(frames_of(x, w, take_last)[mask])
     ys = overlap_add(frames_of(y, w, take_last)[mask])
     if f32:
@@ -211,10 +224,16 @@ MUTANTS = {
     "columns_before_rows": dict(columns_first=True),
     "decision_from_y": dict(decide_from_y=True),
 }
+# what a kept-frame pass does when it goes wrong past one trip of KEEP_TRIP frames; only a row of more frames can tell
+LONG_MUTANTS = {
+    "max_of_first_trip": dict(trip="max_of_first_trip"),      # the keep threshold from the maximum over frames 0 .. 1023
+    "frames_of_one_trip": dict(trip="frames_of_one_trip"),    # frames >= 1024 are never kept
+    "scan_not_carried": dict(trip="scan_not_carried"),        # the second trip's list starts at position 0 again
+}
 
 
 def score(x, y, fs, f32=False, dyn=DYN_RANGE, take_last=False, periodic=False, edges=EDGES, clip=True, n_seg=N_SEG,
-          columns_first=False, decide_from_y=False):
+          columns_first=False, decide_from_y=False, trip=None):
     """-> dict(stoi, estoi, frames, kept, segments) of the processed y against the clean x (float32 samples at ``fs``)"""
     if fs not in (16000, 10000):
         raise ValueError("fs must be 16000 or 10000")
@@ -223,7 +242,7 @@ def score(x, y, fs, f32=False, dyn=DYN_RANGE, take_last=False, periodic=False, e
         raise ValueError("x and y must be 1-D and of one length")
     if fs == 16000:
         x, y = resample(x, f32), resample(y, f32)
-    xs, ys, n_frames, kept = remove_silent(x, y, dyn, periodic, take_last, decide_from_y, f32)
+    xs, ys, n_frames, kept = remove_silent(x, y, dyn, periodic, take_last, decide_from_y, f32, trip)
     X = band_spectra(xs, edges, periodic, take_last, f32)
     Y = band_spectra(ys, edges, periodic, take_last, f32)
     M = X.shape[1]
@@ -261,6 +280,29 @@ def speech_pair(seed, n, fs, snr_db, off=0.5):
     return x.astype(np.float32), (x + noise).astype(np.float32)
 
 
+def loud_tail_pair(seed, n, fs, snr_db, off, blocks):
+    """``speech_pair`` at 10 kHz under a piecewise gain, the same for x and y: the last fifth times 2, so the loudest frame
+    lies there, and 60 ms blocks near the sample offsets ``blocks`` (each moved on to the first place whose frames all lie
+    within 10 dB of the first part's loudest) brought to the level halfway between the keep threshold and the threshold
+    that the maximum over frames 0 .. KEEP_TRIP - 1 alone would give.  The true rule drops the blocks; the wrong one keeps
+    them."""
+    assert fs == FS
+    x, y = (v.astype(np.float64) for v in speech_pair(seed, n, fs, snr_db, off))
+    gain = np.ones(n)
+    gain[n - n // 5:] = 2.0
+    e = energies(x * gain)
+    first, top = np.max(e[:KEEP_TRIP]), np.max(e)
+    level = top - DYN_RANGE - 0.5 * (top - first)
+    for s0 in blocks:
+        f0 = s0 // HOP
+        while np.min(e[f0 - 2:f0 + 7]) < first - 10.0:
+            f0 += 1
+        assert f0 + 7 < KEEP_TRIP
+        # frames f0, f0 + 1, f0 + 2 lie inside samples 128 f0 .. 128 f0 + 599
+        gain[f0 * HOP:f0 * HOP + 600] *= 10.0 ** ((level - np.mean(e[f0:f0 + 3])) / 20.0)
+    return (x * gain).astype(np.float32), (y * gain).astype(np.float32)
+
+
 def committed_pair():
     """the committed 48100-sample utterance: clean, and babble at -5 dB; 16 kHz"""
     load = lambda name: np.load(os.path.join(GOLDEN, name))["samples"].astype(np.float32) / 32768.0   # noqa: E731
@@ -289,14 +331,33 @@ _SPECS = {
 }
 CASE_NAMES = tuple(_SPECS) + ("committed",)
 
+# The cases past one trip, in a table of their own (MEASURED_STANDIN is measured over CASE_NAMES): more than 256 frames
+# (invert_kept's second workgroup), more than KEEP_TRIP frames (keep_frames' second trip; an evaluation utterance of 14 s or
+# more), with frames dropped on both sides of frame 1024, at both rates, and one at -5 dB.
+_LONG_SPECS = {
+    "k10_60000_mid": (10000, 60000, 20.0, 0.3, 73),
+    "k10_141100": (10000, 141100, 20.0, 0.15, 62),
+    "k10_211650_both_sides": (10000, 211650, 20.0, 0.45, 61),
+    "k16_230003": (16000, 230003, 20.0, 0.15, 63),
+    "k16_345004_both_sides": (16000, 345004, 20.0, 0.30, 63),
+    "k10_166700_noisy": (10000, 166700, -5.0, 0.10, 52),
+}
+# name -> speech_pair's arguments and the sample offsets of loud_tail_pair's blocks
+_LOUD_TAIL = {"k10_170000_loud_tail": (10000, 170000, 20.0, 0.15, 61, (20000, 55000, 90000, 120000))}
+LOUD_TAIL_CASE = "k10_170000_loud_tail"
+LONG_CASE_NAMES = tuple(_LONG_SPECS) + tuple(_LOUD_TAIL)
+
 
 @functools.lru_cache(maxsize=None)
 def case(name):
     """-> (fs, x, y) float32, read-only"""
     if name == "committed":
         fs, (x, y) = 16000, committed_pair()
+    elif name in _LOUD_TAIL:
+        fs, n, snr, off, seed, blocks = _LOUD_TAIL[name]
+        x, y = loud_tail_pair(seed, n, fs, snr, off, blocks)
     else:
-        fs, n, snr, off, seed = _SPECS[name]
+        fs, n, snr, off, seed = _SPECS[name] if name in _SPECS else _LONG_SPECS[name]
         x, y = speech_pair(seed, n, fs, snr, off)
     x.setflags(write=False), y.setflags(write=False)
     return fs, x, y
@@ -313,3 +374,31 @@ def reference(name):
 def case_margin(name):
     fs, x, _ = case(name)
     return margin(x, fs)
+
+
+# ---------------------------------------------------------------------------------------------- the checks of a result
+# What the GPU tests assert of ``d`` (STOI, ESTOI as floats) and ``info`` (frames, kept, segments as ints) of a case; the CPU
+# tests hand the same functions a mutant's result to show that they can fail.
+def check_info(name, info):
+    ref = reference(name)
+    assert case_margin(name) >= MIN_MARGIN_DB
+    assert [int(v) for v in info] == [ref["frames"], ref["kept"], ref["segments"]]
+
+
+def score_error(name, d):
+    ref = reference(name)
+    return max(abs(float(d[0]) - ref["stoi"]), abs(float(d[1]) - ref["estoi"]))
+
+
+def check_d(name, d):
+    assert score_error(name, d) <= GPU_BOUND
+
+
+def check_scores(name, d, info, label=""):
+    """-> |d - float64|, after printing it"""
+    err = score_error(name, d)
+    print("%s%-22s info %s  stoi %.9f estoi %.9f  |d - float64| = %.3g (bound %.3g)"
+          % (label, name, [int(v) for v in info], float(d[0]), float(d[1]), err, GPU_BOUND))
+    check_info(name, info)
+    check_d(name, d)
+    return err

@@ -1,6 +1,7 @@
 """GPU tests of STOI / ESTOI (csrc/stoi.hip, ops.stoi) against the float64 restatement tests/stoi_ref.py on the shared
 inputs of that module: the smallest shapes that can still go wrong (one segment, none, every L mod 8 of the resampler, a
-ragged batch with a row shorter than a frame, the committed 48100-sample pair).
+ragged batch with a row shorter than a frame, the committed 48100-sample pair).  These stop at 233 frames and 5 rows;
+tests/test_stoi_long_gpu.py carries the same checks past 256 and 1024 frames and past 64 rows.
 
 ``info`` (frames, kept, segments) must equal the reference exactly -- every input has a margin of at least 0.01 dB, which
 the test asserts of the reference alone -- and ``d`` must lie within stoi_ref.GPU_BOUND = 8 x the float32 stand-in's worst
@@ -44,14 +45,8 @@ def _alone(name):
 
 
 def _check(name, d, info, label=""):
-    ref = R.reference(name)
-    got = [float(v) for v in d.tolist()]
-    err = max(abs(got[0] - ref["stoi"]), abs(got[1] - ref["estoi"]))
-    print("%s%-22s info %s  stoi %.9f estoi %.9f  |d - float64| = %.3g (bound %.3g)"
-          % (label, name, info.tolist(), got[0], got[1], err, R.GPU_BOUND))
-    assert R.case_margin(name) >= R.MIN_MARGIN_DB
-    assert info.tolist() == [ref["frames"], ref["kept"], ref["segments"]]
-    assert err <= R.GPU_BOUND
+    """margin, info exactly, |d - float64| <= GPU_BOUND: stoi_ref's checks, shared with the cases past one trip"""
+    return R.check_scores(name, d.tolist(), info.tolist(), label)
 
 
 @pytest.mark.parametrize("name", R.CASE_NAMES)
