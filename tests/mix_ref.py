@@ -21,6 +21,10 @@ Bounds of ``check`` -- each follows from the arithmetic, not from a run:
   SNR       10 log10(sum s^2 / sum noise^2) within 1e-5 dB of the request (g's rounding moves it by at most
             20 log10(1 + 2^-24) = 5.2e-7 dB, the products' roundings average out below that).
   peak      == max |noisy| of the returned row, bit for bit; zeros from len_b to L in noisy and noise.
+
+Cases: "ragged" (the 12 rows of ROWS), "wide" (B = 33) and "wide70" (B = 70: mix_gain takes one thread per row in
+workgroups of 64, so rows 64 to 69 -- ROWS[4..9], none degenerate -- are the second workgroup's, which nothing below
+B = 65 launches).  The mutant "gain_past_64_rows" is that second workgroup missing; only "wide70" can see it.
 """
 import functools
 
@@ -107,6 +111,17 @@ def wide_case():
     return make_case(rows, clips())
 
 
+@functools.lru_cache(maxsize=None)
+def wide70_case():
+    """B = 70: as wide_case, past the 64 rows of one mix_gain workgroup; rows 64 to 69 are ROWS[4..9]"""
+    snrs = (-20.0, 0.0, 7.5, 40.0)
+    rows = [ROWS[i % len(ROWS)][:3] + (snrs[i % 4], ROWS[i % len(ROWS)][4]) for i in range(70)]
+    return make_case(rows, clips())
+
+
+NAMED = {"ragged": ragged_case, "wide": wide_case, "wide70": wide70_case}
+
+
 def rows_of(case, rows):
     """the given rows of a case as a case of its own (the same pitch)"""
     sub = dict(case)
@@ -123,7 +138,7 @@ def single_row(case, b):
 
 @functools.lru_cache(maxsize=None)
 def _reference_of(name):
-    return reference({"ragged": ragged_case, "wide": wide_case}[name]())
+    return reference(NAMED[name]())
 
 
 def check(impl, case, ref=None):
@@ -168,18 +183,19 @@ def check(impl, case, ref=None):
 
 
 def check_named(impl, name):
-    """``check`` on the shared case ``name`` ("ragged", "wide") with its reference computed once"""
-    return check(impl, {"ragged": ragged_case, "wide": wide_case}[name](), _reference_of(name))
+    """``check`` on the shared case ``name`` ("ragged", "wide", "wide70") with its reference computed once"""
+    return check(impl, NAMED[name](), _reference_of(name))
 
 
 MUTANTS = ("no_wrap", "start_ignored", "en_whole_clip", "energies_over_pitch", "snr_over_20", "gain_on_speech",
            "tail_not_zeroed", "noise_without_gain", "gain_through_float16")
+LOOP_MUTANTS = ("gain_past_64_rows",)      # rows b >= 64 get g = 0, energies 0 and the speech passed through: "wide70" alone sees it
 
 
 def standin(case, mutant=None):
     """A float32 numpy implementation of the semantics (float64 energies, one rounded product, one rounded sum); with
-    ``mutant`` one of MUTANTS, that mistake built in."""
-    assert mutant is None or mutant in MUTANTS
+    ``mutant`` one of MUTANTS or LOOP_MUTANTS, that mistake built in."""
+    assert mutant is None or mutant in MUTANTS + LOOP_MUTANTS
     B, L = case["clean"].shape
     out = {"noisy": np.zeros((B, L), np.float32), "noise": np.zeros((B, L), np.float32), "gain": np.zeros(B, np.float32),
            "energies": np.zeros((B, 2), np.float64), "peak": np.zeros(B, np.float32)}
@@ -196,6 +212,8 @@ def standin(case, mutant=None):
         es = float(np.sum(es_src.astype(np.float64) ** 2))
         en = float(np.sum(en_src.astype(np.float64) ** 2))
         ratio = 10.0 ** (case["snr_db"][b] / (20.0 if mutant == "snr_over_20" else 10.0))
+        if mutant == "gain_past_64_rows" and b >= 64:
+            es = en = 0.0
         g = np.float32(np.sqrt(es / (en * ratio))) if n > 0 and es > 0 and en > 0 else np.float32(0)
         if mutant == "gain_through_float16":
             g = np.float32(np.float16(g))

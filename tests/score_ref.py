@@ -7,12 +7,17 @@
   gram_ratios(..., chunk)                the closed form in the six inner products, each summed the way the kernel sums:
                                          per chunk 256 lanes striding over it, the lanes added, the chunks ascending
   confusion                              tp, tn, fp, fn as integers
+  draw / many_chunk_lengths              the signals the CPU and GPU tests share: a draw whose every ratio lies in [-10, 60] dB,
+                                         and the five row lengths of 8 to 17 chunks at which the finishing kernel's unrolled
+                                         sum of a row's partials (add_ascending<8>) runs its body, body + remainder
 
 pinned by tests/golden/scores.npz (tools/gen_golden.py scores: the reference's own functions on the same inputs).
 A plain module: no fixtures."""
 import numpy as np
 
 LANES = 256
+GAINS = (1.0, 0.1, 1e-3)
+ART_DB = (0.0, 20.0, 40.0)
 
 
 def _f64(*xs):
@@ -91,3 +96,46 @@ def mix(rng, L, g, art_db, dtype=np.float32):
     n = rng.standard_normal(L)
     e = rng.standard_normal(L) * 10.0 ** (-art_db / 20.0)
     return (0.7 * s + g * n + e).astype(dtype), s.astype(dtype), n.astype(dtype)
+
+
+_DRAWN = {}
+
+
+def draw(L, k):
+    """(s_hat, s, n, ratios, alphas) of length L with the k-th (gain, artefact) pair: float32 signals s_hat = 0.7 s + g n +
+    e and their float64 reference, drawn (next seed on a miss, judged by the REFERENCE alone) so that every ratio lies in
+    [-10, 60] dB and the condition number of both projections is below 1e3; computed once per (L, k) and shared."""
+    if (L, k) not in _DRAWN:
+        g, art = GAINS[k % 3], ART_DB[(k // 3) % 3]
+        for seed in range(100 * k, 100 * k + 100):
+            e, s, n = mix(np.random.default_rng([L, seed]), L, g, art)
+            r = np.array(energy_ratios(e, s, n))
+            e64, s64, n64 = (x.astype(np.float64) for x in (e, s, n))
+            cond = max(np.abs(e64 * s64).sum() / abs(np.dot(e64, s64)), np.abs(e64 * n64).sum() / abs(np.dot(e64, n64)))
+            if np.all((r >= -10.0) & (r <= 60.0)) and cond < 1e3:
+                break
+        else:
+            raise AssertionError("no draw of length %d with every ratio in [-10, 60] dB" % L)
+        for x in (e, s, n):
+            x.setflags(write=False)
+        _DRAWN[(L, k)] = (e, s, n, r, np.array(alphas(e, s, n)), seed - 100 * k)
+    return _DRAWN[(L, k)][:5]
+
+
+def draw_misses(L, k):
+    """how many seeds ``draw(L, k)`` passed over"""
+    draw(L, k)
+    return _DRAWN[(L, k)][5]
+
+
+def many_chunk_lengths(chunk):
+    """rows of 8 and 16 chunks (add_ascending<8>: one and two trips of the unrolled body, no remainder), of 9 chunks (body
+    + a remainder chunk of one sample) and of 10 and 18 chunks (body + two remainder chunks, the last of 5 and 3 samples)"""
+    return [8 * chunk, 8 * chunk + 1, 9 * chunk + 5, 16 * chunk, 17 * chunk + 3]
+
+
+def mixture_of(s, n):
+    """(x, n') for third_mode 2: the float32 mixture x = s + n as a file holds it, and the noise the kernel forms from it,
+    float64(x) - float64(s)"""
+    x = (s + n).astype(np.float32)
+    return x, x.astype(np.float64) - s.astype(np.float64)

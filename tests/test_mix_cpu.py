@@ -1,7 +1,8 @@
 """The SNR mix (csrc/mix.hip), the part that needs no GPU: the declared / bound / exported symbols, the chunk constant and
 the workspace query, the refusals of the C ABI with never-dereferenced pointers, the host logic (``NoiseBank``, the
 seeded draws, the argument errors of ``train_main`` and ``check_objective``), and the assertions of tests/mix_ref.py
-themselves: a float32 numpy stand-in passes them and each of nine built-in mistakes is rejected."""
+themselves: a float32 numpy stand-in passes them and each of nine built-in mistakes is rejected; the 70-row case, and the
+mistake of a gain kernel that stops after its first 64 rows, which that case alone rejects."""
 import ctypes as C
 import os
 import re
@@ -159,6 +160,29 @@ def test_float32_standin_passes_the_assertions(name):
     for b in mix_ref.DEGENERATE:
         assert got["gain"][b] == 0.0
     assert (got["gain"][[b for b in range(12) if b not in mix_ref.DEGENERATE]] > 0).all()
+
+
+def test_wide70_puts_live_rows_behind_the_first_64():
+    case = mix_ref.wide70_case()
+    assert case["clean"].shape[0] == len(case["lengths"]) == 70 and case["L"] > max(case["lengths"])
+    assert [case["lengths"][b] for b in range(64, 70)] == [r[0] for r in mix_ref.ROWS[4:10]]
+    assert [(case["clip"][b], case["start"][b]) for b in range(64, 70)] == [r[1:3] for r in mix_ref.ROWS[4:10]]
+    assert not any(b % len(mix_ref.ROWS) in mix_ref.DEGENERATE for b in range(64, 70))
+    assert {case["snr_db"][b] for b in range(64, 70)} == {-20.0, 0.0, 7.5, 40.0}
+    got = mix_ref.check_named(mix_ref.standin, "wide70")
+    for b in range(70):
+        assert (got["gain"][b] == 0.0) == (b % len(mix_ref.ROWS) in mix_ref.DEGENERATE), b
+    assert (got["energies"][64:] > 0).all()
+
+
+@pytest.mark.parametrize("mutant", mix_ref.LOOP_MUTANTS)
+def test_the_loop_mutant_is_rejected_on_wide70_alone(mutant):
+    broken = lambda case: mix_ref.standin(case, mutant)      # noqa: E731
+    with pytest.raises(AssertionError):
+        mix_ref.check_named(broken, "wide70")
+    for name in ("ragged", "wide"):                          # at most 33 rows: the old cases could not see it
+        got, want = mix_ref.check_named(broken, name), mix_ref.standin(mix_ref.NAMED[name]())
+        assert all(np.array_equal(got[k], want[k]) for k in want), name
 
 
 def test_a_row_alone_is_a_case_of_its_own():

@@ -1,7 +1,8 @@
 """The SNR mix on the GPU (csrc/mix.hip through ``ops.mix``) against the float64 reference and the bounds of
 tests/mix_ref.py: a ragged batch whose row and clip lengths reach every branch of the circular read (rows of 0, 1, 255,
 4095, 4096, 4097 and 3 * 4096 + 17 samples; clips of 1, 255, 4096, 5000 samples, one as long as its row, a 300-sample
-clip under a 9000-sample row), SNRs of -20, 0, 7.5 and 40 dB, B = 1, 12 and 33, every base pointer 4 bytes off a 16-byte
+clip under a 9000-sample row), SNRs of -20, 0, 7.5 and 40 dB, B = 1, 12, 33 and 70 (``mix_gain`` takes one thread per
+row in workgroups of 64: the 70-row case is the one that launches its second workgroup), every base pointer 4 bytes off a 16-byte
 boundary, NaN behind every row's length, degenerate rows; equal bits from run to run, for a row alone and under a CU cap;
 then the chain (``mix_step`` on the committed clean utterance) and two short trainings on mixtures made in the step."""
 import os
@@ -98,6 +99,30 @@ def test_ragged_batch_meets_the_bounds(name):
         degenerate = (b % len(mix_ref.ROWS)) in mix_ref.DEGENERATE
         assert (got["gain"][b] == 0.0) == degenerate
     print("%s: gains %s" % (name, got["gain"][:12]))
+
+
+def test_seventy_rows_reach_the_second_gain_workgroup(lib_options):
+    """B = 70 ("wide70"): the bounds with 4-byte-off pointers and NaN tails; a zero gain exactly on the degenerate rows;
+    two runs bit-equal; rows 63, 64 and 69 alone equal their batch rows; equal bits under a cap of 8 CUs."""
+    from avvad import _lib as L
+    case = mix_ref.wide70_case()
+    got = mix_ref.check_named(_impl, "wide70")
+    assert len(case["lengths"]) == 70
+    for b in range(70):
+        assert (got["gain"][b] == 0.0) == ((b % len(mix_ref.ROWS)) in mix_ref.DEGENERATE), b
+    print("wide70: gains of rows 60 .. 69 %s" % got["gain"][60:])
+    first, second = _all_bits(case), _all_bits(case)
+    for a, b in zip(first, second):
+        assert torch.equal(a, b)
+    for b in (63, 64, 69):
+        for whole, one in zip(first, _all_bits(mix_ref.single_row(case, b))):
+            assert torch.equal(whole[b:b + 1], one), b
+    default = L.get_option("max_cus")
+    lib_options("max_cus", 8)
+    capped = _all_bits(case)
+    lib_options("max_cus", default)
+    for a, b in zip(first, capped):
+        assert torch.equal(a, b)
 
 
 def test_plain_call_returns_new_tensors():

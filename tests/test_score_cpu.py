@@ -2,7 +2,10 @@
 ``energy_ratios`` / ``si_sdr_components`` / ``f1_loss`` produced (tests/golden/scores.npz), and the check the GPU tests'
 tolerance rests on -- the closed form in six chunk-summed inner products against the planes-and-norms form, to 1e-6 dB
 over lengths 255 .. 70 001, artefact levels -5 .. 80 dB and noise gains 1 .. 1e-3.  Host-side pieces that need no GPU:
-``f1_from_counts``, the chunk constant and the workspace query, the refusals of the C ABI."""
+``f1_from_counts``, the chunk constant and the workspace query, the refusals of the C ABI.  And the twins of the GPU
+tests past 8 chunks and 64 rows: the five rows of 8 to 17 chunks draw on their first seed, and cutting any of them to the
+chunks a finish would keep if it stopped after (or skipped) the unrolled body of its sum moves every ratio of the float64
+reference by over 100 tolerances; the confusion shapes hold the value counts their names promise."""
 import ctypes as C
 import os
 import re
@@ -112,3 +115,44 @@ def test_refusals_need_no_gpu():
         ops.score_state(1, "cpu")
     with pytest.raises(L.AvvadError, match="GPU"):
         ops.confusion_counts(torch.zeros(1, 2, 3), torch.zeros(1, 2, 3))
+
+
+def _chunk():
+    from avvad import _lib as L
+    return L.SCORE_CHUNK
+
+
+def test_many_chunk_rows_draw_at_once_and_a_truncated_sum_cannot_pass():
+    """The GPU test's five rows (8, 8 + 1 sample, 9, 16, 17 chunks), noise and mixture as the third signal: every
+    reference ratio in [-10, 60] dB on the first seed; on the float64 reference alone, a row longer than 8 chunks cut to
+    its first 8 chunks, and the 8-chunk row cut to 7, moves each of its three ratios by more than 100 * TOL_DB -- so a
+    finish that stops after the unrolled body of its sum, or skips it, is far outside the tolerance."""
+    Cn = _chunk()
+    lengths = score_ref.many_chunk_lengths(Cn)
+    assert lengths == [8 * Cn, 8 * Cn + 1, 9 * Cn + 5, 16 * Cn, 17 * Cn + 3]
+    assert [-(-n // Cn) for n in lengths] == [8, 9, 10, 16, 18] and [n // Cn % 8 for n in lengths] == [0, 0, 1, 0, 1]
+    smallest = np.inf
+    for k, n_ in enumerate(lengths):
+        e, s, n, want, _ = score_ref.draw(n_, k)
+        assert score_ref.draw_misses(n_, k) == 0 and np.all((want >= -10.0) & (want <= 60.0)), (k, want)
+        x, n_mix = score_ref.mixture_of(s, n)
+        want_mix = np.array(score_ref.energy_ratios(e, s, n_mix))
+        assert np.all((want_mix >= -10.0) & (want_mix <= 60.0)), (k, want_mix)
+        cut = 7 * Cn if n_ == 8 * Cn else 8 * Cn
+        for third, full in ((n, want), (n_mix, want_mix)):
+            moved = np.abs(np.array(score_ref.energy_ratios(e[:cut], s[:cut], third[:cut])) - full)
+            print("row of %d samples cut to %d: ratios move by %s dB" % (n_, cut, moved))
+            assert moved.min() > 100 * TOL_DB, (n_, cut, moved)
+            smallest = min(smallest, moved.min())
+    print("smallest move %.3g dB" % smallest)
+
+
+def test_many_row_lengths_and_confusion_shapes_are_what_the_gpu_tests_name():
+    lengths = [2 + (37 * b) % 299 for b in range(70)]
+    assert min(lengths) == 2 and max(lengths) <= 300 and len(set(lengths)) == 70
+    source = open(os.path.join(ROOT, "audio-visual-vad_amd", "csrc", "scores.hip")).read()
+    conf = int(re.search(r"constexpr int CONF_CHUNK = (\d+);", source).group(1))
+    assert conf == 4096
+    values = [n * 512 for n in (24, 8, 9, 0, 17)]
+    assert values == [3 * conf, conf, conf + 512, 0, 2 * conf + 512] == [12288, 4096, 4608, 0, 8704]
+    assert -(-24 * 512 // conf) == 3                          # the grid: three chunks per row, so row 1's second chunk exits

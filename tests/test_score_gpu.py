@@ -6,7 +6,12 @@ Tolerance: 1e-6 dB on every ratio.  The closed form's cancellation e.e - a_s e.s
 the CPU the sweep that measured 2.9e-9 dB at worst.  The signals are s_hat = 0.7 s + g n + e with g in {1, 0.1, 1e-3} and
 e 0, 20 or 40 dB below s, drawn (next seed on a miss, judged by the REFERENCE alone) so that every ratio lies in
 [-10, 60] dB.  alpha: 1e-12 relative -- a double dot product's relative error is a few 2^-53 times sum|terms| / |sum|,
-and the draw also keeps that condition number of both projections below 1e3."""
+and the draw also keeps that condition number of both projections below 1e3.
+
+Past one trip of the finishing kernels: rows of 8, 9, 10, 16 and 18 chunks (``gram_add``'s add_ascending<8>: the unrolled
+body once and twice, alone and with a remainder, all six products under third_mode 1 and 2), an 18-chunk row in packets,
+B = 70 (the second workgroup of ``gram_finalize``, rows behind 64 in ``gram_add``'s grid), and confusion counts of ragged
+batches whose rows hold several chunks next to chunks that exit ((5, 24, 512)) and of 70 rows ((70, 9, 7))."""
 import os
 
 import numpy as np
@@ -21,8 +26,6 @@ NAN = float("nan")
 TOL_DB = 1e-6
 TOL_ALPHA = 1e-12
 T_ = torch.from_numpy
-GAINS = (1.0, 0.1, 1e-3)
-ART_DB = (0.0, 20.0, 40.0)
 
 
 def _ops():
@@ -32,27 +35,7 @@ def _ops():
 
 C = _ops().SCORE_CHUNK
 
-_DRAWN = {}
-
-
-def _draw(L, k):
-    """(s_hat, s, n, ratios, alphas) of length L with the k-th (gain, artefact) pair: float32 signals and their float64
-    reference, computed once per (L, k) and shared."""
-    if (L, k) not in _DRAWN:
-        g, art = GAINS[k % 3], ART_DB[(k // 3) % 3]
-        for seed in range(100 * k, 100 * k + 100):
-            e, s, n = score_ref.mix(np.random.default_rng([L, seed]), L, g, art)
-            r = np.array(score_ref.energy_ratios(e, s, n))
-            e64, s64, n64 = (x.astype(np.float64) for x in (e, s, n))
-            cond = max(np.abs(e64 * s64).sum() / abs(np.dot(e64, s64)), np.abs(e64 * n64).sum() / abs(np.dot(e64, n64)))
-            if np.all((r >= -10.0) & (r <= 60.0)) and cond < 1e3:
-                break
-        else:
-            raise AssertionError("no draw of length %d with every ratio in [-10, 60] dB" % L)
-        for x in (e, s, n):
-            x.setflags(write=False)
-        _DRAWN[(L, k)] = (e, s, n, r, np.array(score_ref.alphas(e, s, n)))
-    return _DRAWN[(L, k)]
+_draw = score_ref.draw           # (s_hat, s, n, ratios, alphas) of length L with the k-th (gain, artefact) pair
 
 
 def _gpu(*xs):
@@ -174,6 +157,119 @@ def test_packets_add_up_and_repeat_bit_for_bit(lib_options):
     assert torch.equal(capped[0], first["single"][0]) and torch.equal(capped[1], first["single"][1])
 
 
+def _ragged(rows, P):
+    """(est, ref, noise) (B, P) float32 on the GPU from per-row (s_hat, s, n) or None, NaN behind every row's length"""
+    planes = [np.full((len(rows), P), NAN, dtype=np.float32) for _ in range(3)]
+    for b, sig in enumerate(rows):
+        if sig is not None:
+            for plane, x in zip(planes, sig):
+                plane[b, :x.size] = x
+    return _gpu(*planes)
+
+
+@pytest.mark.parametrize("third", ["noise", "mixture"])
+def test_rows_of_eight_to_eighteen_chunks(third):
+    """One ragged batch of rows of 8 C, 8 C + 1, 9 C + 5, 16 C and 17 C + 3 samples, NaN behind every length: the sum of a
+    row's partials runs its unrolled body once or twice, alone and followed by a remainder of one or two chunks.  Ratios and
+    alphas against float64; each row alone (a partial pitch of its own chunk count) gives the batch row's bits; two runs
+    give equal bits."""
+    ops = _ops()
+    lengths = score_ref.many_chunk_lengths(C)
+    P = max(lengths) + 77
+    rows, want, want_a = [], [], []
+    for k, L in enumerate(lengths):
+        e, s, n, r, a = _draw(L, k)
+        if third == "mixture":
+            x, n64 = score_ref.mixture_of(s, n)
+            rows.append((e, s, x))
+            want.append(score_ref.energy_ratios(e, s, n64))
+            want_a.append(score_ref.alphas(e, s, n64))
+        else:
+            rows.append((e, s, n))
+            want.append(r)
+            want_a.append(a)
+    want, want_a = np.array(want), np.array(want_a)
+    assert np.all((want >= -10.0) & (want <= 60.0))
+    ed, sd, td = _ragged(rows, P)
+    ratios, alpha = ops.energy_ratios(ed, sd, lengths=lengths, return_alpha=True, **{third: td})
+    assert ratios.shape == (5, 3) and alpha.shape == (5, 2)
+    for b, L in enumerate(lengths):
+        _close("%s, row of %d samples" % (third, L), ratios[b].cpu().numpy(), want[b])
+        rel = np.abs(alpha[b].cpu().numpy() - want_a[b]) / np.abs(want_a[b])
+        print("alpha rel %s" % rel)
+        assert rel.max() <= TOL_ALPHA
+        one, one_a = ops.energy_ratios(ed[b:b + 1, :L], sd[b:b + 1, :L], return_alpha=True, **{third: td[b:b + 1, :L]})
+        _close("%s, the row of %d samples alone" % (third, L), one[0].cpu().numpy(), want[b])
+        assert torch.equal(one[0], ratios[b]) and torch.equal(one_a[0], alpha[b]), (third, L)
+    again, again_a = ops.energy_ratios(ed, sd, lengths=lengths, return_alpha=True, **{third: td})
+    assert torch.equal(again, ratios) and torch.equal(again_a, alpha)
+
+
+def test_packets_over_more_than_eight_chunks():
+    """the row of 17 C + 3 samples (18 chunks) whole and in packets cut at 8 C, at 1 and at (9 C + 5, 16 C): a packet's
+    partials are added on top of what the accumulator holds, through the unrolled body and the remainder"""
+    ops = _ops()
+    L = 17 * C + 3
+    e, s, n, want, _ = _draw(L, 4)
+    ed, sd, nd = _gpu(e, s, n)
+
+    def run(cuts):
+        acc = ops.score_state(1, DEV)
+        edges = [0] + list(cuts) + [L]
+        for a, b in zip(edges[:-1], edges[1:]):
+            assert ops.score_accumulate(acc, ed[a:b], sd[a:b], noise=nd[a:b]) is acc
+        return ops.score_finalize(acc, "noise"), acc.clone()
+    for name, cuts in {"single": (), "8C | rest": (8 * C,), "1 | rest": (1,), "9C+5 | 16C | rest": (9 * C + 5, 16 * C)}.items():
+        first = run(cuts)
+        _close("packets %s" % name, first[0][0].cpu().numpy(), want)
+        again = run(cuts)
+        assert torch.equal(again[0], first[0]) and torch.equal(again[1], first[1]), name
+
+
+def test_seventy_rows():
+    """B = 70, lengths 2 + 37 b mod 299: the second workgroup of the finalize and rows behind 64 everywhere.  Rows 64 and
+    69 are the exact dyadic one-sample row ((inf, 0, 0), alphas [0.5, -2.0]), row 66 is empty (all NaN); every other row
+    against float64.  Then the same through a caller-owned accumulator, twice: x + x is exact, so the accumulator doubles
+    bit for bit and the second pass read what the first had left at every row."""
+    ops = _ops()
+    B = 70
+    lengths = [2 + (37 * b) % 299 for b in range(B)]
+    dyadic = (np.float32([0.25]), np.float32([0.5]), np.float32([-0.125]))
+    rows = [_draw(L, b % 9)[:3] for b, L in enumerate(lengths)]
+    for b in (64, 69):
+        rows[b], lengths[b] = dyadic, 1
+    rows[66], lengths[66] = None, 0
+    P = 300 + 5
+    ed, sd, nd = _ragged(rows, P)
+    ratios_d, alpha_d = ops.energy_ratios(ed, sd, noise=nd, lengths=lengths, return_alpha=True)
+    ratios, alpha = ratios_d.cpu().numpy(), alpha_d.cpu().numpy()
+    assert ratios.shape == (B, 3) and alpha.shape == (B, 2)
+    worst = 0.0
+    for b in range(B):
+        if b in (64, 69):
+            assert ratios[b].tolist() == [np.inf, 0.0, 0.0] == list(score_ref.energy_ratios(*dyadic)), (b, ratios[b])
+            assert alpha[b].tolist() == [0.5, -2.0] == list(score_ref.alphas(*dyadic)), (b, alpha[b])
+        elif b == 66:
+            assert np.isnan(ratios[b]).all() and np.isnan(alpha[b]).all()
+        else:
+            want, want_a = np.array(score_ref.energy_ratios(*rows[b])), np.array(score_ref.alphas(*rows[b]))
+            assert np.isfinite(ratios[b]).all() and np.isfinite(want).all(), b
+            d = np.abs(ratios[b] - want).max()
+            worst = max(worst, d)
+            assert d <= TOL_DB, (b, lengths[b], ratios[b], want)
+            assert (np.abs(alpha[b] - want_a) <= TOL_ALPHA * np.abs(want_a)).all(), (b, alpha[b], want_a)
+    print("70 rows: worst |d| %.3g dB; rows 63 .. 69 %s" % (worst, ratios[63:]))
+    acc = ops.score_state(B, DEV)
+    assert ops.score_accumulate(acc, ed, sd, noise=nd, lengths=lengths) is acc
+    once = acc.clone()
+    got, got_a = ops.score_finalize(acc, "noise", return_alpha=True)
+    same = lambda a, b: torch.equal(a.view(torch.int64), b.view(torch.int64))      # noqa: E731  (bits: NaN rows included)
+    assert same(got, ratios_d) and same(got_a, alpha_d)
+    assert not once[66].any() and bool((once[:, 0] > 0)[[b for b in range(B) if b != 66]].all())
+    ops.score_accumulate(acc, ed, sd, noise=nd, lengths=lengths)
+    assert torch.equal(acc, once + once)
+
+
 def _f1_rows(hard, target, lengths):
     from packages.models.utils import f1_loss
     rows = []
@@ -182,7 +278,10 @@ def _f1_rows(hard, target, lengths):
     return torch.stack(rows)
 
 
-@pytest.mark.parametrize("shape,lengths", [((3, 7, 1), [7, 1, 0]), ((3, 5, 513), [5, 1, 0]), ((1, 370, 513), [370])])
+# (5, 24, 512): 12 288 values (three full chunks of 4096), 4096 (one chunk exactly, the next exits), 4608, 0 and 8704 -- rows
+# of several chunks next to chunks that exit at once; (70, 9, 7): rows behind 64
+@pytest.mark.parametrize("shape,lengths", [((3, 7, 1), [7, 1, 0]), ((3, 5, 513), [5, 1, 0]), ((1, 370, 513), [370]),
+                                           ((5, 24, 512), [24, 8, 9, 0, 17]), ((70, 9, 7), [[9, 4, 0, 1, 7][b % 5] for b in range(70)])])
 def test_confusion_counts(shape, lengths):
     ops = _ops()
     B, T, Y = shape

@@ -1,6 +1,7 @@
 """The mask-regression losses (csrc/spectral_loss.hip), the part that needs no GPU: the float64 restatement of
 tests/spectral_loss_ref.py against the values recorded from the reference's own three functions, the float32 stand-in
-within the recorded bounds and each built-in mistake rejected at them, the declared / bound / exported symbols with the
+within the recorded bounds and each built-in mistake rejected at them (the loop mutants of a finish that stops after one
+trip: rejected at "chunks130" / "rows67", accepted on every smaller shape), the declared / bound / exported symbols with the
 chunk constant and the workspace query, the refusals of the C ABI with never-dereferenced pointers, and the argument
 checks of ``check_objective``, ``train_main`` and ``ops.spectral_loss``."""
 import ctypes as C
@@ -17,6 +18,7 @@ from conftest import ROOT
 NEW = ("avvad_spectral_loss_workspace", "avvad_spectral_loss")
 NAMES = ("mse_mask", "mse_signal", "msa")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "spectral_loss.npz")
+ORIGINAL = ("one", "small", "ragged", "boundary", "three", "clamped", "saturated", "batch5")   # the shapes of at most 16 rows and 3 chunks
 
 
 def golden_case(tag, kind):
@@ -52,6 +54,15 @@ def test_case_list_has_the_shapes_the_kernel_can_go_wrong_at():
     sat = R.case("saturated", "mask", 2)["pred"]
     assert {30.0, -30.0, 100.0, -100.0} <= set(sat[0].reshape(-1).tolist())
     assert len(R.CASES) == 3 * (2 * len(R.SHAPES) - 1)
+    # the finishing loops: a wave adds a row's partials 64 at a time, 16 waves take a row each, 64 lanes add the rows
+    B, T, F, lens = R.SHAPES["chunks130"]
+    assert [R.n_chunks(n, F) for n in lens] == [130, 65, 64, 0] and R.n_chunks(T, F) == 130 and F % 2 == 1 and T % 2 == 1
+    assert B == len(lens) == 4 and sum(n == 0 for n in lens) <= 1 and max(lens) == T
+    B, T, F, lens = R.SHAPES["rows67"]
+    assert B == len(lens) == 67 > 64 and -(-B // 16) == 5 and -(-B // 64) == 2 and max(lens) <= T
+    assert lens[64:] == (5, 3, 7) and all(n > 0 for n in lens[64:]) and all(lens[b] > 0 for b in (16, 17, 32, 48, 63))
+    assert set(ORIGINAL) | {"chunks130", "rows67"} == set(R.SHAPES) and len(ORIGINAL) == 8
+    assert all(R.SHAPES[n][0] <= 16 and R.n_chunks(*R.SHAPES[n][1:3]) <= 64 for n in ORIGINAL)
 
 
 @pytest.mark.parametrize("name, kind, pred_mode", R.CASES)
@@ -83,6 +94,23 @@ def test_each_mutant_is_rejected(mutant):
     R.check_spectral(R.standin, c)
     with pytest.raises(AssertionError):
         R.check_spectral(lambda case: R.standin(case, mutant), c)
+
+
+@pytest.mark.parametrize("mutant", sorted(R.LOOP_MUTANTS))
+def test_each_loop_mutant_is_rejected_on_its_new_case_alone(mutant):
+    """a finish that stops after one trip of one of its three loops: rejected by the shape that turns that loop, and
+    accepted on every shape the list had before -- none of them could see it"""
+    name, kind, pred_mode = R.LOOP_MUTANTS[mutant]
+    broken = lambda case: R.standin(case, mutant)                                       # noqa: E731
+    c = R.case(name, kind, pred_mode)
+    R.check_spectral(R.standin, c)
+    with pytest.raises(AssertionError):
+        R.check_spectral(broken, c)
+    for old in ORIGINAL:
+        c = R.case(old, kind, pred_mode)
+        got = R.check_spectral(broken, c)
+        want = R.standin(c)
+        assert got[0] == want[0] and np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2]), (mutant, old)
 
 
 def test_spectral_symbols_are_declared_bound_and_exported():

@@ -1,6 +1,12 @@
 """GPU tests of the mask-regression losses (csrc/spectral_loss.hip, ``ops.spectral_loss``, the three drop-ins of
 ``packages/models/utils.py`` and the objectives "mse_mask" / "mse_signal" / "msa" of ``train_main``) against the float64
-restatement of tests/spectral_loss_ref.py, at the bounds that file derives from its float32 stand-in."""
+restatement of tests/spectral_loss_ref.py, at the bounds that file derives from its float32 stand-in.
+
+The case list reaches every loop of ``spectral_finish`` past its first trip: "chunks130" (4 x 517 x 513, rows of 130, 65,
+64 and 0 chunks: the lane loop over a row's partials runs three trips, two with one chunk in the second, exactly one, none;
+``spectral_pass`` runs workgroups with blockIdx.x up to 129) and "rows67" (67 x 7 x 33: five trips of the wave-per-row
+loop of 16 waves, two of the 64-lane sum over rows).  Both go through the parametrised value test, through the C ABI with
+a NaN-filled workspace, and row by row against the same row alone."""
 import ctypes as Ct
 import os
 import re
@@ -101,6 +107,34 @@ def test_c_abi_run_to_run_without_dpred_and_off_alignment(name, kind):
         bare = run_abi(c, want_dpred=False, want_rows=False)
         assert torch.equal(bare[0], first[0]) and bare[1] is None and bare[2] is None
         assert torch.equal(run_abi(c, want_dpred=False)[1], first[1])
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+@pytest.mark.parametrize("name", ["chunks130", "rows67"])
+def test_c_abi_past_64_chunks_and_64_rows(name, kind):
+    """The two shapes that turn the finishing loops, through the C ABI with NaN in the workspace and in every output: the
+    bounds; two runs bit-equal; the bits of ops; dpred = NULL leaves the loss and row bits alone."""
+    c = R.case(name, kind, 2)
+    first = run_abi(c)
+    R.check_spectral(lambda _: as_numpy(first), c)
+    for other in (run_abi(c), run_ops(c)):
+        assert all(torch.equal(a, b) for a, b in zip(first, other))
+    bare = run_abi(c, want_dpred=False)
+    assert torch.equal(bare[0], first[0]) and torch.equal(bare[1], first[1]) and bare[2] is None
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+@pytest.mark.parametrize("name, picked", [("rows67", (0, 15, 16, 63, 64, 66)), ("chunks130", (0, 1))])
+def test_a_row_has_the_same_bits_alone_and_past_64_rows_or_chunks(name, picked, kind):
+    """the file header's promise where the finish loops turn: rows on both sides of the 16-wave and 64-lane strides of
+    "rows67", and the rows of 130 and 65 chunks of "chunks130", each alone (B = 1) against its batch row"""
+    c = R.case(name, kind, 2)
+    _, rows, dpred = run_ops(c)
+    for b in picked:
+        assert R.lens_of(c)[b] > 0
+        loss1, rows1, dpred1 = run_ops(R.single_row(c, b))
+        assert torch.equal(rows1[0], rows[b]) and torch.equal(dpred1[0], dpred[b]), (name, kind, b)
+        assert float(loss1) == float(np.float32(float(rows[b])))
 
 
 @pytest.mark.parametrize("kind", ["signal", "spectrum"])
